@@ -11,7 +11,10 @@ projection (divergence, Jacobi sweeps, gradient), accumulation, re-initialisatio
 HBM; nothing crosses PCIe inside the timed region (with --dump the density download of frame f
 overlaps frame f+1 on a third stream).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size S] [--jacobi-iters 200]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--size S] [--jacobi-iters 200] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times K steps and prints the line.  --full adds everything else this file measures: the
+CPU baseline, the extra and knob legs, per-phase times, z-slab diagnostics, the rocprofv3 counter passes.
 
 Workloads:
     N = 1 (default)   BASELINE config 3: 256^3, 200 Jacobi iterations, one MI355X
@@ -117,6 +120,13 @@ def parse():
     ap.add_argument("--emulate-rank", type=int, default=None, help="which rank to emulate (default: a middle one)")
     ap.add_argument("--transport", choices=["rccl", "host"], default="rccl",
                     help="N > 1: ghost planes over RCCL/xGMI (default) or staged through the host over gloo (debug)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the CPU baseline, the extra and knob legs, per-phase times, the "
+                         "diagnostics of z-slab runs and the rocprofv3 counter passes (--no-cpu-baseline, --no-extra, "
+                         "--no-measure-traffic and --diag-steps select among them); a plain run times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the fields they left (rho, T, u, v, w, p) as DIR/<name>.npy, float32; a field "
+                         "larger than its share of 48 MiB is written as a fixed, seeded sample of its elements")
     return ap.parse_args()
 
 
@@ -359,8 +369,31 @@ def measure_traffic(n, kernel_hint, timeout_s=120):
         shutil.rmtree(work, ignore_errors=True)
 
 
+DUMP_FIELDS = ("rho", "T", "u", "v", "w", "p")
+DUMP_ELEMENTS = 2 << 20         # per field and job: 6 fields x 2 Mi x 4 B = 48 MiB at most
+
+
+def dump_outputs(s, out, rank, world):
+    """--dump-outputs: what a caller of advance() reads back after the last timed step, one float32 .npy per field (per
+    rank and field when N > 1: the planes the rank owns).  A field with more elements than its share is written as a
+    sample: sorted element indices drawn by a generator seeded per field, so the same grid gives the same indices in every
+    run and two builds can be compared element for element."""
+    import numpy as np
+    os.makedirs(out, exist_ok=True)
+    keep = DUMP_ELEMENTS // world
+    for i, name in enumerate(DUMP_FIELDS):
+        a = s.owned(name)
+        if a.size > keep:
+            a = a[np.sort(np.random.default_rng(1000 + i).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(out, f"{name}.npy" if world == 1 else f"{name}.rank{rank}.npy"), a)
+
+
 def main():
     args = parse()
+    if not args.full:
+        # a plain run is the headline only: set up, warm up, time the steps, print the line
+        args.no_extra = args.no_cpu_baseline = args.no_measure_traffic = True
+        args.diag_steps = 0
     under_launcher = "RANK" in os.environ and "WORLD_SIZE" in os.environ
     if args.gpus > 1 and not under_launcher:
         self_launch(args)
@@ -561,6 +594,8 @@ def main():
     run(args.steps)
     barrier()
     el = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(s, args.dump_outputs, rank, world)     # before any later leg advances the solver
     stage(f"timed region done: {el / max(1, args.steps) * 1e3:.3f} ms per step on this rank; diagnostics and knob legs follow")
     if dist is not None:
         t = torch.tensor([el], dtype=torch.float64)

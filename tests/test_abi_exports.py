@@ -2,8 +2,11 @@
 include/bimocq_gpu.h and include/bimocq_solver.h declare, the ctypes tables cover the header, and the
 product path fails loudly (no CPU fallback) when no GPU is present.  No compute calls."""
 import ctypes as C
+import hashlib
+import json
 import os
 import re
+import sys
 
 import pytest
 
@@ -32,7 +35,7 @@ def test_headers_declare_the_reference_entry_points():
     assert len(names) >= 50
 
 
-REF_HEADER = "/root/reference/src/bimocq3D/GPU_Advection.h"
+REF_DIGESTS = os.path.join(ROOT, "tests", "golden", "reference_prototypes.json")
 REF_NAMES = ["gpu_solve_forward", "gpu_solve_backwardDMC", "gpu_advect_velocity", "gpu_advect_vel_double", "gpu_advect_field",
              "gpu_advect_field_double", "gpu_accumulate_velocity", "gpu_accumulate_field", "gpu_estimate_distortion", "gpu_add",
              "gpu_compensate_velocity", "gpu_compensate_field", "gpu_semilag", "gpu_emit_smoke", "gpu_add_buoyancy",
@@ -65,17 +68,23 @@ def prototypes(text):
     return out
 
 
-@pytest.mark.skipif(not os.path.exists(REF_HEADER), reason="the reference tree is not present on this box")
+def digest(proto):
+    """SHA-256 of one normalised prototype (return type, [parameter types])"""
+    return hashlib.sha256(json.dumps([proto[0], proto[1]]).encode()).hexdigest()
+
+
 def test_prototypes_equal_the_reference_header():
     """all 22 extern "C" prototypes of the reference's operator boundary (GPU_Advection.h:26-108): same return type,
-    same parameter types in the same order in include/bimocq_gpu.h -- parsed from both headers at test time"""
-    ref = prototypes(open(REF_HEADER).read())
+    same parameter types in the same order in include/bimocq_gpu.h -- ours parsed at test time, the reference's pinned as
+    digests of its normalised prototypes in tests/golden/reference_prototypes.json (`python tests/test_abi_exports.py
+    <reference>/src/bimocq3D/GPU_Advection.h` rewrites that file)"""
+    with open(REF_DIGESTS) as f:
+        ref = json.load(f)["sha256"]
     ours = prototypes(open(os.path.join(ROOT, "include", "bimocq_gpu.h")).read())
-    assert sorted(n for n in ref) == sorted(REF_NAMES), sorted(ref)
+    assert sorted(ref) == sorted(REF_NAMES), sorted(ref)
     for name in REF_NAMES:
         assert name in ours, name
-        assert ours[name][0] == ref[name][0], (name, ours[name][0], ref[name][0])
-        assert ours[name][1] == ref[name][1], (name, ours[name][1], ref[name][1])
+        assert digest(ours[name]) == ref[name], (name, ours[name])
 
 
 def test_every_reference_entry_point_is_declared_and_exported():
@@ -117,3 +126,11 @@ def test_no_gpu_means_loud_failure():
     lib.fl_clear_error()
     with pytest.raises(bq.BimocqError):
         solver.BimocqGPUSolver(16, 16, 16, 1.0)
+
+
+if __name__ == "__main__":
+    protos = prototypes(open(sys.argv[1]).read())
+    with open(REF_DIGESTS, "w") as f:
+        json.dump({"source": "src/bimocq3D/GPU_Advection.h of the reference, prototypes() of tests/test_abi_exports.py",
+                   "sha256": {n: digest(protos[n]) for n in sorted(protos)}}, f, indent=1)
+        f.write("\n")

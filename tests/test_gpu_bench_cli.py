@@ -28,7 +28,7 @@ def run_bench(*args, timeout=900):
 
 
 def test_single_gpu_line_has_the_contract_fields():
-    line = run_bench("--size", 64, "--steps", 3, "--warmup", 1, "--jacobi-iters", 40, "--cpu-n", 16, "--cpu-steps", 1)
+    line = run_bench("--full", "--size", 64, "--steps", 3, "--warmup", 1, "--jacobi-iters", 40, "--cpu-n", 16, "--cpu-steps", 1)
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert key in line, key
@@ -52,10 +52,37 @@ def test_single_gpu_line_has_the_contract_fields():
     assert 0.05 < cl["ta_busy"]["single_field"][1] < 1.3 and cl["l1_to_l2_bytes_over_algorithmic"]["single_field"][1] > 0.5
 
 
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run is the headline line only.  --dump-outputs writes the fields of its last timed step as float32: whole where
+    they fit their share (rho, T, p at 128^3), a seeded sample where they do not (the staggered u, v, w), the same in two runs
+    with the same arguments and unchanged by what --full measures after the timed steps"""
+    common = ["--size", 128, "--steps", 3, "--warmup", 1, "--jacobi-iters", 40]
+    a = run_bench(*common, "--dump-outputs", tmp_path / "a")
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert key in a, key
+    assert a["steps"] == 3 and a["warmup"] == 1 and a["ms_per_step"] > 0 and a["dtype"] == "f32"
+    assert not {"cpu_baseline", "extra", "phase_ms_per_step", "roofline_gather", "diagnostics"} & set(a), sorted(a)
+    run_bench(*common, "--dump-outputs", tmp_path / "b")
+    c = run_bench(*common, "--full", "--no-cpu-baseline", "--no-measure-traffic", "--dump-outputs", tmp_path / "c")
+    assert "extra" in c and "phase_ms_per_step" in c
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(f"{k}.npy" for k in ("rho", "T", "u", "v", "w", "p")), names
+    total = 0
+    for f in names:
+        x = np.load(tmp_path / "a" / f)
+        assert x.dtype == np.float32 and x.size == 128 ** 3, (f, x.size)          # (= the share: 2 Mi elements per field)
+        assert np.isfinite(x).all(), f
+        total += x.nbytes
+        for other in ("b", "c"):
+            assert np.array_equal(x, np.load(tmp_path / other / f)), (other, f)
+    assert total <= 64 << 20 and np.abs(np.load(tmp_path / "a" / "rho.npy")).max() > 0
+
+
 def test_multi_rank_bench_launches_itself():
     """`python bench.py --gpus 2` with no launcher around it: rc 0, ONE JSON line, strong scaling of ONE grid (the
     shape of BASELINE config 4), two ranks in the communicator, the reference-faithful map border"""
-    line = run_bench("--gpus", 2, "--transport", "host", "--size", 64, "--steps", 2, "--warmup", 1, "--jacobi-iters", 30, "--no-extra")
+    line = run_bench("--full", "--gpus", 2, "--transport", "host", "--size", 64, "--steps", 2, "--warmup", 1, "--jacobi-iters", 30,
+                     "--no-extra")
     assert line["n_gpus"] == 2 and line["scaling"] == "strong"
     assert line["config"]["global_grid"] == [64, 64, 64] and line["config"]["grid_per_gpu"] == [64, 64, 32]
     assert line["config"]["comm_size"] == 2
@@ -71,7 +98,7 @@ def test_multi_rank_bench_launches_itself():
 def test_emulated_rank_line_carries_phases_and_knob_legs():
     """--emulate-slab: one process plays a middle rank with a transport that moves nothing; the diagnostic leg gives the
     per-phase times of the slab code path and the compute-side price of each knob (the CU-masked stream included)"""
-    line = run_bench("--size", 64, "--emulate-slab", 2, "--steps", 3, "--warmup", 1, "--jacobi-iters", 40, "--no-cpu-baseline",
+    line = run_bench("--full", "--size", 64, "--emulate-slab", 2, "--steps", 3, "--warmup", 1, "--jacobi-iters", 40, "--no-cpu-baseline",
                      "--no-extra", "--diag-steps", 2)
     assert "EMULATED" in line["metric"]
     d = line["diagnostics"]

@@ -233,7 +233,7 @@ def test_bench_gpus_2_runs_the_rccl_branch(fake, tmp_path):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     one, two = str(tmp_path / "one"), str(tmp_path / "two")
-    common = ["--size", "64", "--steps", "3", "--warmup", "0", "--jacobi-iters", "40", "--no-cpu-baseline", "--no-extra"]
+    common = ["--full", "--size", "64", "--steps", "3", "--warmup", "0", "--jacobi-iters", "40", "--no-cpu-baseline", "--no-extra"]
 
     def run(*args):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args], cwd=ROOT, env=env, stdout=subprocess.PIPE,

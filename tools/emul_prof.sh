@@ -1,8 +1,10 @@
+out=${OUT:-build}
+mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
-rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_emul -o run -- python3 bench.py --emulate-slab --steps 20 --warmup 60 --no-cpu-baseline > gpurun_out/prof_emul.log 2>&1
-python3 - <<'PY'
-import csv, collections
-rows=list(csv.DictReader(open('gpurun_out/prof_emul/run_kernel_trace.csv')))
+rocprofv3 --kernel-trace --stats --output-format csv -d "$out/prof_emul" -o run -- python3 bench.py --full --emulate-slab --steps 20 --warmup 60 --no-cpu-baseline > "$out/prof_emul.log" 2>&1
+python3 - "$out/prof_emul" <<'PY'
+import csv, collections, sys
+rows=list(csv.DictReader(open(f'{sys.argv[1]}/run_kernel_trace.csv')))
 rows.sort(key=lambda r:int(r['Start_Timestamp']))
 starts=[i for i,r in enumerate(rows) if 'max_abs3_partial' in r['Kernel_Name']]
 a,b=starts[60],starts[80]
