@@ -136,6 +136,14 @@ HIP_SIGS = {
     "fl_p2p_exchange_begin": (None, [c_i, VP, VP, VP, VP, VP]),
     "fl_comm_set_custom_p2p": (None, [VP]),
     "gpu_accumulate_wall_fixup": (None, [VP, c_i, c_i, VP, VP, VP, VP, VP, c_f, c_i, c_i, c_i, c_i, c_f, VP, c_i, VP, c_i, VP, c_i]),
+    # solid obstacles (the bq_boundary list travels as a HOST pointer: solver.Boundary arrays)
+    "gpu_obstacle_flags": (None, [VP, VP, VP, c_i, c_f, c_i, c_i, c_i]),
+    "gpu_obstacle_faces": (None, [VP] * 7 + [VP, c_i, c_i, c_i, c_i]),
+    "gpu_jacobi_sweep_masked": (None, [VP] * 5 + [c_i, c_i, c_i, c_f, c_f]),
+    "gpu_jacobi_sweeps_masked": (c_i, [VP] * 5 + [c_i, c_i, c_i, c_i, c_f, c_f]),
+    "gpu_gradient_masked": (None, [VP] * 8 + [c_i, c_i, c_i, c_f]),
+    "gpu_semilag_band": (None, [VP] * 5 + [c_i, c_i, c_i] + _G + [c_f, c_f, VP, c_i]),
+    "gpu_obstacle_blend": (None, [VP] * 11 + [VP, c_i] + _G),
 }
 
 FL_OK, FL_ERR_NO_DEVICE, FL_ERR_HIP, FL_ERR_BAD_ARGUMENT, FL_ERR_UNSUPPORTED, FL_ERR_COMM = range(6)

@@ -1,0 +1,275 @@
+// bq_obstacle.hip -- solid obstacles (reference: setBoundary / updateBoundary, blendBoundary,
+// clearBoundary and the masked projection of BimocqSolver.cpp:879-1413): cell flags + tile summary, the solid face
+// write, the masked Jacobi sweep, the masked gradient, and the band blend fused with the density clear.
+// The band semi-Lagrangian pass lives beside semilag_kernel in bq_advect.hip.
+#include "bq_device.hip.h"
+#include "bq_host.h"
+#include "bq_obstacle.hip.h"
+
+namespace bq {
+
+static const dim3 kBlockO(64, 4, 1);
+static inline dim3 grid_o(int a, int b, int c) { return dim3((a + 63) / 64, (b + 3) / 4, c); }
+
+// ---- flags: one thread per cell; a solid cell marks the rows summary of its own row and plane and the neighbouring ones --
+__global__ __launch_bounds__(256) void obstacle_flags_kernel(unsigned char *__restrict__ solid, unsigned char *__restrict__ rows,
+                                                             ObsSet ob, float h, int ni, int nj, int nk)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x, j = blockIdx.y * 4 + threadIdx.y, k = blockIdx.z;
+    if (i >= ni || j >= nj) return;
+    const int c = obs_classify(ob, obs_pos(i, 0, h), obs_pos(j, 0, h), obs_pos(k, 0, h));
+    const unsigned char f = c > 0 ? (unsigned char)c : 0;
+    solid[(size_t)i + (size_t)ni * ((size_t)j + (size_t)nj * k)] = f;
+    if (!f) return;
+    for (int kk = max(k - 1, 0); kk <= min(k + 1, nk - 1); kk++)
+        for (int jj = max(j - 1, 0); jj <= min(j + 1, nj - 1); jj++)
+            rows[(size_t)jj + (size_t)nj * kk] = 1;                 // same value from every writer
+}
+
+__device__ __forceinline__ int flag_at(const unsigned char *solid, int i, int j, int k, int ni, int nj, int nk)
+{
+    return (i >= 0 && i < ni && j >= 0 && j < nj && k >= 0 && k < nk) ? solid[(size_t)i + (size_t)ni * ((size_t)j + (size_t)nj * k)] : 0;
+}
+
+// ---- solid faces: one thread per node of the (ni+1, nj+1, nk+1) super-grid ------------------------------------------
+__global__ __launch_bounds__(256) void obstacle_faces_kernel(float *__restrict__ u, float *__restrict__ v, float *__restrict__ w,
+                                                             float *__restrict__ du, float *__restrict__ dv, float *__restrict__ dw,
+                                                             const unsigned char *__restrict__ solid, ObsVel ov, int ni, int nj, int nk)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x, j = blockIdx.y * 4 + threadIdx.y, k = blockIdx.z;
+    if (i > ni || j > nj || k > nk) return;
+    if (j < nj && k < nk) {                                         // u face between cells i-1 and i
+        const int o = max(flag_at(solid, i - 1, j, k, ni, nj, nk), flag_at(solid, i, j, k, ni, nj, nk));
+        if (o) {
+            const size_t id = (size_t)i + (size_t)(ni + 1) * ((size_t)j + (size_t)nj * k);
+            const float vo = ov.vx[o - 1];
+            if (du) du[id] = vo - u[id];
+            u[id] = vo;
+        }
+    }
+    if (i < ni && k < nk) {                                         // v face between cells j-1 and j
+        const int o = max(flag_at(solid, i, j - 1, k, ni, nj, nk), flag_at(solid, i, j, k, ni, nj, nk));
+        if (o) {
+            const size_t id = (size_t)i + (size_t)ni * ((size_t)j + (size_t)(nj + 1) * k);
+            const float vo = ov.vy[o - 1];
+            if (dv) dv[id] = vo - v[id];
+            v[id] = vo;
+        }
+    }
+    if (i < ni && j < nj) {                                         // w face between cells k-1 and k
+        const int o = max(flag_at(solid, i, j, k - 1, ni, nj, nk), flag_at(solid, i, j, k, ni, nj, nk));
+        if (o) {
+            const size_t id = (size_t)i + (size_t)ni * ((size_t)j + (size_t)nj * k);
+            const float vo = ov.vz[o - 1];
+            if (dw) dw[id] = vo - w[id];
+            w[id] = vo;
+        }
+    }
+}
+
+// ---- masked Jacobi sweep, one per launch ------------------------------------------------------------------------------
+// Odd sweep counts and the test baseline of the fused masked sweeps (jacobi_lds_kernel<8, 1, 3, true>, bq_project.hip).  A
+// cell whose rows summary is clean (no solid cell in its row or the neighbouring rows and planes) evaluates
+// jacobi_generic_kernel's expression without reading a flag; the others skip solid cells and scale the same sum by beta_s.
+// Solid cells hold +0 in both buffers, so their terms add +0: the sum is the Neumann sum over the fluid neighbours.
+struct BetaTab { float b[7]; };
+__global__ __launch_bounds__(256) void jacobi_masked_kernel(const float *__restrict__ p, const float *__restrict__ div,
+                                                            float *__restrict__ out, const unsigned char *__restrict__ solid,
+                                                            const unsigned char *__restrict__ rows,
+                                                            int ni, int nj, int nk, float alpha, BetaTab bt)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x, j = blockIdx.y * 4 + threadIdx.y, k = blockIdx.z;
+    if (!(i > 0 && i < ni - 1 && j > 0 && j < nj - 1 && k > 0 && k < nk - 1)) return;
+    const size_t sj = ni, sk = (size_t)ni * nj;
+    const size_t id = (size_t)i + sj * j + sk * k;
+    if (!rows[(size_t)j + (size_t)nj * k]) {
+        out[id] = (p[id - 1] + p[id + 1] + p[id - sj] + p[id + sj] + p[id - sk] + p[id + sk] + alpha * div[id]) * bt.b[0];
+        return;
+    }
+    if (solid[id]) return;
+    const int s = (solid[id - 1] != 0) + (solid[id + 1] != 0) + (solid[id - sj] != 0) + (solid[id + sj] != 0)
+                + (solid[id - sk] != 0) + (solid[id + sk] != 0);
+    const float sum = p[id - 1] + p[id + 1] + p[id - sj] + p[id + sj] + p[id - sk] + p[id + sk] + alpha * div[id];
+    out[id] = s == 6 ? 0.f : sum * bt.b[s];
+}
+
+// ---- masked gradient (gradient_delta_kernel / gradient_kernel with solid faces left alone) ----------------------------
+__global__ __launch_bounds__(256) void gradient_masked_kernel(float *__restrict__ u, float *__restrict__ v, float *__restrict__ w,
+                                                              const float *__restrict__ p,
+                                                              float *__restrict__ du, float *__restrict__ dv, float *__restrict__ dw,
+                                                              const unsigned char *__restrict__ solid, int ni, int nj, int nk, float halfrdx)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x, j = blockIdx.y * 4 + threadIdx.y, k = blockIdx.z;
+    if (i > ni || j > nj || k > nk) return;
+    const bool win = !(i < 2 || i >= ni || j < 2 || j >= nj || k < 2 || k >= nk);
+    const size_t iu = (size_t)i + (size_t)(ni + 1) * ((size_t)j + (size_t)nj * k);
+    const size_t iv = (size_t)i + (size_t)ni * ((size_t)j + (size_t)(nj + 1) * k);
+    const size_t ic = (size_t)i + (size_t)ni * ((size_t)j + (size_t)nj * k);
+    const bool hu = j < nj && k < nk, hv = i < ni && k < nk, hw = i < ni && j < nj;
+    const bool su = hu && (flag_at(solid, i - 1, j, k, ni, nj, nk) | flag_at(solid, i, j, k, ni, nj, nk));
+    const bool sv = hv && (flag_at(solid, i, j - 1, k, ni, nj, nk) | flag_at(solid, i, j, k, ni, nj, nk));
+    const bool sw = hw && (flag_at(solid, i, j, k - 1, ni, nj, nk) | flag_at(solid, i, j, k, ni, nj, nk));
+    if (win) {
+        const float p0 = p[ic];
+        if (!su) {
+            const float uo = u[iu], un = uo - halfrdx * (p0 - p[ic - 1]);
+            u[iu] = un;
+            if (du) du[iu] = un - uo;
+        }
+        if (!sv) {
+            const float vo = v[iv], vn = vo - halfrdx * (p0 - p[ic - ni]);
+            v[iv] = vn;
+            if (dv) dv[iv] = vn - vo;
+        }
+        if (!sw) {
+            const float wo = w[ic], wn = wo - halfrdx * (p0 - p[ic - (size_t)ni * nj]);
+            w[ic] = wn;
+            if (dw) dw[ic] = wn - wo;
+        }
+    } else if (du) {
+        if (hu && !su) du[iu] = 0.f;
+        if (hv && !sv) dv[iv] = 0.f;
+        if (hw && !sw) dw[ic] = 0.f;
+    }
+}
+
+// ---- band blend + density clear: one thread per super-grid node -------------------------------------------------------
+__global__ __launch_bounds__(256) void obstacle_blend_kernel(float *__restrict__ u, float *__restrict__ v, float *__restrict__ w,
+                                                             float *__restrict__ rho, float *__restrict__ T,
+                                                             const float *__restrict__ us, const float *__restrict__ vs,
+                                                             const float *__restrict__ ws, const float *__restrict__ rhos,
+                                                             const float *__restrict__ Ts, const unsigned char *__restrict__ solid,
+                                                             ObsSet ob, float h, int ni, int nj, int nk)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x, j = blockIdx.y * 4 + threadIdx.y, k = blockIdx.z;
+    if (i > ni || j > nj || k > nk) return;
+    const float x0 = obs_pos(i, 0, h), y0 = obs_pos(j, 0, h), z0 = obs_pos(k, 0, h);
+    const float x1 = obs_pos(i, 1, h), y1 = obs_pos(j, 1, h), z1 = obs_pos(k, 1, h);
+    if (us) {
+        if (j < nj && k < nk && obs_classify(ob, x1, y0, z0) == -1) {
+            const size_t id = (size_t)i + (size_t)(ni + 1) * ((size_t)j + (size_t)nj * k);
+            u[id] = us[id];
+        }
+        if (i < ni && k < nk && obs_classify(ob, x0, y1, z0) == -1) {
+            const size_t id = (size_t)i + (size_t)ni * ((size_t)j + (size_t)(nj + 1) * k);
+            v[id] = vs[id];
+        }
+        if (i < ni && j < nj && obs_classify(ob, x0, y0, z1) == -1) {
+            const size_t id = (size_t)i + (size_t)ni * ((size_t)j + (size_t)nj * k);
+            w[id] = ws[id];
+        }
+    }
+    if (i < ni && j < nj && k < nk) {
+        const size_t id = (size_t)i + (size_t)ni * ((size_t)j + (size_t)nj * k);
+        if (us && obs_classify(ob, x0, y0, z0) == -1) { rho[id] = rhos[id]; T[id] = Ts[id]; }
+        if (solid[id]) rho[id] = 0.f;
+    }
+}
+
+static bool obs_args_ok(const bq_boundary *b, int n, int ni, int nj, int nk, const char *op)
+{
+    if (!ensure_ready(op)) return false;
+    if (ni < 3 || nj < 3 || nk < 3 || 4.0 * (double)(ni + 1) * (double)(nj + 1) * (double)(nk + 1) >= 4294967296.0 || nk + 1 > 65535) {
+        latch(FL_ERR_BAD_ARGUMENT, op, "grid dims out of range");
+        return false;
+    }
+    if (n < 0 || n > BQ_MAX_BOUNDARIES || (n > 0 && !b)) { latch(FL_ERR_BAD_ARGUMENT, op, "1 .. 16 obstacles"); return false; }
+    if (rt().slab_on) { latch(FL_ERR_UNSUPPORTED, op, "obstacles on z-slab ranks"); return false; }
+    return true;
+}
+
+bool jacobi_sweep_triple_masked(const float *in, const float *div, float *out, int ni, int nj, int nk, float alpha,
+                                const unsigned char *solid, const unsigned char *rows, const float betas[7]);   // bq_project.hip
+
+} // namespace bq
+
+using namespace bq;
+
+extern "C" {
+
+void gpu_obstacle_flags(unsigned char *solid, unsigned char *rows, const bq_boundary *b, int n, float h, int ni, int nj, int nk)
+{
+    if (!obs_args_ok(b, n, ni, nj, nk, "gpu_obstacle_flags")) return;
+    if (!solid || !rows) { latch(FL_ERR_BAD_ARGUMENT, "gpu_obstacle_flags", "null device pointer"); return; }
+    if (!BQ_HIP(hipMemsetAsync(rows, 0, (size_t)nj * (size_t)nk, rt().compute))) return;
+    obstacle_flags_kernel<<<grid_o(ni, nj, nk), kBlockO, 0, rt().compute>>>(solid, rows, make_obs(b, n, h), h, ni, nj, nk);
+    BQ_LAUNCH_CHECK("obstacle_flags_kernel");
+}
+
+void gpu_obstacle_faces(float *u, float *v, float *w, float *du, float *dv, float *dw, const unsigned char *solid,
+                        const bq_boundary *b, int n, int ni, int nj, int nk)
+{
+    if (!obs_args_ok(b, n, ni, nj, nk, "gpu_obstacle_faces")) return;
+    if (!u || !v || !w || !solid || (!du) != (!dv) || (!du) != (!dw)) { latch(FL_ERR_BAD_ARGUMENT, "gpu_obstacle_faces", "null device pointer"); return; }
+    ObsVel ov{};
+    for (int o = 0; o < n; o++) { ov.vx[o] = b[o].vx; ov.vy[o] = b[o].vy; ov.vz[o] = b[o].vz; }
+    obstacle_faces_kernel<<<grid_o(ni + 1, nj + 1, nk + 1), kBlockO, 0, rt().compute>>>(u, v, w, du, dv, dw, solid, ov, ni, nj, nk);
+    BQ_LAUNCH_CHECK("obstacle_faces_kernel");
+}
+
+static BetaTab beta_table(float beta)
+{
+    BetaTab t;
+    t.b[0] = beta;
+    for (int s = 1; s < 6; s++) t.b[s] = (float)(1.0 / (1.0 / (double)beta - (double)s));
+    t.b[6] = 0.f;
+    return t;
+}
+
+void gpu_jacobi_sweep_masked(const float *in, const float *div, float *out, const unsigned char *solid,
+                             const unsigned char *rows, int ni, int nj, int nk, float alpha, float beta)
+{
+    if (!obs_args_ok(nullptr, 0, ni, nj, nk, "gpu_jacobi_sweep_masked")) return;
+    if (!in || !div || !out || !solid || !rows || in == out) { latch(FL_ERR_BAD_ARGUMENT, "gpu_jacobi_sweep_masked", "null or aliased buffers"); return; }
+    jacobi_masked_kernel<<<grid_o(ni, nj, nk), kBlockO, 0, rt().compute>>>(in, div, out, solid, rows, ni, nj, nk, alpha, beta_table(beta));
+    BQ_LAUNCH_CHECK("jacobi_masked_kernel");
+}
+
+// FL_OPT_JACOBI_FUSE >= 2 (the caller vouches that p and p_temp carry the same boundary layer and the same values in solid
+// cells): three sweeps per launch through the masked LDS kernel where it applies; the rest one per launch
+int gpu_jacobi_sweeps_masked(float *p, const float *div, float *p_temp, const unsigned char *solid,
+                             const unsigned char *rows, int ni, int nj, int nk, int sweeps, float alpha, float beta)
+{
+    if (!obs_args_ok(nullptr, 0, ni, nj, nk, "gpu_jacobi_sweeps_masked")) return 0;
+    if (!p || !div || !p_temp || !solid || !rows || p == p_temp) { latch(FL_ERR_BAD_ARGUMENT, "gpu_jacobi_sweeps_masked", "null or aliased buffers"); return 0; }
+    const BetaTab bt = beta_table(beta);
+    float *in = p, *out = p_temp;
+    ProfileSpan span;
+    const bool prof = sweeps > 0 && profile_begin(span);      // FL_OPT_PROFILE_JACOBI, like gpu_jacobi_sweeps
+    int s = 0;
+    long long launches = 0;
+    while (rt().opt_jacobi_fuse >= 2 && rt().opt_jacobi_fuse != 4 && s + 3 <= sweeps &&
+           jacobi_sweep_triple_masked(in, div, out, ni, nj, nk, alpha, solid, rows, bt.b)) {
+        float *t = in; in = out; out = t;
+        s += 3; launches++;
+    }
+    for (; s < sweeps; s++) {
+        jacobi_masked_kernel<<<grid_o(ni, nj, nk), kBlockO, 0, rt().compute>>>(in, div, out, solid, rows, ni, nj, nk, alpha, bt);
+        if (!BQ_LAUNCH_CHECK("jacobi_masked_kernel")) break;
+        float *t = in; in = out; out = t;
+        launches++;
+    }
+    if (prof) profile_end(span, launches, sweeps);
+    return in == p ? 0 : 1;
+}
+
+void gpu_gradient_masked(float *u, float *v, float *w, const float *p, float *du, float *dv, float *dw,
+                         const unsigned char *solid, int ni, int nj, int nk, float halfrdx)
+{
+    if (!obs_args_ok(nullptr, 0, ni, nj, nk, "gpu_gradient_masked")) return;
+    if (!u || !v || !w || !p || !solid || (!du) != (!dv) || (!du) != (!dw)) { latch(FL_ERR_BAD_ARGUMENT, "gpu_gradient_masked", "null device pointer"); return; }
+    gradient_masked_kernel<<<grid_o(ni + 1, nj + 1, nk + 1), kBlockO, 0, rt().compute>>>(u, v, w, p, du, dv, dw, solid, ni, nj, nk, halfrdx);
+    BQ_LAUNCH_CHECK("gradient_masked_kernel");
+}
+
+void gpu_obstacle_blend(float *u, float *v, float *w, float *rho, float *T, const float *us, const float *vs,
+                        const float *ws, const float *rhos, const float *Ts, const unsigned char *solid,
+                        const bq_boundary *b, int n, float h, int ni, int nj, int nk)
+{
+    if (!obs_args_ok(b, n, ni, nj, nk, "gpu_obstacle_blend")) return;
+    if (!rho || !solid || (us && (!u || !v || !w || !T || !vs || !ws || !rhos || !Ts))) { latch(FL_ERR_BAD_ARGUMENT, "gpu_obstacle_blend", "null device pointer"); return; }
+    obstacle_blend_kernel<<<grid_o(ni + 1, nj + 1, nk + 1), kBlockO, 0, rt().compute>>>(u, v, w, rho, T, us, vs, ws, rhos, Ts, solid, make_obs(b, n, h), h, ni, nj, nk);
+    BQ_LAUNCH_CHECK("obstacle_blend_kernel");
+}
+
+} // extern "C"

@@ -1028,6 +1028,43 @@ __global__ __launch_bounds__(256) void jacobi_lean3r_kernel(const float *__restr
 #undef BQ_SL3
 }
 
+// Obstacles (MASK = true; bq_obstacle.hip).  solid: one byte per cell, 0 = fluid; rows: one byte per
+// (row, plane), 1 when a solid cell lies in rows j-1 .. j+1 of planes k-1 .. k+1; b0 .. b6: beta_s for s solid neighbours.
+struct SweepMask { const unsigned char *solid = nullptr, *rows = nullptr; float b0 = 0.f, b1 = 0.f, b2 = 0.f, b3 = 0.f, b4 = 0.f, b5 = 0.f, b6 = 0.f; };
+
+// Per cell of a float4 column a code byte: 7 = solid, else s = the number of solid neighbours.  own / lw / rw: the flag words
+// (one byte per cell) of the column, of the column to the left (lane - 1) and to the right (lane + 1); yl, yh, zl, zh: of
+// the same column in the neighbouring rows and planes.  Computed once per (row, plane), when the plane's level 1 is formed.
+__device__ __forceinline__ unsigned mask_code(unsigned own, unsigned lw, unsigned rw, unsigned yl, unsigned yh, unsigned zl, unsigned zh)
+{
+    unsigned code = 0;
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+        const unsigned lb = c == 0 ? lw >> 24 : own >> (8 * (c - 1));
+        const unsigned rb = c == 3 ? rw : own >> (8 * (c + 1));
+        const unsigned n = ((lb & 255u) != 0) + ((rb & 255u) != 0) + (((yl >> (8 * c)) & 255u) != 0) + (((yh >> (8 * c)) & 255u) != 0)
+                         + (((zl >> (8 * c)) & 255u) != 0) + (((zh >> (8 * c)) & 255u) != 0);
+        code |= (((own >> (8 * c)) & 255u) ? 7u : n) << (8 * c);
+    }
+    return code;
+}
+// the masked sweep's value from the UNSCALED sum (jac_r4 with beta = 1: the same float as the sum): solid cells keep `ce`, a
+// cell with s solid neighbours takes sum * beta_s (s = 6: 0), x-boundary cells keep `ce`
+__device__ __forceinline__ float mask_one(float sum, float ce, unsigned k, const SweepMask &mk)
+{
+    const float bs = k == 0 ? mk.b0 : k == 1 ? mk.b1 : k == 2 ? mk.b2 : k == 3 ? mk.b3 : k == 4 ? mk.b4 : mk.b5;
+    return k == 7 ? ce : (k == 6 ? 0.f : sum * bs);
+}
+__device__ __forceinline__ R4 mask_finish(R4 sum, R4 ce, unsigned code, const SweepMask &mk, bool xlo, bool xhi)
+{
+    R4 o;
+    o.a.x = xlo ? ce.a.x : mask_one(sum.a.x, ce.a.x, code & 255u, mk);
+    o.a.y = mask_one(sum.a.y, ce.a.y, (code >> 8) & 255u, mk);
+    o.b.x = mask_one(sum.b.x, ce.b.x, (code >> 16) & 255u, mk);
+    o.b.y = xhi ? ce.b.y : mask_one(sum.b.y, ce.b.y, code >> 24, mk);
+    return o;
+}
+
 // ---- THREE sweeps per launch, the intermediate levels' neighbour rows exchanged through LDS (round 3) ------------------
 // jacobi_lean3r_kernel is bound by instruction ISSUE: a thread that owns rows j, j+1 evaluates the first sweep on six rows and
 // the second on four to produce the third on two -- 12 evaluations for 6 useful ones -- and its ~400 registers leave one wave
@@ -1051,10 +1088,11 @@ __global__ __launch_bounds__(256) void jacobi_lean3r_kernel(const float *__restr
 // A halo wave whose nearest row lies dn rows outside the block owes the block levels 1 .. S - dn only: the march is instantiated
 // once per level count and a block's waves run different code between the same barriers (S = 4 in row pairs: 11.4 -> 10.0 us
 // per sweep at 256^3; S = 3 unchanged, 10.7 -- its waves wait for each other, not for the VALU).
-template <int W, int R, int S>
+template <int W, int R, int S, bool MASK = false>
 __global__ __launch_bounds__((W + 2 * ((S - 1 + R - 1) / R)) * 64) void jacobi_lds_kernel(const float *__restrict__ p, const float *__restrict__ div,
                                                                   float *__restrict__ out, int nx, int ny, int nz,
-                                                                  int nby, int nblk, int kchunk, float alpha, float beta, Slab sl, PairRanges rg)
+                                                                  int nby, int nblk, int kchunk, float alpha, float beta, Slab sl, PairRanges rg,
+                                                                  SweepMask mk)
 {
     static_assert((R == 1 || R == 2) && (S == 3 || S == 4), "one or two rows per wave, three or four sweeps per launch");
     constexpr int H = (S - 1 + R - 1) / R, NW = W + 2 * H, NS = NW * R, P = 4, A = P - 2;   // A: the plane loaded in step q is q + A
@@ -1103,11 +1141,31 @@ __global__ __launch_bounds__((W + 2 * ((S - 1 + R - 1) / R)) * 64) void jacobi_l
     auto put = [&](v4f (*buf)[64], int a, R4 v) { buf[r0 + a][lane] = v4f{v.a.x, v.a.y, v.b.x, v.b.y}; };
     auto get = [&](v4f (*buf)[64], int r) -> R4 { const v4f v = buf[r][lane]; return R4{v2f{v.x, v.y}, v2f{v.z, v.w}}; };
 
-    auto run = [&](auto EDGE_T, auto SM_T) __attribute__((always_inline)) {
+    // masked blocks: the flag words of this thread's column in row `row` of plane `pl` and the masked value of a level there
+    // (rows and planes clamped into the array: what a clamped neighbour contributes is never used -- boundary rows and
+    // planes keep their input)
+    const size_t fplane = (size_t)nx * (size_t)ny;
+    auto fword = [&](int row, int pl) -> unsigned {
+        return *(const unsigned *)(mk.solid + (size_t)x + (size_t)nx * (size_t)min(max(row, 0), ny - 1) + fplane * (size_t)min(max(pl, 0), nz - 1));
+    };
+    auto code_of = [&](unsigned own, unsigned yl, unsigned yh, unsigned zl, unsigned zh) -> unsigned {
+        return mask_code(own, __shfl_up(own, 1), __shfl_down(own, 1), yl, yh, zl, zh);
+    };
+    auto run = [&](auto EDGE_T, auto SM_T, auto MASK_T) __attribute__((always_inline)) {
     constexpr bool EDGE = decltype(EDGE_T)::value;
+    constexpr bool MK = decltype(MASK_T)::value;                    // this block lies near a solid cell
     constexpr int SM = decltype(SM_T)::value;                       // the levels this wave evaluates (halo waves: fewer than S)
     R4 L0[P][R + 2], D[P][R], Lv[S][P][R];                          // Lv[s]: level s (1 .. S-1) on the wave's own rows
+    // masked blocks: flag words of rows j-1 .. j+R in the same ring as L0 (loaded with it, A planes ahead), and the code
+    // words (mask_code) of the own rows per plane, formed with level 1 and reused by the later levels of that plane
+    unsigned Fw[P][R + 2], Cd[P][R];
     const R4 zero = R4{v2f{0.f, 0.f}, v2f{0.f, 0.f}};
+    if (MK) {
+#pragma unroll
+        for (int a = 0; a < P; a++)
+#pragma unroll
+            for (int c = 0; c < R; c++) Cd[a][c] = 0u;
+    }
 #pragma unroll
     for (int a = 0; a < P; a++)
 #pragma unroll
@@ -1124,6 +1182,10 @@ __global__ __launch_bounds__((W + 2 * ((S - 1 + R - 1) / R)) * 64) void jacobi_l
         const unsigned pp = po(q + d);
 #pragma unroll
         for (int a = 0; a < R + 2; a++) L0[sl_][a] = ld_r4(rp, vo[a], pp);
+        if (MK) {
+#pragma unroll
+            for (int a = 0; a < R + 2; a++) Fw[sl_][a] = fword(j - 1 + a, q + d);
+        }
         if (d >= 0 && d <= A - 2) {
 #pragma unroll
             for (int a = 0; a < R; a++) D[sl_][a] = ld_r4(rd, vo[a + 1], pp);
@@ -1134,6 +1196,8 @@ __global__ __launch_bounds__((W + 2 * ((S - 1 + R - 1) / R)) * 64) void jacobi_l
         constexpr int im = BQ_SL4(T, -1), ic = BQ_SL4(T, 0), in_ = BQ_SL4(T, 1), ia = BQ_SL4(T, A), id_ = BQ_SL4(T, A - 1); \
         const unsigned pa = po(q + A), pb = po(q + A - 1);                                                          \
         _Pragma("unroll") for (int a = 0; a < R + 2; a++) L0[ia][a] = ld_r4(rp, vo[a], pa);                           \
+        if (MK) { _Pragma("unroll") for (int a = 0; a < R + 2; a++) Fw[ia][a] = fword(j - 1 + a, q + A); }               \
+        if (MK) { _Pragma("unroll") for (int a = 0; a < R; a++) Cd[ic][a] = code_of(Fw[ic][a + 1], Fw[ic][a], Fw[ic][a + 2], Fw[im][a + 1], Fw[in_][a + 1]); } \
         if (S == 3) { _Pragma("unroll") for (int a = 0; a < R; a++) D[id_][a] = ld_r4(rd, vo[a + 1], pb); }           \
         /* the neighbour rows every later level of this step needs were put into LDS before the last barrier: fetch them   \
            all now, ahead of the first level's arithmetic (the compiler cannot hoist them over this step's own puts) */     \
@@ -1147,7 +1211,8 @@ __global__ __launch_bounds__((W + 2 * ((S - 1 + R - 1) / R)) * 64) void jacobi_l
         } else {                                                                                                    \
             _Pragma("unroll") for (int a = 0; a < R; a++) {                                                          \
                 D[ic][a].a = alpha * D[ic][a].a; D[ic][a].b = alpha * D[ic][a].b;                                   \
-                Lv[1][ic][a] = jac_r4<false, true, true>(L0[ic][a + 1], L0[ic][a], L0[ic][a + 2], L0[im][a + 1], L0[in_][a + 1], D[ic][a], alpha, beta, xlo, xhi); \
+                if (MK) Lv[1][ic][a] = mask_finish(jac_r4<false, true, true>(L0[ic][a + 1], L0[ic][a], L0[ic][a + 2], L0[im][a + 1], L0[in_][a + 1], D[ic][a], alpha, 1.0f, false, false), L0[ic][a + 1], Cd[ic][a], mk, xlo, xhi); \
+                else Lv[1][ic][a] = jac_r4<false, true, true>(L0[ic][a + 1], L0[ic][a], L0[ic][a + 2], L0[im][a + 1], L0[in_][a + 1], D[ic][a], alpha, beta, xlo, xhi); \
                 if (EDGE && rowb[a]) Lv[1][ic][a] = L0[ic][a + 1];                                                  \
             }                                                                                                       \
         }                                                                                                           \
@@ -1161,7 +1226,8 @@ __global__ __launch_bounds__((W + 2 * ((S - 1 + R - 1) / R)) * 64) void jacobi_l
                 _Pragma("unroll") for (int a = 0; a < R; a++) {                                                      \
                     const R4 ce = Lv[s - 1][cs][a];                                                                 \
                     const R4 fr = a == 0 ? nlo[s] : Lv[s - 1][cs][a == 0 ? 0 : a - 1], bk = a == R - 1 ? nhi[s] : Lv[s - 1][cs][a == R - 1 ? a : a + 1]; \
-                    R4 v = jac_r4<false, true, true>(ce, fr, bk, Lv[s - 1][ds][a], Lv[s - 1][us][a], D[cs][a], alpha, beta, xlo, xhi); \
+                    R4 v = MK ? mask_finish(jac_r4<false, true, true>(ce, fr, bk, Lv[s - 1][ds][a], Lv[s - 1][us][a], D[cs][a], alpha, 1.0f, false, false), ce, Cd[cs][a], mk, xlo, xhi) \
+                              : jac_r4<false, true, true>(ce, fr, bk, Lv[s - 1][ds][a], Lv[s - 1][us][a], D[cs][a], alpha, beta, xlo, xhi); \
                     if (keep || (EDGE && rowb[a])) v = ce;                                                          \
                     if (s < S) { Lv[s][cs][a] = v; put(lds[s - 1][ps & 1], a, v); }                                 \
                     else if (active[a]) st_r4(v, ro, vo[a + 1], pstride * (unsigned)ps);                            \
@@ -1184,13 +1250,26 @@ __global__ __launch_bounds__((W + 2 * ((S - 1 + R - 1) / R)) * 64) void jacobi_l
     }
     };
     // one instance of the march per number of levels: the waves of a block run different code between the same barriers
-    auto go = [&](auto E) __attribute__((always_inline)) {
-        if (smax >= S) run(E, std::integral_constant<int, S>{});
-        else if (smax == 1) run(E, std::integral_constant<int, 1>{});
-        else if (smax == 2) run(E, std::integral_constant<int, 2>{});
-        else run(E, std::integral_constant<int, 3>{});
+    auto go = [&](auto E, auto M) __attribute__((always_inline)) {
+        if (smax >= S) run(E, std::integral_constant<int, S>{}, M);
+        else if (smax == 1) run(E, std::integral_constant<int, 1>{}, M);
+        else if (smax == 2) run(E, std::integral_constant<int, 2>{}, M);
+        else run(E, std::integral_constant<int, 3>{}, M);
     };
-    if (edge_block) go(std::true_type{}); else go(std::false_type{});
+    if constexpr (MASK) {
+        // a block is clean when no solid cell lies within S cells of its output rows and planes (rows summary: already one
+        // cell wide): then every value it computes equals the unmasked one, and it runs the unmasked stream
+        const int r0 = max(jb - S, 0), r1 = min(jb + W * R + S, ny), k0 = max(kbeg - S, 0), k1 = min(kend + S, nz);
+        const int nr = max(r1 - r0, 0), cnt = nr * max(k1 - k0, 0);
+        int any = 0;
+        for (int t = (int)threadIdx.x; t < cnt; t += (int)blockDim.x)
+            any |= mk.rows[(size_t)(r0 + t % nr) + (size_t)ny * (size_t)(k0 + t / nr)];
+        if (__syncthreads_or(any)) {
+            if (edge_block) go(std::true_type{}, std::true_type{}); else go(std::false_type{}, std::true_type{});
+            return;
+        }
+    }
+    if (edge_block) go(std::true_type{}, std::false_type{}); else go(std::false_type{}, std::false_type{});
 #undef BQ_LDS_PHASE
 #undef BQ_SL4
 }
@@ -1693,7 +1772,7 @@ static bool jacobi_sweep_pair(const float *in, const float *div, float *out, int
 // FL_OPT_JACOBI_ROWS: 4 forces it wherever it applies, 5 keeps it off (A/B timing); auto: see jacobi_sweep_triple.
 // k0a .. k1b: the OUTPUT planes as up to two ranges (gpu_jacobi_sweep_triple_ranges: the pieces of a z-slab chunk); default: the whole array.
 static bool jacobi_sweep_lds(const float *in, const float *div, float *out, int ni, int nj, int nk, float alpha, float beta, int S,
-                             int k0a = 0, int k1a = 1 << 30, int k0b = 0, int k1b = 0)
+                             int k0a = 0, int k1a = 1 << 30, int k0b = 0, int k1b = 0, const SweepMask *mask = nullptr)
 {
     k0a = std::max(k0a, 0); k1a = std::min(k1a, nk); k0b = std::max(k0b, 0); k1b = std::min(k1b, nk);
     const int lenA = std::max(k1a - k0a, 0), lenB = std::max(k1b - k0b, 0);
@@ -1725,6 +1804,8 @@ static bool jacobi_sweep_lds(const float *in, const float *div, float *out, int 
     // parked on waitcnt / barrier 40 % and stalled at issue 33 % (the L1 path: with the prefetch last the stall moves to the
     // barrier) -- VALU, LDS and L1 path are each 25-40 % busy but take turns between the barriers.
     // rows of 260 .. 512 floats: the two-segment kernel (three sweeps only), 8 output rows per block
+    if (mask && !(S == 3 && ni <= 256 && rt().opt_jacobi_kchunk != 24 && rt().opt_jacobi_kchunk != 25 && rt().opt_jacobi_kchunk != 26 &&
+                  rt().opt_jacobi_kchunk != 19)) return false;           // masked: the default three-sweep shape only
     if (S == 3 && ni > 256 && ni <= 512 && ni % 4 == 0 && nj >= 8 && nk >= 12 && aligned16(in) && aligned16(div) && aligned16(out) &&
         g_klo == 0 && g_khi >= nk && (double)ni * nj * nk * 4.0 < 2147483648.0) {
         constexpr int LW = 8;
@@ -1757,7 +1838,13 @@ static bool jacobi_sweep_lds(const float *in, const float *div, float *out, int 
     const int nbz = rg.nchA + chunks_of(lenB, kc);
     const int nblk = nby * nbz, grid = 8 * ((nblk + 7) / 8);
     hipStream_t st = rt().compute;
-#define BQ_LDS(WV, RV, SV) jacobi_lds_kernel<WV, RV, SV><<<grid, (WV + 2 * ((SV - 1 + RV - 1) / RV)) * 64, 0, st>>>(in, div, out, ni, nj, nk, nby, nblk, kc, alpha, beta, slab_of(nk), rg)
+#define BQ_LDS(WV, RV, SV) jacobi_lds_kernel<WV, RV, SV><<<grid, (WV + 2 * ((SV - 1 + RV - 1) / RV)) * 64, 0, st>>>(in, div, out, ni, nj, nk, nby, nblk, kc, alpha, beta, slab_of(nk), rg, SweepMask{})
+    if (mask) {
+        jacobi_lds_kernel<8, 1, 3, true><<<grid, (8 + 2 * 2) * 64, 0, st>>>(in, div, out, ni, nj, nk, nby, nblk, kc, alpha, beta, slab_of(nk), rg, *mask);
+        BQ_LAUNCH_CHECK("jacobi_lds_kernel<masked>");
+        g_last_pair_kernel = "jacobi_lds3_masked_kernel";
+        return true;
+    }
     if (S == 4) {
         if (shape == 24) BQ_LDS(4, 2, 4); else BQ_LDS(6, 1, 4);      // (18 with four sweeps: 6 single rows + 6 halo waves)
     } else {
@@ -1769,6 +1856,15 @@ static bool jacobi_sweep_lds(const float *in, const float *div, float *out, int 
     BQ_LAUNCH_CHECK("jacobi_lds_kernel");
     g_last_pair_kernel = S == 4 ? "jacobi_lds_kernel<4 sweeps>" : "jacobi_lds3_kernel";
     return true;
+}
+
+// Three MASKED sweeps in one launch (bq_obstacle.hip: gpu_jacobi_sweeps_masked); false = not applicable, nothing launched
+bool jacobi_sweep_triple_masked(const float *in, const float *div, float *out, int ni, int nj, int nk, float alpha,
+                                const unsigned char *solid, const unsigned char *rows, const float betas[7])
+{
+    if (ni < 3 || nj < 4 || nk < 3 || rt().slab_on) return false;
+    const SweepMask mk{solid, rows, betas[0], betas[1], betas[2], betas[3], betas[4], betas[5], betas[6]};
+    return jacobi_sweep_lds(in, div, out, ni, nj, nk, alpha, betas[0], 3, 0, 1 << 30, 0, 0, &mk);
 }
 
 // Four sweeps in one launch (jacobi_lds_kernel<.., 4>): on request only for now (FL_OPT_JACOBI_ROWS = 6)

@@ -18,6 +18,15 @@
 #include <cstdlib>
 #include <cstring>
 
+// The obstacle operators are weak references: the CPU stand-ins of the operator ABI that the host tests link against need
+// not provide them (the references resolve to null there), and setBoundary refuses obstacles when they are missing.
+#pragma weak gpu_obstacle_flags
+#pragma weak gpu_obstacle_faces
+#pragma weak gpu_jacobi_sweeps_masked
+#pragma weak gpu_gradient_masked
+#pragma weak gpu_semilag_band
+#pragma weak gpu_obstacle_blend
+
 namespace bqhost {
 
 // BQ_TRACE=1 (debug): after each stage print the sum of squares of the planes this rank owns, so a
@@ -206,6 +215,7 @@ void BimocqGPUSolver::advanceReflection(int framenum, float dt)
         fl_memcpy_d2d(*scal[a], *tmp[a], n * sizeof(float));
         gs.produced(*scal[a], tmp[a]->valid);
     }
+    if (!boundaries.empty()) blendBoundary(false);        // clearBoundary (BimocqSolver.cpp:406)
     // :267-287
     semilagVelocity(VelocityUTemp, VelocityVTemp, VelocityWTemp, VelocityU, VelocityV, VelocityW, -0.5f * dt);
     semilagVelocity(TempSrcU, TempSrcV, TempSrcW, VelocityUTemp, VelocityVTemp, VelocityWTemp, 0.5f * dt);
@@ -447,6 +457,129 @@ std::vector<double> BimocqGPUSolver::mgHistory() const
     return h;
 }
 
+// setBoundary (BimocqSolver.cpp:936-1064 without the domain walls): the list replaces the previous one, the flags are built
+// at the given centres.  n = 0 removes every obstacle and the step is exactly the one without this feature.
+bool BimocqGPUSolver::setBoundary(const bq_boundary *b, int n)
+{
+    if (n < 0 || n > BQ_MAX_BOUNDARIES || (n > 0 && !b)) {
+        fl_report_error(FL_ERR_BAD_ARGUMENT, "setBoundary: 0 .. 16 obstacles");
+        return false;
+    }
+    if (n == 0) {
+        boundaries.clear();
+        solid.release();
+        rows.release();
+        return true;
+    }
+    if (GpuSolver->slab.on) {
+        fl_report_error(FL_ERR_UNSUPPORTED, "setBoundary: obstacles are not supported on z-slab ranks");
+        return false;
+    }
+    if (projection_kind != BQ_PROJECTION_JACOBI) {
+        fl_report_error(FL_ERR_UNSUPPORTED, "setBoundary: obstacles need the Jacobi projection (not BQ_PROJECTION_MGCG)");
+        return false;
+    }
+    if (!gpu_obstacle_flags || !gpu_obstacle_faces || !gpu_jacobi_sweeps_masked || !gpu_gradient_masked || !gpu_semilag_band ||
+        !gpu_obstacle_blend) {
+        fl_report_error(FL_ERR_UNSUPPORTED, "setBoundary: the operator library has no obstacle operators");
+        return false;
+    }
+    for (int o = 0; o < n; o++) {
+        const bq_boundary &x = b[o];
+        const bool sphere = x.shape == BQ_SHAPE_SPHERE;
+        if ((!sphere && x.shape != BQ_SHAPE_BOX) || !(x.rx > 0.f) || (!sphere && !(x.ry > 0.f && x.rz > 0.f)) ||
+            !std::isfinite(x.cx) || !std::isfinite(x.cy) || !std::isfinite(x.cz) || !std::isfinite(x.rx) ||
+            !std::isfinite(x.ry) || !std::isfinite(x.rz) || !std::isfinite(x.vx) || !std::isfinite(x.vy) || !std::isfinite(x.vz)) {
+            fl_report_error(FL_ERR_BAD_ARGUMENT, "setBoundary: unknown shape, non-positive size or non-finite value");
+            return false;
+        }
+    }
+    const size_t nrows = (size_t)g.nj * (size_t)g.nk;
+    if (solid.bytes() != g.n() && !solid.alloc(g.n())) return false;
+    if (rows.bytes() != nrows && !rows.alloc(nrows)) return false;
+    std::vector<bq_boundary> list(b, b + n);
+    if (!buildFlags(list)) return false;
+    boundaries.swap(list);
+    return true;
+}
+
+// the flags of `list`; on failure the obstacles are dropped (no step may run on flags that were never built)
+bool BimocqGPUSolver::buildFlags(const std::vector<bq_boundary> &list)
+{
+    gpu_obstacle_flags(solid.u8(), rows.u8(), list.data(), (int)list.size(), CellSize, g.ni, g.nj, g.nk);
+    if (fl_last_error() == FL_OK) return true;
+    boundaries.clear();
+    solid.release();
+    rows.release();
+    return false;
+}
+
+// updateBoundary: Boundary::update (BimocqSolver.h:71-73, b_pos += vel_func(framenum) * dt) with the velocity of the list,
+// then the flags at the new centres
+bool BimocqGPUSolver::updateBoundary(int /*framenum*/, float dt)
+{
+    if (boundaries.empty()) return true;
+    std::vector<bq_boundary> list = boundaries;
+    for (bq_boundary &b : list) {
+        b.cx += b.vx * dt;
+        b.cy += b.vy * dt;
+        b.cz += b.vz * dt;
+    }
+    if (!buildFlags(list)) return false;
+    boundaries.swap(list);
+    return true;
+}
+
+// the semi-Lagrangian values of blendBoundary (BimocqSolver.cpp:106): u, v, w, rho, T traced back over dt, at band nodes only,
+// into scratch fields the step does not read before the blend consumes them
+void BimocqGPUSolver::semilagBand(float cfldt, float dt)
+{
+    gpuMapper &gs = *GpuSolver;
+    for (DeviceField *f : { &DensityTemp, &TemperatureTemp })
+        if (!f->get() && !gs.allocField(*f, FIELD_S)) return;
+    const bq_boundary *b = boundaries.data();
+    const int n = (int)boundaries.size(), ni = g.ni, nj = g.nj, nk = g.nk;
+    const float h = CellSize;
+    gpu_semilag_band(TempSrcU, VelocityU, VelocityU, VelocityV, VelocityW, 1, 0, 0, h, ni, nj, nk, cfldt, -dt, b, n);
+    gpu_semilag_band(TempSrcV, VelocityV, VelocityU, VelocityV, VelocityW, 0, 1, 0, h, ni, nj, nk, cfldt, -dt, b, n);
+    gpu_semilag_band(TempSrcW, VelocityW, VelocityU, VelocityV, VelocityW, 0, 0, 1, h, ni, nj, nk, cfldt, -dt, b, n);
+    gpu_semilag_band(DensityTemp, Density, VelocityU, VelocityV, VelocityW, 0, 0, 0, h, ni, nj, nk, cfldt, -dt, b, n);
+    gpu_semilag_band(TemperatureTemp, Temperature, VelocityU, VelocityV, VelocityW, 0, 0, 0, h, ni, nj, nk, cfldt, -dt, b, n);
+}
+
+// blendBoundary (:879-912) of all five fields from semilagBand's values + clearBoundary (:914-934) of rho; band = false:
+// the clear only (the reflection scheme has no blend)
+void BimocqGPUSolver::blendBoundary(bool band)
+{
+    const bq_boundary *b = boundaries.data();
+    if (band)
+        gpu_obstacle_blend(VelocityU, VelocityV, VelocityW, Density, Temperature, TempSrcU, TempSrcV, TempSrcW, DensityTemp,
+                           TemperatureTemp, solid.u8(), b, (int)boundaries.size(), CellSize, g.ni, g.nj, g.nk);
+    else
+        gpu_obstacle_blend(nullptr, nullptr, nullptr, Density, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                           solid.u8(), b, (int)boundaries.size(), CellSize, g.ni, g.nj, g.nk);
+}
+
+// the Jacobi projection with obstacles (:1120-1413): solid faces take the obstacle velocity (with_delta: its share of
+// d*Proj), divergence as always, iter-1 masked sweeps, gradient on the faces between fluid cells only
+bool BimocqGPUSolver::projectionObstacles(bool with_delta)
+{
+    const float alpha = -1.f, beta = (float)(1.0 / 6.0);
+    float *du = with_delta ? duProj.get() : nullptr, *dv = with_delta ? dvProj.get() : nullptr, *dw = with_delta ? dwProj.get() : nullptr;
+    div.zero(); p.zero(); p_temp.zero();
+    gpu_obstacle_faces(VelocityU, VelocityV, VelocityW, du, dv, dw, solid.u8(), boundaries.data(), (int)boundaries.size(), g.ni, g.nj, g.nk);
+    gpu_divergence(VelocityU, VelocityV, VelocityW, div, g.ni, g.nj, g.nk, halfrdx);
+    // p and p_temp carry the same (zero) boundary layer and +0 in every solid cell: three masked sweeps per launch
+    const int fuse_was = fl_get_option(FL_OPT_JACOBI_FUSE);
+    if (fuse_was == 1) fl_set_option(FL_OPT_JACOBI_FUSE, 2);
+    const int where = jacobi_iters > 1 ? gpu_jacobi_sweeps_masked(p, div, p_temp, solid.u8(), rows.u8(), g.ni, g.nj, g.nk,
+                                                                  jacobi_iters - 1, alpha, beta) : 0;
+    fl_set_option(FL_OPT_JACOBI_FUSE, fuse_was);
+    if (where) p.swap(p_temp);
+    gpu_gradient_masked(VelocityU, VelocityV, VelocityW, p, du, dv, dw, solid.u8(), g.ni, g.nj, g.nk, halfrdx);
+    return with_delta;
+}
+
 // with_delta: d*Proj = (projected - unprojected) velocity comes out of the gradient pass itself
 // (gpu_gradient_delta) instead of a snapshot before and a subtraction after; Jacobi branch only (returns
 // whether it did).
@@ -467,6 +600,7 @@ bool BimocqGPUSolver::projection(bool with_delta)
                                           mg.levels.data(), (int)mg.levels.size(), mg_iters, (double)halfrdx);
         return false;
     }
+    if (!boundaries.empty()) return projectionObstacles(with_delta);   // (setBoundary admits one GPU + Jacobi only)
     if (!gs.slab.on || gs.slab.nranks <= 1) {
         if (!with_delta) {
             gs.projectionJacobi(VelocityU, VelocityV, VelocityW, div, p, p_temp, debugParam, jacobi_iters, halfrdx, alpha, beta);
@@ -720,10 +854,12 @@ void BimocqGPUSolver::advanceBimocq(int framenum, float dt)
     phaseMark(PH_ADVECT);
 
     // :143-145
+    if (!boundaries.empty()) semilagBand(cfldt, dt);      // BimocqSolver.cpp:106 (band nodes only)
     VelocityAdvector.advectVelocity(VelocityU, VelocityV, VelocityW, VelocityUInit, VelocityVInit, VelocityWInit,
                                     VelocityUPrev, VelocityVPrev, VelocityWPrev);
     // density and temperature live on the same nodes and use the same maps: batched (one map look-up)
     ScalarAdvector.advectFields2(Density, DensityInit, DensityPrev, Temperature, TemperatureInit, TemperaturePrev);
+    if (!boundaries.empty()) blendBoundary(true);         // BimocqSolver.cpp:121-125 + clearBoundary (:134)
     const bool policy1 = reinit_policy == 1;
     trace_stage(*this, "advect", framenum);
     phaseMark(PH_FORCES);

@@ -119,6 +119,17 @@ public:
     bool mgcg_shared_ran = false;                   // the last MGCG projection on slabs took the shared path
     std::vector<double> mgHistory() const;          // tempResult (4096 doubles), downloaded
 
+    // Solid obstacles (setBoundary / updateBoundary, BimocqSolver.cpp:936-1064).  Jacobi projection on
+    // one GPU only.  With an empty list a step issues exactly the launches it issues without this feature.
+    std::vector<bq_boundary> boundaries;
+    DeviceBytes solid, rows;                        // cell flags (0 fluid, o + 1 solid by obstacle o), rows summary (include/bimocq_gpu.h)
+    bool setBoundary(const bq_boundary *b, int n);
+    bool updateBoundary(int framenum, float dt);
+    bool buildFlags(const std::vector<bq_boundary> &list);
+    bool projectionObstacles(bool with_delta);
+    void blendBoundary(bool band);                  // band: blendBoundary + clearBoundary, else clearBoundary only
+    void semilagBand(float cfldt, float dt);
+
     std::vector<float> host_density, host_u, host_v, host_w;    // outputResult staging (:538-541)
 
     gpuMapper *GpuSolver;

@@ -37,6 +37,7 @@ public:
     bool alloc(size_t bytes) { release(); p_ = fl_malloc(bytes ? bytes : 8); n_ = p_ ? bytes : 0; return p_ != nullptr; }
     void release() { if (p_) fl_free(p_); p_ = nullptr; n_ = 0; }
     double *f64() const { return static_cast<double *>(p_); }
+    unsigned char *u8() const { return static_cast<unsigned char *>(p_); }
     size_t bytes() const { return n_; }
 private:
     void *p_ = nullptr;

@@ -75,6 +75,10 @@ void bq_solver_set_smoke(bq_solver *s, float drop, float rise, const bq_emitter 
 void bq_solver_set_projection(bq_solver *s, int kind, int iters, float halfrdx)
 {
     if (!s) return;
+    if (kind == BQ_PROJECTION_MGCG && !s->solver->boundaries.empty()) {
+        fl_report_error(FL_ERR_UNSUPPORTED, "bq_solver_set_projection: obstacles need the Jacobi projection");
+        return;
+    }
     if (kind == BQ_PROJECTION_MGCG) {
         s->solver->projection_kind = kind;
         s->solver->mg_iters = iters;
@@ -202,6 +206,37 @@ long bq_solver_download(bq_solver *s, int which, float *host, long capacity)
     long count = (long)f[which]->count();
     if (host && capacity > 0)
         fl_memcpy_d2h(host, f[which]->get(), (size_t)std::min(count, capacity) * sizeof(float));
+    return count;
+}
+
+int bq_solver_set_boundary(bq_solver *s, const bq_boundary *b, int n)
+{
+    BQ_ENTER(s);
+    if (!s) return -1;
+    return s->solver->setBoundary(b, n) ? 0 : -1;
+}
+
+int bq_solver_update_boundary(bq_solver *s, int framenum, float dt)
+{
+    BQ_ENTER(s);
+    if (!s) return -1;
+    return s->solver->updateBoundary(framenum, dt) ? 0 : -1;
+}
+
+long bq_solver_download_solid(bq_solver *s, unsigned char *host, long capacity)
+{
+    BQ_ENTER(s);
+    if (!s) return 0;
+    BimocqGPUSolver &b = *s->solver;
+    const long count = (long)b.g.n();
+    if (!host || capacity <= 0) return count;
+    const size_t m = (size_t)std::min(count, capacity);
+    if (b.boundaries.empty()) {
+        std::fill(host, host + m, (unsigned char)0);
+        return count;
+    }
+    fl_memcpy_d2h(host, b.solid.u8(), m);
+    for (size_t a = 0; a < m; a++) host[a] = host[a] ? 1 : 0;
     return count;
 }
 

@@ -20,6 +20,26 @@ class Emitter(C.Structure):
                 ("emit_frames", C.c_int)]
 
 
+SHAPE_SPHERE, SHAPE_BOX = 0, 1
+MAX_BOUNDARIES = 16
+
+
+class Boundary(C.Structure):
+    """bq_boundary: shape, centre, radius (sphere: rx) or half extents (box), velocity"""
+    _fields_ = [("shape", C.c_int), ("cx", C.c_float), ("cy", C.c_float), ("cz", C.c_float),
+                ("rx", C.c_float), ("ry", C.c_float), ("rz", C.c_float),
+                ("vx", C.c_float), ("vy", C.c_float), ("vz", C.c_float)]
+
+
+def boundary_array(boundaries):
+    """(Boundary array, count) from Boundary objects or tuples (shape, cx, cy, cz, rx, ry, rz, vx, vy, vz)"""
+    boundaries = list(boundaries)
+    arr = (Boundary * max(1, len(boundaries)))()
+    for i, b in enumerate(boundaries):
+        arr[i] = b if isinstance(b, Boundary) else Boundary(*b)
+    return arr, len(boundaries)
+
+
 HOST_SIGS = {
     "bq_solver_create": (C.c_void_p, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int]),
     "bq_solver_create_slab": (C.c_void_p, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int,
@@ -42,6 +62,9 @@ HOST_SIGS = {
     "bq_solver_last_ms": (C.c_float, [C.c_void_p]),
     "bq_solver_reinit_count": (C.c_int, [C.c_void_p]),
     "bq_solver_phase_ms": (C.c_longlong, [C.c_void_p, C.POINTER(C.c_double), C.c_int]),
+    "bq_solver_set_boundary": (C.c_int, [C.c_void_p, C.POINTER(Boundary), C.c_int]),
+    "bq_solver_update_boundary": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
+    "bq_solver_download_solid": (C.c_long, [C.c_void_p, C.c_void_p, C.c_long]),
 }
 PHASES = ("maps", "advect_compensate", "forces", "projection", "accumulate_reinit")
 
@@ -142,6 +165,30 @@ class BimocqGPUSolver:
 
     def lastDistortion(self):
         return self.lib.bq_solver_last_distortion(self.s, 0), self.lib.bq_solver_last_distortion(self.s, 1)
+
+    def setBoundary(self, boundaries):
+        """setBoundary: replaces the obstacle list (Boundary objects or (shape, cx, cy, cz, rx, ry, rz, vx, vy, vz)
+        tuples; [] removes every obstacle) and builds the cell flags at the given centres.  One GPU, Jacobi only."""
+        arr, n = boundary_array(boundaries)
+        rc = self.lib.bq_solver_set_boundary(self.s, arr, n)
+        self._check()
+        if rc != 0:
+            raise _lib.BimocqError("bq_solver_set_boundary failed")
+
+    def updateBoundary(self, framenum, dt):
+        """updateBoundary: every centre moves by v * dt, then the flags are rebuilt"""
+        rc = self.lib.bq_solver_update_boundary(self.s, framenum, dt)
+        self._check()
+        if rc != 0:
+            raise _lib.BimocqError("bq_solver_update_boundary failed")
+
+    def solidMask(self):
+        """cell flags, 1 = obstacle, as a (nz, ny, nx) uint8 array"""
+        count = self.lib.bq_solver_download_solid(self.s, None, 0)
+        out = np.zeros(count, dtype=np.uint8)
+        self.lib.bq_solver_download_solid(self.s, out.ctypes.data, count)
+        self._check()
+        return out.reshape(self.nk_local, self.ny, self.nx)
 
     def advance(self, framenum, dt):
         self.lib.bq_solver_advance(self.s, framenum, dt)

@@ -636,6 +636,56 @@ void gpu_advect_field_double_global(float *field, float *field_prev_global,
                                     float *backward_xprev, float *backward_yprev, float *backward_zprev,
                                     float h, int ni, int nj, int nk, bool is_point, float blend_coeff);
 
+/* ---- solid obstacles ------------------------------------------------------------------------
+ * Analytic obstacles, classified by squared distances at the reference CPU solver's sample positions: cell (i,j,k) at
+ * (i h, j h, k h), the u face at ((i - 1/2) h, j h, k h), v and w likewise.  `solid`: one byte per cell, 0 = fluid,
+ * o + 1 = solid, made so by obstacle o (the last obstacle in the list that covers the cell).  `rows`: the rows summary of
+ * the masked sweeps, one byte per (row j, plane k) (nj * nk bytes, j fastest), 1 when a solid cell lies in rows j-1 .. j+1
+ * of planes k-1 .. k+1.  At most BQ_MAX_BOUNDARIES obstacles; the list is passed by host pointer.  Single GPU. */
+#ifndef BQ_BOUNDARY_DEFINED
+#define BQ_BOUNDARY_DEFINED
+enum { BQ_SHAPE_SPHERE = 0, BQ_SHAPE_BOX = 1 };
+enum { BQ_MAX_BOUNDARIES = 16 };
+typedef struct bq_boundary {
+    int   shape;
+    float cx, cy, cz;        /* centre, world units                                          */
+    float rx, ry, rz;        /* sphere: radius in rx; box: half extents                      */
+    float vx, vy, vz;        /* velocity: the solid face velocity, and the motion per update */
+} bq_boundary;
+#endif
+/* cell flags and rows summary of the obstacles at their current centres (one launch after a clear of `rows`) */
+void gpu_obstacle_flags(unsigned char *solid, unsigned char *rows, const bq_boundary *b, int n, float h,
+                        int ni, int nj, int nk);
+/* every face of a solid cell takes the velocity of the obstacle that owns it (the later of the two cells' owners);
+ * where du/dv/dw are non-NULL they receive obstacle velocity - previous value on those faces (the d*Proj share of the
+ * face write) and are left alone elsewhere */
+void gpu_obstacle_faces(float *u, float *v, float *w, float *du, float *dv, float *dw, const unsigned char *solid,
+                        const bq_boundary *b, int n, int ni, int nj, int nk);
+/* one masked Jacobi sweep in -> out: interior fluid cells with s solid neighbours take today's sum times
+ * beta_s = (float)(1 / (1/(double)beta - s)) (beta_0 = beta; s = 6: 0); solid and boundary cells are not written.
+ * Cells whose rows summary is 0 run today's expression without reading the flags. */
+void gpu_jacobi_sweep_masked(const float *in, const float *div, float *out, const unsigned char *solid,
+                             const unsigned char *rows, int ni, int nj, int nk, float alpha, float beta);
+/* `sweeps` masked sweeps ping-ponging p <-> p_temp from p; returns 0 when the newest iterate ends in p, 1 in p_temp.
+ * With FL_OPT_JACOBI_FUSE = 2 (the caller vouches that p and p_temp carry the same boundary layer and the same values in
+ * solid cells) three sweeps per launch through the masked form of the LDS three-sweep kernel (rows of 32 .. 256 floats,
+ * ni % 4 == 0): a block with no solid cell within three cells of its outputs runs the unmasked instruction stream. */
+int  gpu_jacobi_sweeps_masked(float *p, const float *div, float *p_temp, const unsigned char *solid,
+                              const unsigned char *rows, int ni, int nj, int nk, int sweeps, float alpha, float beta);
+/* gpu_gradient_delta (du != NULL) or gpu_gradient (du == NULL) that leaves every face with a solid cell on either side
+ * alone: velocity and delta keep what gpu_obstacle_faces wrote */
+void gpu_gradient_masked(float *u, float *v, float *w, const float *p, float *du, float *dv, float *dw,
+                         const unsigned char *solid, int ni, int nj, int nk, float halfrdx);
+/* gpu_semilag at the band nodes of the obstacles only (0 < distance outside the surface < 3 h, no obstacle covering the
+ * node): there the same value gpu_semilag writes into a cleared field; every other node is left alone */
+void gpu_semilag_band(float *field, float *field_src, float *u, float *v, float *w, int dim_x, int dim_y, int dim_z,
+                      float h, int ni, int nj, int nk, float cfldt, float dt, const bq_boundary *b, int n);
+/* blendBoundary + clearBoundary in one launch: at band nodes u, v, w, rho, T take the values of us, vs, ws, rhos, Ts
+ * (skipped when us == NULL), then rho = 0 in solid cells */
+void gpu_obstacle_blend(float *u, float *v, float *w, float *rho, float *T, const float *us, const float *vs,
+                        const float *ws, const float *rhos, const float *Ts, const unsigned char *solid,
+                        const bq_boundary *b, int n, float h, int ni, int nj, int nk);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,8 @@
 #ifndef BIMOCQ_SOLVER_H
 #define BIMOCQ_SOLVER_H
 
+#include "bimocq_gpu.h"        /* bq_boundary */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -159,6 +161,14 @@ long  bq_solver_mg_history(const bq_solver *s, double *host, long capacity);
  * the first).  _wait returns the voxel count of the last asynchronous dump, or -1. */
 int   bq_solver_output_result_async(bq_solver *s, unsigned frame, const char *path);
 long  bq_solver_output_wait(bq_solver *s);
+/* Solid obstacles (setBoundary / updateBoundary, BimocqSolver.cpp:936-1064).  set_boundary
+ * replaces the whole list (n = 0 removes every obstacle; at most BQ_MAX_BOUNDARIES) and builds the cell flags at the
+ * given centres; update_boundary moves every centre by v * dt (Boundary::update) and rebuilds them.  Jacobi projection
+ * on one GPU only: z-slab ranks and BQ_PROJECTION_MGCG are refused through fl_last_error.  Returns 0 on success.
+ * download_solid copies min(cells, capacity) flags (1 = obstacle) and returns the cell count. */
+int   bq_solver_set_boundary(bq_solver *s, const bq_boundary *b, int n);
+int   bq_solver_update_boundary(bq_solver *s, int framenum, float dt);
+long  bq_solver_download_solid(bq_solver *s, unsigned char *host, long capacity);
 float bq_solver_last_cfldt(const bq_solver *s);
 float bq_solver_last_ms(const bq_solver *s);          /* event time of the last advance()        */
 int   bq_solver_reinit_count(const bq_solver *s);
