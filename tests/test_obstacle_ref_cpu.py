@@ -1,0 +1,132 @@
+"""The fp64 obstacle reference (tests/obstacle_ref.py) checked on its own and against the two float32 restatements: its
+masked Jacobi converges to scipy's solution of the Neumann system, and on every mask family of the GPU edge tests the
+C restatement (tests/cpu_abi/obstacle_abi.c) and tests/obstacle_case.py stay within the derived float32 bound of it;
+flags, rows and face owners agree exactly away from near ties.  No GPU."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import fields as F
+import obstacle_case as OC
+import obstacle_ref as R
+from build_cpu_host_obstacles import build as build_obstacles
+
+SHAPES = [(32, 8, 12), (36, 13, 13), (252, 17, 40), (256, 24, 27), (99, 21, 18), (384, 12, 14), (40, 5, 16), (40, 16, 11)]
+FLAG_DIMS = [(99, 37, 23), (48, 40, 36), (64, 21, 30)]
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from gpufluidsimulation_amd import solver, _lib
+    lib = solver.bind_host(C.CDLL(build_obstacles(), mode=C.RTLD_LOCAL))
+    OC.bind_errors(lib)
+    for name in ("gpu_obstacle_flags", "gpu_obstacle_faces", "gpu_jacobi_sweep_masked"):
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = _lib.HIP_SIGS[name]
+    return lib
+
+
+def test_masked_jacobi_converges_to_the_neumann_solution():
+    """16^3 with a box, a wall-cut slab and scattered cells; every fluid region touches the Dirichlet border"""
+    import scipy.ndimage as ndi
+    import scipy.sparse.linalg as spla
+    n = 16
+    dims = (n, n, n)
+    cells = [(i, j, k) for i in range(5, 9) for j in range(6, 11) for k in range(4, 8)]
+    cells += [(i, j, 12) for i in range(0, 6) for j in range(3, 14)]                    # touches the x = 0 wall
+    rng = np.random.default_rng(3)
+    cells += [tuple(int(c) for c in rng.integers(1, n - 1, 3)) for _ in range(60)]
+    cells += [(2, 3, 3), (4, 3, 3), (3, 2, 3), (3, 4, 3), (3, 3, 2)]                  # fluid (3, 3, 3): s = 5, open upwards
+    solid = R.mask_from_cells(dims, cells)
+    fluid_lab, nlab = ndi.label(solid == 0)
+    border = np.ones(solid.shape, bool)
+    border[1:-1, 1:-1, 1:-1] = False
+    assert set(np.unique(fluid_lab[border & (solid == 0)])) >= set(range(1, nlab + 1)), "a fluid pocket without border"
+    s = R.neighbour_count(solid)[solid[1:-1, 1:-1, 1:-1] == 0]
+    assert s.max() == 5 and (s == 0).any()
+    div = np.random.default_rng(4).standard_normal(solid.shape)
+    A, b, unk = R.neumann_system(div, solid)
+    x = spla.spsolve(A.tocsc(), b)
+    p = np.zeros(solid.shape)
+    for it in range(20000):
+        q, _ = R.masked_sweep(p, div, solid)
+        step = np.abs(q - p).max()
+        p = q
+        if step < 1e-14:
+            break
+    assert step < 1e-14, f"no convergence after {it + 1} sweeps"
+    assert np.allclose(p[unk], x, rtol=0, atol=1e-11 * np.abs(x).max())
+    assert np.all(p[solid != 0] == 0) and np.all(p[border] == 0)
+
+
+@pytest.mark.parametrize("dims", SHAPES)
+def test_restatements_within_the_bound_of_the_reference(lib, dims):
+    ni, nj, nk = dims
+    beta = R.beta32()
+    fams = R.mask_families(dims)
+    assert (nj <= 8 or any(name.startswith("row") for name, _ in fams)) and any(name.startswith("i = 3") for name, _ in fams)
+    for seed, (name, solid) in enumerate(fams):
+        rows = R.rows_of(solid)
+        p = R.initial_p(solid, seed)
+        div = np.random.default_rng(100 + seed).standard_normal(solid.shape).astype(np.float32)
+        its, bounds = R.masked_sweeps(p, div, solid, 7)
+        a, b = p.copy(), p.copy()
+        o = p.copy()
+        for n in range(7):
+            lib.gpu_jacobi_sweep_masked(a.ctypes.data, div.ctypes.data, b.ctypes.data, solid.ctypes.data, rows.ctypes.data,
+                                        ni, nj, nk, R.ALPHA, beta)
+            o = OC.masked_sweep(o, div, solid, R.ALPHA, np.float32(beta))
+            assert np.array_equal(b, o), (name, n)
+            err = np.abs(b - its[n]).max()
+            assert err <= bounds[n], (name, n, err, bounds[n])
+            a, b = b, a
+        assert np.all(a[solid != 0] == 0)
+    codes = R.codes(fams[-1][1])
+    assert set(np.unique(codes[codes < 7])) == set(range(7)), "random mask: some code s = 0 .. 6 missing"
+
+
+@pytest.mark.parametrize("dims", FLAG_DIMS)
+def test_flags_rows_and_face_owners_match_the_geometry(lib, dims):
+    from gpufluidsimulation_amd.solver import boundary_array
+    ni, nj, nk = dims
+    h, bnd = R.edge_scene(dims)
+    arr, n = boundary_array(bnd)
+    solid = np.zeros((nk, nj, ni), np.uint8)
+    rows = np.zeros(nj * nk, np.uint8)
+    lib.gpu_obstacle_flags(solid.ctypes.data, rows.ctypes.data, C.addressof(arr), n, h, ni, nj, nk)
+    flag, tie = R.classify(bnd, h, (nk, nj, ni))
+    assert tie.mean() < 1e-3
+    assert np.array_equal(solid[~tie], np.maximum(flag, 0)[~tie])
+    assert set(np.unique(flag)) == {-1, 0, 1, 2, 3, 4}
+    ok = ~R.rows_tie(tie)
+    assert np.array_equal(rows.reshape(nk, nj)[ok], R.rows_of(np.maximum(flag, 0))[ok])
+    assert np.array_equal(rows.reshape(nk, nj), R.rows_of(solid))
+    # obstacle_case.py classifies in float32 like the kernels: the same flags, band included, at every node
+    for stag in ((0, 0, 0), (1, 0, 0), (0, 1, 0), (0, 0, 1)):
+        shape = (nk + stag[2], nj + stag[1], ni + stag[0])
+        want, t = R.classify(bnd, h, shape, stag)
+        got = OC.classify(bnd, h, shape, stag)
+        assert np.array_equal(got[~t], want[~t]), stag
+    # solid faces: the owner's velocity (the later obstacle where two meet), its share of the delta
+    u, v, w = F.velocity(ni, nj, nk, h)
+    hu, hv, hw = u.copy(), v.copy(), w.copy()
+    du, dv, dw = (np.full_like(x, 9.0) for x in (u, v, w))
+    lib.gpu_obstacle_faces(hu.ctypes.data, hv.ctypes.data, hw.ctypes.data, du.ctypes.data, dv.ctypes.data, dw.ctypes.data,
+                           solid.ctypes.data, C.addressof(arr), n, ni, nj, nk)
+    shapes = ((nk, nj, ni + 1), (nk, nj + 1, ni), (nk + 1, nj, ni))
+    ref = R.solid_faces(*(x.reshape(s) for x, s in zip((u, v, w), shapes)), flag, bnd)
+    tie_faces = R.face_owners(tie.astype(np.int32))
+    shared = 0
+    for comp, (got, d, s) in enumerate(zip((hu, hv, hw), (du, dv, dw), shapes)):
+        got, d, ok = got.reshape(s), d.reshape(s), tie_faces[comp] == 0
+        assert np.array_equal(got[ok], ref[comp][ok].astype(np.float32)), comp
+        dref = ref[3 + comp]
+        solid_face = ok & ~np.isnan(dref)
+        assert np.array_equal(d[solid_face], dref[solid_face].astype(np.float32)), comp
+        assert np.all(d[ok & np.isnan(dref)] == 9.0)
+        lo, hi = R.face_cells(flag, comp)
+        shared += int(((lo > 0) & (hi > 0) & (lo != hi) & ok).sum())
+    if dims == (48, 40, 36):
+        assert shared > 0, "no face between cells of two different obstacles"
+
