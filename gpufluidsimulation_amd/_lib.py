@@ -144,6 +144,10 @@ HIP_SIGS = {
     "gpu_gradient_masked": (None, [VP] * 8 + [c_i, c_i, c_i, c_f]),
     "gpu_semilag_band": (None, [VP] * 5 + [c_i, c_i, c_i] + _G + [c_f, c_f, VP, c_i]),
     "gpu_obstacle_blend": (None, [VP] * 11 + [VP, c_i] + _G),
+    # level-set obstacles (the bq_levelset array travels as a HOST pointer, its phi device pointers: solver.LevelSetDesc)
+    "gpu_obstacle_flags_ls": (None, [VP, VP, VP, c_i, VP] + _G),
+    "gpu_semilag_band_ls": (None, [VP] * 5 + [c_i, c_i, c_i] + _G + [c_f, c_f, VP, c_i, VP]),
+    "gpu_obstacle_blend_ls": (None, [VP] * 11 + [VP, c_i, VP] + _G),
 }
 
 FL_OK, FL_ERR_NO_DEVICE, FL_ERR_HIP, FL_ERR_BAD_ARGUMENT, FL_ERR_UNSUPPORTED, FL_ERR_COMM = range(6)

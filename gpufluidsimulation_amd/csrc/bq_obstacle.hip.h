@@ -4,6 +4,9 @@
 #include <hip/hip_runtime.h>
 #include "bimocq_gpu.h"
 
+#include <climits>
+#include <cmath>
+
 namespace bq {
 
 struct ObsSet {
@@ -29,13 +32,99 @@ static inline ObsSet make_obs(const bq_boundary *b, int n, float h)
     return s;
 }
 
+// the level sets of a list (entries whose shape is BQ_SHAPE_LEVELSET; the others are left empty): a kernel argument
+struct LsSet {
+    const float *phi[BQ_MAX_BOUNDARIES];
+    int nx[BQ_MAX_BOUNDARIES], ny[BQ_MAX_BOUNDARIES], nz[BQ_MAX_BOUNDARIES];
+    int i0[BQ_MAX_BOUNDARIES], j0[BQ_MAX_BOUNDARIES], k0[BQ_MAX_BOUNDARIES];
+    float voxel[BQ_MAX_BOUNDARIES], bg[BQ_MAX_BOUNDARIES];
+};
+
+static inline LsSet make_ls(const bq_boundary *b, const bq_levelset *ls, int n)
+{
+    LsSet s{};
+    for (int o = 0; o < n; o++) {
+        if (b[o].shape != BQ_SHAPE_LEVELSET) continue;
+        const bq_levelset &l = ls[o];
+        s.phi[o] = l.phi;
+        s.nx[o] = l.nx; s.ny[o] = l.ny; s.nz[o] = l.nz;
+        s.i0[o] = l.i0; s.j0[o] = l.j0; s.k0[o] = l.k0;
+        s.voxel[o] = l.voxel; s.bg[o] = l.background;
+    }
+    return s;
+}
+
+// NULL when every level-set entry of b[0 .. n) has a usable descriptor in ls[], else what is wrong
+static inline const char *ls_check(const bq_boundary *b, const bq_levelset *ls, int n)
+{
+    for (int o = 0; o < n; o++) {
+        if (b[o].shape != BQ_SHAPE_LEVELSET) continue;
+        if (!ls) return "level-set entry without descriptors";
+        const bq_levelset &l = ls[o];
+        if (!l.phi) return "level set with a null grid";
+        if (l.nx < 2 || l.ny < 2 || l.nz < 2 || (double)l.nx * (double)l.ny * (double)l.nz >= 2147483648.0)
+            return "level-set dimensions below 2 or 2^31 nodes and more";
+        if ((long long)l.i0 - 1 < INT_MIN || (long long)l.j0 - 1 < INT_MIN || (long long)l.k0 - 1 < INT_MIN ||
+            (long long)l.i0 + l.nx > INT_MAX || (long long)l.j0 + l.ny > INT_MAX || (long long)l.k0 + l.nz > INT_MAX)
+            return "level-set index range beyond int";
+        if (!(l.voxel > 0.f) || !(l.background > 0.f) || !std::isfinite(l.voxel) || !std::isfinite(l.background))
+            return "level-set voxel or background not finite and positive";
+    }
+    return nullptr;
+}
+
+// p + (q - p) t with the difference and the sum in float and the product in double (BoxSampler's lerp)
+__device__ __forceinline__ float ls_lerp(float p, float q, double t) { return p + (float)((double)(q - p) * t); }
+
+// trilinear sample of level set o at (x, y, z), its index origin at (cx, cy, cz) ("Level sets").
+// false when all eight corners lie outside the stored nodes (the sample is exactly the background there): the exact
+// early-out, taken before any load.  Otherwise corners outside the stored nodes read the background.
+__device__ __forceinline__ bool ls_sample(const LsSet &l, int o, float x, float y, float z, float cx, float cy, float cz,
+                                          float &sdf)
+{
+    const double vox = (double)l.voxel[o];
+    const double gx = ((double)x - (double)cx) / vox, gy = ((double)y - (double)cy) / vox, gz = ((double)z - (double)cz) / vox;
+    const int nx = l.nx[o], ny = l.ny[o], nz = l.nz[o], i0 = l.i0[o], j0 = l.j0[o], k0 = l.k0[o];
+    if (gx < (double)(i0 - 1) || gx >= (double)(i0 + nx) || gy < (double)(j0 - 1) || gy >= (double)(j0 + ny) ||
+        gz < (double)(k0 - 1) || gz >= (double)(k0 + nz))
+        return false;
+    const double fx = floor(gx), fy = floor(gy), fz = floor(gz);
+    const double tx = gx - fx, ty = gy - fy, tz = gz - fz;
+    const int ia = (int)fx - i0, ja = (int)fy - j0, ka = (int)fz - k0;     // corners a = -1 .. n-1 and a + 1
+    const float bg = l.bg[o];
+    const float *phi = l.phi[o];
+    const bool xa = ia >= 0, xb = ia + 1 < nx, ya = ja >= 0, yb = ja + 1 < ny, za = ka >= 0, zb = ka + 1 < nz;
+    const size_t sy = (size_t)nx, sz = (size_t)nx * (size_t)ny;
+    const float *c = phi + (ptrdiff_t)ia + (ptrdiff_t)ja * (ptrdiff_t)sy + (ptrdiff_t)ka * (ptrdiff_t)sz;   // corner (a, a, a)
+    const float v000 = xa && ya && za ? c[0] : bg,           v001 = xa && ya && zb ? c[sz] : bg;
+    const float v010 = xa && yb && za ? c[sy] : bg,          v011 = xa && yb && zb ? c[sy + sz] : bg;
+    const float v100 = xb && ya && za ? c[1] : bg,           v101 = xb && ya && zb ? c[1 + sz] : bg;
+    const float v110 = xb && yb && za ? c[1 + sy] : bg,      v111 = xb && yb && zb ? c[1 + sy + sz] : bg;
+    const float a0 = ls_lerp(ls_lerp(v000, v001, tz), ls_lerp(v010, v011, tz), ty);
+    const float a1 = ls_lerp(ls_lerp(v100, v101, tz), ls_lerp(v110, v111, tz), ty);
+    sdf = ls_lerp(a0, a1, tx);
+    return true;
+}
+
 // o + 1 when obstacle o is the last one covering (x, y, z); -1 when the point lies in the band of some obstacle and
-// inside none; 0 otherwise
-__device__ __forceinline__ int obs_classify(const ObsSet &s, float x, float y, float z)
+// inside none; 0 otherwise.  LS = false: analytic entries only (ls unread); LS = true: level-set entries are sampled,
+// solid when the sample is <= 0, band when 0 < sample < background.
+template <bool LS>
+__device__ __forceinline__ int obs_classify_t(const ObsSet &s, const LsSet *ls, float x, float y, float z)
 {
     int solid = 0;
     bool band = false;
     for (int o = 0; o < s.n; o++) {
+        if constexpr (LS) {
+            if (s.shape[o] == BQ_SHAPE_LEVELSET) {
+                float sdf;
+                if (ls_sample(*ls, o, x, y, z, s.cx[o], s.cy[o], s.cz[o], sdf)) {
+                    if (sdf <= 0.f) solid = o + 1;
+                    else if (sdf < ls->bg[o]) band = true;
+                }
+                continue;
+            }
+        }
         const float dx = x - s.cx[o], dy = y - s.cy[o], dz = z - s.cz[o];
         if (s.shape[o] == BQ_SHAPE_SPHERE) {
             const float d2 = dx * dx + dy * dy + dz * dz;
@@ -55,6 +144,8 @@ __device__ __forceinline__ int obs_classify(const ObsSet &s, float x, float y, f
     }
     return solid ? solid : (band ? -1 : 0);
 }
+
+__device__ __forceinline__ int obs_classify(const ObsSet &s, float x, float y, float z) { return obs_classify_t<false>(s, nullptr, x, y, z); }
 
 // sample position of node i on an axis with stagger d (0: cell centre, 1: face): (i - d/2) h
 __device__ __forceinline__ float obs_pos(int i, int d, float h) { return ((float)i - (d ? 0.5f : 0.f)) * h; }

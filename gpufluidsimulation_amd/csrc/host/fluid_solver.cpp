@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <climits>
 #include <cstdlib>
 #include <cstring>
 
@@ -26,6 +27,9 @@
 #pragma weak gpu_gradient_masked
 #pragma weak gpu_semilag_band
 #pragma weak gpu_obstacle_blend
+#pragma weak gpu_obstacle_flags_ls
+#pragma weak gpu_semilag_band_ls
+#pragma weak gpu_obstacle_blend_ls
 
 namespace bqhost {
 
@@ -466,9 +470,7 @@ bool BimocqGPUSolver::setBoundary(const bq_boundary *b, int n)
         return false;
     }
     if (n == 0) {
-        boundaries.clear();
-        solid.release();
-        rows.release();
+        dropBoundaries();
         return true;
     }
     if (GpuSolver->slab.on) {
@@ -498,19 +500,138 @@ bool BimocqGPUSolver::setBoundary(const bq_boundary *b, int n)
     if (solid.bytes() != g.n() && !solid.alloc(g.n())) return false;
     if (rows.bytes() != nrows && !rows.alloc(nrows)) return false;
     std::vector<bq_boundary> list(b, b + n);
-    if (!buildFlags(list)) return false;
+    if (!buildFlags(list, nullptr)) return false;
     boundaries.swap(list);
+    levelsets.clear();
+    lsgrids.release();
     return true;
 }
 
-// the flags of `list`; on failure the obstacles are dropped (no step may run on flags that were never built)
-bool BimocqGPUSolver::buildFlags(const std::vector<bq_boundary> &list)
+// setBoundary for lists that may hold level sets ("Level sets"): ls[o] is read for the entries of
+// shape BQ_SHAPE_LEVELSET, its phi a HOST array that is copied into one device allocation with every other grid of the
+// list.  Any failure leaves no obstacles at all.
+bool BimocqGPUSolver::setBoundaryLevelsets(const bq_boundary *b, const bq_levelset *ls, int n)
 {
-    gpu_obstacle_flags(solid.u8(), rows.u8(), list.data(), (int)list.size(), CellSize, g.ni, g.nj, g.nk);
-    if (fl_last_error() == FL_OK) return true;
+    if (setBoundaryLevelsetsOrFail(b, ls, n)) return true;
+    dropBoundaries();
+    return false;
+}
+
+bool BimocqGPUSolver::setBoundaryLevelsetsOrFail(const bq_boundary *b, const bq_levelset *ls, int n)
+{
+    bool any = false;
+    for (int o = 0; b && o < n && o < BQ_MAX_BOUNDARIES; o++) any |= b[o].shape == BQ_SHAPE_LEVELSET;
+    if (!any) return setBoundary(b, n);                 // the refusals of n, slab, MGCG and every analytic check
+    if (n > BQ_MAX_BOUNDARIES) {
+        fl_report_error(FL_ERR_BAD_ARGUMENT, "setBoundary: 0 .. 16 obstacles");
+        return false;
+    }
+    if (GpuSolver->slab.on) {
+        fl_report_error(FL_ERR_UNSUPPORTED, "setBoundary: obstacles are not supported on z-slab ranks");
+        return false;
+    }
+    if (projection_kind != BQ_PROJECTION_JACOBI) {
+        fl_report_error(FL_ERR_UNSUPPORTED, "setBoundary: obstacles need the Jacobi projection (not BQ_PROJECTION_MGCG)");
+        return false;
+    }
+    if (!gpu_obstacle_flags || !gpu_obstacle_faces || !gpu_jacobi_sweeps_masked || !gpu_gradient_masked || !gpu_semilag_band ||
+        !gpu_obstacle_blend) {
+        fl_report_error(FL_ERR_UNSUPPORTED, "setBoundary: the operator library has no obstacle operators");
+        return false;
+    }
+    if (!gpu_obstacle_flags_ls || !gpu_semilag_band_ls || !gpu_obstacle_blend_ls) {
+        fl_report_error(FL_ERR_UNSUPPORTED, "setBoundary: the operator library has no level-set obstacle operators");
+        return false;
+    }
+    if (!ls) {
+        fl_report_error(FL_ERR_BAD_ARGUMENT, "setBoundary: level-set entries without descriptors");
+        return false;
+    }
+    const double cap = (double)kMaxLevelsetBytes;
+    double total = 0.0;
+    for (int o = 0; o < n; o++) {
+        const bq_boundary &x = b[o];
+        if (x.shape != BQ_SHAPE_LEVELSET) {
+            const bool sphere = x.shape == BQ_SHAPE_SPHERE;
+            if ((!sphere && x.shape != BQ_SHAPE_BOX) || !(x.rx > 0.f) || (!sphere && !(x.ry > 0.f && x.rz > 0.f)) ||
+                !std::isfinite(x.rx) || !std::isfinite(x.ry) || !std::isfinite(x.rz)) {
+                fl_report_error(FL_ERR_BAD_ARGUMENT, "setBoundary: unknown shape, non-positive size or non-finite value");
+                return false;
+            }
+        }
+        if (!std::isfinite(x.cx) || !std::isfinite(x.cy) || !std::isfinite(x.cz) || !std::isfinite(x.vx) ||
+            !std::isfinite(x.vy) || !std::isfinite(x.vz)) {
+            fl_report_error(FL_ERR_BAD_ARGUMENT, "setBoundary: unknown shape, non-positive size or non-finite value");
+            return false;
+        }
+        if (x.shape != BQ_SHAPE_LEVELSET) continue;
+        const bq_levelset &l = ls[o];
+        const double nodes = (double)l.nx * (double)l.ny * (double)l.nz;
+        if (!l.phi || l.nx < 2 || l.ny < 2 || l.nz < 2 || nodes >= 2147483648.0) {
+            fl_report_error(FL_ERR_BAD_ARGUMENT, "setBoundary: level set without a grid, a dimension below 2 or 2^31 nodes");
+            return false;
+        }
+        if ((long long)l.i0 - 1 < INT_MIN || (long long)l.j0 - 1 < INT_MIN || (long long)l.k0 - 1 < INT_MIN ||
+            (long long)l.i0 + l.nx > INT_MAX || (long long)l.j0 + l.ny > INT_MAX || (long long)l.k0 + l.nz > INT_MAX) {
+            fl_report_error(FL_ERR_BAD_ARGUMENT, "setBoundary: level-set index range beyond int");
+            return false;
+        }
+        if (!(l.voxel > 0.f) || !(l.background > 0.f) || !std::isfinite(l.voxel) || !std::isfinite(l.background)) {
+            fl_report_error(FL_ERR_BAD_ARGUMENT, "setBoundary: level-set voxel or background not finite and positive");
+            return false;
+        }
+        total += nodes * sizeof(float);
+        if (total > cap) {
+            fl_report_error(FL_ERR_BAD_ARGUMENT, "setBoundary: level-set grids above 256 MiB in all");
+            return false;
+        }
+    }
+    // every grid into one allocation, the descriptors pointing into it
+    DeviceBytes grids;
+    if (!grids.alloc((size_t)total)) return false;
+    std::vector<bq_levelset> descs((size_t)n, bq_levelset{});
+    size_t at = 0;
+    for (int o = 0; o < n; o++) {
+        if (b[o].shape != BQ_SHAPE_LEVELSET) continue;
+        descs[o] = ls[o];
+        const size_t bytes = (size_t)ls[o].nx * (size_t)ls[o].ny * (size_t)ls[o].nz * sizeof(float);
+        float *dst = reinterpret_cast<float *>(grids.u8() + at);
+        fl_memcpy_h2d(dst, ls[o].phi, bytes);
+        descs[o].phi = dst;
+        at += bytes;
+    }
+    if (fl_last_error() != FL_OK) return false;
+    const size_t nrows = (size_t)g.nj * (size_t)g.nk;
+    if (solid.bytes() != g.n() && !solid.alloc(g.n())) return false;
+    if (rows.bytes() != nrows && !rows.alloc(nrows)) return false;
+    std::vector<bq_boundary> list(b, b + n);
+    if (!buildFlags(list, descs.data())) return false;
+    boundaries.swap(list);
+    levelsets.swap(descs);
+    lsgrids = std::move(grids);
+    return true;
+}
+
+// no obstacles: the list, the flags, the rows summary and the level-set grids released
+void BimocqGPUSolver::dropBoundaries()
+{
     boundaries.clear();
+    levelsets.clear();
     solid.release();
     rows.release();
+    lsgrids.release();
+}
+
+// the flags of `list` (ls: its level-set descriptors, or NULL when it holds none -- then the analytic operator); on
+// failure the obstacles are dropped (no step may run on flags that were never built)
+bool BimocqGPUSolver::buildFlags(const std::vector<bq_boundary> &list, const bq_levelset *ls)
+{
+    if (ls)
+        gpu_obstacle_flags_ls(solid.u8(), rows.u8(), list.data(), (int)list.size(), ls, CellSize, g.ni, g.nj, g.nk);
+    else
+        gpu_obstacle_flags(solid.u8(), rows.u8(), list.data(), (int)list.size(), CellSize, g.ni, g.nj, g.nk);
+    if (fl_last_error() == FL_OK) return true;
+    dropBoundaries();
     return false;
 }
 
@@ -525,7 +646,7 @@ bool BimocqGPUSolver::updateBoundary(int /*framenum*/, float dt)
         b.cy += b.vy * dt;
         b.cz += b.vz * dt;
     }
-    if (!buildFlags(list)) return false;
+    if (!buildFlags(list, levelsetList())) return false;
     boundaries.swap(list);
     return true;
 }
@@ -540,6 +661,14 @@ void BimocqGPUSolver::semilagBand(float cfldt, float dt)
     const bq_boundary *b = boundaries.data();
     const int n = (int)boundaries.size(), ni = g.ni, nj = g.nj, nk = g.nk;
     const float h = CellSize;
+    if (const bq_levelset *ls = levelsetList()) {
+        gpu_semilag_band_ls(TempSrcU, VelocityU, VelocityU, VelocityV, VelocityW, 1, 0, 0, h, ni, nj, nk, cfldt, -dt, b, n, ls);
+        gpu_semilag_band_ls(TempSrcV, VelocityV, VelocityU, VelocityV, VelocityW, 0, 1, 0, h, ni, nj, nk, cfldt, -dt, b, n, ls);
+        gpu_semilag_band_ls(TempSrcW, VelocityW, VelocityU, VelocityV, VelocityW, 0, 0, 1, h, ni, nj, nk, cfldt, -dt, b, n, ls);
+        gpu_semilag_band_ls(DensityTemp, Density, VelocityU, VelocityV, VelocityW, 0, 0, 0, h, ni, nj, nk, cfldt, -dt, b, n, ls);
+        gpu_semilag_band_ls(TemperatureTemp, Temperature, VelocityU, VelocityV, VelocityW, 0, 0, 0, h, ni, nj, nk, cfldt, -dt, b, n, ls);
+        return;
+    }
     gpu_semilag_band(TempSrcU, VelocityU, VelocityU, VelocityV, VelocityW, 1, 0, 0, h, ni, nj, nk, cfldt, -dt, b, n);
     gpu_semilag_band(TempSrcV, VelocityV, VelocityU, VelocityV, VelocityW, 0, 1, 0, h, ni, nj, nk, cfldt, -dt, b, n);
     gpu_semilag_band(TempSrcW, VelocityW, VelocityU, VelocityV, VelocityW, 0, 0, 1, h, ni, nj, nk, cfldt, -dt, b, n);
@@ -552,6 +681,15 @@ void BimocqGPUSolver::semilagBand(float cfldt, float dt)
 void BimocqGPUSolver::blendBoundary(bool band)
 {
     const bq_boundary *b = boundaries.data();
+    if (const bq_levelset *ls = levelsetList()) {
+        if (band)
+            gpu_obstacle_blend_ls(VelocityU, VelocityV, VelocityW, Density, Temperature, TempSrcU, TempSrcV, TempSrcW, DensityTemp,
+                                  TemperatureTemp, solid.u8(), b, (int)boundaries.size(), ls, CellSize, g.ni, g.nj, g.nk);
+        else
+            gpu_obstacle_blend_ls(nullptr, nullptr, nullptr, Density, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                  solid.u8(), b, (int)boundaries.size(), ls, CellSize, g.ni, g.nj, g.nk);
+        return;
+    }
     if (band)
         gpu_obstacle_blend(VelocityU, VelocityV, VelocityW, Density, Temperature, TempSrcU, TempSrcV, TempSrcW, DensityTemp,
                            TemperatureTemp, solid.u8(), b, (int)boundaries.size(), CellSize, g.ni, g.nj, g.nk);

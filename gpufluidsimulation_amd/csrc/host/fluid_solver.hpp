@@ -125,7 +125,16 @@ public:
     DeviceBytes solid, rows;                        // cell flags (0 fluid, o + 1 solid by obstacle o), rows summary (include/bimocq_gpu.h)
     bool setBoundary(const bq_boundary *b, int n);
     bool updateBoundary(int framenum, float dt);
-    bool buildFlags(const std::vector<bq_boundary> &list);
+    // Level sets (shape BQ_SHAPE_LEVELSET): `levelsets` holds one descriptor per entry of `boundaries` (phi into lsgrids)
+    // when the list holds a level set, and is empty otherwise -- then every obstacle operator call is the analytic one.
+    static constexpr size_t kMaxLevelsetBytes = (size_t)256 << 20;
+    std::vector<bq_levelset> levelsets;
+    DeviceBytes lsgrids;                            // every level-set grid of the list, one allocation
+    const bq_levelset *levelsetList() const { return levelsets.empty() ? nullptr : levelsets.data(); }
+    bool setBoundaryLevelsets(const bq_boundary *b, const bq_levelset *ls, int n);
+    bool setBoundaryLevelsetsOrFail(const bq_boundary *b, const bq_levelset *ls, int n);
+    void dropBoundaries();
+    bool buildFlags(const std::vector<bq_boundary> &list, const bq_levelset *ls);
     bool projectionObstacles(bool with_delta);
     void blendBoundary(bool band);                  // band: blendBoundary + clearBoundary, else clearBoundary only
     void semilagBand(float cfldt, float dt);

@@ -216,6 +216,13 @@ int bq_solver_set_boundary(bq_solver *s, const bq_boundary *b, int n)
     return s->solver->setBoundary(b, n) ? 0 : -1;
 }
 
+int bq_solver_set_boundary_levelsets(bq_solver *s, const bq_boundary *b, const bq_levelset *ls, int n)
+{
+    BQ_ENTER(s);
+    if (!s) return -1;
+    return s->solver->setBoundaryLevelsets(b, ls, n) ? 0 : -1;
+}
+
 int bq_solver_update_boundary(bq_solver *s, int framenum, float dt)
 {
     BQ_ENTER(s);

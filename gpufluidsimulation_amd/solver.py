@@ -20,7 +20,7 @@ class Emitter(C.Structure):
                 ("emit_frames", C.c_int)]
 
 
-SHAPE_SPHERE, SHAPE_BOX = 0, 1
+SHAPE_SPHERE, SHAPE_BOX, SHAPE_LEVELSET = 0, 1, 2
 MAX_BOUNDARIES = 16
 
 
@@ -38,6 +38,84 @@ def boundary_array(boundaries):
     for i, b in enumerate(boundaries):
         arr[i] = b if isinstance(b, Boundary) else Boundary(*b)
     return arr, len(boundaries)
+
+
+class LevelSetDesc(C.Structure):
+    """bq_levelset: grid pointer, dimensions, index of phi[0, 0, 0], voxel size, background"""
+    _fields_ = [("phi", C.c_void_p), ("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int),
+                ("i0", C.c_int), ("j0", C.c_int), ("k0", C.c_int), ("voxel", C.c_float), ("background", C.c_float)]
+
+
+class LevelSet:
+    """A dense signed-distance grid (DESIGN.md section 14, "Level sets"): phi (nz, ny, nx) float32, negative inside;
+    phi[k, j, i] is the value at index (i0 + i, j0 + j, k0 + k) = index_min + (i, j, k) of the level set's own index space,
+    whose index (0, 0, 0) sits at the obstacle's position and whose spacing is `voxel`.  Outside the stored nodes the level
+    set reads `background` (OpenVDB's half_width * voxel): the stored nodes must enclose the solid and its band."""
+
+    def __init__(self, phi, voxel, index_min=(0, 0, 0), background=None):
+        self.phi = np.ascontiguousarray(phi, dtype=np.float32)
+        if self.phi.ndim != 3:
+            raise ValueError("phi must be a (nz, ny, nx) array")
+        self.voxel = float(np.float32(voxel))
+        self.index_min = tuple(int(x) for x in index_min)
+        self.background = float(np.float32(3 * self.voxel if background is None else background))
+
+    def descriptor(self):
+        """bq_levelset with phi pointing at this object's HOST array (valid while the object lives)"""
+        nz, ny, nx = self.phi.shape
+        return LevelSetDesc(self.phi.ctypes.data, nx, ny, nz, *self.index_min, self.voxel, self.background)
+
+
+def levelset_sphere(radius, voxel, half_width=3):
+    """the dense equivalent of OpenVDB's createLevelSetSphere centred on index 0: indices -m .. m on every axis,
+    m = ceil(radius / voxel + half_width), phi = (|index| - radius / voxel) * voxel clamped to +-background"""
+    m = int(np.ceil(radius / voxel + half_width))
+    bg = np.float32(half_width * voxel)
+    i = np.arange(-m, m + 1, dtype=np.float64)
+    d = np.sqrt(i[:, None, None] ** 2 + i[None, :, None] ** 2 + i[None, None, :] ** 2)
+    phi = np.clip((d - radius / voxel) * voxel, -bg, bg).astype(np.float32)
+    return LevelSet(phi, voxel, (-m, -m, -m), bg)
+
+
+def levelset_from_sdf(fn, lo, hi, voxel, half_width=3):
+    """a LevelSet sampled from fn(x, y, z) -> signed distance (numpy arrays, world units, in the obstacle's frame): the
+    index box that covers [lo, hi] on every axis, widened by half_width + 1 voxels so that it holds the band too, values
+    clamped to +-background (background = half_width * voxel)"""
+    pad = int(np.ceil(half_width)) + 1
+    a = [int(np.floor(lo[d] / voxel)) - pad for d in range(3)]
+    b = [int(np.ceil(hi[d] / voxel)) + pad for d in range(3)]
+    x, y, z = (np.arange(a[d], b[d] + 1, dtype=np.float64) * voxel for d in range(3))
+    bg = np.float32(half_width * voxel)
+    phi = np.asarray(fn(x[None, None, :], y[None, :, None], z[:, None, None]), dtype=np.float64)
+    phi = np.broadcast_to(phi, (z.size, y.size, x.size))
+    return LevelSet(np.clip(phi, -bg, bg).astype(np.float32), voxel, tuple(a), bg)
+
+
+class LevelSetObstacle:
+    """an obstacle whose shape is a LevelSet, placed at `position` (the level set's index origin), moving with `velocity`"""
+
+    def __init__(self, levelset, position, velocity=(0.0, 0.0, 0.0)):
+        self.levelset = levelset
+        self.position = tuple(float(x) for x in position)
+        self.velocity = tuple(float(x) for x in velocity)
+
+    def boundary(self):
+        return Boundary(SHAPE_LEVELSET, *self.position, 0.0, 0.0, 0.0, *self.velocity)
+
+
+def levelset_arrays(boundaries):
+    """(Boundary array, LevelSetDesc array, count) for a list mixing Boundary objects, tuples and LevelSetObstacles;
+    the descriptors point at the LevelSets' host arrays"""
+    boundaries = list(boundaries)
+    arr = (Boundary * max(1, len(boundaries)))()
+    ls = (LevelSetDesc * max(1, len(boundaries)))()
+    for i, b in enumerate(boundaries):
+        if isinstance(b, LevelSetObstacle):
+            arr[i] = b.boundary()
+            ls[i] = b.levelset.descriptor()
+        else:
+            arr[i] = b if isinstance(b, Boundary) else Boundary(*b)
+    return arr, ls, len(boundaries)
 
 
 HOST_SIGS = {
@@ -63,6 +141,7 @@ HOST_SIGS = {
     "bq_solver_reinit_count": (C.c_int, [C.c_void_p]),
     "bq_solver_phase_ms": (C.c_longlong, [C.c_void_p, C.POINTER(C.c_double), C.c_int]),
     "bq_solver_set_boundary": (C.c_int, [C.c_void_p, C.POINTER(Boundary), C.c_int]),
+    "bq_solver_set_boundary_levelsets": (C.c_int, [C.c_void_p, C.POINTER(Boundary), C.POINTER(LevelSetDesc), C.c_int]),
     "bq_solver_update_boundary": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
     "bq_solver_download_solid": (C.c_long, [C.c_void_p, C.c_void_p, C.c_long]),
 }
@@ -168,9 +247,16 @@ class BimocqGPUSolver:
 
     def setBoundary(self, boundaries):
         """setBoundary: replaces the obstacle list (Boundary objects or (shape, cx, cy, cz, rx, ry, rz, vx, vy, vz)
-        tuples; [] removes every obstacle) and builds the cell flags at the given centres.  One GPU, Jacobi only."""
-        arr, n = boundary_array(boundaries)
-        rc = self.lib.bq_solver_set_boundary(self.s, arr, n)
+        tuples, or LevelSetObstacles; [] removes every obstacle) and builds the cell flags at the given centres.  One GPU,
+        Jacobi only.  A list with a level set goes through bq_solver_set_boundary_levelsets, which copies the grids to
+        the device; after a failed call with a level set there are no obstacles."""
+        boundaries = list(boundaries)
+        if any(isinstance(b, LevelSetObstacle) for b in boundaries):
+            arr, ls, n = levelset_arrays(boundaries)
+            rc = self.lib.bq_solver_set_boundary_levelsets(self.s, arr, ls, n)
+        else:
+            arr, n = boundary_array(boundaries)
+            rc = self.lib.bq_solver_set_boundary(self.s, arr, n)
         self._check()
         if rc != 0:
             raise _lib.BimocqError("bq_solver_set_boundary failed")

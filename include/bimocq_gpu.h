@@ -644,7 +644,7 @@ void gpu_advect_field_double_global(float *field, float *field_prev_global,
  * of planes k-1 .. k+1.  At most BQ_MAX_BOUNDARIES obstacles; the list is passed by host pointer.  Single GPU. */
 #ifndef BQ_BOUNDARY_DEFINED
 #define BQ_BOUNDARY_DEFINED
-enum { BQ_SHAPE_SPHERE = 0, BQ_SHAPE_BOX = 1 };
+enum { BQ_SHAPE_SPHERE = 0, BQ_SHAPE_BOX = 1, BQ_SHAPE_LEVELSET = 2 };
 enum { BQ_MAX_BOUNDARIES = 16 };
 typedef struct bq_boundary {
     int   shape;
@@ -652,6 +652,19 @@ typedef struct bq_boundary {
     float rx, ry, rz;        /* sphere: radius in rx; box: half extents                      */
     float vx, vy, vz;        /* velocity: the solid face velocity, and the motion per update */
 } bq_boundary;
+/* A level set (shape BQ_SHAPE_LEVELSET; DESIGN.md section 14, "Level sets"): a dense float32 signed-distance grid,
+ * phi[k][j][i] (x fastest, nx, ny, nz >= 2, nx * ny * nz < 2^31), negative inside.  phi[k][j][i] is the value at index
+ * (i0 + i, j0 + j, k0 + k) of the level set's own index space, whose index (0, 0, 0) sits at the obstacle's centre
+ * (cx, cy, cz) of its bq_boundary entry (rx, ry, rz unused); `voxel` > 0 is its spacing, `background` > 0 the value it
+ * takes outside the stored nodes (OpenVDB's half_width * voxel).  A node is solid when the trilinear sample is <= 0 and
+ * band when 0 < sample < background.  Outside the stored nodes the sample is `background`, i.e. fluid: the stored nodes
+ * must enclose the solid and its band. */
+typedef struct bq_levelset {
+    const float *phi;        /* nz * ny * nx floats (device pointer for the gpu_*_ls operators)  */
+    int   nx, ny, nz;
+    int   i0, j0, k0;        /* index of phi[0][0][0]                                         */
+    float voxel, background;
+} bq_levelset;
 #endif
 /* cell flags and rows summary of the obstacles at their current centres (one launch after a clear of `rows`) */
 void gpu_obstacle_flags(unsigned char *solid, unsigned char *rows, const bq_boundary *b, int n, float h,
@@ -685,6 +698,19 @@ void gpu_semilag_band(float *field, float *field_src, float *u, float *v, float 
 void gpu_obstacle_blend(float *u, float *v, float *w, float *rho, float *T, const float *us, const float *vs,
                         const float *ws, const float *rhos, const float *Ts, const unsigned char *solid,
                         const bq_boundary *b, int n, float h, int ni, int nj, int nk);
+/* gpu_obstacle_flags, gpu_semilag_band and gpu_obstacle_blend for lists that may hold level sets: `ls` is a host array
+ * of n descriptors whose phi are device pointers; entry o is read only when b[o].shape == BQ_SHAPE_LEVELSET (ls may be
+ * NULL when no entry is one).  Analytic entries are classified exactly as above.  A bad descriptor (null phi, a
+ * dimension below 2, nx * ny * nz >= 2^31, an index range beyond int, a non-finite or non-positive voxel or background)
+ * latches FL_ERR_BAD_ARGUMENT. */
+void gpu_obstacle_flags_ls(unsigned char *solid, unsigned char *rows, const bq_boundary *b, int n,
+                           const bq_levelset *ls, float h, int ni, int nj, int nk);
+void gpu_semilag_band_ls(float *field, float *field_src, float *u, float *v, float *w, int dim_x, int dim_y, int dim_z,
+                         float h, int ni, int nj, int nk, float cfldt, float dt, const bq_boundary *b, int n,
+                         const bq_levelset *ls);
+void gpu_obstacle_blend_ls(float *u, float *v, float *w, float *rho, float *T, const float *us, const float *vs,
+                           const float *ws, const float *rhos, const float *Ts, const unsigned char *solid,
+                           const bq_boundary *b, int n, const bq_levelset *ls, float h, int ni, int nj, int nk);
 
 #ifdef __cplusplus
 }

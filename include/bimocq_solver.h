@@ -167,6 +167,13 @@ long  bq_solver_output_wait(bq_solver *s);
  * on one GPU only: z-slab ranks and BQ_PROJECTION_MGCG are refused through fl_last_error.  Returns 0 on success.
  * download_solid copies min(cells, capacity) flags (1 = obstacle) and returns the cell count. */
 int   bq_solver_set_boundary(bq_solver *s, const bq_boundary *b, int n);
+/* set_boundary for lists that may hold level sets (shape BQ_SHAPE_LEVELSET; DESIGN.md section 14, "Level sets"): ls is
+ * an array of n descriptors, ls[o] read only where b[o].shape == BQ_SHAPE_LEVELSET, whose phi are HOST arrays.  Every grid
+ * is copied into one device allocation (at most 256 MiB in all): the caller may free its arrays after the call.  The
+ * level set moves with its entry's centre (update_boundary); the grid is never uploaded again.  The refusals of
+ * set_boundary apply, plus bad descriptors and a library without the level-set operators.  Any failure leaves no
+ * obstacles.  Returns 0 on success. */
+int   bq_solver_set_boundary_levelsets(bq_solver *s, const bq_boundary *b, const bq_levelset *ls, int n);
 int   bq_solver_update_boundary(bq_solver *s, int framenum, float dt);
 long  bq_solver_download_solid(bq_solver *s, unsigned char *host, long capacity);
 float bq_solver_last_cfldt(const bq_solver *s);

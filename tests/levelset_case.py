@@ -1,0 +1,124 @@
+"""Shared pieces of the level-set obstacle tests: a numpy restatement of the level-set sampler and of the classification of
+mixed lists ("Level sets": float64 index math, float32 lerps), the scene the step tests run, and
+loaders of the CPU stand-in with the level-set operators."""
+import ctypes as C
+import hashlib
+
+import numpy as np
+
+import obstacle_case as OC
+
+f32, f64 = np.float32, np.float64
+
+
+def sample(ls, c, x, y, z):
+    """the level set `ls` (solver.LevelSet) with its index origin at c = (cx, cy, cz), sampled at the float32 points
+    (x, y, z) (broadcastable arrays): float32 result, `background` where every corner lies outside the stored nodes"""
+    nz, ny, nx = ls.phi.shape
+    n, lo = (nx, ny, nz), ls.index_min
+    bg = f32(ls.background)
+    g = [(np.asarray(p, f32).astype(f64) - f64(f32(cc))) / f64(f32(ls.voxel)) for p, cc in zip((x, y, z), c)]
+    g = np.broadcast_arrays(*g)
+    inside = np.ones(g[0].shape, bool)
+    for d in range(3):
+        inside &= (g[d] >= lo[d] - 1) & (g[d] < lo[d] + n[d])
+    gi = [np.where(inside, gd, f64(lo[d])) for d, gd in enumerate(g)]      # keep the casts in range
+    f = [np.floor(gd) for gd in gi]
+    t = [gd - fd for gd, fd in zip(gi, f)]
+    a = [fd.astype(np.int64) - lo[d] for d, fd in enumerate(f)]
+    pad = np.pad(ls.phi, 1, constant_values=bg)                           # index -1 .. n on every axis
+
+    def node(di, dj, dk):
+        return pad[a[2] + dk + 1, a[1] + dj + 1, a[0] + di + 1]
+
+    def lerp(p, q, w):
+        return p + ((q - p).astype(f64) * w).astype(f32)
+
+    y0 = lerp(lerp(node(0, 0, 0), node(0, 0, 1), t[2]), lerp(node(0, 1, 0), node(0, 1, 1), t[2]), t[1])
+    y1 = lerp(lerp(node(1, 0, 0), node(1, 0, 1), t[2]), lerp(node(1, 1, 0), node(1, 1, 1), t[2]), t[1])
+    return np.where(inside, lerp(y0, y1, t[0]), bg).astype(f32)
+
+
+def classify(entries, h, shape, stag=(0, 0, 0)):
+    """(nk, nj, ni) int array for a list of analytic tuples and solver.LevelSetObstacles: o + 1 solid by the last entry o
+    that covers the node, -1 band (in some entry's band, covered by none), 0 elsewhere"""
+    from gpufluidsimulation_amd.solver import LevelSetObstacle
+    nk, nj, ni = shape
+    x = OC.positions(ni, stag[0], h)[None, None, :]
+    y = OC.positions(nj, stag[1], h)[None, :, None]
+    z = OC.positions(nk, stag[2], h)[:, None, None]
+    solid = np.zeros(shape, np.int32)
+    band = np.zeros(shape, bool)
+    for o, e in enumerate(entries):
+        if isinstance(e, LevelSetObstacle):
+            s = np.broadcast_to(sample(e.levelset, e.position, x, y, z), shape)
+            cov, bb = s <= 0, (s > 0) & (s < f32(e.levelset.background))
+        else:
+            c = OC.classify([tuple(e)], h, shape, stag)
+            cov, bb = c == 1, c == -1
+        solid = np.where(cov, o + 1, solid)
+        band |= bb
+    return np.where(solid > 0, solid, np.where(band, -1, 0))
+
+
+def box_levelset(half, voxel, half_width=3):
+    """a box of half extents `half` as a level set sampled from its exact signed distance"""
+    from gpufluidsimulation_amd.solver import levelset_from_sdf
+    hx, hy, hz = half
+
+    def sdf(x, y, z):
+        q = [np.abs(x) - hx, np.abs(y) - hy, np.abs(z) - hz]
+        out = np.sqrt(sum(np.maximum(a, 0.0) ** 2 for a in q))
+        return out + np.minimum(np.maximum(np.maximum(q[0], q[1]), q[2]), 0.0)
+
+    return levelset_from_sdf(sdf, (-hx, -hy, -hz), (hx, hy, hz), voxel, half_width)
+
+
+def scene(n):
+    """the step scene: rising smoke at the bottom, a static level-set sphere above it, an analytic box, and a level-set box
+    (voxel 0.75 h) moving sideways through the plume"""
+    from gpufluidsimulation_amd.solver import LevelSetObstacle, levelset_sphere
+    h = 1.0 / n
+    em = [(0.5, 0.2, 0.5, 0.1, 1.0, 1.0, 0.0, 1000)]
+    entries = [LevelSetObstacle(levelset_sphere(0.12, h), (0.5, 0.55, 0.5)),
+               (1, 0.3, 0.8, 0.45, 0.08, 0.05, 0.1, 0.0, 0.0, 0.0),
+               LevelSetObstacle(box_levelset((0.06, 0.04, 0.08), 0.75 * h), (0.75, 0.75, 0.55), (-0.5, 0.0, 0.0))]
+    return h, em, entries
+
+
+def run_scene(lib, errlib, n, scheme, steps, iters):
+    """the scene for `steps` steps (updateBoundary before every advance); per-step SHA-256 of rho, T, u, v, w, p and the
+    flags, and the final max rho"""
+    from gpufluidsimulation_amd.solver import BimocqGPUSolver
+    _, em, entries = scene(n)
+    s = BimocqGPUSolver(n, n, n, 1.0, 0.0, 1.0, lib=lib, errlib=errlib, scheme=scheme)
+    s.setSmoke(0.0, 1.0, em)
+    s.setProjection(iters, 0.5)
+    s.setBoundary(entries)
+    out = []
+    for f in range(steps):
+        s.updateBoundary(f, 1.0 / n)
+        s.advance(f, 1.0 / n)
+        d = hashlib.sha256()
+        for name in ("rho", "T", "u", "v", "w", "p"):
+            d.update(s.field(name).tobytes())
+        d.update(s.solidMask().tobytes())
+        out.append(d.hexdigest())
+    rho_max = float(s.field("rho").max())
+    s.close()
+    return {"hashes": out, "rho_max": rho_max}
+
+
+def bind_ops(lib):
+    """the three level-set operators (and the analytic ones) of a stand-in, typed from _lib.HIP_SIGS"""
+    from gpufluidsimulation_amd import _lib
+    for name in ("gpu_obstacle_flags_ls", "gpu_semilag_band_ls", "gpu_obstacle_blend_ls",
+                 "gpu_obstacle_flags", "gpu_semilag_band", "gpu_obstacle_blend"):
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = _lib.HIP_SIGS[name]
+    return lib
+
+
+def load(path):
+    from gpufluidsimulation_amd import solver
+    return bind_ops(OC.bind_errors(solver.bind_host(C.CDLL(path, mode=C.RTLD_LOCAL))))

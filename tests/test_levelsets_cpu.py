@@ -1,0 +1,278 @@
+"""Level-set obstacles on the CPU stand-in (tests/cpu_abi/levelset_abi.c linked with the product's host sources): the C
+restatement against the numpy sampler on odd grids, a level-set sphere against the analytic sphere, an exact one-cell
+shift, the refusals, the failure rule and the empty list.  No GPU."""
+import ctypes as C
+import hashlib
+import re
+
+import numpy as np
+import pytest
+
+import levelset_case as LC
+import obstacle_case as OC
+from build_cpu_host_levelsets import build as build_levelsets
+from build_cpu_host_obstacles import build as build_obstacles
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return LC.load(build_levelsets())
+
+
+def make(lib, n=24, scheme=0, iters=20):
+    from gpufluidsimulation_amd.solver import BimocqGPUSolver
+    _, em, _ = OC.scene(n)
+    s = BimocqGPUSolver(n, n, n, 1.0, 0.0, 1.0, lib=lib, errlib=lib, scheme=scheme)
+    s.setSmoke(0.0, 1.0, em)
+    s.setProjection(iters, 0.5)
+    return s
+
+
+def c_flags(lib, entries, h, dims):
+    from gpufluidsimulation_amd.solver import levelset_arrays
+    ni, nj, nk = dims
+    arr, ls, n = levelset_arrays(entries)
+    solid = np.full(ni * nj * nk, 7, np.uint8)
+    rows = np.full(nj * nk, 7, np.uint8)
+    lib.gpu_obstacle_flags_ls(solid.ctypes.data, rows.ctypes.data, C.addressof(arr), n, C.addressof(ls), h, ni, nj, nk)
+    assert lib.fl_last_error() == 0, lib.fl_last_error_string()
+    return solid.reshape(nk, nj, ni), rows
+
+
+def c_band(lib, entries, h, dims, solid):
+    """band nodes of the four node families, read off gpu_obstacle_blend_ls: sources 1, destinations 0"""
+    from gpufluidsimulation_amd.solver import levelset_arrays
+    ni, nj, nk = dims
+    arr, ls, n = levelset_arrays(entries)
+    shapes = [(nk, nj, ni + 1), (nk, nj + 1, ni), (nk + 1, nj, ni), (nk, nj, ni), (nk, nj, ni)]
+    dst = [np.zeros(s, np.float32) for s in shapes]
+    src = [np.ones(s, np.float32) for s in shapes]
+    lib.gpu_obstacle_blend_ls(*[d.ctypes.data for d in dst], *[s.ctypes.data for s in src], solid.ctypes.data,
+                              C.addressof(arr), n, C.addressof(ls), h, ni, nj, nk)
+    assert lib.fl_last_error() == 0, lib.fl_last_error_string()
+    return dst
+
+
+def mixed_lists(dims, h):
+    """level sets with voxel != h, negative index_min, a grid partly outside the domain and one whose stored nodes cut
+    through its band (so that the one-voxel rim just outside them samples real values), between analytic entries"""
+    from gpufluidsimulation_amd.solver import LevelSet, LevelSetObstacle, levelset_sphere
+    ni, nj, nk = dims
+    X, Y, Z = ni * h, nj * h, nk * h
+    sph = levelset_sphere(0.3 * min(Y, Z), 0.7 * h)                       # voxel != h, index_min < 0
+    box = LC.box_levelset((0.1 * X, 0.2 * Y, 0.15 * Z), 1.3 * h, half_width=2)
+    cut = levelset_sphere(0.25 * min(Y, Z), h)
+    m = cut.phi.shape[0]
+    rim = LevelSet(cut.phi[2:m - 2, 2:m - 2, 2:m - 2], h, tuple(x + 2 for x in cut.index_min), cut.background)
+    return [
+        [LevelSetObstacle(sph, (0.02 * X, 0.5 * Y, 0.5 * Z))],                                    # cut by the x = 0 wall
+        [(0, 0.55 * X, 0.45 * Y, 0.5 * Z, 0.25 * min(Y, Z), 0, 0, 0, 0, 0),
+         LevelSetObstacle(box, (0.6 * X + 0.3 * h, 0.5 * Y, 0.45 * Z - 0.2 * h)),
+         (1, 0.62 * X, 0.5 * Y, 0.45 * Z, 0.05 * X, 0.1 * Y, 0.08 * Z, 0, 0, 0)],               # overlapping, later wins
+        [LevelSetObstacle(rim, (0.3 * X + 0.1 * h, 0.5 * Y, 0.55 * Z)),
+         LevelSetObstacle(sph, (0.95 * X, 0.9 * Y, 0.1 * Z))],                                   # rim nodes; a corner
+    ]
+
+
+@pytest.mark.parametrize("dims", [(37, 29, 23), (99, 21, 18)])
+@pytest.mark.parametrize("case", [0, 1, 2])
+def test_c_restatement_equals_numpy(lib, dims, case):
+    ni, nj, nk = dims
+    h = 1.0 / ni
+    entries = mixed_lists(dims, h)[case]
+    solid, rows = c_flags(lib, entries, h, dims)
+    want = LC.classify(entries, h, (nk, nj, ni))
+    assert np.array_equal(solid, np.maximum(want, 0).astype(np.uint8))
+    assert solid.any() and (want == -1).any()
+    pad = np.pad((solid != 0).any(axis=2), 1)
+    want_r = np.zeros((nk, nj), bool)
+    for c in range(3):
+        for b in range(3):
+            want_r |= pad[c:c + nk, b:b + nj]
+    assert np.array_equal(rows.reshape(nk, nj), want_r.astype(np.uint8))
+    dst = c_band(lib, entries, h, dims, solid)
+    for stag, d in zip([(1, 0, 0), (0, 1, 0), (0, 0, 1), (0, 0, 0)], dst[:4]):
+        assert np.array_equal(d == 1, LC.classify(entries, h, d.shape, stag) == -1), stag
+    if case == 2:
+        # nodes whose sample point lies in the one-voxel rim just outside the stored nodes, and which sample real values
+        from gpufluidsimulation_amd.solver import LevelSetObstacle
+        e = entries[0]
+        ls = e.levelset
+        x, y, z = (OC.positions(n_, 0, h) for n_ in (ni, nj, nk))
+        g = [((p.astype(np.float64) - np.float64(np.float32(c))) / np.float64(np.float32(ls.voxel))) for p, c in
+             zip((x, y, z), e.position)]
+        n3 = ls.phi.shape[::-1]
+        ax = [((gd >= lo - 1) & (gd < lo)) | ((gd >= lo + nn - 1) & (gd < lo + nn)) for gd, lo, nn in zip(g, ls.index_min, n3)]
+        inn = [(gd >= lo - 1) & (gd < lo + nn) for gd, lo, nn in zip(g, ls.index_min, n3)]
+        rim = (ax[0][None, None, :] | ax[1][None, :, None] | ax[2][:, None, None]) & \
+            inn[0][None, None, :] & inn[1][None, :, None] & inn[2][:, None, None]
+        s = LC.sample(ls, e.position, x[None, None, :], y[None, :, None], z[:, None, None])
+        live = rim & (s < np.float32(ls.background))
+        print(f"rim nodes {int(rim.sum())}, of which below the background {int(live.sum())}")
+        assert isinstance(e, LevelSetObstacle) and live.sum() > 0
+        assert (want[live] != 0).any()
+
+
+def test_levelset_sphere_classifies_like_the_analytic_sphere(lib):
+    """Bound: trilinear interpolation of a C2 function errs by at most voxel^2 / 8 * (|f_xx| + |f_yy| + |f_zz|) over the
+    cell; for d = |x| - r that sum is trace((I - n n^T) / |x|) = 2 / |x| <= 2 / (r - sqrt(3) voxel) near the surface, so
+    E = voxel^2 / (4 (r - sqrt(3) voxel)), plus 1e-6 h for float32 rounding of phi, the lerps and the analytic squared
+    distances.  Nodes within E of the surface are excluded, and nodes within sqrt(3) voxel + E of the band's outer edge
+    r + 3h (where the stored distances are clamped to the background, a kink the bound does not cover)."""
+    from gpufluidsimulation_amd.solver import LevelSetObstacle, levelset_sphere
+    n = 48
+    h = 1.0 / n
+    r, c = 0.21, (0.5 + 0.3 * h, 0.47, 0.52 - 0.1 * h)
+    ls = levelset_sphere(r, h)
+    solid, _ = c_flags(lib, [LevelSetObstacle(ls, c)], h, (n, n, n))
+    ana = OC.classify([(0, *c, r, 0, 0, 0, 0, 0)], h, (n, n, n))
+    band_ls = c_band(lib, [LevelSetObstacle(ls, c)], h, (n, n, n), solid)[3] == 1
+    E = h * h / (4 * (r - np.sqrt(3) * h)) + 1e-6 * h
+    p = OC.positions(n, 0, h).astype(np.float64)
+    d = np.sqrt((p[None, None, :] - c[0]) ** 2 + (p[None, :, None] - c[1]) ** 2 + (p[:, None, None] - c[2]) ** 2) - r
+    keep = (np.abs(d) > E) & (np.abs(d - 3 * h) > np.sqrt(3) * h + E)
+    excluded = int((~keep).sum())
+    print(f"E = {E / h:.4f} h; excluded {excluded} of {n ** 3} nodes")
+    assert excluded < 0.1 * n ** 3
+    assert np.array_equal((solid != 0)[keep], (ana > 0)[keep])
+    assert np.array_equal(band_ls[keep], (ana == -1)[keep])
+    assert (solid != 0).sum() > 1000 and band_ls.sum() > 1000
+
+
+def test_one_voxel_motion_shifts_the_mask_by_one_cell(lib):
+    """dyadic h, voxel = h, v dt = h: the sample points move by exactly one voxel, so the mask moves by exactly one cell"""
+    from gpufluidsimulation_amd.solver import LevelSetObstacle, levelset_sphere
+    n = 32
+    h = 1.0 / n
+    s = make(lib, n)
+    s.setBoundary([LevelSetObstacle(levelset_sphere(0.15, h), (0.40625, 0.5, 0.53125), (0.5, 0.0, 0.0)),
+                   LevelSetObstacle(LC.box_levelset((0.1, 0.06, 0.08), h), (0.5, 0.25, 0.5), (0.5, 0.0, 0.0))])
+    m0 = s.solidMask()
+    s.updateBoundary(0, 2 * h)
+    m1 = s.solidMask()
+    assert m0.sum() > 500
+    assert np.array_equal(m1[:, :, 1:], m0[:, :, :-1])
+    assert not m1[:, :, 0].any() and not m0[:, :, -1].any()
+    s.close()
+
+
+def test_levelset_scene_runs_and_moves(lib):
+    for scheme in (0, 3):
+        n = 24
+        h, em, entries = LC.scene(n)
+        s = make(lib, n, scheme)
+        s.setBoundary(entries)
+        for f in range(3):
+            s.updateBoundary(f, 0.5 / n)
+            s.advance(f, 0.5 / n)
+        solid = s.solidMask().astype(bool)
+        moved = list(entries)
+        cx = np.float32(entries[2].position[0])
+        for _ in range(3):
+            cx = np.float32(cx + np.float32(-0.5) * np.float32(0.5 / n))
+        from gpufluidsimulation_amd.solver import LevelSetObstacle
+        moved[2] = LevelSetObstacle(entries[2].levelset, (float(cx),) + entries[2].position[1:], entries[2].velocity)
+        assert np.array_equal(solid, LC.classify(moved, h, (n, n, n)) > 0)
+        rho = s.field("rho").reshape(n, n, n)
+        assert np.all(rho[solid] == 0) and np.isfinite(rho).all() and rho.max() > 0
+        s.close()
+
+
+def bad(lib, s, entries, ls_fields=None):
+    """bq_solver_set_boundary_levelsets with the descriptor of entry 0 edited; returns (rc, error text)"""
+    from gpufluidsimulation_amd.solver import levelset_arrays
+    arr, ls, n = levelset_arrays(entries)
+    for k, v in (ls_fields or {}).items():
+        setattr(ls[0], k, v)
+    rc = lib.bq_solver_set_boundary_levelsets(s.s, arr, ls, n)
+    text = lib.fl_last_error_string().decode()
+    lib.fl_clear_error()
+    return rc, text
+
+
+def test_every_new_refusal(lib):
+    from gpufluidsimulation_amd import _lib
+    from gpufluidsimulation_amd.solver import BimocqGPUSolver, LevelSetObstacle, levelset_arrays, levelset_sphere
+    n = 16
+    ob = LevelSetObstacle(levelset_sphere(0.2, 1.0 / n), (0.5, 0.5, 0.5))
+    s = make(lib, n)
+    for fields, match in [({"phi": None}, "grid"), ({"nx": 1}, "below 2"), ({"nz": 0}, "below 2"),
+                          ({"nx": 2048, "ny": 1024, "nz": 1024}, "2\\^31"), ({"voxel": 0.0}, "voxel"),
+                          ({"voxel": float("nan")}, "voxel"), ({"background": -1.0}, "background"),
+                          ({"background": float("inf")}, "background"), ({"i0": 2 ** 31 - 3}, "beyond int"),
+                          ({"nx": 512, "ny": 512, "nz": 300}, "256 MiB")]:
+        rc, text = bad(lib, s, [ob], fields)
+        assert rc != 0 and re.search(match, text), (fields, text)
+    rc, text = bad(lib, s, [ob] * 17)
+    assert rc != 0 and "0 .. 16" in text
+    rc = lib.bq_solver_set_boundary_levelsets(s.s, levelset_arrays([ob])[0], None, 1)
+    assert rc != 0 and "descriptors" in lib.fl_last_error_string().decode()
+    lib.fl_clear_error()
+    # the projection refusals, in either order
+    s.setProjection(5, 0.5, kind=1)
+    with pytest.raises(_lib.BimocqError, match="Jacobi"):
+        s.setBoundary([ob])
+    s.setProjection(5, 0.5, kind=0)
+    s.setBoundary([ob])
+    with pytest.raises(_lib.BimocqError, match="Jacobi"):
+        s.setProjection(5, 0.5, kind=1)
+    s.close()
+    r = BimocqGPUSolver(16, 16, 16, 1.0, lib=lib, errlib=lib, rank=0, nranks=2, ghost=3)
+    with pytest.raises(_lib.BimocqError, match="z-slab"):
+        r.setBoundary([ob])
+    r.close()
+    # the operators latch FL_ERR_BAD_ARGUMENT on a bad descriptor
+    arr, ls, cnt = levelset_arrays([ob])
+    ls[0].voxel = -1.0
+    buf = np.zeros(n ** 3, np.uint8)
+    lib.gpu_obstacle_flags_ls(buf.ctypes.data, buf.ctypes.data, C.addressof(arr), cnt, C.addressof(ls), 1.0 / n, n, n, n)
+    assert lib.fl_last_error() == _lib.FL_ERR_BAD_ARGUMENT
+    lib.fl_clear_error()
+
+
+def test_stand_in_without_levelset_operators_refuses():
+    """the obstacle stand-in has the analytic operators but not the level-set ones: its weak references are null"""
+    from gpufluidsimulation_amd import _lib, solver
+    lib = OC.bind_errors(solver.bind_host(C.CDLL(build_obstacles(), mode=C.RTLD_LOCAL)))
+    s = solver.BimocqGPUSolver(16, 16, 16, 1.0, lib=lib, errlib=lib)
+    s.setBoundary([OC.scene(16)[2][0]])                   # analytic lists still work there
+    with pytest.raises(_lib.BimocqError, match="no level-set obstacle operators"):
+        s.setBoundary(LC.scene(16)[2])
+    assert not s.solidMask().any()
+    s.close()
+
+
+def test_failed_call_leaves_no_obstacles(lib):
+    n = 20
+    s = make(lib, n)
+    for first in (LC.scene(n)[2], [OC.scene(n)[2][0]]):
+        s.setBoundary(first)
+        assert s.solidMask().any()
+        rc, text = bad(lib, s, LC.scene(n)[2], {"nx": 1})
+        assert rc != 0
+        assert not s.solidMask().any()
+        s.updateBoundary(0, 0.5 / n)                       # nothing to move, nothing rebuilt
+        assert not s.solidMask().any()
+    s.setProjection(5, 0.5, kind=1)                        # MGCG is admitted again: the list is empty
+    assert lib.fl_last_error() == 0
+    s.close()
+
+
+def test_empty_list_is_no_obstacle_at_all(lib):
+    hashes = []
+    for call in (False, True):
+        n = 20
+        s = make(lib, n)
+        if call:
+            s.setBoundary(LC.scene(n)[2])
+            s.setBoundary([])
+        digest = hashlib.sha256()
+        for f in range(3):
+            s.updateBoundary(f, 0.5 / n)
+            s.advance(f, 0.5 / n)
+            for name in ("rho", "T", "u", "v", "w", "p"):
+                digest.update(s.field(name).tobytes())
+        assert not s.solidMask().any()
+        hashes.append(digest.hexdigest())
+        s.close()
+    assert hashes[0] == hashes[1]
