@@ -38,7 +38,7 @@ $(OBJDIR)/bq_advect_fast.o: $(CSRC)/bq_advect.hip $(KERNEL_HDRS) include/bimocq_
 $(PKG)/libbimocq_hip.so: $(KERNEL_OBJS) $(OBJDIR)/bq_advect_fast.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(KERNEL_OBJS) $(OBJDIR)/bq_advect_fast.o $(RCCL_LIB)
 
-$(OBJDIR)/host_%.o: $(CSRC)/host/%.cpp $(wildcard $(CSRC)/host/*.hpp) include/bimocq_gpu.h include/bimocq_solver.h
+$(OBJDIR)/host_%.o: $(CSRC)/host/%.cpp $(wildcard $(CSRC)/host/*.hpp) $(CSRC)/bq_levelset.h include/bimocq_gpu.h include/bimocq_solver.h
 	@mkdir -p $(OBJDIR)
 	g++ -O2 -std=c++17 -fPIC -pthread -Wall -Wextra -Iinclude $(VDB_FLAGS) -c $< -o $@
 

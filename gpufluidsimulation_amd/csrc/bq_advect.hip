@@ -544,37 +544,16 @@ __global__ __launch_bounds__(256) void semilag_kernel(float *field, const float 
 // semilag_kernel at the band nodes of the obstacles only (blendBoundary's semi-Lagrangian values, BimocqSolver.cpp:106,
 // 121-125): a thread outside the band returns after the classification, so the cost of the traces scales with the band.
 // Band nodes outside semilag_kernel's window get the 0 that kernel leaves in a cleared field.
-template <bool P2>
+template <bool P2, typename... Ls>
 __global__ __launch_bounds__(256) void semilag_band_kernel(float *field, const float *field_src,
                                                            const float *u, const float *v, const float *w,
-                                                           Spacing sp, Grid g, int dx, int dy, int dz, float cfldt, float dt, ObsSet ob)
+                                                           Spacing sp, Grid g, int dx, int dy, int dz, float cfldt, float dt,
+                                                           ObsSet ob, Ls... ls)
 {
     const int bi = g.ni + dx, bj = g.nj + dy, bk = g.nk + dz;
     BQ_IJK(bi, bj, bk)
     const float h = sp.h;
-    if (obs_classify(ob, obs_pos(i, dx, h), obs_pos(j, dy, h), obs_pos(kg, dz, h)) != -1) return;
-    const size_t id = (size_t)i + (size_t)bi * j + (size_t)bi * bj * k;
-    if (!(i > 1 && i < bi - 2 - dx && j > 1 && j < bj - 2 - dy && kg > 1 && kg < g.nkg - 2)) { field[id] = 0.f; return; }
-    Vel3 vel{make_field(u, g.ni + 1, g.nj, g.nk, g.koff), make_field(v, g.ni, g.nj + 1, g.nk, g.koff), make_field(w, g.ni, g.nj, g.nk + 1, g.koff)};
-    Field src = make_field(field_src, bi, bj, bk, g.koff);
-    f3 org = mk3(-(float)dx * 0.5f * h, -(float)dy * 0.5f * h, -(float)dz * 0.5f * h);
-    f3 hi = mk3((float)g.ni * h - h, (float)g.nj * h - h, (float)g.nkg * h - h);
-    f3 pt = mk3(h * (float)i + org.x, h * (float)j + org.y, h * (float)kg + org.z);
-    f3 pn = trace<P2>(vel, sp, hi, cfldt, dt, pt);
-    field[id] = sample<P2>(src, sp, org, pn);
-}
-
-// semilag_band_kernel for lists that hold level sets (obs_classify_t<true>)
-template <bool P2>
-__global__ __launch_bounds__(256) void semilag_band_ls_kernel(float *field, const float *field_src,
-                                                              const float *u, const float *v, const float *w,
-                                                              Spacing sp, Grid g, int dx, int dy, int dz, float cfldt, float dt,
-                                                              ObsSet ob, LsSet ls)
-{
-    const int bi = g.ni + dx, bj = g.nj + dy, bk = g.nk + dz;
-    BQ_IJK(bi, bj, bk)
-    const float h = sp.h;
-    if (obs_classify_t<true>(ob, &ls, obs_pos(i, dx, h), obs_pos(j, dy, h), obs_pos(kg, dz, h)) != -1) return;
+    if (obs_classify(obs_pos(i, dx, h), obs_pos(j, dy, h), obs_pos(kg, dz, h), ob, ls...) != -1) return;
     const size_t id = (size_t)i + (size_t)bi * j + (size_t)bi * bj * k;
     if (!(i > 1 && i < bi - 2 - dx && j > 1 && j < bj - 2 - dy && kg > 1 && kg < g.nkg - 2)) { field[id] = 0.f; return; }
     Vel3 vel{make_field(u, g.ni + 1, g.nj, g.nk, g.koff), make_field(v, g.ni, g.nj + 1, g.nk, g.koff), make_field(w, g.ni, g.nj, g.nk + 1, g.koff)};
@@ -1345,34 +1324,37 @@ BQ_ENTRY(gpu_semilag, (float *field, float *field_src, float *u, float *v, float
     BQ_DISPATCH1(semilag_kernel, sp.pow2, grid_for(ni + dim_x, nj + dim_y, nk + dim_z), field, field_src, u, v, w, sp, g, dim_x, dim_y, dim_z, cfldt, dt);
 }
 
+// gpu_semilag_band and gpu_semilag_band_ls: one set of checks, the analytic kernel whenever there are no descriptors
+static void semilag_band(float *field, float *field_src, float *u, float *v, float *w, int dim_x, int dim_y, int dim_z,
+                         float h, int ni, int nj, int nk, float cfldt, float dt, const bq_boundary *b, int n,
+                         const bq_levelset *ls, const char *op)
+{
+    BQ_ENTER(op, field, field_src, u, v, w)
+    BQ_REQUIRE(cfldt > 0.f || dt == 0.f, op);
+    BQ_REQUIRE((dim_x | dim_y | dim_z) == 0 || (dim_x + dim_y + dim_z) == 1, op);
+    BQ_REQUIRE(n >= 0 && n <= BQ_MAX_BOUNDARIES && (b || n == 0), op);
+    if (const char *why = ls_check(b, ls, n)) { latch(FL_ERR_BAD_ARGUMENT, op, why); return; }
+    if (n == 0) return;
+    Spacing sp = make_spacing(h); Grid g = mk_grid(ni, nj, nk);
+    const dim3 grid = grid_for(ni + dim_x, nj + dim_y, nk + dim_z);
+    if (ls)
+        BQ_DISPATCH1(semilag_band_kernel, sp.pow2, grid, field, field_src, u, v, w, sp, g, dim_x, dim_y, dim_z, cfldt, dt, make_obs(b, n, h), make_ls(b, ls, n));
+    else
+        BQ_DISPATCH1(semilag_band_kernel, sp.pow2, grid, field, field_src, u, v, w, sp, g, dim_x, dim_y, dim_z, cfldt, dt, make_obs(b, n, h));
+}
+
 BQ_ENTRY(gpu_semilag_band, (float *field, float *field_src, float *u, float *v, float *w, int dim_x, int dim_y, int dim_z,
                       float h, int ni, int nj, int nk, float cfldt, float dt, const bq_boundary *b, int n),
          (field, field_src, u, v, w, dim_x, dim_y, dim_z, h, ni, nj, nk, cfldt, dt, b, n))
 {
-    BQ_ENTER("gpu_semilag_band", field, field_src, u, v, w)
-    BQ_REQUIRE(cfldt > 0.f || dt == 0.f, "gpu_semilag_band");
-    BQ_REQUIRE((dim_x | dim_y | dim_z) == 0 || (dim_x + dim_y + dim_z) == 1, "gpu_semilag_band");
-    BQ_REQUIRE(n >= 0 && n <= BQ_MAX_BOUNDARIES && (b || n == 0), "gpu_semilag_band");
-    if (n == 0) return;
-    Spacing sp = make_spacing(h); Grid g = mk_grid(ni, nj, nk);
-    const ObsSet ob = make_obs(b, n, h);
-    BQ_DISPATCH1(semilag_band_kernel, sp.pow2, grid_for(ni + dim_x, nj + dim_y, nk + dim_z), field, field_src, u, v, w, sp, g, dim_x, dim_y, dim_z, cfldt, dt, ob);
+    semilag_band(field, field_src, u, v, w, dim_x, dim_y, dim_z, h, ni, nj, nk, cfldt, dt, b, n, nullptr, "gpu_semilag_band");
 }
 
 BQ_ENTRY(gpu_semilag_band_ls, (float *field, float *field_src, float *u, float *v, float *w, int dim_x, int dim_y, int dim_z,
                          float h, int ni, int nj, int nk, float cfldt, float dt, const bq_boundary *b, int n, const bq_levelset *ls),
          (field, field_src, u, v, w, dim_x, dim_y, dim_z, h, ni, nj, nk, cfldt, dt, b, n, ls))
 {
-    BQ_ENTER("gpu_semilag_band_ls", field, field_src, u, v, w)
-    BQ_REQUIRE(cfldt > 0.f || dt == 0.f, "gpu_semilag_band_ls");
-    BQ_REQUIRE((dim_x | dim_y | dim_z) == 0 || (dim_x + dim_y + dim_z) == 1, "gpu_semilag_band_ls");
-    BQ_REQUIRE(n >= 0 && n <= BQ_MAX_BOUNDARIES && (b || n == 0), "gpu_semilag_band_ls");
-    if (const char *why = ls_check(b, ls, n)) { latch(FL_ERR_BAD_ARGUMENT, "gpu_semilag_band_ls", why); return; }
-    if (n == 0) return;
-    Spacing sp = make_spacing(h); Grid g = mk_grid(ni, nj, nk);
-    const ObsSet ob = make_obs(b, n, h);
-    const LsSet lss = make_ls(b, ls, n);
-    BQ_DISPATCH1(semilag_band_ls_kernel, sp.pow2, grid_for(ni + dim_x, nj + dim_y, nk + dim_z), field, field_src, u, v, w, sp, g, dim_x, dim_y, dim_z, cfldt, dt, ob, lss);
+    semilag_band(field, field_src, u, v, w, dim_x, dim_y, dim_z, h, ni, nj, nk, cfldt, dt, b, n, ls, "gpu_semilag_band_ls");
 }
 
 BQ_ENTRY(gpu_clamp_extrema, (float *field, float *fieldTemp, float *u, float *v, float *w,

@@ -12,12 +12,13 @@ static const dim3 kBlockO(64, 4, 1);
 static inline dim3 grid_o(int a, int b, int c) { return dim3((a + 63) / 64, (b + 3) / 4, c); }
 
 // ---- flags: one thread per cell; a solid cell marks the rows summary of its own row and plane and the neighbouring ones --
+template <typename... Ls>
 __global__ __launch_bounds__(256) void obstacle_flags_kernel(unsigned char *__restrict__ solid, unsigned char *__restrict__ rows,
-                                                             ObsSet ob, float h, int ni, int nj, int nk)
+                                                             ObsSet ob, Ls... ls, float h, int ni, int nj, int nk)
 {
     const int i = blockIdx.x * 64 + threadIdx.x, j = blockIdx.y * 4 + threadIdx.y, k = blockIdx.z;
     if (i >= ni || j >= nj) return;
-    const int c = obs_classify(ob, obs_pos(i, 0, h), obs_pos(j, 0, h), obs_pos(k, 0, h));
+    const int c = obs_classify(obs_pos(i, 0, h), obs_pos(j, 0, h), obs_pos(k, 0, h), ob, ls...);
     const unsigned char f = c > 0 ? (unsigned char)c : 0;
     solid[(size_t)i + (size_t)ni * ((size_t)j + (size_t)nj * k)] = f;
     if (!f) return;
@@ -134,81 +135,35 @@ __global__ __launch_bounds__(256) void gradient_masked_kernel(float *__restrict_
 }
 
 // ---- band blend + density clear: one thread per super-grid node -------------------------------------------------------
+template <typename... Ls>
 __global__ __launch_bounds__(256) void obstacle_blend_kernel(float *__restrict__ u, float *__restrict__ v, float *__restrict__ w,
                                                              float *__restrict__ rho, float *__restrict__ T,
                                                              const float *__restrict__ us, const float *__restrict__ vs,
                                                              const float *__restrict__ ws, const float *__restrict__ rhos,
                                                              const float *__restrict__ Ts, const unsigned char *__restrict__ solid,
-                                                             ObsSet ob, float h, int ni, int nj, int nk)
+                                                             ObsSet ob, Ls... ls, float h, int ni, int nj, int nk)
 {
     const int i = blockIdx.x * 64 + threadIdx.x, j = blockIdx.y * 4 + threadIdx.y, k = blockIdx.z;
     if (i > ni || j > nj || k > nk) return;
     const float x0 = obs_pos(i, 0, h), y0 = obs_pos(j, 0, h), z0 = obs_pos(k, 0, h);
     const float x1 = obs_pos(i, 1, h), y1 = obs_pos(j, 1, h), z1 = obs_pos(k, 1, h);
     if (us) {
-        if (j < nj && k < nk && obs_classify(ob, x1, y0, z0) == -1) {
+        if (j < nj && k < nk && obs_classify(x1, y0, z0, ob, ls...) == -1) {
             const size_t id = (size_t)i + (size_t)(ni + 1) * ((size_t)j + (size_t)nj * k);
             u[id] = us[id];
         }
-        if (i < ni && k < nk && obs_classify(ob, x0, y1, z0) == -1) {
+        if (i < ni && k < nk && obs_classify(x0, y1, z0, ob, ls...) == -1) {
             const size_t id = (size_t)i + (size_t)ni * ((size_t)j + (size_t)(nj + 1) * k);
             v[id] = vs[id];
         }
-        if (i < ni && j < nj && obs_classify(ob, x0, y0, z1) == -1) {
+        if (i < ni && j < nj && obs_classify(x0, y0, z1, ob, ls...) == -1) {
             const size_t id = (size_t)i + (size_t)ni * ((size_t)j + (size_t)nj * k);
             w[id] = ws[id];
         }
     }
     if (i < ni && j < nj && k < nk) {
         const size_t id = (size_t)i + (size_t)ni * ((size_t)j + (size_t)nj * k);
-        if (us && obs_classify(ob, x0, y0, z0) == -1) { rho[id] = rhos[id]; T[id] = Ts[id]; }
-        if (solid[id]) rho[id] = 0.f;
-    }
-}
-
-// ---- the flags and blend kernels for lists that hold level sets: the same threads, obs_classify_t<true> ------------------
-__global__ __launch_bounds__(256) void obstacle_flags_ls_kernel(unsigned char *__restrict__ solid, unsigned char *__restrict__ rows,
-                                                                ObsSet ob, LsSet ls, float h, int ni, int nj, int nk)
-{
-    const int i = blockIdx.x * 64 + threadIdx.x, j = blockIdx.y * 4 + threadIdx.y, k = blockIdx.z;
-    if (i >= ni || j >= nj) return;
-    const int c = obs_classify_t<true>(ob, &ls, obs_pos(i, 0, h), obs_pos(j, 0, h), obs_pos(k, 0, h));
-    const unsigned char f = c > 0 ? (unsigned char)c : 0;
-    solid[(size_t)i + (size_t)ni * ((size_t)j + (size_t)nj * k)] = f;
-    if (!f) return;
-    for (int kk = max(k - 1, 0); kk <= min(k + 1, nk - 1); kk++)
-        for (int jj = max(j - 1, 0); jj <= min(j + 1, nj - 1); jj++)
-            rows[(size_t)jj + (size_t)nj * kk] = 1;
-}
-
-__global__ __launch_bounds__(256) void obstacle_blend_ls_kernel(float *__restrict__ u, float *__restrict__ v, float *__restrict__ w,
-                                                                float *__restrict__ rho, float *__restrict__ T,
-                                                                const float *__restrict__ us, const float *__restrict__ vs,
-                                                                const float *__restrict__ ws, const float *__restrict__ rhos,
-                                                                const float *__restrict__ Ts, const unsigned char *__restrict__ solid,
-                                                                ObsSet ob, LsSet ls, float h, int ni, int nj, int nk)
-{
-    const int i = blockIdx.x * 64 + threadIdx.x, j = blockIdx.y * 4 + threadIdx.y, k = blockIdx.z;
-    if (i > ni || j > nj || k > nk) return;
-    const float x0 = obs_pos(i, 0, h), y0 = obs_pos(j, 0, h), z0 = obs_pos(k, 0, h);
-    const float x1 = obs_pos(i, 1, h), y1 = obs_pos(j, 1, h), z1 = obs_pos(k, 1, h);
-    if (us) {
-        if (j < nj && k < nk && obs_classify_t<true>(ob, &ls, x1, y0, z0) == -1) {
-            const size_t id = (size_t)i + (size_t)(ni + 1) * ((size_t)j + (size_t)nj * k);
-            u[id] = us[id];
-        }
-        if (i < ni && k < nk && obs_classify_t<true>(ob, &ls, x0, y1, z0) == -1) {
-            const size_t id = (size_t)i + (size_t)ni * ((size_t)j + (size_t)(nj + 1) * k);
-            v[id] = vs[id];
-        }
-        if (i < ni && j < nj && obs_classify_t<true>(ob, &ls, x0, y0, z1) == -1) {
-            const size_t id = (size_t)i + (size_t)ni * ((size_t)j + (size_t)nj * k);
-            w[id] = ws[id];
-        }
-    }
-    if (i < ni && j < nj && k < nk) {
-        const size_t id = (size_t)i + (size_t)ni * ((size_t)j + (size_t)nj * k);
-        if (us && obs_classify_t<true>(ob, &ls, x0, y0, z0) == -1) { rho[id] = rhos[id]; T[id] = Ts[id]; }
+        if (us && obs_classify(x0, y0, z0, ob, ls...) == -1) { rho[id] = rhos[id]; T[id] = Ts[id]; }
         if (solid[id]) rho[id] = 0.f;
     }
 }
@@ -225,6 +180,37 @@ static bool obs_args_ok(const bq_boundary *b, int n, int ni, int nj, int nk, con
     return true;
 }
 
+// gpu_obstacle_flags and gpu_obstacle_blend with (ls non-NULL) and without level sets: one set of checks, and the
+// analytic kernels whenever there are no descriptors
+static void obstacle_flags(unsigned char *solid, unsigned char *rows, const bq_boundary *b, int n, const bq_levelset *ls,
+                           float h, int ni, int nj, int nk, const char *op)
+{
+    if (!obs_args_ok(b, n, ni, nj, nk, op)) return;
+    if (const char *why = ls_check(b, ls, n)) { latch(FL_ERR_BAD_ARGUMENT, op, why); return; }
+    if (!solid || !rows) { latch(FL_ERR_BAD_ARGUMENT, op, "null device pointer"); return; }
+    if (!BQ_HIP(hipMemsetAsync(rows, 0, (size_t)nj * (size_t)nk, rt().compute))) return;
+    if (ls)
+        obstacle_flags_kernel<LsSet><<<grid_o(ni, nj, nk), kBlockO, 0, rt().compute>>>(solid, rows, make_obs(b, n, h), make_ls(b, ls, n), h, ni, nj, nk);
+    else
+        obstacle_flags_kernel<><<<grid_o(ni, nj, nk), kBlockO, 0, rt().compute>>>(solid, rows, make_obs(b, n, h), h, ni, nj, nk);
+    BQ_LAUNCH_CHECK("obstacle_flags_kernel");
+}
+
+static void obstacle_blend(float *u, float *v, float *w, float *rho, float *T, const float *us, const float *vs,
+                           const float *ws, const float *rhos, const float *Ts, const unsigned char *solid,
+                           const bq_boundary *b, int n, const bq_levelset *ls, float h, int ni, int nj, int nk, const char *op)
+{
+    if (!obs_args_ok(b, n, ni, nj, nk, op)) return;
+    if (const char *why = ls_check(b, ls, n)) { latch(FL_ERR_BAD_ARGUMENT, op, why); return; }
+    if (!rho || !solid || (us && (!u || !v || !w || !T || !vs || !ws || !rhos || !Ts))) { latch(FL_ERR_BAD_ARGUMENT, op, "null device pointer"); return; }
+    const dim3 grid = grid_o(ni + 1, nj + 1, nk + 1);
+    if (ls)
+        obstacle_blend_kernel<LsSet><<<grid, kBlockO, 0, rt().compute>>>(u, v, w, rho, T, us, vs, ws, rhos, Ts, solid, make_obs(b, n, h), make_ls(b, ls, n), h, ni, nj, nk);
+    else
+        obstacle_blend_kernel<><<<grid, kBlockO, 0, rt().compute>>>(u, v, w, rho, T, us, vs, ws, rhos, Ts, solid, make_obs(b, n, h), h, ni, nj, nk);
+    BQ_LAUNCH_CHECK("obstacle_blend_kernel");
+}
+
 bool jacobi_sweep_triple_masked(const float *in, const float *div, float *out, int ni, int nj, int nk, float alpha,
                                 const unsigned char *solid, const unsigned char *rows, const float betas[7]);   // bq_project.hip
 
@@ -236,11 +222,7 @@ extern "C" {
 
 void gpu_obstacle_flags(unsigned char *solid, unsigned char *rows, const bq_boundary *b, int n, float h, int ni, int nj, int nk)
 {
-    if (!obs_args_ok(b, n, ni, nj, nk, "gpu_obstacle_flags")) return;
-    if (!solid || !rows) { latch(FL_ERR_BAD_ARGUMENT, "gpu_obstacle_flags", "null device pointer"); return; }
-    if (!BQ_HIP(hipMemsetAsync(rows, 0, (size_t)nj * (size_t)nk, rt().compute))) return;
-    obstacle_flags_kernel<<<grid_o(ni, nj, nk), kBlockO, 0, rt().compute>>>(solid, rows, make_obs(b, n, h), h, ni, nj, nk);
-    BQ_LAUNCH_CHECK("obstacle_flags_kernel");
+    obstacle_flags(solid, rows, b, n, nullptr, h, ni, nj, nk, "gpu_obstacle_flags");
 }
 
 void gpu_obstacle_faces(float *u, float *v, float *w, float *du, float *dv, float *dw, const unsigned char *solid,
@@ -313,33 +295,20 @@ void gpu_obstacle_blend(float *u, float *v, float *w, float *rho, float *T, cons
                         const float *ws, const float *rhos, const float *Ts, const unsigned char *solid,
                         const bq_boundary *b, int n, float h, int ni, int nj, int nk)
 {
-    if (!obs_args_ok(b, n, ni, nj, nk, "gpu_obstacle_blend")) return;
-    if (!rho || !solid || (us && (!u || !v || !w || !T || !vs || !ws || !rhos || !Ts))) { latch(FL_ERR_BAD_ARGUMENT, "gpu_obstacle_blend", "null device pointer"); return; }
-    obstacle_blend_kernel<<<grid_o(ni + 1, nj + 1, nk + 1), kBlockO, 0, rt().compute>>>(u, v, w, rho, T, us, vs, ws, rhos, Ts, solid, make_obs(b, n, h), h, ni, nj, nk);
-    BQ_LAUNCH_CHECK("obstacle_blend_kernel");
+    obstacle_blend(u, v, w, rho, T, us, vs, ws, rhos, Ts, solid, b, n, nullptr, h, ni, nj, nk, "gpu_obstacle_blend");
 }
 
 void gpu_obstacle_flags_ls(unsigned char *solid, unsigned char *rows, const bq_boundary *b, int n, const bq_levelset *ls,
                            float h, int ni, int nj, int nk)
 {
-    if (!obs_args_ok(b, n, ni, nj, nk, "gpu_obstacle_flags_ls")) return;
-    if (const char *why = ls_check(b, ls, n)) { latch(FL_ERR_BAD_ARGUMENT, "gpu_obstacle_flags_ls", why); return; }
-    if (!solid || !rows) { latch(FL_ERR_BAD_ARGUMENT, "gpu_obstacle_flags_ls", "null device pointer"); return; }
-    if (!BQ_HIP(hipMemsetAsync(rows, 0, (size_t)nj * (size_t)nk, rt().compute))) return;
-    obstacle_flags_ls_kernel<<<grid_o(ni, nj, nk), kBlockO, 0, rt().compute>>>(solid, rows, make_obs(b, n, h), make_ls(b, ls, n), h, ni, nj, nk);
-    BQ_LAUNCH_CHECK("obstacle_flags_ls_kernel");
+    obstacle_flags(solid, rows, b, n, ls, h, ni, nj, nk, "gpu_obstacle_flags_ls");
 }
 
 void gpu_obstacle_blend_ls(float *u, float *v, float *w, float *rho, float *T, const float *us, const float *vs,
                            const float *ws, const float *rhos, const float *Ts, const unsigned char *solid,
                            const bq_boundary *b, int n, const bq_levelset *ls, float h, int ni, int nj, int nk)
 {
-    if (!obs_args_ok(b, n, ni, nj, nk, "gpu_obstacle_blend_ls")) return;
-    if (const char *why = ls_check(b, ls, n)) { latch(FL_ERR_BAD_ARGUMENT, "gpu_obstacle_blend_ls", why); return; }
-    if (!rho || !solid || (us && (!u || !v || !w || !T || !vs || !ws || !rhos || !Ts))) { latch(FL_ERR_BAD_ARGUMENT, "gpu_obstacle_blend_ls", "null device pointer"); return; }
-    obstacle_blend_ls_kernel<<<grid_o(ni + 1, nj + 1, nk + 1), kBlockO, 0, rt().compute>>>(u, v, w, rho, T, us, vs, ws, rhos, Ts, solid,
-                                                                                          make_obs(b, n, h), make_ls(b, ls, n), h, ni, nj, nk);
-    BQ_LAUNCH_CHECK("obstacle_blend_ls_kernel");
+    obstacle_blend(u, v, w, rho, T, us, vs, ws, rhos, Ts, solid, b, n, ls, h, ni, nj, nk, "gpu_obstacle_blend_ls");
 }
 
 } // extern "C"

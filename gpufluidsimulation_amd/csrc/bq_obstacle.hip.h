@@ -3,8 +3,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "bimocq_gpu.h"
+#include "bq_levelset.h"
 
-#include <climits>
 #include <cmath>
 
 namespace bq {
@@ -32,7 +32,9 @@ static inline ObsSet make_obs(const bq_boundary *b, int n, float h)
     return s;
 }
 
-// the level sets of a list (entries whose shape is BQ_SHAPE_LEVELSET; the others are left empty): a kernel argument
+// the level sets of a list (entries whose shape is BQ_SHAPE_LEVELSET; the others are left empty).  A kernel takes the
+// list as `ObsSet ob, Ls... ls`: the pack Ls is empty for lists without level sets and LsSet for the others.  (As one
+// aggregate kernel argument, the level-set band semi-Lagrangian kernel's trace is scheduled for fewer waves.)
 struct LsSet {
     const float *phi[BQ_MAX_BOUNDARIES];
     int nx[BQ_MAX_BOUNDARIES], ny[BQ_MAX_BOUNDARIES], nz[BQ_MAX_BOUNDARIES];
@@ -52,25 +54,6 @@ static inline LsSet make_ls(const bq_boundary *b, const bq_levelset *ls, int n)
         s.voxel[o] = l.voxel; s.bg[o] = l.background;
     }
     return s;
-}
-
-// NULL when every level-set entry of b[0 .. n) has a usable descriptor in ls[], else what is wrong
-static inline const char *ls_check(const bq_boundary *b, const bq_levelset *ls, int n)
-{
-    for (int o = 0; o < n; o++) {
-        if (b[o].shape != BQ_SHAPE_LEVELSET) continue;
-        if (!ls) return "level-set entry without descriptors";
-        const bq_levelset &l = ls[o];
-        if (!l.phi) return "level set with a null grid";
-        if (l.nx < 2 || l.ny < 2 || l.nz < 2 || (double)l.nx * (double)l.ny * (double)l.nz >= 2147483648.0)
-            return "level-set dimensions below 2 or 2^31 nodes and more";
-        if ((long long)l.i0 - 1 < INT_MIN || (long long)l.j0 - 1 < INT_MIN || (long long)l.k0 - 1 < INT_MIN ||
-            (long long)l.i0 + l.nx > INT_MAX || (long long)l.j0 + l.ny > INT_MAX || (long long)l.k0 + l.nz > INT_MAX)
-            return "level-set index range beyond int";
-        if (!(l.voxel > 0.f) || !(l.background > 0.f) || !std::isfinite(l.voxel) || !std::isfinite(l.background))
-            return "level-set voxel or background not finite and positive";
-    }
-    return nullptr;
 }
 
 // p + (q - p) t with the difference and the sum in float and the product in double (BoxSampler's lerp)
@@ -107,20 +90,22 @@ __device__ __forceinline__ bool ls_sample(const LsSet &l, int o, float x, float 
 }
 
 // o + 1 when obstacle o is the last one covering (x, y, z); -1 when the point lies in the band of some obstacle and
-// inside none; 0 otherwise.  LS = false: analytic entries only (ls unread); LS = true: level-set entries are sampled,
-// solid when the sample is <= 0, band when 0 < sample < background.
-template <bool LS>
-__device__ __forceinline__ int obs_classify_t(const ObsSet &s, const LsSet *ls, float x, float y, float z)
+// inside none; 0 otherwise.  Without ls: analytic entries only; with ls (one LsSet): level-set entries are sampled, solid
+// when the sample is <= 0, band when 0 < sample < background.
+template <typename... Ls>
+__device__ __forceinline__ int obs_classify(float x, float y, float z, const ObsSet &s, const Ls &...ls)
 {
+    static_assert(sizeof...(Ls) <= 1, "one LsSet at most");
     int solid = 0;
     bool band = false;
     for (int o = 0; o < s.n; o++) {
-        if constexpr (LS) {
+        if constexpr (sizeof...(Ls) == 1) {
             if (s.shape[o] == BQ_SHAPE_LEVELSET) {
+                const LsSet &l = (ls, ...);
                 float sdf;
-                if (ls_sample(*ls, o, x, y, z, s.cx[o], s.cy[o], s.cz[o], sdf)) {
+                if (ls_sample(l, o, x, y, z, s.cx[o], s.cy[o], s.cz[o], sdf)) {
                     if (sdf <= 0.f) solid = o + 1;
-                    else if (sdf < ls->bg[o]) band = true;
+                    else if (sdf < l.bg[o]) band = true;
                 }
                 continue;
             }
@@ -144,8 +129,6 @@ __device__ __forceinline__ int obs_classify_t(const ObsSet &s, const LsSet *ls, 
     }
     return solid ? solid : (band ? -1 : 0);
 }
-
-__device__ __forceinline__ int obs_classify(const ObsSet &s, float x, float y, float z) { return obs_classify_t<false>(s, nullptr, x, y, z); }
 
 // sample position of node i on an axis with stagger d (0: cell centre, 1: face): (i - d/2) h
 __device__ __forceinline__ float obs_pos(int i, int d, float h) { return ((float)i - (d ? 0.5f : 0.f)) * h; }

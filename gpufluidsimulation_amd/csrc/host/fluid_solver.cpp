@@ -11,13 +11,14 @@
 // planes of every field are correct and exchange them with the z-neighbours exactly when an operator
 // reaches further than that (no-ops on a single GPU).
 #include "fluid_solver.hpp"
+#include "../bq_levelset.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
-#include <climits>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 
 // The obstacle operators are weak references: the CPU stand-ins of the operator ABI that the host tests link against need
 // not provide them (the references resolve to null there), and setBoundary refuses obstacles when they are missing.
@@ -32,6 +33,31 @@
 #pragma weak gpu_obstacle_blend_ls
 
 namespace bqhost {
+
+// The obstacle operators for a list with level-set descriptors ls (non-NULL only when it holds a level set, and then
+// setBoundary has found the _ls operators), else the analytic ones: runs without level sets issue the launches they did
+// before level sets existed, and the stand-ins without the _ls operators still run analytic lists.
+static void obstacle_flags(unsigned char *solid, unsigned char *rows, const bq_boundary *b, int n, const bq_levelset *ls, float h,
+                           int ni, int nj, int nk)
+{
+    if (ls) gpu_obstacle_flags_ls(solid, rows, b, n, ls, h, ni, nj, nk);
+    else    gpu_obstacle_flags(solid, rows, b, n, h, ni, nj, nk);
+}
+
+static void semilag_band(float *field, float *field_src, float *u, float *v, float *w, int dim_x, int dim_y, int dim_z, float h,
+                         int ni, int nj, int nk, float cfldt, float dt, const bq_boundary *b, int n, const bq_levelset *ls)
+{
+    if (ls) gpu_semilag_band_ls(field, field_src, u, v, w, dim_x, dim_y, dim_z, h, ni, nj, nk, cfldt, dt, b, n, ls);
+    else    gpu_semilag_band(field, field_src, u, v, w, dim_x, dim_y, dim_z, h, ni, nj, nk, cfldt, dt, b, n);
+}
+
+static void obstacle_blend(float *u, float *v, float *w, float *rho, float *T, const float *us, const float *vs, const float *ws,
+                           const float *rhos, const float *Ts, const unsigned char *solid, const bq_boundary *b, int n,
+                           const bq_levelset *ls, float h, int ni, int nj, int nk)
+{
+    if (ls) gpu_obstacle_blend_ls(u, v, w, rho, T, us, vs, ws, rhos, Ts, solid, b, n, ls, h, ni, nj, nk);
+    else    gpu_obstacle_blend(u, v, w, rho, T, us, vs, ws, rhos, Ts, solid, b, n, h, ni, nj, nk);
+}
 
 // BQ_TRACE=1 (debug): after each stage print the sum of squares of the planes this rank owns, so a
 // slab run can be compared stage by stage with a single-GPU run (sum the ranks' lines).
@@ -462,8 +488,10 @@ std::vector<double> BimocqGPUSolver::mgHistory() const
 }
 
 // setBoundary (BimocqSolver.cpp:936-1064 without the domain walls): the list replaces the previous one, the flags are built
-// at the given centres.  n = 0 removes every obstacle and the step is exactly the one without this feature.
-bool BimocqGPUSolver::setBoundary(const bq_boundary *b, int n)
+// at the given centres.  n = 0 removes every obstacle and the step is exactly the one without this feature.  ls[o] is read
+// for the entries of shape BQ_SHAPE_LEVELSET ("Level sets"), its phi a HOST array that is copied into
+// one device allocation with every other grid of the list.  A refused list leaves the previous one in place.
+bool BimocqGPUSolver::setBoundary(const bq_boundary *b, const bq_levelset *ls, int n)
 {
     if (n < 0 || n > BQ_MAX_BOUNDARIES || (n > 0 && !b)) {
         fl_report_error(FL_ERR_BAD_ARGUMENT, "setBoundary: 0 .. 16 obstacles");
@@ -486,126 +514,60 @@ bool BimocqGPUSolver::setBoundary(const bq_boundary *b, int n)
         fl_report_error(FL_ERR_UNSUPPORTED, "setBoundary: the operator library has no obstacle operators");
         return false;
     }
-    for (int o = 0; o < n; o++) {
-        const bq_boundary &x = b[o];
-        const bool sphere = x.shape == BQ_SHAPE_SPHERE;
-        if ((!sphere && x.shape != BQ_SHAPE_BOX) || !(x.rx > 0.f) || (!sphere && !(x.ry > 0.f && x.rz > 0.f)) ||
-            !std::isfinite(x.cx) || !std::isfinite(x.cy) || !std::isfinite(x.cz) || !std::isfinite(x.rx) ||
-            !std::isfinite(x.ry) || !std::isfinite(x.rz) || !std::isfinite(x.vx) || !std::isfinite(x.vy) || !std::isfinite(x.vz)) {
-            fl_report_error(FL_ERR_BAD_ARGUMENT, "setBoundary: unknown shape, non-positive size or non-finite value");
-            return false;
-        }
-    }
-    const size_t nrows = (size_t)g.nj * (size_t)g.nk;
-    if (solid.bytes() != g.n() && !solid.alloc(g.n())) return false;
-    if (rows.bytes() != nrows && !rows.alloc(nrows)) return false;
-    std::vector<bq_boundary> list(b, b + n);
-    if (!buildFlags(list, nullptr)) return false;
-    boundaries.swap(list);
-    levelsets.clear();
-    lsgrids.release();
-    return true;
-}
-
-// setBoundary for lists that may hold level sets ("Level sets"): ls[o] is read for the entries of
-// shape BQ_SHAPE_LEVELSET, its phi a HOST array that is copied into one device allocation with every other grid of the
-// list.  Any failure leaves no obstacles at all.
-bool BimocqGPUSolver::setBoundaryLevelsets(const bq_boundary *b, const bq_levelset *ls, int n)
-{
-    if (setBoundaryLevelsetsOrFail(b, ls, n)) return true;
-    dropBoundaries();
-    return false;
-}
-
-bool BimocqGPUSolver::setBoundaryLevelsetsOrFail(const bq_boundary *b, const bq_levelset *ls, int n)
-{
-    bool any = false;
-    for (int o = 0; b && o < n && o < BQ_MAX_BOUNDARIES; o++) any |= b[o].shape == BQ_SHAPE_LEVELSET;
-    if (!any) return setBoundary(b, n);                 // the refusals of n, slab, MGCG and every analytic check
-    if (n > BQ_MAX_BOUNDARIES) {
-        fl_report_error(FL_ERR_BAD_ARGUMENT, "setBoundary: 0 .. 16 obstacles");
-        return false;
-    }
-    if (GpuSolver->slab.on) {
-        fl_report_error(FL_ERR_UNSUPPORTED, "setBoundary: obstacles are not supported on z-slab ranks");
-        return false;
-    }
-    if (projection_kind != BQ_PROJECTION_JACOBI) {
-        fl_report_error(FL_ERR_UNSUPPORTED, "setBoundary: obstacles need the Jacobi projection (not BQ_PROJECTION_MGCG)");
-        return false;
-    }
-    if (!gpu_obstacle_flags || !gpu_obstacle_faces || !gpu_jacobi_sweeps_masked || !gpu_gradient_masked || !gpu_semilag_band ||
-        !gpu_obstacle_blend) {
-        fl_report_error(FL_ERR_UNSUPPORTED, "setBoundary: the operator library has no obstacle operators");
-        return false;
-    }
-    if (!gpu_obstacle_flags_ls || !gpu_semilag_band_ls || !gpu_obstacle_blend_ls) {
-        fl_report_error(FL_ERR_UNSUPPORTED, "setBoundary: the operator library has no level-set obstacle operators");
-        return false;
-    }
-    if (!ls) {
+    const bool any_ls = std::any_of(b, b + n, [](const bq_boundary &x) { return x.shape == BQ_SHAPE_LEVELSET; });
+    if (any_ls && !ls) {
         fl_report_error(FL_ERR_BAD_ARGUMENT, "setBoundary: level-set entries without descriptors");
         return false;
     }
-    const double cap = (double)kMaxLevelsetBytes;
-    double total = 0.0;
+    if (any_ls && (!gpu_obstacle_flags_ls || !gpu_semilag_band_ls || !gpu_obstacle_blend_ls)) {
+        fl_report_error(FL_ERR_UNSUPPORTED, "setBoundary: the operator library has no level-set obstacle operators");
+        return false;
+    }
     for (int o = 0; o < n; o++) {
         const bq_boundary &x = b[o];
-        if (x.shape != BQ_SHAPE_LEVELSET) {
-            const bool sphere = x.shape == BQ_SHAPE_SPHERE;
-            if ((!sphere && x.shape != BQ_SHAPE_BOX) || !(x.rx > 0.f) || (!sphere && !(x.ry > 0.f && x.rz > 0.f)) ||
-                !std::isfinite(x.rx) || !std::isfinite(x.ry) || !std::isfinite(x.rz)) {
-                fl_report_error(FL_ERR_BAD_ARGUMENT, "setBoundary: unknown shape, non-positive size or non-finite value");
-                return false;
-            }
-        }
-        if (!std::isfinite(x.cx) || !std::isfinite(x.cy) || !std::isfinite(x.cz) || !std::isfinite(x.vx) ||
+        const bool sphere = x.shape == BQ_SHAPE_SPHERE, levelset = x.shape == BQ_SHAPE_LEVELSET;   // a level set has no radii
+        if ((!levelset && ((!sphere && x.shape != BQ_SHAPE_BOX) || !(x.rx > 0.f) || (!sphere && !(x.ry > 0.f && x.rz > 0.f)) ||
+                           !std::isfinite(x.rx) || !std::isfinite(x.ry) || !std::isfinite(x.rz))) ||
+            !std::isfinite(x.cx) || !std::isfinite(x.cy) || !std::isfinite(x.cz) || !std::isfinite(x.vx) ||
             !std::isfinite(x.vy) || !std::isfinite(x.vz)) {
             fl_report_error(FL_ERR_BAD_ARGUMENT, "setBoundary: unknown shape, non-positive size or non-finite value");
             return false;
         }
-        if (x.shape != BQ_SHAPE_LEVELSET) continue;
-        const bq_levelset &l = ls[o];
-        const double nodes = (double)l.nx * (double)l.ny * (double)l.nz;
-        if (!l.phi || l.nx < 2 || l.ny < 2 || l.nz < 2 || nodes >= 2147483648.0) {
-            fl_report_error(FL_ERR_BAD_ARGUMENT, "setBoundary: level set without a grid, a dimension below 2 or 2^31 nodes");
-            return false;
-        }
-        if ((long long)l.i0 - 1 < INT_MIN || (long long)l.j0 - 1 < INT_MIN || (long long)l.k0 - 1 < INT_MIN ||
-            (long long)l.i0 + l.nx > INT_MAX || (long long)l.j0 + l.ny > INT_MAX || (long long)l.k0 + l.nz > INT_MAX) {
-            fl_report_error(FL_ERR_BAD_ARGUMENT, "setBoundary: level-set index range beyond int");
-            return false;
-        }
-        if (!(l.voxel > 0.f) || !(l.background > 0.f) || !std::isfinite(l.voxel) || !std::isfinite(l.background)) {
-            fl_report_error(FL_ERR_BAD_ARGUMENT, "setBoundary: level-set voxel or background not finite and positive");
-            return false;
-        }
-        total += nodes * sizeof(float);
-        if (total > cap) {
-            fl_report_error(FL_ERR_BAD_ARGUMENT, "setBoundary: level-set grids above 256 MiB in all");
-            return false;
-        }
+    }
+    if (const char *why = bq::ls_check(b, ls, n)) {
+        fl_report_error(FL_ERR_BAD_ARGUMENT, (std::string("setBoundary: ") + why).c_str());
+        return false;
+    }
+    auto grid_bytes = [&](int o) { return (size_t)ls[o].nx * (size_t)ls[o].ny * (size_t)ls[o].nz * sizeof(float); };
+    size_t total = 0;                                   // below 16 * 2^33 bytes: no overflow
+    for (int o = 0; o < n; o++)
+        if (b[o].shape == BQ_SHAPE_LEVELSET) total += grid_bytes(o);
+    if (total > kMaxLevelsetBytes) {
+        fl_report_error(FL_ERR_BAD_ARGUMENT, "setBoundary: level-set grids above 256 MiB in all");
+        return false;
     }
     // every grid into one allocation, the descriptors pointing into it
     DeviceBytes grids;
-    if (!grids.alloc((size_t)total)) return false;
-    std::vector<bq_levelset> descs((size_t)n, bq_levelset{});
-    size_t at = 0;
-    for (int o = 0; o < n; o++) {
-        if (b[o].shape != BQ_SHAPE_LEVELSET) continue;
-        descs[o] = ls[o];
-        const size_t bytes = (size_t)ls[o].nx * (size_t)ls[o].ny * (size_t)ls[o].nz * sizeof(float);
-        float *dst = reinterpret_cast<float *>(grids.u8() + at);
-        fl_memcpy_h2d(dst, ls[o].phi, bytes);
-        descs[o].phi = dst;
-        at += bytes;
+    std::vector<bq_levelset> descs;
+    if (any_ls) {
+        if (!grids.alloc(total)) return false;
+        descs.assign((size_t)n, bq_levelset{});
+        size_t at = 0;
+        for (int o = 0; o < n; o++) {
+            if (b[o].shape != BQ_SHAPE_LEVELSET) continue;
+            float *dst = reinterpret_cast<float *>(grids.u8() + at);
+            fl_memcpy_h2d(dst, ls[o].phi, grid_bytes(o));
+            descs[o] = ls[o];
+            descs[o].phi = dst;
+            at += grid_bytes(o);
+        }
+        if (fl_last_error() != FL_OK) return false;
     }
-    if (fl_last_error() != FL_OK) return false;
     const size_t nrows = (size_t)g.nj * (size_t)g.nk;
     if (solid.bytes() != g.n() && !solid.alloc(g.n())) return false;
     if (rows.bytes() != nrows && !rows.alloc(nrows)) return false;
     std::vector<bq_boundary> list(b, b + n);
-    if (!buildFlags(list, descs.data())) return false;
+    if (!buildFlags(list, any_ls ? descs.data() : nullptr)) return false;
     boundaries.swap(list);
     levelsets.swap(descs);
     lsgrids = std::move(grids);
@@ -622,14 +584,11 @@ void BimocqGPUSolver::dropBoundaries()
     lsgrids.release();
 }
 
-// the flags of `list` (ls: its level-set descriptors, or NULL when it holds none -- then the analytic operator); on
-// failure the obstacles are dropped (no step may run on flags that were never built)
+// the flags of `list` (ls: its level-set descriptors, or NULL when it holds none); on failure the obstacles are dropped (no
+// step may run on flags that were never built)
 bool BimocqGPUSolver::buildFlags(const std::vector<bq_boundary> &list, const bq_levelset *ls)
 {
-    if (ls)
-        gpu_obstacle_flags_ls(solid.u8(), rows.u8(), list.data(), (int)list.size(), ls, CellSize, g.ni, g.nj, g.nk);
-    else
-        gpu_obstacle_flags(solid.u8(), rows.u8(), list.data(), (int)list.size(), CellSize, g.ni, g.nj, g.nk);
+    obstacle_flags(solid.u8(), rows.u8(), list.data(), (int)list.size(), ls, CellSize, g.ni, g.nj, g.nk);
     if (fl_last_error() == FL_OK) return true;
     dropBoundaries();
     return false;
@@ -660,20 +619,13 @@ void BimocqGPUSolver::semilagBand(float cfldt, float dt)
         if (!f->get() && !gs.allocField(*f, FIELD_S)) return;
     const bq_boundary *b = boundaries.data();
     const int n = (int)boundaries.size(), ni = g.ni, nj = g.nj, nk = g.nk;
+    const bq_levelset *ls = levelsetList();
     const float h = CellSize;
-    if (const bq_levelset *ls = levelsetList()) {
-        gpu_semilag_band_ls(TempSrcU, VelocityU, VelocityU, VelocityV, VelocityW, 1, 0, 0, h, ni, nj, nk, cfldt, -dt, b, n, ls);
-        gpu_semilag_band_ls(TempSrcV, VelocityV, VelocityU, VelocityV, VelocityW, 0, 1, 0, h, ni, nj, nk, cfldt, -dt, b, n, ls);
-        gpu_semilag_band_ls(TempSrcW, VelocityW, VelocityU, VelocityV, VelocityW, 0, 0, 1, h, ni, nj, nk, cfldt, -dt, b, n, ls);
-        gpu_semilag_band_ls(DensityTemp, Density, VelocityU, VelocityV, VelocityW, 0, 0, 0, h, ni, nj, nk, cfldt, -dt, b, n, ls);
-        gpu_semilag_band_ls(TemperatureTemp, Temperature, VelocityU, VelocityV, VelocityW, 0, 0, 0, h, ni, nj, nk, cfldt, -dt, b, n, ls);
-        return;
-    }
-    gpu_semilag_band(TempSrcU, VelocityU, VelocityU, VelocityV, VelocityW, 1, 0, 0, h, ni, nj, nk, cfldt, -dt, b, n);
-    gpu_semilag_band(TempSrcV, VelocityV, VelocityU, VelocityV, VelocityW, 0, 1, 0, h, ni, nj, nk, cfldt, -dt, b, n);
-    gpu_semilag_band(TempSrcW, VelocityW, VelocityU, VelocityV, VelocityW, 0, 0, 1, h, ni, nj, nk, cfldt, -dt, b, n);
-    gpu_semilag_band(DensityTemp, Density, VelocityU, VelocityV, VelocityW, 0, 0, 0, h, ni, nj, nk, cfldt, -dt, b, n);
-    gpu_semilag_band(TemperatureTemp, Temperature, VelocityU, VelocityV, VelocityW, 0, 0, 0, h, ni, nj, nk, cfldt, -dt, b, n);
+    semilag_band(TempSrcU, VelocityU, VelocityU, VelocityV, VelocityW, 1, 0, 0, h, ni, nj, nk, cfldt, -dt, b, n, ls);
+    semilag_band(TempSrcV, VelocityV, VelocityU, VelocityV, VelocityW, 0, 1, 0, h, ni, nj, nk, cfldt, -dt, b, n, ls);
+    semilag_band(TempSrcW, VelocityW, VelocityU, VelocityV, VelocityW, 0, 0, 1, h, ni, nj, nk, cfldt, -dt, b, n, ls);
+    semilag_band(DensityTemp, Density, VelocityU, VelocityV, VelocityW, 0, 0, 0, h, ni, nj, nk, cfldt, -dt, b, n, ls);
+    semilag_band(TemperatureTemp, Temperature, VelocityU, VelocityV, VelocityW, 0, 0, 0, h, ni, nj, nk, cfldt, -dt, b, n, ls);
 }
 
 // blendBoundary (:879-912) of all five fields from semilagBand's values + clearBoundary (:914-934) of rho; band = false:
@@ -681,21 +633,13 @@ void BimocqGPUSolver::semilagBand(float cfldt, float dt)
 void BimocqGPUSolver::blendBoundary(bool band)
 {
     const bq_boundary *b = boundaries.data();
-    if (const bq_levelset *ls = levelsetList()) {
-        if (band)
-            gpu_obstacle_blend_ls(VelocityU, VelocityV, VelocityW, Density, Temperature, TempSrcU, TempSrcV, TempSrcW, DensityTemp,
-                                  TemperatureTemp, solid.u8(), b, (int)boundaries.size(), ls, CellSize, g.ni, g.nj, g.nk);
-        else
-            gpu_obstacle_blend_ls(nullptr, nullptr, nullptr, Density, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                  solid.u8(), b, (int)boundaries.size(), ls, CellSize, g.ni, g.nj, g.nk);
-        return;
-    }
+    const int n = (int)boundaries.size();
     if (band)
-        gpu_obstacle_blend(VelocityU, VelocityV, VelocityW, Density, Temperature, TempSrcU, TempSrcV, TempSrcW, DensityTemp,
-                           TemperatureTemp, solid.u8(), b, (int)boundaries.size(), CellSize, g.ni, g.nj, g.nk);
+        obstacle_blend(VelocityU, VelocityV, VelocityW, Density, Temperature, TempSrcU, TempSrcV, TempSrcW, DensityTemp,
+                       TemperatureTemp, solid.u8(), b, n, levelsetList(), CellSize, g.ni, g.nj, g.nk);
     else
-        gpu_obstacle_blend(nullptr, nullptr, nullptr, Density, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                           solid.u8(), b, (int)boundaries.size(), CellSize, g.ni, g.nj, g.nk);
+        obstacle_blend(nullptr, nullptr, nullptr, Density, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                       solid.u8(), b, n, levelsetList(), CellSize, g.ni, g.nj, g.nk);
 }
 
 // the Jacobi projection with obstacles (:1120-1413): solid faces take the obstacle velocity (with_delta: its share of

@@ -123,7 +123,7 @@ public:
     // one GPU only.  With an empty list a step issues exactly the launches it issues without this feature.
     std::vector<bq_boundary> boundaries;
     DeviceBytes solid, rows;                        // cell flags (0 fluid, o + 1 solid by obstacle o), rows summary (include/bimocq_gpu.h)
-    bool setBoundary(const bq_boundary *b, int n);
+    bool setBoundary(const bq_boundary *b, const bq_levelset *ls, int n);      // ls: NULL when no entry is a level set
     bool updateBoundary(int framenum, float dt);
     // Level sets (shape BQ_SHAPE_LEVELSET): `levelsets` holds one descriptor per entry of `boundaries` (phi into lsgrids)
     // when the list holds a level set, and is empty otherwise -- then every obstacle operator call is the analytic one.
@@ -131,8 +131,6 @@ public:
     std::vector<bq_levelset> levelsets;
     DeviceBytes lsgrids;                            // every level-set grid of the list, one allocation
     const bq_levelset *levelsetList() const { return levelsets.empty() ? nullptr : levelsets.data(); }
-    bool setBoundaryLevelsets(const bq_boundary *b, const bq_levelset *ls, int n);
-    bool setBoundaryLevelsetsOrFail(const bq_boundary *b, const bq_levelset *ls, int n);
     void dropBoundaries();
     bool buildFlags(const std::vector<bq_boundary> &list, const bq_levelset *ls);
     bool projectionObstacles(bool with_delta);

@@ -213,14 +213,16 @@ int bq_solver_set_boundary(bq_solver *s, const bq_boundary *b, int n)
 {
     BQ_ENTER(s);
     if (!s) return -1;
-    return s->solver->setBoundary(b, n) ? 0 : -1;
+    return s->solver->setBoundary(b, nullptr, n) ? 0 : -1;
 }
 
 int bq_solver_set_boundary_levelsets(bq_solver *s, const bq_boundary *b, const bq_levelset *ls, int n)
 {
     BQ_ENTER(s);
     if (!s) return -1;
-    return s->solver->setBoundaryLevelsets(b, ls, n) ? 0 : -1;
+    if (s->solver->setBoundary(b, ls, n)) return 0;
+    s->solver->dropBoundaries();                    // after any failure no obstacles are left
+    return -1;
 }
 
 int bq_solver_update_boundary(bq_solver *s, int framenum, float dt)

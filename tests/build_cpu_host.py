@@ -1,6 +1,10 @@
-"""Builds tests/_build/libbimocq_host_cpu.so: the product's C++ HOST sources (csrc/host/*.cpp)
-linked against the test-only CPU stand-in of the C-ABI (tests/cpu_abi/oracle_abi.c + the oracle).
-Used by the `-m "not gpu"` tests to check the host step logic without a GPU.  Test infrastructure."""
+"""Builds the CPU stand-ins of the C-ABI: the product's C++ HOST sources (csrc/host/*.cpp) linked against test-only C
+restatements of the operators.  Used by the `-m "not gpu"` tests to check the host step logic without a GPU, and by the
+GPU tests as references.  Test infrastructure.
+  build()            tests/_build/libbimocq_host_cpu.so: tests/cpu_abi/oracle_abi.c + the oracle
+  build_obstacles()  ..._obstacles.so: + the obstacle operators (tests/cpu_abi/obstacle_abi.c)
+  build_levelsets()  ..._levelsets.so: + the level-set operators (tests/cpu_abi/levelset_abi.c)
+A stand-in without some operators leaves the host solver's weak references to them null: set_boundary refuses there."""
 import glob
 import os
 import subprocess
@@ -12,32 +16,45 @@ SANITIZE = os.environ.get("BQ_SANITIZE", "0") not in ("", "0")
 OUT = os.path.join(ROOT, "tests", "_build_san" if SANITIZE else "_build")
 SO = os.path.join(OUT, "libbimocq_host_cpu.so")
 SAN_FLAGS = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-g"]
+ABI = os.path.join(ROOT, "tests", "cpu_abi")
+CSRC = os.path.join(ROOT, "gpufluidsimulation_amd", "csrc")
 
 
-def build():
+def _build(so, extra_abi):
+    """the stand-in `so` with the C restatements `extra_abi` (file names under tests/cpu_abi) on top of oracle_abi.c"""
     os.makedirs(OUT, exist_ok=True)
-    host = sorted(glob.glob(os.path.join(ROOT, "gpufluidsimulation_amd", "csrc", "host", "*.cpp")))
-    deps = host + glob.glob(os.path.join(ROOT, "gpufluidsimulation_amd", "csrc", "host", "*.hpp")) + [
-        os.path.join(ROOT, "tests", "cpu_abi", "oracle_abi.c"),
-        os.path.join(ROOT, "oracle", "bimocq_oracle.c"), os.path.join(ROOT, "oracle", "mgcg_oracle.c"),
-        os.path.join(ROOT, "oracle", "bimocq_oracle.h"),
+    host = sorted(glob.glob(os.path.join(CSRC, "host", "*.cpp")))
+    c_srcs = [(os.path.join(ABI, name), "-std=gnu11") for name in ["oracle_abi.c"] + extra_abi] + [
+        (os.path.join(ROOT, "oracle", name), "-std=c11") for name in ("bimocq_oracle.c", "mgcg_oracle.c")]
+    deps = host + [src for src, _ in c_srcs] + glob.glob(os.path.join(CSRC, "host", "*.hpp")) + [
+        os.path.join(CSRC, "bq_levelset.h"), os.path.join(ROOT, "oracle", "bimocq_oracle.h"),
         os.path.join(ROOT, "include", "bimocq_gpu.h"), os.path.join(ROOT, "include", "bimocq_solver.h")]
-    if os.path.exists(SO) and all(os.path.getmtime(d) <= os.path.getmtime(SO) for d in deps):
-        return SO
+    if os.path.exists(so) and all(os.path.getmtime(d) <= os.path.getmtime(so) for d in deps):
+        return so
     cflags = ["-O2", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-fopenmp"]
     if SANITIZE:
         cflags = ["-O1"] + cflags[1:] + SAN_FLAGS
+    prefix = os.path.basename(so)[:-len(".so")] + "_"
     objs = []
-    for src, cc, std in ([(os.path.join(ROOT, "tests", "cpu_abi", "oracle_abi.c"), "gcc", "-std=gnu11"),
-                          (os.path.join(ROOT, "oracle", "bimocq_oracle.c"), "gcc", "-std=c11"),
-                          (os.path.join(ROOT, "oracle", "mgcg_oracle.c"), "gcc", "-std=c11")]
-                         + [(h, "g++", "-std=c++17") for h in host]):
-        obj = os.path.join(OUT, os.path.basename(src) + ".o")
+    for src, cc, std in [(src, "gcc", std) for src, std in c_srcs] + [(h, "g++", "-std=c++17") for h in host]:
+        obj = os.path.join(OUT, prefix + os.path.basename(src) + ".o")
         subprocess.check_call([cc, std, *cflags, "-I" + os.path.join(ROOT, "include"), "-c", src, "-o", obj])
         objs.append(obj)
-    subprocess.check_call(["g++", "-shared", "-fopenmp", "-pthread", *(SAN_FLAGS if SANITIZE else []), "-o", SO, *objs, "-lm"])
-    return SO
+    subprocess.check_call(["g++", "-shared", "-fopenmp", "-pthread", *(SAN_FLAGS if SANITIZE else []), "-o", so, *objs, "-lm"])
+    return so
+
+
+def build():
+    return _build(SO, [])
+
+
+def build_obstacles():
+    return _build(os.path.join(OUT, "libbimocq_host_cpu_obstacles.so"), ["obstacle_abi.c"])
+
+
+def build_levelsets():
+    return _build(os.path.join(OUT, "libbimocq_host_cpu_levelsets.so"), ["obstacle_abi.c", "levelset_abi.c"])
 
 
 if __name__ == "__main__":
-    print(build())
+    print(build(), build_obstacles(), build_levelsets())

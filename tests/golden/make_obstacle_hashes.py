@@ -1,9 +1,10 @@
-"""Generates tests/golden/obstacle_hashes.json: per-step SHA-256 of rho, T, u, v, w, p and the cell flags of the 64^3
-obstacle scene (tests/obstacle_case.py: a static sphere and a moving box in the rising smoke), 20 steps, 30 Jacobi sweeps,
-both schemes, computed by the host solver linked to the CPU stand-in with the obstacle operators
-(tests/build_cpu_host_obstacles.py).  tests/test_gpu_obstacles.py checks the GPU run against these.
+"""Generates tests/golden/obstacle_hashes.json and tests/golden/levelset_hashes.json: per-step SHA-256 of rho, T, u, v, w,
+p and the cell flags of the 64^3 obstacle scene (tests/obstacle_case.py: a static sphere and a moving box in the rising
+smoke) and of the 64^3 level-set scene (tests/levelset_case.py: a static level-set sphere, an analytic box and a moving
+level-set box), 20 steps, 30 Jacobi sweeps, both schemes, computed by the host solver linked to the CPU stand-ins with the
+obstacle and the level-set operators (tests/build_cpu_host.py).  tests/test_gpu_obstacles.py and
+tests/test_gpu_levelsets.py check the GPU runs against these.
 Usage: python tests/golden/make_obstacle_hashes.py"""
-import ctypes as C
 import json
 import os
 import sys
@@ -12,20 +13,20 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 
+import levelset_case as LC                                  # noqa: E402
 import obstacle_case as OC                                  # noqa: E402
-from build_cpu_host_obstacles import build                  # noqa: E402
-from gpufluidsimulation_amd import solver                   # noqa: E402
 
 N, STEPS, ITERS = 64, 20, 30
 
 
 def main():
-    lib = OC.bind_errors(solver.bind_host(C.CDLL(build(), mode=C.RTLD_LOCAL)))
-    out = {"n": N, "steps": STEPS, "jacobi_iters": ITERS}
-    for scheme in (0, 3):
-        out[f"scheme{scheme}"] = OC.run_scene(lib, lib, N, scheme, STEPS, ITERS)
-    with open(os.path.join(HERE, "obstacle_hashes.json"), "w") as f:
-        json.dump(out, f, indent=1)
+    for name, lib, scene in (("obstacle_hashes.json", OC.load_obstacles(), OC.scene),
+                             ("levelset_hashes.json", OC.load_levelsets(), LC.scene)):
+        out = {"n": N, "steps": STEPS, "jacobi_iters": ITERS}
+        for scheme in (0, 3):
+            out[f"scheme{scheme}"] = OC.run_scene(lib, lib, N, scheme, STEPS, ITERS, scene)
+        with open(os.path.join(HERE, name), "w") as f:
+            json.dump(out, f, indent=1)
 
 
 if __name__ == "__main__":

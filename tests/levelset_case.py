@@ -1,9 +1,6 @@
 """Shared pieces of the level-set obstacle tests: a numpy restatement of the level-set sampler and of the classification of
-mixed lists ("Level sets": float64 index math, float32 lerps), the scene the step tests run, and
-loaders of the CPU stand-in with the level-set operators."""
-import ctypes as C
-import hashlib
-
+mixed lists ("Level sets": float64 index math, float32 lerps) and the scene the step tests run
+(obstacle_case.run_scene(..., scene=scene))."""
 import numpy as np
 
 import obstacle_case as OC
@@ -84,41 +81,3 @@ def scene(n):
                (1, 0.3, 0.8, 0.45, 0.08, 0.05, 0.1, 0.0, 0.0, 0.0),
                LevelSetObstacle(box_levelset((0.06, 0.04, 0.08), 0.75 * h), (0.75, 0.75, 0.55), (-0.5, 0.0, 0.0))]
     return h, em, entries
-
-
-def run_scene(lib, errlib, n, scheme, steps, iters):
-    """the scene for `steps` steps (updateBoundary before every advance); per-step SHA-256 of rho, T, u, v, w, p and the
-    flags, and the final max rho"""
-    from gpufluidsimulation_amd.solver import BimocqGPUSolver
-    _, em, entries = scene(n)
-    s = BimocqGPUSolver(n, n, n, 1.0, 0.0, 1.0, lib=lib, errlib=errlib, scheme=scheme)
-    s.setSmoke(0.0, 1.0, em)
-    s.setProjection(iters, 0.5)
-    s.setBoundary(entries)
-    out = []
-    for f in range(steps):
-        s.updateBoundary(f, 1.0 / n)
-        s.advance(f, 1.0 / n)
-        d = hashlib.sha256()
-        for name in ("rho", "T", "u", "v", "w", "p"):
-            d.update(s.field(name).tobytes())
-        d.update(s.solidMask().tobytes())
-        out.append(d.hexdigest())
-    rho_max = float(s.field("rho").max())
-    s.close()
-    return {"hashes": out, "rho_max": rho_max}
-
-
-def bind_ops(lib):
-    """the three level-set operators (and the analytic ones) of a stand-in, typed from _lib.HIP_SIGS"""
-    from gpufluidsimulation_amd import _lib
-    for name in ("gpu_obstacle_flags_ls", "gpu_semilag_band_ls", "gpu_obstacle_blend_ls",
-                 "gpu_obstacle_flags", "gpu_semilag_band", "gpu_obstacle_blend"):
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = _lib.HIP_SIGS[name]
-    return lib
-
-
-def load(path):
-    from gpufluidsimulation_amd import solver
-    return bind_ops(OC.bind_errors(solver.bind_host(C.CDLL(path, mode=C.RTLD_LOCAL))))

@@ -1,9 +1,12 @@
-"""Shared pieces of the obstacle tests: a numpy restatement of the classification and of the masked sweep
-(DESIGN.md section 14), the scene the step tests run, and loaders of the CPU stand-in with the obstacle operators."""
+"""Shared pieces of the obstacle and level-set tests: a numpy restatement of the classification and of the masked sweep
+(DESIGN.md section 14), the scene the step tests run, loaders of the CPU stand-ins with the obstacle and level-set
+operators, and device buffers for the GPU tests."""
 import ctypes as C
 import hashlib
 
 import numpy as np
+
+from build_cpu_host import build_levelsets, build_obstacles
 
 f32 = np.float32
 
@@ -77,9 +80,9 @@ def bind_errors(lib):
     return lib
 
 
-def run_scene(lib, errlib, n, scheme, steps, iters):
-    """the scene for `steps` steps (updateBoundary before every advance); per-step SHA-256 of rho, T, u, v, w, p and the
-    flags, and the final max rho"""
+def run_scene(lib, errlib, n, scheme, steps, iters, scene=scene):
+    """`scene` (this one, or levelset_case.scene) for `steps` steps (updateBoundary before every advance); per-step SHA-256
+    of rho, T, u, v, w, p and the flags, and the final max rho"""
     from gpufluidsimulation_amd.solver import BimocqGPUSolver
     _, em, obstacles = scene(n)
     s = BimocqGPUSolver(n, n, n, 1.0, 0.0, 1.0, lib=lib, errlib=errlib, scheme=scheme)
@@ -98,3 +101,67 @@ def run_scene(lib, errlib, n, scheme, steps, iters):
     rho_max = float(s.field("rho").max())
     s.close()
     return {"hashes": out, "rho_max": rho_max}
+
+
+OPS = ("gpu_obstacle_flags", "gpu_obstacle_faces", "gpu_jacobi_sweep_masked", "gpu_jacobi_sweeps_masked",
+       "gpu_gradient_masked", "gpu_semilag_band", "gpu_obstacle_blend")
+LS_OPS = ("gpu_obstacle_flags_ls", "gpu_semilag_band_ls", "gpu_obstacle_blend_ls")
+
+
+def _load(path, ops):
+    """a stand-in with the host C API, the error functions and `ops` typed from _lib.HIP_SIGS"""
+    from gpufluidsimulation_amd import _lib, solver
+    lib = bind_errors(solver.bind_host(C.CDLL(path, mode=C.RTLD_LOCAL)))
+    for name in ops:
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = _lib.HIP_SIGS[name]
+    return lib
+
+
+def load_obstacles():
+    """the stand-in with the obstacle operators (not the level-set ones)"""
+    return _load(build_obstacles(), OPS)
+
+
+def load_levelsets():
+    """the stand-in with the obstacle and the level-set operators"""
+    return _load(build_levelsets(), OPS + LS_OPS)
+
+
+class Dev:
+    """device copies of host arrays for the GPU tests: put(name, a) uploads (reusing the buffer of that name when the size
+    matches) and returns the device pointer, dev[name] is that pointer, get(name) downloads in the uploaded shape"""
+    def __init__(self, hip):
+        self.hip, self.bufs = hip, {}
+
+    def put(self, name, a):
+        a = np.ascontiguousarray(a)
+        if name in self.bufs and self.bufs[name][2] == a.nbytes:
+            p = self.bufs[name][0]
+        else:
+            if name in self.bufs:
+                self.hip.fl_free(self.bufs[name][0])
+            p = self.hip.fl_malloc(max(a.nbytes, 4))
+            assert p
+        self.hip.fl_memcpy_h2d(p, a.ctypes.data, a.nbytes)
+        self.bufs[name] = (p, a.dtype, a.nbytes, a.shape)
+        return p
+
+    def get(self, name):
+        p, dt, nb, shape = self.bufs[name]
+        out = np.empty(shape, dt)
+        self.hip.fl_sync()
+        self.hip.fl_memcpy_d2h(out.ctypes.data, p, nb)
+        return out
+
+    def __getitem__(self, name):
+        return self.bufs[name][0]
+
+    def free(self):
+        for v in self.bufs.values():
+            self.hip.fl_free(v[0])
+        self.bufs = {}
+
+
+def check(hip):
+    assert hip.fl_last_error() == 0, hip.fl_last_error_string()

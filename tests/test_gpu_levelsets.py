@@ -11,7 +11,8 @@ import pytest
 
 import fields as F
 import levelset_case as LC
-from build_cpu_host_levelsets import build as build_levelsets
+import obstacle_case as OC
+from obstacle_case import Dev, check
 
 pytestmark = pytest.mark.gpu
 
@@ -21,37 +22,7 @@ def libs():
     import gpufluidsimulation_amd as bq
     hip = bq.hip_lib()
     assert hip.fl_init(0) == 0
-    return hip, LC.load(build_levelsets())
-
-
-class Dev:
-    """device copies of host arrays; .get(name) downloads"""
-    def __init__(self, hip):
-        self.hip, self.bufs = hip, {}
-
-    def put(self, name, a):
-        a = np.ascontiguousarray(a)
-        if name in self.bufs:
-            self.hip.fl_free(self.bufs.pop(name)[0])
-        p = self.hip.fl_malloc(max(a.nbytes, 4))
-        self.hip.fl_memcpy_h2d(p, a.ctypes.data, a.nbytes)
-        self.bufs[name] = (p, a.dtype, a.size)
-        return p
-
-    def get(self, name):
-        p, dt, n = self.bufs[name]
-        out = np.empty(n, dt)
-        self.hip.fl_sync()
-        self.hip.fl_memcpy_d2h(out.ctypes.data, p, out.nbytes)
-        return out
-
-    def free(self):
-        for p, _, _ in self.bufs.values():
-            self.hip.fl_free(p)
-
-
-def check(hip):
-    assert hip.fl_last_error() == 0, hip.fl_last_error_string()
+    return hip, OC.load_levelsets()
 
 
 def lists(entries, dev):
@@ -165,12 +136,12 @@ def test_analytic_lists_through_the_levelset_entries(libs):
 
 @pytest.mark.parametrize("scheme", [0, 3])
 def test_levelset_scene_matches_the_stand_in(libs, scheme):
-    """hashes of the CPU stand-in: tests/golden/make_levelset_hashes.py"""
+    """hashes of the CPU stand-in: tests/golden/make_obstacle_hashes.py"""
     from gpufluidsimulation_amd import solver
     hip, _ = libs
     with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "levelset_hashes.json")) as f:
         gold = json.load(f)
-    got = LC.run_scene(solver.host_lib(), hip, gold["n"], scheme, gold["steps"], gold["jacobi_iters"])
+    got = OC.run_scene(solver.host_lib(), hip, gold["n"], scheme, gold["steps"], gold["jacobi_iters"], LC.scene)
     want = gold[f"scheme{scheme}"]
     first = next((i for i, (a, b) in enumerate(zip(want["hashes"], got["hashes"])) if a != b), None)
     assert first is None, f"step {first} differs (rho max {got['rho_max']} vs {want['rho_max']})"

@@ -11,7 +11,7 @@ import pytest
 import fields as F
 import obstacle_case as OC
 import obstacle_ref as R
-from build_cpu_host_obstacles import build as build_obstacles
+from obstacle_case import Dev, check
 
 pytestmark = pytest.mark.gpu
 
@@ -23,51 +23,9 @@ COUNTS = (1, 2, 3, 4, 6, 7)
 @pytest.fixture(scope="module")
 def libs():
     import gpufluidsimulation_amd as bq
-    from gpufluidsimulation_amd import _lib, solver
     hip = bq.hip_lib()
     assert hip.fl_init(0) == 0
-    cpu = OC.bind_errors(solver.bind_host(C.CDLL(build_obstacles(), mode=C.RTLD_LOCAL)))
-    for name in ("gpu_obstacle_flags", "gpu_jacobi_sweep_masked", "gpu_jacobi_sweeps_masked"):
-        fn = getattr(cpu, name)
-        fn.restype, fn.argtypes = _lib.HIP_SIGS[name]
-    return hip, cpu
-
-
-class Dev:
-    def __init__(self, hip):
-        self.hip, self.bufs = hip, {}
-
-    def put(self, name, a):
-        a = np.ascontiguousarray(a)
-        if name in self.bufs and self.bufs[name][2] == a.nbytes:
-            p = self.bufs[name][0]
-        else:
-            if name in self.bufs:
-                self.hip.fl_free(self.bufs[name][0])
-            p = self.hip.fl_malloc(max(a.nbytes, 4))
-            assert p
-        self.hip.fl_memcpy_h2d(p, a.ctypes.data, a.nbytes)
-        self.bufs[name] = (p, a.dtype, a.nbytes, a.shape)
-        return p
-
-    def get(self, name):
-        p, dt, nb, shape = self.bufs[name]
-        out = np.empty(shape, dt)
-        self.hip.fl_sync()
-        self.hip.fl_memcpy_d2h(out.ctypes.data, p, nb)
-        return out
-
-    def __getitem__(self, name):
-        return self.bufs[name][0]
-
-    def free(self):
-        for v in self.bufs.values():
-            self.hip.fl_free(v[0])
-        self.bufs = {}
-
-
-def check(hip):
-    assert hip.fl_last_error() == 0, hip.fl_last_error_string()
+    return hip, OC.load_obstacles()
 
 
 class options:

@@ -11,53 +11,16 @@ import pytest
 
 import fields as F
 import obstacle_case as OC
-from build_cpu_host_obstacles import build as build_obstacles
+from obstacle_case import Dev, check
 
 pytestmark = pytest.mark.gpu
-
-OPS = ("gpu_obstacle_flags", "gpu_obstacle_faces", "gpu_jacobi_sweep_masked", "gpu_jacobi_sweeps_masked",
-       "gpu_gradient_masked", "gpu_semilag_band", "gpu_obstacle_blend")
-
 
 @pytest.fixture(scope="module")
 def libs():
     import gpufluidsimulation_amd as bq
-    from gpufluidsimulation_amd import _lib, solver
     hip = bq.hip_lib()
     assert hip.fl_init(0) == 0
-    cpu = OC.bind_errors(solver.bind_host(C.CDLL(build_obstacles(), mode=C.RTLD_LOCAL)))
-    for name in OPS:
-        fn = getattr(cpu, name)
-        fn.restype, fn.argtypes = _lib.HIP_SIGS[name]
-    return hip, cpu
-
-
-class Dev:
-    """device copies of host arrays; .get(name) downloads"""
-    def __init__(self, hip):
-        self.hip, self.bufs = hip, {}
-
-    def put(self, name, a):
-        a = np.ascontiguousarray(a)
-        p = self.hip.fl_malloc(max(a.nbytes, 4))
-        self.hip.fl_memcpy_h2d(p, a.ctypes.data, a.nbytes)
-        self.bufs[name] = (p, a.dtype, a.size)
-        return p
-
-    def get(self, name):
-        p, dt, n = self.bufs[name]
-        out = np.empty(n, dt)
-        self.hip.fl_sync()
-        self.hip.fl_memcpy_d2h(out.ctypes.data, p, out.nbytes)
-        return out
-
-    def free(self):
-        for p, _, _ in self.bufs.values():
-            self.hip.fl_free(p)
-
-
-def check(hip):
-    assert hip.fl_last_error() == 0, hip.fl_last_error_string()
+    return hip, OC.load_obstacles()
 
 
 DIMS = [(100, 21, 18), (64, 64, 64), (128, 36, 20)]
@@ -112,7 +75,7 @@ def test_operators_match_the_restatement(libs, dims):
         s_c, t_c, arr, n = flags_both(hip, cpu, dev, dims, bnd, h)
         assert np.array_equal(dev.get("solid"), s_c) and np.array_equal(dev.get("rows"), t_c)
         assert s_c.any() and (t_c == 0).any()
-        solid_p, tiles_p = dev.bufs["solid"][0], dev.bufs["rows"][0]
+        solid_p, tiles_p = dev["solid"], dev["rows"]
         u, v, w = F.velocity(ni, nj, nk, h)
         # solid faces (+ delta share)
         for with_d in (True, False):
@@ -140,7 +103,7 @@ def test_operators_match_the_restatement(libs, dims):
             dptrs = [dev.put(nm, x) for nm, x in zip(("du", "dv", "dw"), hd)] if with_d else [None] * 3
             cpu.gpu_gradient_masked(hu.ctypes.data, hv.ctypes.data, hw.ctypes.data, p.ctypes.data,
                                     *([x.ctypes.data for x in hd] if with_d else [None] * 3), s_c.ctypes.data, ni, nj, nk, 0.5)
-            hip.gpu_gradient_masked(dev.bufs["u"][0], dev.bufs["v"][0], dev.bufs["w"][0], pp, *dptrs, solid_p, ni, nj, nk, 0.5)
+            hip.gpu_gradient_masked(dev["u"], dev["v"], dev["w"], pp, *dptrs, solid_p, ni, nj, nk, 0.5)
             check(hip)
             for nm, want in zip(("u", "v", "w"), (hu, hv, hw)):
                 assert np.array_equal(dev.get(nm), want), nm

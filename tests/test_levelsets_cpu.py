@@ -10,13 +10,11 @@ import pytest
 
 import levelset_case as LC
 import obstacle_case as OC
-from build_cpu_host_levelsets import build as build_levelsets
-from build_cpu_host_obstacles import build as build_obstacles
 
 
 @pytest.fixture(scope="module")
 def lib():
-    return LC.load(build_levelsets())
+    return OC.load_levelsets()
 
 
 def make(lib, n=24, scheme=0, iters=20):
@@ -233,7 +231,7 @@ def test_every_new_refusal(lib):
 def test_stand_in_without_levelset_operators_refuses():
     """the obstacle stand-in has the analytic operators but not the level-set ones: its weak references are null"""
     from gpufluidsimulation_amd import _lib, solver
-    lib = OC.bind_errors(solver.bind_host(C.CDLL(build_obstacles(), mode=C.RTLD_LOCAL)))
+    lib = OC.load_obstacles()
     s = solver.BimocqGPUSolver(16, 16, 16, 1.0, lib=lib, errlib=lib)
     s.setBoundary([OC.scene(16)[2][0]])                   # analytic lists still work there
     with pytest.raises(_lib.BimocqError, match="no level-set obstacle operators"):

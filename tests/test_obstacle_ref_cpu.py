@@ -10,7 +10,6 @@ import pytest
 import fields as F
 import obstacle_case as OC
 import obstacle_ref as R
-from build_cpu_host_obstacles import build as build_obstacles
 
 SHAPES = [(32, 8, 12), (36, 13, 13), (252, 17, 40), (256, 24, 27), (99, 21, 18), (384, 12, 14), (40, 5, 16), (40, 16, 11)]
 FLAG_DIMS = [(99, 37, 23), (48, 40, 36), (64, 21, 30)]
@@ -18,13 +17,7 @@ FLAG_DIMS = [(99, 37, 23), (48, 40, 36), (64, 21, 30)]
 
 @pytest.fixture(scope="module")
 def lib():
-    from gpufluidsimulation_amd import solver, _lib
-    lib = solver.bind_host(C.CDLL(build_obstacles(), mode=C.RTLD_LOCAL))
-    OC.bind_errors(lib)
-    for name in ("gpu_obstacle_flags", "gpu_obstacle_faces", "gpu_jacobi_sweep_masked"):
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = _lib.HIP_SIGS[name]
-    return lib
+    return OC.load_obstacles()
 
 
 def test_masked_jacobi_converges_to_the_neumann_solution():

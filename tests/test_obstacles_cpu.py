@@ -9,18 +9,11 @@ import pytest
 
 import obstacle_case as OC
 from build_cpu_host import build as build_cpu_host
-from build_cpu_host_obstacles import build as build_obstacles
 
 
 @pytest.fixture(scope="module")
 def lib():
-    from gpufluidsimulation_amd import solver, _lib
-    lib = solver.bind_host(C.CDLL(build_obstacles(), mode=C.RTLD_LOCAL))
-    OC.bind_errors(lib)
-    for name in ("gpu_obstacle_flags", "gpu_jacobi_sweep_masked"):
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = _lib.HIP_SIGS[name]
-    return lib
+    return OC.load_obstacles()
 
 
 def make(lib, n=24, scheme=0, iters=20):
