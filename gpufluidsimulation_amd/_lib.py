@@ -142,6 +142,9 @@ HIP_SIGS = {
     "gpu_jacobi_sweep_masked": (None, [VP] * 5 + [c_i, c_i, c_i, c_f, c_f]),
     "gpu_jacobi_sweeps_masked": (c_i, [VP] * 5 + [c_i, c_i, c_i, c_i, c_f, c_f]),
     "gpu_gradient_masked": (None, [VP] * 8 + [c_i, c_i, c_i, c_f]),
+    "gpu_divergence_double": (None, [VP] * 4 + [c_i, c_i, c_i, c_d]),
+    "gpu_pcg_solve": (None, [VP] * 10 + [c_i, c_i, c_d, VP]),
+    "gpu_pcg_gradient": (None, [VP] * 5 + [c_i, c_i, c_i, c_d]),
     "gpu_semilag_band": (None, [VP] * 5 + [c_i, c_i, c_i] + _G + [c_f, c_f, VP, c_i]),
     "gpu_obstacle_blend": (None, [VP] * 11 + [VP, c_i] + _G),
     # level-set obstacles (the bq_levelset array travels as a HOST pointer, its phi device pointers: solver.LevelSetDesc)

@@ -83,6 +83,10 @@ bool comm_allreduce(void *dev, size_t count, bool is_double, bool is_max, hipStr
 int  comm_ranks();
 void mgcg_release_graph();              // bq_mgcg.hip: drop the cached V-cycle graphs of the current context (fl_free / fl_shutdown)
 void mgcg_release_state(Runtime &r);    // ... and free the per-context state itself (fl_shutdown)
+// bq_mgcg.hip: the coarse machinery of the V-cycle for the PCG projection (bq_pcg.hip)
+void mgcg_restrict(const double *fine, double *coarse, const SCoarseLevelInfo &F, const SCoarseLevelInfo &Cl);
+void mgcg_prolong(double *x, const double *coarse, const SCoarseLevelInfo &F, const SCoarseLevelInfo &Cl);
+void mgcg_pcg_coarse(const SCoarseLevelInfo *L, int levelnum, double *temp, int down, int up, int bottom);
 void halo_release_state(Runtime &r);    // bq_halo.hip
 void halo_abandon_comm(Runtime &r);     // bq_halo.hip: forget the communicator without destroying it (process exit)
 void project_release_state(Runtime &r); // bq_project.hip

@@ -1752,6 +1752,54 @@ static void v_cycle_replayed(const double *b, double *x, double *residual, const
     BQ_HIP(hipGraphLaunch(g_vcg.exec, st));
 }
 
+// ---- coarse machinery for the PCG projection (bq_pcg.hip) ----------------------------------------
+// restriction / prolongation between two levels, the kernels V_Cycle picks (bit-identical to orc_mg_restrict / orc_mg_prolong)
+void mgcg_restrict(const double *fine, double *coarse, const SCoarseLevelInfo &F, const SCoarseLevelInfo &Cl)
+{
+    mg_restrict_kernel<<<grid_of(Cl.ni, Cl.nj, Cl.nk), kBlk, 0, rt().compute>>>(fine, coarse, F.ni, F.nj, F.nk, Cl.ni, Cl.nj, Cl.nk);
+    BQ_LAUNCH_CHECK("mg_restrict_kernel");
+}
+void mgcg_prolong(double *x, const double *coarse, const SCoarseLevelInfo &F, const SCoarseLevelInfo &Cl)
+{
+    if (rt().opt_mgcg_tile && (long long)Cl.ni * Cl.nj * Cl.nk < (1ll << 31) && F.ni < (1 << 22) && F.nj < (1 << 22) &&
+        F.nk < (1 << 22) && F.ni >= 3 && F.nj >= 3 && F.nk >= 3)
+        mg_prolong_block_kernel<<<grid_of((F.ni - 1) / 2, (F.nj - 1) / 2, (F.nk - 1) / 2), kBlk, 0, rt().compute>>>(
+            x, coarse, F.ni, F.nj, F.nk, Cl.ni, Cl.nj, Cl.nk);
+    else
+        mg_prolong_kernel<<<grid_of(F.ni, F.nj, F.nk), kBlk, 0, rt().compute>>>(x, coarse, F.ni, F.nj, F.nk, Cl.ni, Cl.nj, Cl.nk);
+    BQ_LAUNCH_CHECK("mg_prolong_kernel");
+}
+__global__ __launch_bounds__(256) void mg_scale_kernel(double *x, double c, size_t count)
+{
+    const size_t id = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (id < count) x[id] = x[id] * c;
+}
+// One V-cycle on levels 1 .. levelnum-1 for L x = b (L = sum of the six neighbours - 6 c), L[1].b holding the right-hand
+// side: `down` sweeps from a cleared x, residual, restriction, the coarse right-hand side times 4 (the (2h)^2 / h^2 of the
+// Galerkin operator of this restriction / prolongation pair; exact in binary), `bottom` sweeps on the coarsest level, then
+// prolongation and `up` sweeps on the way back.  Unmasked, every level with its own alpha and beta (no M3).  temp: at least
+// L[1].number doubles, not read before it is written.  Leaves the correction in L[1].x.
+void mgcg_pcg_coarse(const SCoarseLevelInfo *L, int levelnum, double *temp, int down, int up, int bottom)
+{
+    auto smooth = [&](int l, int iter, bool clear_x) {
+        if (mg_smooth_tiled(L[l].x, L[l].b, temp, L[l].alpha, L[l].beta, L[l].ni, L[l].nj, L[l].nk, iter, clear_x)) return;
+        mg_smooth(L[l].x, L[l].b, temp, L[l].alpha, L[l].beta, L[l].ni, L[l].nj, L[l].nk, iter, clear_x ? 3 : 1);
+    };
+    const int c = levelnum - 1;
+    for (int l = 1; l < c; l++) {
+        smooth(l, down, true);
+        mg_residual(L[l].r, L[l].b, L[l].x, L[l].ni, L[l].nj, L[l].nk);
+        mgcg_restrict(L[l].r, L[l + 1].b, L[l], L[l + 1]);
+        mg_scale_kernel<<<blocks1d((size_t)L[l + 1].number), 256, 0, rt().compute>>>(L[l + 1].b, 4.0, (size_t)L[l + 1].number);
+        BQ_LAUNCH_CHECK("mg_scale_kernel");
+    }
+    smooth(c, bottom, true);
+    for (int l = c - 1; l >= 1; --l) {
+        mgcg_prolong(L[l].x, L[l + 1].x, L[l], L[l + 1]);
+        smooth(l, up, false);
+    }
+}
+
 void mgcg_release_graph()
 {
     if (!rt().mgcg_state) return;

@@ -31,6 +31,9 @@
 #pragma weak gpu_obstacle_flags_ls
 #pragma weak gpu_semilag_band_ls
 #pragma weak gpu_obstacle_blend_ls
+#pragma weak gpu_divergence_double
+#pragma weak gpu_pcg_solve
+#pragma weak gpu_pcg_gradient
 
 namespace bqhost {
 
@@ -505,7 +508,7 @@ bool BimocqGPUSolver::setBoundary(const bq_boundary *b, const bq_levelset *ls, i
         fl_report_error(FL_ERR_UNSUPPORTED, "setBoundary: obstacles are not supported on z-slab ranks");
         return false;
     }
-    if (projection_kind != BQ_PROJECTION_JACOBI) {
+    if (projection_kind == BQ_PROJECTION_MGCG) {
         fl_report_error(FL_ERR_UNSUPPORTED, "setBoundary: obstacles need the Jacobi projection (not BQ_PROJECTION_MGCG)");
         return false;
     }
@@ -662,6 +665,29 @@ bool BimocqGPUSolver::projectionObstacles(bool with_delta)
     return with_delta;
 }
 
+bool BimocqGPUSolver::pcgOperators() { return gpu_divergence_double && gpu_pcg_solve && gpu_pcg_gradient; }
+
+// BQ_PROJECTION_PCG: solid faces (obstacles only), fp64 divergence, the solve to pcg_tol, the masked
+// gradient.  d*Proj comes from the snapshot the caller takes before this call (as for the MGCG projection).
+bool BimocqGPUSolver::projectionPcg()
+{
+    if (!allocMgcg()) return false;
+    const bool obst = !boundaries.empty();
+    const unsigned char *sol = obst ? solid.u8() : nullptr;
+    if (obst)
+        gpu_obstacle_faces(VelocityU, VelocityV, VelocityW, nullptr, nullptr, nullptr, solid.u8(), boundaries.data(),
+                           (int)boundaries.size(), g.ni, g.nj, g.nk);
+    gpu_divergence_double(VelocityU, VelocityV, VelocityW, mg.div.f64(), g.ni, g.nj, g.nk, (double)halfrdx);
+    SCoarseLevelInfo &L0 = mg.levels[0];
+    gpu_pcg_solve(mg.div.f64(), mg.p.f64(), sol, mg.residual.f64(), mg.dir.f64(), mg.temp0.f64(), mg.temp1.f64(), L0.b, L0.r,
+                  mg.levels.data(), (int)mg.levels.size(), pcg_iters, pcg_tol, pcg_stats);
+    if (fl_last_error() != FL_OK) return false;
+    pcg_projections++;
+    if (pcg_stats[3] != BQ_PCG_CONVERGED) pcg_unconverged++;
+    gpu_pcg_gradient(VelocityU, VelocityV, VelocityW, mg.p.f64(), sol, g.ni, g.nj, g.nk, (double)halfrdx);
+    return false;
+}
+
 // with_delta: d*Proj = (projected - unprojected) velocity comes out of the gradient pass itself
 // (gpu_gradient_delta) instead of a snapshot before and a subtraction after; Jacobi branch only (returns
 // whether it did).
@@ -669,6 +695,7 @@ bool BimocqGPUSolver::projection(bool with_delta)
 {
     gpuMapper &gs = *GpuSolver;
     const float alpha = -1.f, beta = (float)(1.0 / 6.0);
+    if (projection_kind == BQ_PROJECTION_PCG) return projectionPcg();   // (refused on slabs by bq_solver_set_projection)
     if (projection_kind == BQ_PROJECTION_MGCG) {            // :443-446
         if (gs.slab.on && gs.slab.nranks > 1) {
             if (projectionMgcgShared()) return false;
@@ -682,7 +709,7 @@ bool BimocqGPUSolver::projection(bool with_delta)
                                           mg.levels.data(), (int)mg.levels.size(), mg_iters, (double)halfrdx);
         return false;
     }
-    if (!boundaries.empty()) return projectionObstacles(with_delta);   // (setBoundary admits one GPU + Jacobi only)
+    if (!boundaries.empty()) return projectionObstacles(with_delta);   // (setBoundary admits one GPU + Jacobi or PCG only)
     if (!gs.slab.on || gs.slab.nranks <= 1) {
         if (!with_delta) {
             gs.projectionJacobi(VelocityU, VelocityV, VelocityW, div, p, p_temp, debugParam, jacobi_iters, halfrdx, alpha, beta);

@@ -73,7 +73,7 @@ public:
     float last_vel_distortion = 0.f, last_scalar_distortion = 0.f;
     int   steps_taken = 0;
     DeviceField DensityTemp, TemperatureTemp, DensityExtern, TemperatureExtern;   // policy 1 only (:53-58)
-    int   projection_kind = 0;          // BQ_PROJECTION_JACOBI / BQ_PROJECTION_MGCG
+    int   projection_kind = 0;          // BQ_PROJECTION_JACOBI / BQ_PROJECTION_MGCG / BQ_PROJECTION_PCG
     int   mg_iters = 50;                // :444
     int   jacobi_iters = 100;           // :409
     float halfrdx = 0.5f;               // :410 (quarter-strength projection; 1.0 is the physical value)
@@ -118,6 +118,14 @@ public:
     bool mgcg_shared = true;                        // BQ_OPT_MGCG_SHARED
     bool mgcg_shared_ran = false;                   // the last MGCG projection on slabs took the shared path
     std::vector<double> mgHistory() const;          // tempResult (4096 doubles), downloaded
+    // BQ_PROJECTION_PCG: the masked system solved to a relative tolerance in the arrays of allocMgcg;
+    // with or without obstacles, one GPU only
+    int    pcg_iters = 1000;                        // most CG updates per projection (BimocqSolver.cpp:1269)
+    double pcg_tol = 1e-6;
+    double pcg_stats[4] = { 0, 0, 0, 0 };           // last projection: iterations, final max|r|, max|b|, stop reason (BQ_PCG_*)
+    long long pcg_projections = 0, pcg_unconverged = 0;
+    static bool pcgOperators();                     // the operator library has the PCG operators
+    bool projectionPcg();
 
     // Solid obstacles (setBoundary / updateBoundary, BimocqSolver.cpp:936-1064).  Jacobi projection on
     // one GPU only.  With an empty list a step issues exactly the launches it issues without this feature.

@@ -82,6 +82,21 @@ void bq_solver_set_projection(bq_solver *s, int kind, int iters, float halfrdx)
     if (kind == BQ_PROJECTION_MGCG) {
         s->solver->projection_kind = kind;
         s->solver->mg_iters = iters;
+    } else if (kind == BQ_PROJECTION_PCG) {
+        if (s->mapper->slab.on) {
+            fl_report_error(FL_ERR_UNSUPPORTED, "bq_solver_set_projection: BQ_PROJECTION_PCG is not built for z-slab ranks");
+            return;
+        }
+        if (!BimocqGPUSolver::pcgOperators()) {
+            fl_report_error(FL_ERR_UNSUPPORTED, "bq_solver_set_projection: the operator library has no PCG operators");
+            return;
+        }
+        if (iters < 0) {
+            fl_report_error(FL_ERR_BAD_ARGUMENT, "bq_solver_set_projection: BQ_PROJECTION_PCG needs iters >= 0");
+            return;
+        }
+        s->solver->projection_kind = kind;
+        s->solver->pcg_iters = iters;
     } else if (kind == BQ_PROJECTION_JACOBI) {
         s->solver->projection_kind = kind;
         s->solver->jacobi_iters = iters;
@@ -266,6 +281,37 @@ long bq_solver_mg_history(const bq_solver *s, double *host, long capacity)
     if (host)
         for (long a = 0; a < capacity && a < (long)h.size(); a++) host[a] = h[(size_t)a];
     return (long)h.size();
+}
+
+int bq_solver_set_pcg_tolerance(bq_solver *s, double tol)
+{
+    if (!s) return -1;
+    if (!(tol > 0.0 && tol < 1.0)) {                   // (NaN fails the test too)
+        fl_report_error(FL_ERR_BAD_ARGUMENT, "bq_solver_set_pcg_tolerance: tol must be finite and in (0, 1)");
+        return -1;
+    }
+    s->solver->pcg_tol = tol;
+    return 0;
+}
+
+int bq_solver_pcg_stats(const bq_solver *s, double out[6])
+{
+    if (!s || !out) return 0;
+    const BimocqGPUSolver &b = *s->solver;
+    for (int a = 0; a < 4; a++) out[a] = b.pcg_stats[a];
+    out[4] = (double)b.pcg_projections;
+    out[5] = (double)b.pcg_unconverged;
+    return b.pcg_projections > 0 ? 1 : 0;
+}
+
+long bq_solver_pcg_pressure(bq_solver *s, double *host, long capacity)
+{
+    BQ_ENTER(s);
+    if (!s || s->solver->pcg_projections == 0) return 0;
+    const BimocqGPUSolver &b = *s->solver;
+    const long count = (long)b.g.n();
+    if (host && capacity > 0) fl_memcpy_d2h(host, b.mg.p.f64(), (size_t)std::min(count, capacity) * sizeof(double));
+    return count;
 }
 
 long long bq_solver_phase_ms(bq_solver *s, double ms[BQ_PHASE_COUNT], int reset)

@@ -144,7 +144,12 @@ HOST_SIGS = {
     "bq_solver_set_boundary_levelsets": (C.c_int, [C.c_void_p, C.POINTER(Boundary), C.POINTER(LevelSetDesc), C.c_int]),
     "bq_solver_update_boundary": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
     "bq_solver_download_solid": (C.c_long, [C.c_void_p, C.c_void_p, C.c_long]),
+    "bq_solver_set_pcg_tolerance": (C.c_int, [C.c_void_p, C.c_double]),
+    "bq_solver_pcg_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "bq_solver_pcg_pressure": (C.c_long, [C.c_void_p, C.POINTER(C.c_double), C.c_long]),
 }
+PROJECTION_JACOBI, PROJECTION_MGCG, PROJECTION_PCG = 0, 1, 2
+PCG_STOP = {0: "converged", 1: "iteration limit", 2: "breakdown"}
 PHASES = ("maps", "advect_compensate", "forces", "projection", "accumulate_reinit")
 
 _host = None
@@ -205,9 +210,36 @@ class BimocqGPUSolver:
         self.lib.bq_solver_set_smoke(self.s, drop, rise, arr, len(emitters))
 
     def setProjection(self, iters, halfrdx, kind=0):
-        """kind 0: Jacobi, iters sweeps; kind 1: fp64 multigrid-CG, iters outer iterations (reference: 50)"""
+        """kind 0: Jacobi, iters sweeps; kind 1: fp64 multigrid-CG, iters outer iterations (reference: 50); kind 2: fp64
+        PCG on the masked system to the tolerance of setPcgTolerance, at most iters CG updates (CPU solver: 1000)"""
         self.lib.bq_solver_set_projection(self.s, kind, iters, halfrdx)
         self._check()
+
+    def setPcgTolerance(self, tol):
+        """kind 2 stops after the update with max|r| <= tol * max|b| (default 1e-6; 0 < tol < 1)"""
+        rc = self.lib.bq_solver_set_pcg_tolerance(self.s, float(tol))
+        self._check()
+        if rc != 0:
+            raise _lib.BimocqError("bq_solver_set_pcg_tolerance failed")
+
+    def pcgStats(self):
+        """the last kind-2 projection: {iterations, max_r, max_b, stop ("converged" / "iteration limit" / "breakdown"),
+        projections, unconverged}, or None before the first one"""
+        out = (C.c_double * 6)()
+        if not self.lib.bq_solver_pcg_stats(self.s, out):
+            return None
+        return {"iterations": int(out[0]), "max_r": out[1], "max_b": out[2], "stop": PCG_STOP.get(int(out[3]), "?"),
+                "projections": int(out[4]), "unconverged": int(out[5])}
+
+    def pcgPressure(self):
+        """the fp64 pressure of the last kind-2 projection as a (nz, ny, nx) array, or None before the first one"""
+        n = self.lib.bq_solver_pcg_pressure(self.s, None, 0)
+        if not n:
+            return None
+        out = np.zeros(n, dtype=np.float64)
+        self.lib.bq_solver_pcg_pressure(self.s, out.ctypes.data_as(C.POINTER(C.c_double)), n)
+        self._check()
+        return out.reshape(self.nz, self.ny, self.nx)
 
     def mgHistory(self):
         """tempResult of the last multigrid-CG projection (4096 doubles), or None before the first one"""
@@ -248,7 +280,7 @@ class BimocqGPUSolver:
     def setBoundary(self, boundaries):
         """setBoundary: replaces the obstacle list (Boundary objects or (shape, cx, cy, cz, rx, ry, rz, vx, vy, vz)
         tuples, or LevelSetObstacles; [] removes every obstacle) and builds the cell flags at the given centres.  One GPU,
-        Jacobi only.  A list with a level set goes through bq_solver_set_boundary_levelsets, which copies the grids to
+        Jacobi or PCG (kind 2) projection.  A list with a level set goes through bq_solver_set_boundary_levelsets, which copies the grids to
         the device; after a failed call with a level set there are no obstacles."""
         boundaries = list(boundaries)
         if any(isinstance(b, LevelSetObstacle) for b in boundaries):

@@ -712,6 +712,28 @@ void gpu_obstacle_blend_ls(float *u, float *v, float *w, float *rho, float *T, c
                            const float *ws, const float *rhos, const float *Ts, const unsigned char *solid,
                            const bq_boundary *b, int n, const bq_levelset *ls, float h, int ni, int nj, int nk);
 
+/* ---- converged fp64 projection, BQ_PROJECTION_PCG -------------------------------------------
+ * The masked Neumann system of section 14 on the interior cells that are fluid with s < 6 solid neighbours (diagonal
+ * 6 - s, -1 per interior fluid neighbour, border cells held at 0, b = -div), solved by flexible preconditioned CG from
+ * p = 0 until max|r| <= tol * max|b| (a geometric V-cycle preconditioner on the levels of gpu_multi_grid_conjugate_gradient).
+ * Single GPU. */
+enum { BQ_PCG_CONVERGED = 0, BQ_PCG_ITER_LIMIT = 1, BQ_PCG_BREAKDOWN = 2 };
+/* div = halfrdx ((u_r - u_l) + (v_b - v_f) + (w_u - w_d)) in fp64 at every cell (mg_divergence_kernel's expression) */
+void gpu_divergence_double(const float *u, const float *v, const float *w, double *div, int ni, int nj, int nk,
+                           double halfrdx);
+/* solve on `div` and `solid` (NULL: no obstacles) into p (every cell written: 0 where no unknown).  r, d, q, z, t, work:
+ * N-double device arrays (N = levels[0].number; their content on entry does not matter); levels[1 .. levelNum-1]: the
+ * coarse levels (dims (n - 1) / 2 per axis, alpha -1, beta 1/6), cleared and used as work arrays; levels[0] gives the
+ * dims only.  At most `iters` CG updates, 0 < tol < 1.  stats (host, 4 doubles): iterations, final max|r| (of the
+ * recursive residual), max|b|, stop reason (BQ_PCG_*).  Blocking: reads a few doubles back per iteration. */
+void gpu_pcg_solve(const double *div, double *p, const unsigned char *solid, double *r, double *d, double *q, double *z,
+                   double *t, double *work, struct SCoarseLevelInfo *levels, int levelNum, int iters, double tol,
+                   double *stats);
+/* u -= (float)(halfrdx (p_c - p_left)) (v, w likewise) on the faces of gpu_multi_grid_conjugate_gradient's gradient
+ * window [2, n) whose two cells are fluid (solid == NULL: every face of the window); other faces are left alone */
+void gpu_pcg_gradient(float *u, float *v, float *w, const double *p, const unsigned char *solid, int ni, int nj, int nk,
+                      double halfrdx);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,7 +30,11 @@ typedef struct bq_emitter {
 enum { BQ_SCHEME_BIMOCQ = 0, BQ_SCHEME_MAC_REFLECTION = 3 };
 enum {
     BQ_PROJECTION_JACOBI = 0,           /* the `#if 0` branch of BimocqGPUSolver::projection (:408-417); iters = sweeps      */
-    BQ_PROJECTION_MGCG = 1              /* the `#else` branch (:443-446): fp64 multigrid-CG; iters = outer iterations (50)  */
+    BQ_PROJECTION_MGCG = 1,             /* the `#else` branch (:443-446): fp64 multigrid-CG; iters = outer iterations (50)  */
+    BQ_PROJECTION_PCG = 2               /* fp64 flexible PCG on the masked system to a tolerance, the
+                                           CPU solver's semantics (BimocqSolver.cpp:1269); iters = most CG updates (1000).
+                                           One GPU: refused (FL_ERR_UNSUPPORTED) on z-slab ranks and when the operator
+                                           library has no PCG operators */
 };
 
 /* which-ids for bq_solver_download */
@@ -156,6 +160,15 @@ long  bq_solver_download(bq_solver *s, int which, float *host, long capacity);
  * residual per outer iteration at [2000..2000+iters] -- what the reference prints, BimocqGPUSolver.cpp:447-452).
  * Returns the count (0 before the first MGCG projection); copies min(count, capacity). */
 long  bq_solver_mg_history(const bq_solver *s, double *host, long capacity);
+/* BQ_PROJECTION_PCG: relative tolerance of the stopping rule max|r| <= tol * max|b| (default 1e-6); a tol that is not
+ * finite or lies outside (0, 1) is refused (FL_ERR_BAD_ARGUMENT, the tolerance is kept).  Returns 0 on success. */
+int   bq_solver_set_pcg_tolerance(bq_solver *s, double tol);
+/* out = {iterations, final max|r|, max|b|, stop reason (BQ_PCG_CONVERGED / _ITER_LIMIT / _BREAKDOWN) of the last PCG
+ * projection, PCG projections so far, those of them that did not converge}; returns 0 before the first one, else 1 */
+int   bq_solver_pcg_stats(const bq_solver *s, double out[6]);
+/* the fp64 pressure of the last PCG projection (nz * ny * nx, x fastest); returns the count (0 before the first one) and
+ * copies min(count, capacity) */
+long  bq_solver_pcg_pressure(bq_solver *s, double *host, long capacity);
 /* The dump without stalling the simulation: asynchronous download on a third stream + a writer thread; the
  * file is the one bq_solver_output_result would write.  At most one dump in flight (a second call waits for
  * the first).  _wait returns the voxel count of the last asynchronous dump, or -1. */
@@ -163,8 +176,9 @@ int   bq_solver_output_result_async(bq_solver *s, unsigned frame, const char *pa
 long  bq_solver_output_wait(bq_solver *s);
 /* Solid obstacles (setBoundary / updateBoundary, BimocqSolver.cpp:936-1064).  set_boundary
  * replaces the whole list (n = 0 removes every obstacle; at most BQ_MAX_BOUNDARIES) and builds the cell flags at the
- * given centres; update_boundary moves every centre by v * dt (Boundary::update) and rebuilds them.  Jacobi projection
- * on one GPU only: z-slab ranks and BQ_PROJECTION_MGCG are refused through fl_last_error.  Returns 0 on success.
+ * given centres; update_boundary moves every centre by v * dt (Boundary::update) and rebuilds them.  One GPU, with the
+ * Jacobi projection or BQ_PROJECTION_PCG (either call order): z-slab ranks and BQ_PROJECTION_MGCG are refused through
+ * fl_last_error.  Returns 0 on success.
  * download_solid copies min(cells, capacity) flags (1 = obstacle) and returns the cell count. */
 int   bq_solver_set_boundary(bq_solver *s, const bq_boundary *b, int n);
 /* set_boundary for lists that may hold level sets (shape BQ_SHAPE_LEVELSET; DESIGN.md section 14, "Level sets"): ls is
