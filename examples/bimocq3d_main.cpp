@@ -27,7 +27,7 @@ int main(int argc, char **argv)
     const int scheme = argc > 4 ? std::atoi(argv[4]) : 0;            // 0 BIMOCQ, 3 MAC_REFLECTION (main.cpp:51 ships 3)
     const int projection = argc > 5 ? std::atoi(argv[5]) : 0;        // 0 Jacobi, 1 multigrid-CG (what the binary ships)
     const bool async_dump = argc > 6 ? std::atoi(argv[6]) != 0 : true;
-    const int scene = argc > 7 ? std::atoi(argv[7]) : 0;             // 0 rising smoke, 1 leapfrogging vortex rings
+    const int scene = argc > 7 ? std::atoi(argv[7]) : 0;             // 0 rising smoke, 1 leapfrogging vortex rings, 2 box-shaped plume source
     if (n < 8 || total_frame < 1 || (scene == 1 && n % 2)) {
         std::fprintf(stderr, "usage: %s [N>=8] [frames] [outdir] [scheme] [projection] [async] [scene]\n", argv[0]); return 2;
     }
@@ -51,6 +51,18 @@ int main(int argc, char **argv)
         a.e_pos[0] = 0.15f; a.e_pos[1] = yc; a.e_pos[2] = zc;
         b.e_pos[0] = 0.35f; b.e_pos[1] = yc; b.e_pos[2] = zc;
         mysolver.setSmoke(smoke_drop, smoke_rise, { a, b });
+    } else if (scene == 2) {
+        // the plume of DESIGN.md section 16 with an analytic box in place of the level set: active on every frame,
+        // blowing upwards with a slow spin about the vertical axis
+        bq_source src{};
+        src.shape.shape = BQ_SHAPE_BOX;
+        src.shape.cx = 0.5f; src.shape.cy = 0.2f; src.shape.cz = 0.5f;
+        src.shape.rx = 0.08f; src.shape.ry = 0.04f; src.shape.rz = 0.08f;
+        src.density = src.temperature = 1.f;
+        src.ey = 0.5f; src.oy = 0.5f;
+        src.emit_frames = total_frame; src.flags = BQ_SOURCE_VELOCITY;
+        mysolver.setSmoke(smoke_drop, smoke_rise, {});
+        if (!mysolver.setSources(&src, nullptr, 1)) { std::fprintf(stderr, "%s\n", fl_last_error_string()); return 1; }
     } else {
         Emitter src;                                                 // one warm sphere, applied at frame 0 only
         src.emitFrame = 1; src.emit_density = 1.f; src.emit_temperature = 1.f; src.emiter = 0.f;

@@ -151,6 +151,8 @@ HIP_SIGS = {
     "gpu_obstacle_flags_ls": (None, [VP, VP, VP, c_i, VP] + _G),
     "gpu_semilag_band_ls": (None, [VP] * 5 + [c_i, c_i, c_i] + _G + [c_f, c_f, VP, c_i, VP]),
     "gpu_obstacle_blend_ls": (None, [VP] * 11 + [VP, c_i, VP] + _G),
+    # shaped sources (bq_source and bq_levelset arrays travel as HOST pointers: solver.SourceDesc / LevelSetDesc)
+    "gpu_emit_sources": (None, [VP] * 5 + [VP, VP, c_i] + _G),
 }
 
 FL_OK, FL_ERR_NO_DEVICE, FL_ERR_HIP, FL_ERR_BAD_ARGUMENT, FL_ERR_UNSUPPORTED, FL_ERR_COMM = range(6)

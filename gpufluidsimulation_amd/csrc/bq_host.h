@@ -74,6 +74,13 @@ struct Runtime {
 };
 
 Runtime &rt();
+// slab context of the library: (koff, nkg); single GPU: (0, nk)
+inline void slab_ctx(int nk, int &koff, int &nkg)
+{
+    const Runtime &r = rt();
+    koff = r.slab_on ? r.slab_koff : 0;
+    nkg = r.slab_on ? r.slab_nkg : nk;
+}
 void latch(int code, const char *what, const char *detail);
 bool ensure_ready(const char *op);      // lazily fl_init(current device); false -> latched
 void *scratch(size_t bytes);            // device scratch of at least `bytes` (grows, never shrinks)

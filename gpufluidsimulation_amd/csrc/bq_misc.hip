@@ -268,14 +268,6 @@ __global__ __launch_bounds__(256) void max2_final_kernel(const float *__restrict
     if (threadIdx.x == 0) { out[0] = fmaxf(fmaxf(sa[0], sa[1]), fmaxf(sa[2], sa[3])); out[1] = fmaxf(fmaxf(sb[0], sb[1]), fmaxf(sb[2], sb[3])); }
 }
 
-// slab context of the library: (koff, nkg); single GPU: (0, nk)
-static inline void slab_ctx(int nk, int &koff, int &nkg)
-{
-    const Runtime &r = rt();
-    koff = r.slab_on ? r.slab_koff : 0;
-    nkg = r.slab_on ? r.slab_nkg : nk;
-}
-
 static inline int stream_blocks(size_t n)
 {
     size_t b = (n + 255) / 256;

@@ -130,6 +130,28 @@ __device__ __forceinline__ int obs_classify(float x, float y, float z, const Obs
     return solid ? solid : (band ? -1 : 0);
 }
 
+// the solid test of obs_classify for ONE entry o, without the band: what makes a node part of a source (DESIGN.md
+// section 16).  Same expressions, same operation order.
+template <typename... Ls>
+__device__ __forceinline__ bool obs_solid(float x, float y, float z, int o, const ObsSet &s, const Ls &...ls)
+{
+    static_assert(sizeof...(Ls) <= 1, "one LsSet at most");
+    if constexpr (sizeof...(Ls) == 1) {
+        if (s.shape[o] == BQ_SHAPE_LEVELSET) {
+            const LsSet &l = (ls, ...);
+            float sdf;
+            return ls_sample(l, o, x, y, z, s.cx[o], s.cy[o], s.cz[o], sdf) && sdf <= 0.f;
+        }
+    }
+    const float dx = x - s.cx[o], dy = y - s.cy[o], dz = z - s.cz[o];
+    if (s.shape[o] == BQ_SHAPE_SPHERE) {
+        const float d2 = dx * dx + dy * dy + dz * dz;
+        return d2 <= s.rx[o] * s.rx[o];
+    }
+    const float ax = fabsf(dx) - s.rx[o], ay = fabsf(dy) - s.ry[o], az = fabsf(dz) - s.rz[o];
+    return ax <= 0.f && ay <= 0.f && az <= 0.f;
+}
+
 // sample position of node i on an axis with stagger d (0: cell centre, 1: face): (i - d/2) h
 __device__ __forceinline__ float obs_pos(int i, int d, float h) { return ((float)i - (d ? 0.5f : 0.f)) * h; }
 

@@ -34,6 +34,7 @@
 #pragma weak gpu_divergence_double
 #pragma weak gpu_pcg_solve
 #pragma weak gpu_pcg_gradient
+#pragma weak gpu_emit_sources
 
 namespace bqhost {
 
@@ -60,6 +61,35 @@ static void obstacle_blend(float *u, float *v, float *w, float *rho, float *T, c
 {
     if (ls) gpu_obstacle_blend_ls(u, v, w, rho, T, us, vs, ws, rhos, Ts, solid, b, n, ls, h, ni, nj, nk);
     else    gpu_obstacle_blend(u, v, w, rho, T, us, vs, ws, rhos, Ts, solid, b, n, h, ni, nj, nk);
+}
+
+// Every level-set grid of a list (entry o is one when is_ls[o]; ls[o].phi a HOST array) copied into ONE device allocation,
+// `descs` receiving one descriptor per entry whose phi points into it.  `who` prefixes the refusal (more than `cap` bytes
+// in all).  Shared by setBoundary and setSources, whose allocations are counted apart.
+static bool upload_levelsets(const std::vector<char> &is_ls, const bq_levelset *ls, size_t cap, const char *who,
+                             DeviceBytes &grids, std::vector<bq_levelset> &descs)
+{
+    const int n = (int)is_ls.size();
+    auto grid_bytes = [&](int o) { return (size_t)ls[o].nx * (size_t)ls[o].ny * (size_t)ls[o].nz * sizeof(float); };
+    size_t total = 0;                                   // below 16 * 2^33 bytes: no overflow
+    for (int o = 0; o < n; o++)
+        if (is_ls[o]) total += grid_bytes(o);
+    if (total > cap) {
+        fl_report_error(FL_ERR_BAD_ARGUMENT, (std::string(who) + ": level-set grids above 256 MiB in all").c_str());
+        return false;
+    }
+    if (!grids.alloc(total)) return false;
+    descs.assign((size_t)n, bq_levelset{});
+    size_t at = 0;
+    for (int o = 0; o < n; o++) {
+        if (!is_ls[o]) continue;
+        float *dst = reinterpret_cast<float *>(grids.u8() + at);
+        fl_memcpy_h2d(dst, ls[o].phi, grid_bytes(o));
+        descs[o] = ls[o];
+        descs[o].phi = dst;
+        at += grid_bytes(o);
+    }
+    return fl_last_error() == FL_OK;
 }
 
 // BQ_TRACE=1 (debug): after each stage print the sum of squares of the planes this rank owns, so a
@@ -288,12 +318,91 @@ float BimocqGPUSolver::getCFL()
 }
 
 // :376-392 with the hard-coded scene constants replaced by the emitter list (pointwise in z)
-void BimocqGPUSolver::emitSmoke(int framenum, float /*dt*/)
+void BimocqGPUSolver::emitSmoke(int framenum, float dt)
 {
     for (const Emitter &e : sim_emitter)
         if (framenum < e.emitFrame)
             GpuSolver->emitSmoke(VelocityU, VelocityV, VelocityW, Density, Temperature,
                                  e.e_pos[0], e.e_pos[1], e.e_pos[2], e.radius, e.emit_density, e.emit_temperature, e.emiter);
+    if (sources.empty()) return;
+    // BimocqSolver.cpp:696-813: Emitter::update moves every source, active or not, before the active test (:698); then
+    // the active ones write at the moved position, in list order (pointwise in z: ghost planes are written too)
+    std::vector<bq_source> act;
+    std::vector<bq_levelset> act_ls;
+    for (size_t o = 0; o < sources.size(); o++) {
+        bq_boundary &b = sources[o].shape;
+        b.cx = b.cx + b.vx * dt;
+        b.cy = b.cy + b.vy * dt;
+        b.cz = b.cz + b.vz * dt;
+        if (framenum >= sources[o].emit_frames) continue;
+        act.push_back(sources[o]);
+        if (!source_levelsets.empty()) act_ls.push_back(source_levelsets[o]);
+    }
+    if (!act.empty())
+        gpu_emit_sources(VelocityU, VelocityV, VelocityW, Density, Temperature, act.data(), act_ls.empty() ? nullptr : act_ls.data(),
+                         (int)act.size(), CellSize, g.ni, g.nj, g.nk);
+}
+
+bool BimocqGPUSolver::velocitySourceActive(int framenum) const
+{
+    return std::any_of(sources.begin(), sources.end(), [&](const bq_source &s) {
+        return framenum < s.emit_frames && (s.flags & BQ_SOURCE_VELOCITY); });
+}
+
+// The source list replaces the previous one (n = 0: none, list and grids released).  ls[o] is read for the entries whose
+// shape is BQ_SHAPE_LEVELSET, its phi a HOST array that is copied into one device allocation with every other grid of the
+// list.  Any refusal leaves no sources.
+bool BimocqGPUSolver::setSources(const bq_source *src, const bq_levelset *ls, int n)
+{
+    dropSources();
+    if (n < 0 || n > BQ_MAX_SOURCES || (n > 0 && !src)) {
+        fl_report_error(FL_ERR_BAD_ARGUMENT, "setSources: 0 .. 16 sources");
+        return false;
+    }
+    if (n == 0) return true;
+    if (!gpu_emit_sources) {
+        fl_report_error(FL_ERR_UNSUPPORTED, "setSources: the operator library has no gpu_emit_sources");
+        return false;
+    }
+    std::vector<bq_boundary> shapes((size_t)n);
+    std::vector<char> is_ls((size_t)n);
+    for (int o = 0; o < n; o++) {
+        const bq_source &s = src[o];
+        const bq_boundary &x = shapes[o] = s.shape;
+        const bool sphere = x.shape == BQ_SHAPE_SPHERE, levelset = x.shape == BQ_SHAPE_LEVELSET;
+        is_ls[o] = levelset;
+        const float fin[] = { x.cx, x.cy, x.cz, x.vx, x.vy, x.vz, s.density, s.temperature, s.ex, s.ey, s.ez, s.ox, s.oy, s.oz };
+        const bool finite = std::all_of(std::begin(fin), std::end(fin), [](float f) { return std::isfinite(f); });
+        if ((!levelset && ((!sphere && x.shape != BQ_SHAPE_BOX) || !(x.rx > 0.f) || (!sphere && !(x.ry > 0.f && x.rz > 0.f)) ||
+                           !std::isfinite(x.rx) || !std::isfinite(x.ry) || !std::isfinite(x.rz))) ||
+            !finite || s.emit_frames < 0 || (s.flags & ~BQ_SOURCE_VELOCITY)) {
+            fl_report_error(FL_ERR_BAD_ARGUMENT, "setSources: unknown shape or flag, non-positive size, negative emit_frames or non-finite value");
+            return false;
+        }
+    }
+    const bool any_ls = std::any_of(is_ls.begin(), is_ls.end(), [](char c) { return c != 0; });
+    if (any_ls && !ls) {
+        fl_report_error(FL_ERR_BAD_ARGUMENT, "setSources: level-set entries without descriptors");
+        return false;
+    }
+    if (const char *why = bq::ls_check(shapes.data(), ls, n)) {
+        fl_report_error(FL_ERR_BAD_ARGUMENT, (std::string("setSources: ") + why).c_str());
+        return false;
+    }
+    DeviceBytes grids;
+    std::vector<bq_levelset> descs;
+    if (any_ls && !upload_levelsets(is_ls, ls, kMaxLevelsetBytes, "setSources", grids, descs)) return false;
+    sources.assign(src, src + n);
+    source_levelsets.swap(descs);
+    source_grids = std::move(grids);
+    return true;
+}
+
+void BimocqGPUSolver::dropSources()
+{
+    sources.clear();
+    source_levelsets.clear();
+    source_grids.release();
 }
 
 // :394-397 (reads rho/T at j and j-1 of the same plane: no reach along z)
@@ -541,30 +650,13 @@ bool BimocqGPUSolver::setBoundary(const bq_boundary *b, const bq_levelset *ls, i
         fl_report_error(FL_ERR_BAD_ARGUMENT, (std::string("setBoundary: ") + why).c_str());
         return false;
     }
-    auto grid_bytes = [&](int o) { return (size_t)ls[o].nx * (size_t)ls[o].ny * (size_t)ls[o].nz * sizeof(float); };
-    size_t total = 0;                                   // below 16 * 2^33 bytes: no overflow
-    for (int o = 0; o < n; o++)
-        if (b[o].shape == BQ_SHAPE_LEVELSET) total += grid_bytes(o);
-    if (total > kMaxLevelsetBytes) {
-        fl_report_error(FL_ERR_BAD_ARGUMENT, "setBoundary: level-set grids above 256 MiB in all");
-        return false;
-    }
     // every grid into one allocation, the descriptors pointing into it
     DeviceBytes grids;
     std::vector<bq_levelset> descs;
     if (any_ls) {
-        if (!grids.alloc(total)) return false;
-        descs.assign((size_t)n, bq_levelset{});
-        size_t at = 0;
-        for (int o = 0; o < n; o++) {
-            if (b[o].shape != BQ_SHAPE_LEVELSET) continue;
-            float *dst = reinterpret_cast<float *>(grids.u8() + at);
-            fl_memcpy_h2d(dst, ls[o].phi, grid_bytes(o));
-            descs[o] = ls[o];
-            descs[o].phi = dst;
-            at += grid_bytes(o);
-        }
-        if (fl_last_error() != FL_OK) return false;
+        std::vector<char> is_ls((size_t)n);
+        for (int o = 0; o < n; o++) is_ls[o] = b[o].shape == BQ_SHAPE_LEVELSET;
+        if (!upload_levelsets(is_ls, ls, kMaxLevelsetBytes, "setBoundary", grids, descs)) return false;
     }
     const size_t nrows = (size_t)g.nj * (size_t)g.nk;
     if (solid.bytes() != g.n() && !solid.alloc(g.n())) return false;
@@ -983,6 +1075,7 @@ void BimocqGPUSolver::advanceBimocq(int framenum, float dt)
     // components, u and w stay what they are until the projection.
     bool forces_touch_uw = Viscosity != 0.f;
     for (const Emitter &e : sim_emitter) forces_touch_uw = forces_touch_uw || framenum < e.emitFrame;
+    forces_touch_uw = forces_touch_uw || velocitySourceActive(framenum);
     // :157-159 snapshots for the force delta (:175-177).  The u and w snapshots are only ever read by that delta
     // (with the Jacobi projection the gradient pass hands out d*Proj, :179-193 needs no snapshot) and by the
     // viscous diffusion, which uses them as work arrays: not taken when nothing will touch u and w.

@@ -16,8 +16,9 @@ namespace bqhost {
 
 enum Scheme { BIMOCQ = 0, SEMILAG, MACCORMACK, MAC_REFLECTION };     // BimocqSolver.h:29
 
-// The reference's Emitter carries an OpenVDB SDF that the GPU solver never samples
-// (BimocqGPUSolver.cpp:376-392 uses hard-coded spheres); what it does use is kept.
+// The legacy emitter: the reference's GPU solver never samples its Emitter's OpenVDB SDF
+// (BimocqGPUSolver.cpp:376-392 uses hard-coded spheres); what it does use is kept.  Sources that are
+// sampled -- spheres, boxes, level sets -- are bq_source entries (setSources below).
 struct Emitter {
     int emitFrame = 0;
     float emit_density = 0.f, emit_temperature = 0.f;
@@ -144,6 +145,17 @@ public:
     bool projectionObstacles(bool with_delta);
     void blendBoundary(bool band);                  // band: blendBoundary + clearBoundary, else clearBoundary only
     void semilagBand(float cfldt, float dt);
+
+    // Shaped, moving smoke sources (Emitter / emitSmoke of the CPU solver, BimocqSolver.h:31-59, BimocqSolver.cpp:696-813;
+    // DESIGN.md section 16): a second list next to sim_emitter.  At every emission point each source first moves by its own
+    // velocity * dt, then the active ones are applied by one gpu_emit_sources call.  With an empty list a step issues
+    // exactly the launches it issues without this feature.
+    std::vector<bq_source> sources;
+    std::vector<bq_levelset> source_levelsets;      // one descriptor per entry of `sources` (phi into source_grids) when the list holds a level set, else empty
+    DeviceBytes source_grids;                       // every level-set grid of the sources, one allocation (counted apart from lsgrids)
+    bool setSources(const bq_source *src, const bq_levelset *ls, int n);       // ls: NULL when no entry is a level set
+    void dropSources();
+    bool velocitySourceActive(int framenum) const;  // some source imposes its velocity this frame
 
     std::vector<float> host_density, host_u, host_v, host_w;    // outputResult staging (:538-541)
 

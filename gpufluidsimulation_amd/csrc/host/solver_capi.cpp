@@ -240,6 +240,21 @@ int bq_solver_set_boundary_levelsets(bq_solver *s, const bq_boundary *b, const b
     return -1;
 }
 
+int bq_solver_set_sources(bq_solver *s, const bq_source *src, const bq_levelset *ls, int n)
+{
+    BQ_ENTER(s);
+    if (!s) return -1;
+    return s->solver->setSources(src, ls, n) ? 0 : -1;      // (a refused list leaves no sources)
+}
+
+int bq_solver_source_position(const bq_solver *s, int i, float out[3])
+{
+    if (!s || !out || i < 0 || i >= (int)s->solver->sources.size()) return -1;
+    const bq_boundary &b = s->solver->sources[(size_t)i].shape;
+    out[0] = b.cx; out[1] = b.cy; out[2] = b.cz;
+    return 0;
+}
+
 int bq_solver_update_boundary(bq_solver *s, int framenum, float dt)
 {
     BQ_ENTER(s);

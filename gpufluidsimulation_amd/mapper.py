@@ -4,6 +4,8 @@ Same method names, argument order and pre-zeroing behaviour as the reference cla
 parity tests read like calls into the reference.  It owns nothing but device buffers and calls
 only the C-ABI; numpy arrays cross the boundary through DeviceBuffer.
 """
+import ctypes as C
+
 import numpy as np
 
 from . import _lib
@@ -140,6 +142,27 @@ class GpuMapper:
     def emitSmoke(self, u, v, w, rho, T, cx, cy, cz, radius, density, temperature, emiter):
         self.lib.gpu_emit_smoke(u.ptr, v.ptr, w.ptr, rho.ptr, T.ptr, *self._g(),
                                 cx, cy, cz, radius, density, temperature, emiter)
+
+    # shaped sources: `sources` solver.Source objects, level-set grids uploaded for the call
+    def emitSources(self, u, v, w, rho, T, sources):
+        from .solver import source_arrays
+        sources = list(sources)
+        arr, ls, n = source_arrays(sources)
+        grids = []
+        if ls is not None:
+            for i, s in enumerate(sources):
+                if getattr(s, "levelset", None) is not None:
+                    phi = s.levelset.phi
+                    d = self.lib.fl_malloc(phi.nbytes)
+                    self.lib.fl_memcpy_h2d(d, phi.ctypes.data, phi.nbytes)
+                    ls[i].phi = d
+                    grids.append(d)
+        self.lib.gpu_emit_sources(u.ptr, v.ptr, w.ptr, rho.ptr, T.ptr, C.addressof(arr), C.addressof(ls) if ls is not None else None,
+                                  n, *self._g())
+        if grids:
+            self.lib.fl_sync()
+            for d in grids:
+                self.lib.fl_free(d)
 
     # GPU_Advection.h:560-564
     def add_buoyancy(self, v, rho, T, alpha, beta, dt):

@@ -33,3 +33,22 @@ def collision(h):
     Q14) -- is nudged off the nodes exactly as the reference nudges its second one (y = 0.201)."""
     return [(0.04, 0.2 + 0.37 * h, 0.2 + 0.29 * h, 0.015, 1.0, 50.0, 1.0, 10),
             (0.16, 0.201, 0.2, 0.015, 1.0, 50.0, -1.0, 10)]
+
+
+def plume(nz_global, h):
+    """a shaped source (solver.Source list for BimocqGPUSolver.setSources): a box of half extents
+    (0.08, 0.04, 0.08) given as a level set of spacing h, under the rising-smoke position, blowing upwards at 0.5 with a slow
+    spin about the vertical axis, active on every frame"""
+    import numpy as np
+
+    from .solver import Source, levelset_from_sdf
+    hx, hy, hz = 0.08, 0.04, 0.08
+
+    def sdf(x, y, z):
+        q = [np.abs(x) - hx, np.abs(y) - hy, np.abs(z) - hz]
+        out = np.sqrt(sum(np.maximum(a, 0.0) ** 2 for a in q))
+        return out + np.minimum(np.maximum(np.maximum(q[0], q[1]), q[2]), 0.0)
+
+    box = levelset_from_sdf(sdf, (-hx, -hy, -hz), (hx, hy, hz), h)
+    return [Source(box, (SMOKE[0], SMOKE[1], 0.5 * nz_global * h), 1.0, 1.0, 1 << 30, velocity=(0.0, 0.5, 0.0),
+                   spin=(0.0, 0.5, 0.0))]

@@ -118,6 +118,66 @@ def levelset_arrays(boundaries):
     return arr, ls, len(boundaries)
 
 
+SOURCE_VELOCITY = 1
+MAX_SOURCES = 16
+
+
+class SourceDesc(C.Structure):
+    """bq_source: shape entry (position, extents, the velocity the source itself moves with), density, temperature,
+    emitted velocity, angular velocity of the emitted field, emit_frames, flags"""
+    _fields_ = [("shape", Boundary), ("density", C.c_float), ("temperature", C.c_float),
+                ("ex", C.c_float), ("ey", C.c_float), ("ez", C.c_float),
+                ("ox", C.c_float), ("oy", C.c_float), ("oz", C.c_float),
+                ("emit_frames", C.c_int), ("flags", C.c_int)]
+
+
+class Source:
+    """A shaped, moving smoke source.  shape: ("sphere", r), ("box", (hx, hy, hz)) or a LevelSet
+    whose index origin sits at `position`.  Nodes inside take `density` and `temperature` while framenum < emit_frames;
+    with velocity = (ex, ey, ez) the u, v, w nodes inside also take velocity + spin x (node - position), velocity=None
+    imposes no velocity at all.  The source itself moves by motion * dt at every emission."""
+
+    def __init__(self, shape, position, density, temperature, emit_frames, velocity=None, spin=(0.0, 0.0, 0.0),
+                 motion=(0.0, 0.0, 0.0)):
+        self.levelset = shape if isinstance(shape, LevelSet) else None
+        if self.levelset is not None:
+            self.code, self.extents = SHAPE_LEVELSET, (0.0, 0.0, 0.0)
+        elif shape[0] == "sphere":
+            self.code, self.extents = SHAPE_SPHERE, (float(shape[1]), 0.0, 0.0)
+        elif shape[0] == "box":
+            self.code, self.extents = SHAPE_BOX, tuple(float(x) for x in shape[1])
+        else:
+            raise ValueError('shape must be ("sphere", r), ("box", (hx, hy, hz)) or a LevelSet')
+        self.position = tuple(float(x) for x in position)
+        self.density, self.temperature, self.emit_frames = float(density), float(temperature), int(emit_frames)
+        self.velocity = None if velocity is None else tuple(float(x) for x in velocity)
+        self.spin = tuple(float(x) for x in spin)
+        self.motion = tuple(float(x) for x in motion)
+
+    def descriptor(self):
+        vel = self.velocity if self.velocity is not None else (0.0, 0.0, 0.0)
+        return SourceDesc(Boundary(self.code, *self.position, *self.extents, *self.motion), self.density, self.temperature,
+                          *vel, *self.spin, self.emit_frames, SOURCE_VELOCITY if self.velocity is not None else 0)
+
+
+def source_arrays(sources):
+    """(SourceDesc array, LevelSetDesc array or None, count) for a list of Sources (or ready SourceDescs); the level-set
+    descriptors point at the LevelSets' host arrays"""
+    sources = list(sources)
+    arr = (SourceDesc * max(1, len(sources)))()
+    ls = (LevelSetDesc * max(1, len(sources)))()
+    any_ls = False
+    for i, s in enumerate(sources):
+        if isinstance(s, SourceDesc):
+            arr[i] = s
+            continue
+        arr[i] = s.descriptor()
+        if s.levelset is not None:
+            ls[i] = s.levelset.descriptor()
+            any_ls = True
+    return arr, (ls if any_ls else None), len(sources)
+
+
 HOST_SIGS = {
     "bq_solver_create": (C.c_void_p, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int]),
     "bq_solver_create_slab": (C.c_void_p, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int,
@@ -144,6 +204,8 @@ HOST_SIGS = {
     "bq_solver_set_boundary_levelsets": (C.c_int, [C.c_void_p, C.POINTER(Boundary), C.POINTER(LevelSetDesc), C.c_int]),
     "bq_solver_update_boundary": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
     "bq_solver_download_solid": (C.c_long, [C.c_void_p, C.c_void_p, C.c_long]),
+    "bq_solver_set_sources": (C.c_int, [C.c_void_p, C.POINTER(SourceDesc), C.POINTER(LevelSetDesc), C.c_int]),
+    "bq_solver_source_position": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
     "bq_solver_set_pcg_tolerance": (C.c_int, [C.c_void_p, C.c_double]),
     "bq_solver_pcg_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "bq_solver_pcg_pressure": (C.c_long, [C.c_void_p, C.POINTER(C.c_double), C.c_long]),
@@ -299,6 +361,24 @@ class BimocqGPUSolver:
         self._check()
         if rc != 0:
             raise _lib.BimocqError("bq_solver_update_boundary failed")
+
+    def setSources(self, sources):
+        """replaces the list of shaped sources (Source objects; [] removes them and releases their grids).  Level-set
+        grids are copied to the device once.  Allowed on z-slab ranks, with every projection kind, with and without
+        obstacles; after a refused call there are no sources."""
+        arr, ls, n = source_arrays(sources)
+        rc = self.lib.bq_solver_set_sources(self.s, arr, ls, n)
+        self._check()
+        if rc != 0:
+            raise _lib.BimocqError("bq_solver_set_sources failed")
+
+    def sourcePositions(self):
+        """the current position of every source as an (n, 3) float32 array"""
+        out = []
+        p = (C.c_float * 3)()
+        while self.lib.bq_solver_source_position(self.s, len(out), p) == 0:
+            out.append(list(p))
+        return np.array(out, dtype=np.float32).reshape(-1, 3)
 
     def solidMask(self):
         """cell flags, 1 = obstacle, as a (nz, ny, nx) uint8 array"""

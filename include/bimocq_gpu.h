@@ -712,6 +712,38 @@ void gpu_obstacle_blend_ls(float *u, float *v, float *w, float *rho, float *T, c
                            const float *ws, const float *rhos, const float *Ts, const unsigned char *solid,
                            const bq_boundary *b, int n, const bq_levelset *ls, float h, int ni, int nj, int nk);
 
+/* ---- shaped, moving smoke sources (reference: Emitter and BimocqSolver::emitSmoke of the CPU
+ * solver, BimocqSolver.h:31-59, BimocqSolver.cpp:696-813) ----------------------------------------------------------------
+ * A source is a shape of section 14 (sphere, box or level set) at a position.  A node belongs to it when the obstacle
+ * classification calls the node solid (no band).  Cell nodes inside take the source's density and temperature; u, v and
+ * w nodes inside, each sampled at its own face position, take the emitted velocity when the source has
+ * BQ_SOURCE_VELOCITY: with d = node position - source position, u = ex + (oy dz - oz dy), v = ey + (oz dx - ox dz),
+ * w = ez + (ox dy - oy dx), every operation one float operation in that order.  Sources act in list order, values are
+ * overwritten: the last source that contains a node (for faces: and has the flag) wins. */
+#ifndef BQ_SOURCE_DEFINED
+#define BQ_SOURCE_DEFINED
+enum { BQ_SOURCE_VELOCITY = 1 };        /* flags: the source also imposes its velocity field */
+enum { BQ_MAX_SOURCES = 16 };
+typedef struct bq_source {
+    bq_boundary shape;                  /* shape code, position cx..cz, extents rx..rz (unused for level sets),
+                                           vx..vz = the velocity the SOURCE ITSELF moves with */
+    float density, temperature;
+    float ex, ey, ez;                   /* emitted velocity at the position */
+    float ox, oy, oz;                   /* angular velocity of the emitted field about the position */
+    int   emit_frames;                  /* active while framenum < emit_frames (read by the host solver only) */
+    int   flags;
+} bq_source;
+#endif
+/* every entry of src[0 .. n) applied to the nodes of the legacy emitter's window (1 < i < n - 2 on every axis of each
+ * buffer's own dimensions, the global plane index on z-slab ranks; pointwise, ghost planes included).  ni, nj, nk: CELL
+ * dims.  `ls`: host array of n descriptors whose phi are device pointers, ls[o] read only when src[o].shape.shape ==
+ * BQ_SHAPE_LEVELSET (NULL allowed when no entry is one).  One launch over the node boxes the entries can reach; nothing
+ * is launched when no box meets the window.  n > BQ_MAX_SOURCES, an unknown shape or flag bit, a level-set entry without
+ * descriptors or with a bad one latch FL_ERR_BAD_ARGUMENT and launch nothing.  So does a list whose boxes hold more than
+ * 65 535 planes in all (planes are launched along grid.z: 16 sources that each span 4096 planes and more). */
+void gpu_emit_sources(float *u, float *v, float *w, float *rho, float *T, const bq_source *src, const bq_levelset *ls,
+                      int n, float h, int ni, int nj, int nk);
+
 /* ---- converged fp64 projection, BQ_PROJECTION_PCG -------------------------------------------
  * The masked Neumann system of section 14 on the interior cells that are fluid with s < 6 solid neighbours (diagonal
  * 6 - s, -1 per interior fluid neighbour, border cells held at 0, b = -div), solved by flexible preconditioned CG from

@@ -189,6 +189,21 @@ int   bq_solver_set_boundary(bq_solver *s, const bq_boundary *b, int n);
  * obstacles.  Returns 0 on success. */
 int   bq_solver_set_boundary_levelsets(bq_solver *s, const bq_boundary *b, const bq_levelset *ls, int n);
 int   bq_solver_update_boundary(bq_solver *s, int framenum, float dt);
+/* Shaped, moving smoke sources (Emitter / emitSmoke of the CPU solver, BimocqSolver.h:31-59, BimocqSolver.cpp:696-813;
+ * DESIGN.md section 16): a second list next to the emitters of set_smoke, which keep their launches and their bits.
+ * set_sources replaces the list (n = 0 releases list and grids; at most BQ_MAX_SOURCES).  ls is an array of n
+ * descriptors, ls[o] read only where src[o].shape.shape == BQ_SHAPE_LEVELSET (NULL allowed when no entry is one), whose
+ * phi are HOST arrays: every grid is copied into one device allocation of the sources' own (at most 256 MiB in all) and
+ * never uploaded again.  At every emission point of a step (once per advance in both schemes, after the emitters) every
+ * source, active or not, first moves by shape.v * dt per component in float; then the sources with framenum <
+ * emit_frames act in list order (gpu_emit_sources).  Allowed on z-slab ranks, with every projection kind, with and
+ * without obstacles.  Refused with FL_ERR_BAD_ARGUMENT: more than 16 entries, an unknown shape or flag, a non-finite
+ * field, a non-positive extent of an analytic shape, a negative emit_frames, a level-set entry without descriptors, a
+ * bad descriptor, the cap; with FL_ERR_UNSUPPORTED: an operator library without gpu_emit_sources.  Any failure leaves
+ * no sources.  Returns 0 on success.
+ * source_position: the current position of source i into out; returns 0 on success, -1 for a bad index. */
+int   bq_solver_set_sources(bq_solver *s, const bq_source *src, const bq_levelset *ls, int n);
+int   bq_solver_source_position(const bq_solver *s, int i, float out[3]);
 long  bq_solver_download_solid(bq_solver *s, unsigned char *host, long capacity);
 float bq_solver_last_cfldt(const bq_solver *s);
 float bq_solver_last_ms(const bq_solver *s);          /* event time of the last advance()        */
