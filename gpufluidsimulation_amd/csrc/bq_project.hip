@@ -1545,7 +1545,7 @@ static bool dims_ok(int ni, int nj, int nk, const char *op)
 struct SweepSpan { hipEvent_t a, b; long long launches, sweeps; };
 struct ProjectState {
     int klo = 0, khi = 1 << 30;             // plane range of the next sweep launches (gpu_jacobi_sweep_range)
-    const char *last_pair_kernel = "";      // name of the fused sweep kernel launched last (fl_jacobi_kernel_name)
+    const char *last_pair_kernel = "";      // name of the fused sweep kernel launched last; gpu_jacobi_sweeps: of the one it launched most (fl_jacobi_kernel_name)
     std::vector<SweepSpan> spans;           // FL_OPT_PROFILE_JACOBI
 };
 static ProjectState &ps()
@@ -1771,8 +1771,9 @@ static bool jacobi_sweep_pair(const float *in, const float *div, float *out, int
 // Three or four sweeps in one launch through jacobi_lds_kernel (neighbour rows of the intermediate levels via LDS); false = not applicable.
 // FL_OPT_JACOBI_ROWS: 4 forces it wherever it applies, 5 keeps it off (A/B timing); auto: see jacobi_sweep_triple.
 // k0a .. k1b: the OUTPUT planes as up to two ranges (gpu_jacobi_sweep_triple_ranges: the pieces of a z-slab chunk); default: the whole array.
+// min_kc > 0: refused when the chunks come out shorter than that, a forced chunk length included (jacobi_sweep_quad's auto rule).
 static bool jacobi_sweep_lds(const float *in, const float *div, float *out, int ni, int nj, int nk, float alpha, float beta, int S,
-                             int k0a = 0, int k1a = 1 << 30, int k0b = 0, int k1b = 0, const SweepMask *mask = nullptr)
+                             int k0a = 0, int k1a = 1 << 30, int k0b = 0, int k1b = 0, const SweepMask *mask = nullptr, int min_kc = 0)
 {
     k0a = std::max(k0a, 0); k1a = std::min(k1a, nk); k0b = std::max(k0b, 0); k1b = std::min(k1b, nk);
     const int lenA = std::max(k1a - k0a, 0), lenB = std::max(k1b - k0b, 0);
@@ -1788,7 +1789,7 @@ static bool jacobi_sweep_lds(const float *in, const float *div, float *out, int 
         const int per_range = std::max(1, ncus / std::max(1, nby * nranges));
         int kc = std::max(2, (std::max(lenA, lenB) + per_range - 1) / per_range);
         if (rt().opt_jacobi_kchunk2 > 0) kc = rt().opt_jacobi_kchunk2;
-        ok = !whole || kc >= (rt().opt_jacobi_kchunk2 > 0 ? 8 : 24);
+        ok = (!whole || kc >= (rt().opt_jacobi_kchunk2 > 0 ? 8 : 24)) && kc >= min_kc;
         return kc;
     };
     // block shape: FL_OPT_JACOBI_KCHUNK = 10 R + W selects R rows per wave and W output waves per block for A/B timing
@@ -1867,18 +1868,26 @@ bool jacobi_sweep_triple_masked(const float *in, const float *div, float *out, i
     return jacobi_sweep_lds(in, div, out, ni, nj, nk, alpha, betas[0], 3, 0, 1 << 30, 0, 0, &mk);
 }
 
-// Four sweeps in one launch (jacobi_lds_kernel<.., 4>): on request only for now (FL_OPT_JACOBI_ROWS = 6)
+// Four sweeps in one launch (jacobi_lds_kernel<.., 4>), whole unmasked arrays.  FL_OPT_JACOBI_ROWS = 6 forces it wherever the
+// kernel applies.  Auto (0): where the chunk rule gives at least 24 planes per chunk (six of a chunk's planes are warm-up; a forced
+// chunk length below that keeps the triples) and the process is not a z-slab rank (nothing measures those) -- 256^3: 49 quads + 1
+// triple for the projection's 199 sweeps instead of 66 triples + 1 single sweep (EXPERIMENTS section 10).  128^3 (chunks of 8),
+// rows of 260 .. 512 floats (two-segment kernel), masked sweeps and plane ranges never come here or are refused below.
+// FL_OPT_JACOBI_ROWS = 7: auto without this kernel, the launch sequence from before it became the default (A/B timing).
 static bool jacobi_sweep_quad(const float *in, const float *div, float *out, int ni, int nj, int nk, float alpha, float beta)
 {
-    if (rt().opt_jacobi_rows != 6 || (rt().opt_jacobi_variant != 0 && rt().opt_jacobi_variant != 3)) return false;
-    return jacobi_sweep_lds(in, div, out, ni, nj, nk, alpha, beta, 4);
+    const int rows = rt().opt_jacobi_rows;
+    if ((rows != 6 && rows != 0) || (rt().opt_jacobi_variant != 0 && rt().opt_jacobi_variant != 3)) return false;
+    if (rows == 6) return jacobi_sweep_lds(in, div, out, ni, nj, nk, alpha, beta, 4);
+    if (rt().slab_on) return false;
+    return jacobi_sweep_lds(in, div, out, ni, nj, nk, alpha, beta, 4, 0, 1 << 30, 0, 0, nullptr, 24);
 }
 
 // Three sweeps in one launch (in -> out holds iterate +3), whole array, rows of one wave; false = not applicable
 static bool jacobi_sweep_triple(const float *in, const float *div, float *out, int ni, int nj, int nk, float alpha, float beta)
 {
     if (ni < 3 || nj < 4 || nk < 3) return false;
-    if ((rt().opt_jacobi_rows == 4 || rt().opt_jacobi_rows == 6 || rt().opt_jacobi_rows == 0) && (rt().opt_jacobi_variant == 0 || rt().opt_jacobi_variant == 3) &&
+    if ((rt().opt_jacobi_rows == 4 || rt().opt_jacobi_rows == 6 || rt().opt_jacobi_rows == 0 || rt().opt_jacobi_rows == 7) && (rt().opt_jacobi_variant == 0 || rt().opt_jacobi_variant == 3) &&
         jacobi_sweep_lds(in, div, out, ni, nj, nk, alpha, beta, 3)) return true;
     const int variant = rt().opt_jacobi_variant;
     if ((variant != 0 && variant != 3) || rt().opt_jacobi_rows == 1 || rt().opt_jacobi_rows == 3) return false;
@@ -1984,19 +1993,26 @@ int gpu_jacobi_sweeps(float *p, const float *div, float *p_temp, int ni, int nj,
     const bool prof = sweeps > 0 && profile_begin(span);      // FL_OPT_PROFILE_JACOBI (the z-slab projection runs through here)
     // FL_OPT_JACOBI_FUSE == 2: the caller vouches that p and p_temp carry the same boundary layer
     // (FL_OPT_JACOBI_FUSE: 2 = pairs and triples, 4 = pairs only)
-    // FL_OPT_JACOBI_ROWS = 6: four sweeps per launch where jacobi_lds_kernel applies (rows 0: auto, see jacobi_sweep_quad)
+    // four sweeps per launch where jacobi_sweep_quad's rule admits them (FL_OPT_JACOBI_ROWS: 0 auto, 6 always, 7 never)
+    // fl_jacobi_kernel_name: the fused kernel this call launched most often (more sweeps per launch first on a tie)
+    const char *most_name = nullptr;
+    long long most = 0, n_here = 0;
+    auto counted = [&]() { if (++n_here > most) { most = n_here; most_name = g_last_pair_kernel; } };
     while (rt().opt_jacobi_fuse >= 2 && rt().opt_jacobi_fuse != 4 && s + 4 <= sweeps && jacobi_sweep_quad(in, div, out, ni, nj, nk, alpha, beta)) {
-        s += 4; launches++;                        // iterate +4 sits in `out`: swap
+        s += 4; launches++; counted();             // iterate +4 sits in `out`: swap
         float *t = in; in = out; out = t;
     }
+    n_here = 0;
     while (rt().opt_jacobi_fuse >= 2 && rt().opt_jacobi_fuse != 4 && s + 3 <= sweeps && jacobi_sweep_triple(in, div, out, ni, nj, nk, alpha, beta)) {
         float *t = in; in = out; out = t;          // iterate +3 sits in the former `out`
-        s += 3; launches++;
+        s += 3; launches++; counted();
     }
+    n_here = 0;
     while (rt().opt_jacobi_fuse >= 2 && s + 2 <= sweeps && jacobi_sweep_pair(in, div, out, ni, nj, nk, alpha, beta)) {
         float *t = in; in = out; out = t;          // iterate +2 sits in the former `out`
-        s += 2; launches++;
+        s += 2; launches++; counted();
     }
+    if (most_name) g_last_pair_kernel = most_name;
     for (; s < sweeps; s++) {
         jacobi_sweep(in, div, out, ni, nj, nk, alpha, beta);
         float *t = in; in = out; out = t;

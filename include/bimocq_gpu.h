@@ -298,7 +298,11 @@ enum {
                                    their chunk length from FL_OPT_JACOBI_KCHUNK2): 1 / 2 = loads run one / two planes ahead */
     FL_OPT_JACOBI_ROWS     = 6, /* float4 rows per thread: tiled kernel 1, 2, 4; fused kernels 1, 2 (0 = auto); 4 = the three-sweep kernel
                                    that exchanges the intermediate levels' neighbour rows through LDS wherever it applies (auto: whole
-                                   arrays with chunks of >= 24 planes), 5 = never that kernel (A/B timing) */
+                                   arrays with chunks of >= 24 planes), 5 = never that kernel (A/B timing), 6 = its four-sweep form
+                                   wherever it applies (auto: whole unmasked arrays with chunks of >= 24 planes, not on a z-slab rank --
+                                   256^3: 49 launches of four sweeps + 1 of three for 199 sweeps,
+                                   10.1 instead of 11.0 us per sweep inside whole steps, 11.40 instead of 11.56 ms per step), 7 = auto without the four-sweep form:
+                                   the launch sequence from before it became the default (A/B timing) */
     FL_OPT_STRUCTURED_MAPS = 7, /* 9-point kernels: compile-time taps when h is a power of two (1)  */
     FL_OPT_JACOBI_FUSE     = 8, /* two or three sweeps per launch (4: at most two): 0 never, 1 in gpu_projection_jacobi after it has checked that p and
                                    p_temp carry the same boundary shell (default), 2 there without the check and also in
@@ -371,7 +375,8 @@ int  fl_get_option(int option);
 /* FL_OPT_PROFILE_JACOBI: total milliseconds, sweep-kernel launches and Jacobi sweeps (a fused launch
  * performs two) of the sweep loops recorded since the previous call (blocking; resets the record) */
 void fl_jacobi_profile(double *total_ms, long long *launches, long long *sweeps);
-/* name of the two-sweep kernel the projection launched last ("" before the first; for reports) */
+/* name of the fused sweep kernel launched last; after gpu_jacobi_sweeps: of the one that call launched most often
+ * ("" before the first; for reports) */
 const char *fl_jacobi_kernel_name(void);
 /* name of the fused kernel the last fp64 smoothing call (gpu_smoothing_jacobi, V_Cycle) launched first ("" if none; for
  * reports and tests) */
