@@ -6,6 +6,7 @@
 // the launch geometry, the buffer-descriptor loads and the fusion are ours.
 #include "bq_device.hip.h"
 #include "bq_host.h"
+#include "bq_launch_geom.h"
 #include "bq_obstacle.hip.h"
 
 #include <algorithm>
@@ -23,9 +24,6 @@ inline namespace BQ_VARIANT {
     if (i >= (nbi) || j >= (nbj) || k >= (nbk)) return;         \
     const int kg = k + g.koff;                                  \
     (void)kg;
-
-static inline dim3 grid_for(int nbi, int nbj, int nbk) { return dim3((nbi + 63) / 64, (nbj + 3) / 4, nbk); }
-static const dim3 kBlock(64, 4, 1);
 
 // The 9-point kernels on the structured power-of-two path stage the map nodes of their block in LDS
 // (bq_device.hip.h: stage_tiles), so every thread of a block has to reach the barrier: the index window
@@ -1026,11 +1024,10 @@ static void clamp_box(const float *before, float *after, int ni, int nj, int nk,
     const int nv = ni % 4 == 1 ? ni - 1 : ni;            // floats per row handled as float4
     const bool pow2row = nv >= 32 && nv <= 1024 && (nv & (nv - 1)) == 0;
     const bool vec_ok = nj >= 3 && nk >= 3 && rt().opt_jacobi_variant != 1 &&
-                        ((ni % 4 == 0 && ni >= 32 && ni <= 1024 && (((uintptr_t)before | (uintptr_t)after) & 15u) == 0) ||
+                        ((ni % 4 == 0 && ni >= 32 && ni <= 1024 && aligned16(before, after)) ||
                          (ni % 4 == 1 && pow2row && (((uintptr_t)before | (uintptr_t)after) & 3u) == 0));
     if (vec_ok) {
-        int cw = 16;
-        while (cw * 4 < nv) cw *= 2;
+        const int cw = geom::pow2_lanes(nv, 4);
         const int rows = 256 / cw, nby = (nj + rows - 1) / rows;
         int kchunk = 32;
         while (kchunk > 8 && (long)nby * ((nk + kchunk - 1) / kchunk) < 1024) kchunk /= 2;

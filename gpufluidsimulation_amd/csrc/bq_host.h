@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include "../../include/bimocq_gpu.h"
 
@@ -26,7 +27,7 @@ struct Runtime {
     int         opt_profile_jacobi = 0;
     int         opt_structured_maps = 1;
     int         opt_jacobi_fuse = 1;        // 0 never, 1 inside gpu_projection_jacobi, 2 also in gpu_jacobi_sweeps
-    int         opt_jacobi_kchunk2 = 0;     // planes per block of the fused kernel (0 = auto)    // structured (compile-time taps) map look-up on power-of-two spacing
+    int         opt_jacobi_kchunk2 = 0;     // FL_OPT_JACOBI_KCHUNK2 (option table in include/bimocq_gpu.h)
     int         opt_jacobi_kchunk = 0;      // 0 = auto
     int         opt_fused_housekeeping = 0; // FL_OPT_FUSED_HOUSEKEEPING bit mask
     int         opt_fast_lerp = 0;          // gather kernels: one fp32 fma per lerp instead of the double-evaluated one
@@ -45,7 +46,7 @@ struct Runtime {
     int         opt_reserve_cus = 0;        // FL_OPT_RESERVE_CUS: CUs the compute stream leaves to the halo stream's RCCL kernels
     int         device_cus = 0;             // CUs of the device (hipDeviceProp_t::multiProcessorCount), set by fl_init
     int         num_cus = 256;              // CUs the compute stream may use (device CUs - opt_reserve_cus)
-    int         opt_jacobi_rows = 0;        // float4 rows per thread in the tiled kernel (0 = auto)
+    int         opt_jacobi_rows = 0;        // FL_OPT_JACOBI_ROWS: one code per kernel choice (option table in include/bimocq_gpu.h)
     // z-slab context (fl_set_slab): local plane k is global plane k + slab_koff of slab_nkg planes;
     // this rank owns global planes [slab_own0, slab_own1) (reductions count only those)
     // plane window (fl_set_plane_window): the map operators that honour it produce the local planes [win_k0, win_k1) only
@@ -60,7 +61,7 @@ struct Runtime {
     void  *pinned = nullptr;            // host-pinned mirror for blocking reductions
     size_t pinned_bytes = 0;
     // state the other translation units keep PER CONTEXT (fl_context_*): the communicator and its event ring (bq_halo.hip),
-    // the sweep-profile spans and plane range (bq_project.hip), the cached V-cycle graphs (bq_mgcg.hip).  Allocated on first
+    // the sweep-profile spans (bq_project.hip), the cached V-cycle graphs (bq_mgcg.hip).  Allocated on first
     // use, released by fl_shutdown through the *_release hooks below.
     void  *halo_state = nullptr, *project_state = nullptr, *mgcg_state = nullptr;
     // tables of the structured map look-up on spacings that are not a power of two (bq_advect.hip: map_tabs): device
@@ -102,6 +103,13 @@ void project_release_state(Runtime &r); // bq_project.hip
 struct ProfileSpan { hipEvent_t a = nullptr, b = nullptr; };
 bool profile_begin(ProfileSpan &sp);
 void profile_end(ProfileSpan &sp, long long launches, long long sweeps);
+
+// one thread per element: blocks of 64 (x) x 4 (y), planes along grid.z
+static const dim3 kBlock(64, 4, 1);
+inline dim3 grid_for(int nbi, int nbj, int nbk) { return dim3((nbi + 63) / 64, (nbj + 3) / 4, nbk); }
+// true when every pointer is 16-byte aligned (float4 / double2 accesses)
+template <typename... P>
+inline bool aligned16(const P *...p) { return ((... | (uintptr_t)p) & 15u) == 0; }
 
 inline bool hip_ok(hipError_t e, const char *what)
 {

@@ -24,14 +24,13 @@
 #include "bq_buffer.hip.h"
 #include <type_traits>
 #include "bq_host.h"
+#include "bq_launch_geom.h"
 
 #include <cstdint>
 
 namespace bq {
 
 // ---- index helpers ------------------------------------------------------------------------------
-static const dim3 kBlk(64, 4, 1);
-static inline dim3 grid_of(int ni, int nj, int nk) { return dim3((ni + 63) / 64, (nj + 3) / 4, nk); }
 #define MG_IJK(NI, NJ, NK)                                                                   \
     const int i = blockIdx.x * 64 + threadIdx.x, j = blockIdx.y * 4 + threadIdx.y, k = blockIdx.z; \
     if (i >= (NI) || j >= (NJ) || k >= (NK)) return;
@@ -1371,24 +1370,18 @@ static void mg_smooth(double *x, const double *b, double *temp, double alpha, do
     // the lean two-row kernel also pays one level down (127^3: 2.05 M cells)
     const bool mid = (long long)ni * nj * nk >= (1ll << 20);
     if (((rt().opt_jacobi_fuse == 1 && (big || mid)) || rt().opt_jacobi_fuse >= 2) && ni >= 8) {
-        const int vec = (ni % 2 == 0 && (((uintptr_t)x | (uintptr_t)temp | (uintptr_t)b) & 15u) == 0) ? 2 : 1;
+        const int vec = (ni % 2 == 0 && aligned16(x, temp, b)) ? 2 : 1;
         // the lean two-row kernel: double2 columns, rows of at most 4 waves, arrays below 2 GiB (32-bit byte offsets).
         // FL_OPT_JACOBI_ROWS = 3 / 8 keep mg_smooth2_kernel (A/B timing)
         // (odd rows: 16-byte loads at 8-byte-aligned addresses, which the memory pipeline splits -- the same mode the
         // gather kernels' dwordx2 loads at 4-byte alignment rely on)
         if ((vec == 2 || ni % 2 == 1) && ni >= 8 && ni <= 512 && nj >= 4 && (double)ni * nj * nk * 8.0 < 2147483648.0 &&
             rt().opt_jacobi_rows != 3 && rt().opt_jacobi_rows != 8) {
-            int cw = 16;
-            while (cw * 2 < ni) cw *= 2;
+            const int cw = geom::pow2_lanes(ni, 2);
             const bool wide = cw > 64;
             const int rows2 = 256 / cw;
             const int nby2 = (nj + 2 * rows2 - 1) / (2 * rows2);
-            int gcd = nby2, rem = 256;
-            while (rem) { const int t = gcd % rem; gcd = rem; rem = t; }
-            const int quantum = 256 / gcd;                              // chunk counts that fill the 256 CUs in whole rounds
-            const int target = wide ? 80 : 32;
-            int nchunks = ((2 * nk + target) / (2 * target) + quantum / 2) / quantum * quantum;
-            if (nchunks < quantum) nchunks = quantum;
+            const int nchunks = geom::whole_round_chunks(nby2, nk, wide ? 80 : 32, 256);
             int kc = (nk + nchunks - 1) / nchunks;
             if (rt().opt_jacobi_kchunk2 > 0) kc = rt().opt_jacobi_kchunk2;
             if (kc < 4) kc = 4;
@@ -1417,8 +1410,7 @@ static void mg_smooth(double *x, const double *b, double *temp, double alpha, do
                 // FL_OPT_JACOBI_KCHUNK = 14: blocks of 4 output rows (8 waves) instead of 8 (12 waves), for A/B timing
                 const int LW = rt().opt_jacobi_kchunk == 14 ? 4 : 8;
                 const int nbyl = (nj + LW - 1) / LW;
-                int nbzl = std::max(1, rt().num_cus / nbyl);
-                int kcl = (nk + nbzl - 1) / nbzl;
+                int kcl = geom::once_per_cu_len(nk, nbyl, 1, rt().num_cus);
                 if (rt().opt_jacobi_kchunk2 > 0) kcl = rt().opt_jacobi_kchunk2;
                 int triples = -1;
                 if (kcl >= (rt().opt_jacobi_kchunk2 > 0 ? 8 : 24))
@@ -1429,7 +1421,7 @@ static void mg_smooth(double *x, const double *b, double *temp, double alpha, do
                 if (triples >= 0) {
                     const int pairs = (iter - s - 3 * triples) / 2;
                     if (zin && (pairs + triples) % 2 == 1) { double *t2 = in; in = out; out = t2; }
-                    nbzl = (nk + kcl - 1) / kcl;
+                    const int nbzl = (nk + kcl - 1) / kcl;
                     const int nblk = nbyl * nbzl, gridl = 8 * ((nblk + 7) / 8);
                     for (int t = 0; t < triples + pairs; t++) {
                         const bool three = t < triples;
@@ -1508,7 +1500,7 @@ static void mg_smooth(double *x, const double *b, double *temp, double alpha, do
     }
     if (!cleared) { if (clear & 1) mg_zero(temp, cells); if (clear & 2) mg_zero(x, cells); }
     for (; s < iter; s++) {
-        mg_smooth_kernel<<<grid_of(ni, nj, nk), kBlk, 0, rt().compute>>>(in, b, out, alpha, beta, ni, nj, nk);
+        mg_smooth_kernel<<<grid_for(ni, nj, nk), kBlock, 0, rt().compute>>>(in, b, out, alpha, beta, ni, nj, nk);
         double *t = in; in = out; out = t;
     }
     BQ_LAUNCH_CHECK("mg_smooth_kernel");
@@ -1548,17 +1540,11 @@ static bool mg_stencil_lean(double *out, const double *rhs, const double *x, int
 {
     if (!rt().opt_mgcg_tile || (long long)ni * nj * nk < (1ll << 20)) return false;
     if (ni < 8 || ni > 512 || nj < 4 || nk < 3 || (double)ni * nj * nk * 8.0 >= 2147483648.0) return false;
-    if (ni % 2 == 0 && ((((uintptr_t)out | (uintptr_t)x | (uintptr_t)(poisson ? x : rhs)) & 15u) != 0)) return false;
-    int cw = 16;
-    while (cw * 2 < ni) cw *= 2;
+    if (ni % 2 == 0 && !aligned16(out, x, poisson ? x : rhs)) return false;
+    const int cw = geom::pow2_lanes(ni, 2);
     const bool wide = cw > 64;
     const int rows2 = 256 / cw, nby2 = (nj + 2 * rows2 - 1) / (2 * rows2);
-    int gcd = nby2, rem = 256;
-    while (rem) { const int t = gcd % rem; gcd = rem; rem = t; }
-    const int quantum = 256 / gcd;
-    const int target = 32;
-    int nchunks = ((2 * nk + target) / (2 * target) + quantum / 2) / quantum * quantum;
-    if (nchunks < quantum) nchunks = quantum;
+    const int nchunks = geom::whole_round_chunks(nby2, nk, 32, 256);
     int kc = (nk + nchunks - 1) / nchunks;
     if (kc < 4) kc = 4;
     const int nbz = (nk + kc - 1) / kc;
@@ -1574,7 +1560,7 @@ static bool mg_stencil_lean(double *out, const double *rhs, const double *x, int
 static void mg_residual(double *r, const double *b, const double *x, int ni, int nj, int nk)
 {
     if (mg_stencil_lean(r, b, x, ni, nj, nk, false)) return;
-    mg_residual_kernel<<<grid_of(ni, nj, nk), kBlk, 0, rt().compute>>>(r, b, x, ni, nj, nk);
+    mg_residual_kernel<<<grid_for(ni, nj, nk), kBlock, 0, rt().compute>>>(r, b, x, ni, nj, nk);
     BQ_LAUNCH_CHECK("mg_residual_kernel");
 }
 
@@ -1654,7 +1640,7 @@ static void v_cycle(const double *b, double *x, double *residual, const SCoarseL
     for (int l = 0; l < (bottom ? lb : levelnum - 1); l++) {
         if (!smooth_level(l, 32, true, rt().opt_mgcg_bottom ? L[l].r : nullptr))
             mg_residual(L[l].r, rhs(l), L[l].x, L[l].ni, L[l].nj, L[l].nk);
-        mg_restrict_kernel<<<grid_of(L[l + 1].ni, L[l + 1].nj, L[l + 1].nk), kBlk, 0, st>>>(
+        mg_restrict_kernel<<<grid_for(L[l + 1].ni, L[l + 1].nj, L[l + 1].nk), kBlock, 0, st>>>(
             L[l].r, L[l + 1].b, L[l].ni, L[l].nj, L[l].nk, L[l + 1].ni, L[l + 1].nj, L[l + 1].nk);
         BQ_LAUNCH_CHECK("mg_restrict_kernel");
     }
@@ -1669,10 +1655,10 @@ static void v_cycle(const double *b, double *x, double *residual, const SCoarseL
         // exact in float (always, at these sizes); FL_OPT_MGCG_TILE = 0 keeps the one-cell form
         if (rt().opt_mgcg_tile && (long long)L[l + 1].ni * L[l + 1].nj * L[l + 1].nk < (1ll << 31) && L[l].ni < (1 << 22) &&
             L[l].nj < (1 << 22) && L[l].nk < (1 << 22) && L[l].ni >= 3 && L[l].nj >= 3 && L[l].nk >= 3)
-            mg_prolong_block_kernel<<<grid_of((L[l].ni - 1) / 2, (L[l].nj - 1) / 2, (L[l].nk - 1) / 2), kBlk, 0, st>>>(
+            mg_prolong_block_kernel<<<grid_for((L[l].ni - 1) / 2, (L[l].nj - 1) / 2, (L[l].nk - 1) / 2), kBlock, 0, st>>>(
                 L[l].x, L[l + 1].x, L[l].ni, L[l].nj, L[l].nk, L[l + 1].ni, L[l + 1].nj, L[l + 1].nk);
         else
-        mg_prolong_kernel<<<grid_of(L[l].ni, L[l].nj, L[l].nk), kBlk, 0, st>>>(
+        mg_prolong_kernel<<<grid_for(L[l].ni, L[l].nj, L[l].nk), kBlock, 0, st>>>(
             L[l].x, L[l + 1].x, L[l].ni, L[l].nj, L[l].nk, L[l + 1].ni, L[l + 1].nj, L[l + 1].nk);
         BQ_LAUNCH_CHECK("mg_prolong_kernel");
         smooth_level(l, 4, false);
@@ -1756,17 +1742,17 @@ static void v_cycle_replayed(const double *b, double *x, double *residual, const
 // restriction / prolongation between two levels, the kernels V_Cycle picks (bit-identical to orc_mg_restrict / orc_mg_prolong)
 void mgcg_restrict(const double *fine, double *coarse, const SCoarseLevelInfo &F, const SCoarseLevelInfo &Cl)
 {
-    mg_restrict_kernel<<<grid_of(Cl.ni, Cl.nj, Cl.nk), kBlk, 0, rt().compute>>>(fine, coarse, F.ni, F.nj, F.nk, Cl.ni, Cl.nj, Cl.nk);
+    mg_restrict_kernel<<<grid_for(Cl.ni, Cl.nj, Cl.nk), kBlock, 0, rt().compute>>>(fine, coarse, F.ni, F.nj, F.nk, Cl.ni, Cl.nj, Cl.nk);
     BQ_LAUNCH_CHECK("mg_restrict_kernel");
 }
 void mgcg_prolong(double *x, const double *coarse, const SCoarseLevelInfo &F, const SCoarseLevelInfo &Cl)
 {
     if (rt().opt_mgcg_tile && (long long)Cl.ni * Cl.nj * Cl.nk < (1ll << 31) && F.ni < (1 << 22) && F.nj < (1 << 22) &&
         F.nk < (1 << 22) && F.ni >= 3 && F.nj >= 3 && F.nk >= 3)
-        mg_prolong_block_kernel<<<grid_of((F.ni - 1) / 2, (F.nj - 1) / 2, (F.nk - 1) / 2), kBlk, 0, rt().compute>>>(
+        mg_prolong_block_kernel<<<grid_for((F.ni - 1) / 2, (F.nj - 1) / 2, (F.nk - 1) / 2), kBlock, 0, rt().compute>>>(
             x, coarse, F.ni, F.nj, F.nk, Cl.ni, Cl.nj, Cl.nk);
     else
-        mg_prolong_kernel<<<grid_of(F.ni, F.nj, F.nk), kBlk, 0, rt().compute>>>(x, coarse, F.ni, F.nj, F.nk, Cl.ni, Cl.nj, Cl.nk);
+        mg_prolong_kernel<<<grid_for(F.ni, F.nj, F.nk), kBlock, 0, rt().compute>>>(x, coarse, F.ni, F.nj, F.nk, Cl.ni, Cl.nj, Cl.nk);
     BQ_LAUNCH_CHECK("mg_prolong_kernel");
 }
 __global__ __launch_bounds__(256) void mg_scale_kernel(double *x, double c, size_t count)
@@ -1855,7 +1841,7 @@ void gpu_multi_grid_conjugate_gradient(float *u, float *v, float *w, double *div
     const size_t number = (size_t)levels[0].number;
     hipStream_t st = rt().compute;
 
-    mg_divergence_kernel<<<grid_of(ni, nj, nk), kBlk, 0, st>>>(u, v, w, div, ni, nj, nk, halfrdx);
+    mg_divergence_kernel<<<grid_for(ni, nj, nk), kBlock, 0, st>>>(u, v, w, div, ni, nj, nk, halfrdx);
     BQ_LAUNCH_CHECK("mg_divergence_kernel");
     mg_zero(p, number);
     mg_residual(residual, div, p, ni, nj, nk);
@@ -1880,7 +1866,7 @@ void gpu_multi_grid_conjugate_gradient(float *u, float *v, float *w, double *div
         // smoothing_conjugate_gradient (:1485-1495): aMulDir = temp0, dotDir = temp1
         if (!fused || it == 0) {
             if (!mg_stencil_lean(temp0, nullptr, dcur, ni, nj, nk, true)) {
-                mg_poisson_kernel<<<grid_of(ni, nj, nk), kBlk, 0, st>>>(dcur, temp0, ni, nj, nk);
+                mg_poisson_kernel<<<grid_for(ni, nj, nk), kBlock, 0, st>>>(dcur, temp0, ni, nj, nk);
                 BQ_LAUNCH_CHECK("mg_poisson_kernel");
             }
             mg_dot(dcur, temp0, temp1, tempResult, number, off + 1);
@@ -1925,7 +1911,7 @@ void gpu_multi_grid_conjugate_gradient(float *u, float *v, float *w, double *div
             dcur = dnext;
         }
     }
-    mg_gradient_kernel<<<grid_of(ni + 1, nj + 1, nk + 1), kBlk, 0, st>>>(u, v, w, p, ni, nj, nk, halfrdx);
+    mg_gradient_kernel<<<grid_for(ni + 1, nj + 1, nk + 1), kBlock, 0, st>>>(u, v, w, p, ni, nj, nk, halfrdx);
     BQ_LAUNCH_CHECK("mg_gradient_kernel");
 }
 
@@ -1964,7 +1950,7 @@ void gpu_multi_grid_conjugate_gradient_slab(float *u, float *v, float *w, double
     const float *vv = v + (size_t)ni * (nj + 1) * (size_t)(L0.lo - ulo);
     const float *ww = w + pd * (size_t)(L0.lo - ulo);
 
-    mg_divergence_kernel<<<grid_of(ni, nj, nkl), kBlk, 0, st>>>(uu, vv, ww, m.div, ni, nj, nkl, halfrdx);
+    mg_divergence_kernel<<<grid_for(ni, nj, nkl), kBlock, 0, st>>>(uu, vv, ww, m.div, ni, nj, nkl, halfrdx);
     BQ_LAUNCH_CHECK("mg_divergence_kernel");
     mg_zero(m.p, n0);
     mg_residual(m.residual, m.div, m.p, ni, nj, nkl);
@@ -1978,7 +1964,7 @@ void gpu_multi_grid_conjugate_gradient_slab(float *u, float *v, float *w, double
         const int off = it * 2;
         // dir and residual are correct on every stored plane here (exchanged below / above)
         if (!mg_stencil_lean(m.temp0, nullptr, m.dir, ni, nj, nkl, true)) {
-            mg_poisson_kernel<<<grid_of(ni, nj, nkl), kBlk, 0, st>>>(m.dir, m.temp0, ni, nj, nkl);
+            mg_poisson_kernel<<<grid_for(ni, nj, nkl), kBlock, 0, st>>>(m.dir, m.temp0, ni, nj, nkl);
             BQ_LAUNCH_CHECK("mg_poisson_kernel");
         }
         slab_dot(m, m.dir, m.temp0, tempResult, off + 1);
@@ -1998,7 +1984,7 @@ void gpu_multi_grid_conjugate_gradient_slab(float *u, float *v, float *w, double
     // p is correct on every stored plane (the cycle's last exchange + elementwise updates); the gradient needs p(k - 1)
     const int k_first = std::max(L0.lo + 1, 2), k_end = std::min(L0.hi, nkg);
     if (k_end > k_first) {
-        mg_gradient_slab_kernel<<<grid_of(ni + 1, nj + 1, k_end - k_first), kBlk, 0, st>>>(u, v, w, m.p, ni, nj, nkg, L0.lo, k_end, ulo, k_first, halfrdx);
+        mg_gradient_slab_kernel<<<grid_for(ni + 1, nj + 1, k_end - k_first), kBlock, 0, st>>>(u, v, w, m.p, ni, nj, nkg, L0.lo, k_end, ulo, k_first, halfrdx);
         BQ_LAUNCH_CHECK("mg_gradient_slab_kernel");
     }
 }

@@ -402,11 +402,7 @@ static FuseGeom fuse_geom(int ni, int nj, int nk)
     g.cw = ni / 2;
     const int rows2 = 256 / g.cw;
     g.nby = (nj + 2 * rows2 - 1) / (2 * rows2);
-    int gcd = g.nby, rem = 256;
-    while (rem) { const int t = gcd % rem; gcd = rem; rem = t; }
-    const int quantum = 256 / gcd, target = 32;
-    int nchunks = ((2 * nk + target) / (2 * target) + quantum / 2) / quantum * quantum;
-    if (nchunks < quantum) nchunks = quantum;
+    const int nchunks = geom::whole_round_chunks(g.nby, nk, 32, 256);
     g.kc = (nk + nchunks - 1) / nchunks;
     if (g.kc < 4) g.kc = 4;
     g.nbz = (nk + g.kc - 1) / g.kc;
@@ -426,7 +422,7 @@ static bool mg_fuse_ok(int ni, int nj, int nk, std::initializer_list<const void 
     if (f < 2 && (long long)ni * nj * nk < (1ll << 20)) return false;
     if ((double)ni * nj * nk * 8.0 >= 2147483648.0) return false;
     for (const void *a : arrays)
-        if (!a || ((uintptr_t)a & 15u)) return false;
+        if (!a || !aligned16(a)) return false;
     return true;
 }
 // FL_OPT_MGCG_FUSE = 3: the wave-per-row kernel on rows of 256 cells (same time as the two-rows-per-thread one inside one process:
@@ -438,8 +434,7 @@ static FuseGeom fuse_geom_rows(int ni, int nj, int nk)
     FuseGeom g = fuse_geom(ni, nj, nk);
     g.cw = 0;
     g.nby = (nj + 7) / 8;
-    const int nbz0 = std::max(1, rt().num_cus / g.nby);
-    g.kc = std::max(4, (nk + nbz0 - 1) / nbz0);
+    g.kc = std::max(4, geom::once_per_cu_len(nk, g.nby, 1, rt().num_cus));
     if (rt().opt_jacobi_kchunk2 > 0) g.kc = std::max(4, rt().opt_jacobi_kchunk2);      // (A/B timing)
     g.nbz = (nk + g.kc - 1) / g.kc;
     g.nblk = (unsigned)(g.nby * g.nbz);

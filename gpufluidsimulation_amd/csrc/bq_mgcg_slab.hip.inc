@@ -286,7 +286,7 @@ static void slab_v_cycle(SlabMg &m, bool last_iteration)
         if (l + 1 < LS) {
             SlabLevel &C = m.lv[l + 1];
             if (ck > 0)
-                mg_restrict_kernel<<<grid_of(ci, cj, ck), kBlk, 0, st>>>(fine, C.b + C.plane() * (size_t)(c0 - C.lo), L.ni, L.nj, fine_planes, ci, cj, ck);
+                mg_restrict_kernel<<<grid_for(ci, cj, ck), kBlock, 0, st>>>(fine, C.b + C.plane() * (size_t)(c0 - C.lo), L.ni, L.nj, fine_planes, ci, cj, ck);
             BQ_LAUNCH_CHECK("mg_restrict_kernel");
             slab_exchange(C, C.b, C.G);
         } else {
@@ -294,7 +294,7 @@ static void slab_v_cycle(SlabMg &m, bool last_iteration)
             SCoarseLevelInfo &F = m.full[l + 1];
             const size_t pc = (size_t)ci * cj;
             if (ck > 0)
-                mg_restrict_kernel<<<grid_of(ci, cj, ck), kBlk, 0, st>>>(fine, F.r + pc * (size_t)c0, L.ni, L.nj, fine_planes, ci, cj, ck);
+                mg_restrict_kernel<<<grid_for(ci, cj, ck), kBlock, 0, st>>>(fine, F.r + pc * (size_t)c0, L.ni, L.nj, fine_planes, ci, cj, ck);
             BQ_LAUNCH_CHECK("mg_restrict_kernel");
             // (every rank's planes land at their global position of F.b)
             slab_gather_planes(m, l + 1, F.r, F.b);
@@ -313,7 +313,7 @@ static void slab_v_cycle(SlabMg &m, bool last_iteration)
         for (int l = LS; l < (bottom ? lb : nl - 1); l++) {
             smooth_full(l, 32, true);
             mg_residual(F[l].r, F[l].b, F[l].x, F[l].ni, F[l].nj, F[l].nk);
-            mg_restrict_kernel<<<grid_of(F[l + 1].ni, F[l + 1].nj, F[l + 1].nk), kBlk, 0, st>>>(F[l].r, F[l + 1].b, F[l].ni, F[l].nj, F[l].nk, F[l + 1].ni, F[l + 1].nj, F[l + 1].nk);
+            mg_restrict_kernel<<<grid_for(F[l + 1].ni, F[l + 1].nj, F[l + 1].nk), kBlock, 0, st>>>(F[l].r, F[l + 1].b, F[l].ni, F[l].nj, F[l].nk, F[l + 1].ni, F[l + 1].nj, F[l + 1].nk);
             BQ_LAUNCH_CHECK("mg_restrict_kernel");
         }
         if (bottom) {
@@ -323,7 +323,7 @@ static void slab_v_cycle(SlabMg &m, bool last_iteration)
             BQ_LAUNCH_CHECK("mg_vbottom_kernel");
         } else smooth_full(nl - 1, 32, true);
         for (int l = bottom ? lb - 1 : nl - 2; l >= LS; --l) {
-            mg_prolong_kernel<<<grid_of(F[l].ni, F[l].nj, F[l].nk), kBlk, 0, st>>>(F[l].x, F[l + 1].x, F[l].ni, F[l].nj, F[l].nk, F[l + 1].ni, F[l + 1].nj, F[l + 1].nk);
+            mg_prolong_kernel<<<grid_for(F[l].ni, F[l].nj, F[l].nk), kBlock, 0, st>>>(F[l].x, F[l + 1].x, F[l].ni, F[l].nj, F[l].nk, F[l + 1].ni, F[l + 1].nj, F[l + 1].nk);
             BQ_LAUNCH_CHECK("mg_prolong_kernel");
             smooth_full(l, 4, false);
         }
@@ -343,7 +343,7 @@ static void slab_v_cycle(SlabMg &m, bool last_iteration)
             coarse = m.full[l + 1].x + (size_t)ci * cj * (size_t)(L.lo / 2);
             ck = m.lv[l + 1].nk - L.lo / 2;
         }
-        mg_prolong_kernel<<<grid_of(L.ni, L.nj, L.nkl()), kBlk, 0, st>>>(L.x, coarse, L.ni, L.nj, L.nkl(), ci, cj, ck);
+        mg_prolong_kernel<<<grid_for(L.ni, L.nj, L.nkl()), kBlock, 0, st>>>(L.x, coarse, L.ni, L.nj, L.nkl(), ci, cj, ck);
         BQ_LAUNCH_CHECK("mg_prolong_kernel");
         slab_exchange(L, L.x, L.G);
         slab_smooth(L, rhs(l), m.temp0, scale[l], 4, false);

@@ -5,9 +5,6 @@
 
 namespace bq {
 
-static const dim3 kBlock3(64, 4, 1);
-static inline dim3 grid3(int a, int b, int c) { return dim3((a + 63) / 64, (b + 3) / 4, c); }
-
 // norm3df / hypotf restated as the correctly rounded sqrt of the double sum of squares
 // (oracle: norm3, hypot2)
 __device__ __forceinline__ float norm3(float x, float y, float z)
@@ -299,10 +296,10 @@ void gpu_emit_smoke(float *u, float *v, float *w, float *rho, float *T, float h,
     hipStream_t st = rt().compute;
     int koff, nkg;
     slab_ctx(nk, koff, nkg);
-    emit_velocity_kernel<<<grid3(ni + 1, nj, nk), kBlock3, 0, st>>>(u, h, ni + 1, nj, nk, centerX, centerY, centerZ, radius, emiter, koff, nkg);
-    emit_velocity_kernel<<<grid3(ni, nj + 1, nk), kBlock3, 0, st>>>(v, h, ni, nj + 1, nk, centerX, centerY, centerZ, radius, 0.f, koff, nkg);
-    emit_velocity_kernel<<<grid3(ni, nj, nk + 1), kBlock3, 0, st>>>(w, h, ni, nj, nk + 1, centerX, centerY, centerZ, radius, 0.f, koff, nkg + 1);
-    emit_field_kernel<<<grid3(ni, nj, nk), kBlock3, 0, st>>>(rho, T, h, ni, nj, nk, centerX, centerY, centerZ, radius, density, temperature, koff, nkg);
+    emit_velocity_kernel<<<grid_for(ni + 1, nj, nk), kBlock, 0, st>>>(u, h, ni + 1, nj, nk, centerX, centerY, centerZ, radius, emiter, koff, nkg);
+    emit_velocity_kernel<<<grid_for(ni, nj + 1, nk), kBlock, 0, st>>>(v, h, ni, nj + 1, nk, centerX, centerY, centerZ, radius, 0.f, koff, nkg);
+    emit_velocity_kernel<<<grid_for(ni, nj, nk + 1), kBlock, 0, st>>>(w, h, ni, nj, nk + 1, centerX, centerY, centerZ, radius, 0.f, koff, nkg + 1);
+    emit_field_kernel<<<grid_for(ni, nj, nk), kBlock, 0, st>>>(rho, T, h, ni, nj, nk, centerX, centerY, centerZ, radius, density, temperature, koff, nkg);
     BQ_LAUNCH_CHECK("gpu_emit_smoke");
 }
 
@@ -312,7 +309,7 @@ void gpu_add_buoyancy(float *field, float *density, float *temperature, int ni, 
     BQ_REQUIRE(field && density && temperature && ni > 0 && nj > 0 && nk > 0 && nk < 65535, "gpu_add_buoyancy");
     int koff, nkg;
     slab_ctx(nk, koff, nkg);
-    buoyancy_kernel<<<grid3(ni, nj, nk), kBlock3, 0, rt().compute>>>(field, density, temperature, ni, nj, nk, alpha, beta, dt, koff, nkg);
+    buoyancy_kernel<<<grid_for(ni, nj, nk), kBlock, 0, rt().compute>>>(field, density, temperature, ni, nj, nk, alpha, beta, dt, koff, nkg);
     BQ_LAUNCH_CHECK("buoyancy_kernel");
 }
 
@@ -349,7 +346,7 @@ void gpu_init_maps(float *x, float *y, float *z, float h, int ni, int nj, int nk
     BQ_REQUIRE(x && y && z && ni > 0 && nj > 0 && nk > 0 && nk < 65535, "gpu_init_maps");
     int koff, nkg;
     slab_ctx(nk, koff, nkg);
-    init_maps_kernel<<<grid3(ni, nj, nk), kBlock3, 0, rt().compute>>>(x, y, z, h, ni, nj, nk, koff, nkg);
+    init_maps_kernel<<<grid_for(ni, nj, nk), kBlock, 0, rt().compute>>>(x, y, z, h, ni, nj, nk, koff, nkg);
     BQ_LAUNCH_CHECK("init_maps_kernel");
 }
 
@@ -435,13 +432,13 @@ void gpu_map_travel_z(const float *bz, const float *fz, float h, int ni, int nj,
     const int p0 = r.slab_on ? r.slab_own0 - r.slab_koff : 0, p1 = r.slab_on ? r.slab_own1 - r.slab_koff : nk;
     int koff, nkg;
     slab_ctx(nk, koff, nkg);
-    const dim3 grid = grid3(ni, nj, p1 - p0);
+    const dim3 grid = grid_for(ni, nj, p1 - p0);
     const int nblocks = (int)(grid.x * grid.y * grid.z);
     float *part = (float *)scratch(((size_t)2 * nblocks + 16) * sizeof(float));
     float *host = (float *)pinned(64);
     if (!part || !host) return;
     hipStream_t st = rt().compute;
-    map_travel_z_kernel<<<grid, kBlock3, 0, st>>>(bz, fz, h, ni, nj, p0, koff, nkg, part, nblocks);
+    map_travel_z_kernel<<<grid, kBlock, 0, st>>>(bz, fz, h, ni, nj, p0, koff, nkg, part, nblocks);
     max2_final_kernel<<<1, 256, 0, st>>>(part, nblocks, part + 2 * nblocks);
     BQ_LAUNCH_CHECK("map_travel_z");
     comm_allreduce(part + 2 * nblocks, 2, false, true, st);

@@ -8,9 +8,6 @@
 
 namespace bq {
 
-static const dim3 kBlockO(64, 4, 1);
-static inline dim3 grid_o(int a, int b, int c) { return dim3((a + 63) / 64, (b + 3) / 4, c); }
-
 // ---- flags: one thread per cell; a solid cell marks the rows summary of its own row and plane and the neighbouring ones --
 template <typename... Ls>
 __global__ __launch_bounds__(256) void obstacle_flags_kernel(unsigned char *__restrict__ solid, unsigned char *__restrict__ rows,
@@ -190,9 +187,9 @@ static void obstacle_flags(unsigned char *solid, unsigned char *rows, const bq_b
     if (!solid || !rows) { latch(FL_ERR_BAD_ARGUMENT, op, "null device pointer"); return; }
     if (!BQ_HIP(hipMemsetAsync(rows, 0, (size_t)nj * (size_t)nk, rt().compute))) return;
     if (ls)
-        obstacle_flags_kernel<LsSet><<<grid_o(ni, nj, nk), kBlockO, 0, rt().compute>>>(solid, rows, make_obs(b, n, h), make_ls(b, ls, n), h, ni, nj, nk);
+        obstacle_flags_kernel<LsSet><<<grid_for(ni, nj, nk), kBlock, 0, rt().compute>>>(solid, rows, make_obs(b, n, h), make_ls(b, ls, n), h, ni, nj, nk);
     else
-        obstacle_flags_kernel<><<<grid_o(ni, nj, nk), kBlockO, 0, rt().compute>>>(solid, rows, make_obs(b, n, h), h, ni, nj, nk);
+        obstacle_flags_kernel<><<<grid_for(ni, nj, nk), kBlock, 0, rt().compute>>>(solid, rows, make_obs(b, n, h), h, ni, nj, nk);
     BQ_LAUNCH_CHECK("obstacle_flags_kernel");
 }
 
@@ -203,11 +200,11 @@ static void obstacle_blend(float *u, float *v, float *w, float *rho, float *T, c
     if (!obs_args_ok(b, n, ni, nj, nk, op)) return;
     if (const char *why = ls_check(b, ls, n)) { latch(FL_ERR_BAD_ARGUMENT, op, why); return; }
     if (!rho || !solid || (us && (!u || !v || !w || !T || !vs || !ws || !rhos || !Ts))) { latch(FL_ERR_BAD_ARGUMENT, op, "null device pointer"); return; }
-    const dim3 grid = grid_o(ni + 1, nj + 1, nk + 1);
+    const dim3 grid = grid_for(ni + 1, nj + 1, nk + 1);
     if (ls)
-        obstacle_blend_kernel<LsSet><<<grid, kBlockO, 0, rt().compute>>>(u, v, w, rho, T, us, vs, ws, rhos, Ts, solid, make_obs(b, n, h), make_ls(b, ls, n), h, ni, nj, nk);
+        obstacle_blend_kernel<LsSet><<<grid, kBlock, 0, rt().compute>>>(u, v, w, rho, T, us, vs, ws, rhos, Ts, solid, make_obs(b, n, h), make_ls(b, ls, n), h, ni, nj, nk);
     else
-        obstacle_blend_kernel<><<<grid, kBlockO, 0, rt().compute>>>(u, v, w, rho, T, us, vs, ws, rhos, Ts, solid, make_obs(b, n, h), h, ni, nj, nk);
+        obstacle_blend_kernel<><<<grid, kBlock, 0, rt().compute>>>(u, v, w, rho, T, us, vs, ws, rhos, Ts, solid, make_obs(b, n, h), h, ni, nj, nk);
     BQ_LAUNCH_CHECK("obstacle_blend_kernel");
 }
 
@@ -232,7 +229,7 @@ void gpu_obstacle_faces(float *u, float *v, float *w, float *du, float *dv, floa
     if (!u || !v || !w || !solid || (!du) != (!dv) || (!du) != (!dw)) { latch(FL_ERR_BAD_ARGUMENT, "gpu_obstacle_faces", "null device pointer"); return; }
     ObsVel ov{};
     for (int o = 0; o < n; o++) { ov.vx[o] = b[o].vx; ov.vy[o] = b[o].vy; ov.vz[o] = b[o].vz; }
-    obstacle_faces_kernel<<<grid_o(ni + 1, nj + 1, nk + 1), kBlockO, 0, rt().compute>>>(u, v, w, du, dv, dw, solid, ov, ni, nj, nk);
+    obstacle_faces_kernel<<<grid_for(ni + 1, nj + 1, nk + 1), kBlock, 0, rt().compute>>>(u, v, w, du, dv, dw, solid, ov, ni, nj, nk);
     BQ_LAUNCH_CHECK("obstacle_faces_kernel");
 }
 
@@ -250,7 +247,7 @@ void gpu_jacobi_sweep_masked(const float *in, const float *div, float *out, cons
 {
     if (!obs_args_ok(nullptr, 0, ni, nj, nk, "gpu_jacobi_sweep_masked")) return;
     if (!in || !div || !out || !solid || !rows || in == out) { latch(FL_ERR_BAD_ARGUMENT, "gpu_jacobi_sweep_masked", "null or aliased buffers"); return; }
-    jacobi_masked_kernel<<<grid_o(ni, nj, nk), kBlockO, 0, rt().compute>>>(in, div, out, solid, rows, ni, nj, nk, alpha, beta_table(beta));
+    jacobi_masked_kernel<<<grid_for(ni, nj, nk), kBlock, 0, rt().compute>>>(in, div, out, solid, rows, ni, nj, nk, alpha, beta_table(beta));
     BQ_LAUNCH_CHECK("jacobi_masked_kernel");
 }
 
@@ -273,7 +270,7 @@ int gpu_jacobi_sweeps_masked(float *p, const float *div, float *p_temp, const un
         s += 3; launches++;
     }
     for (; s < sweeps; s++) {
-        jacobi_masked_kernel<<<grid_o(ni, nj, nk), kBlockO, 0, rt().compute>>>(in, div, out, solid, rows, ni, nj, nk, alpha, bt);
+        jacobi_masked_kernel<<<grid_for(ni, nj, nk), kBlock, 0, rt().compute>>>(in, div, out, solid, rows, ni, nj, nk, alpha, bt);
         if (!BQ_LAUNCH_CHECK("jacobi_masked_kernel")) break;
         float *t = in; in = out; out = t;
         launches++;
@@ -287,7 +284,7 @@ void gpu_gradient_masked(float *u, float *v, float *w, const float *p, float *du
 {
     if (!obs_args_ok(nullptr, 0, ni, nj, nk, "gpu_gradient_masked")) return;
     if (!u || !v || !w || !p || !solid || (!du) != (!dv) || (!du) != (!dw)) { latch(FL_ERR_BAD_ARGUMENT, "gpu_gradient_masked", "null device pointer"); return; }
-    gradient_masked_kernel<<<grid_o(ni + 1, nj + 1, nk + 1), kBlockO, 0, rt().compute>>>(u, v, w, p, du, dv, dw, solid, ni, nj, nk, halfrdx);
+    gradient_masked_kernel<<<grid_for(ni + 1, nj + 1, nk + 1), kBlock, 0, rt().compute>>>(u, v, w, p, du, dv, dw, solid, ni, nj, nk, halfrdx);
     BQ_LAUNCH_CHECK("gradient_masked_kernel");
 }
 

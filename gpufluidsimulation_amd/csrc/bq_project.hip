@@ -10,6 +10,7 @@
 #include "bq_buffer.hip.h"
 #include <type_traits>
 #include "bq_host.h"
+#include "bq_launch_geom.h"
 #include <algorithm>
 #include <vector>
 
@@ -1529,9 +1530,6 @@ __global__ __launch_bounds__(256) void diffuse_kernel(const float *__restrict__ 
     out[id] = (field[id] + coef * s) / (1.0f + 6.0f * coef);
 }
 
-static const dim3 kBlock2(64, 4, 1);
-static inline dim3 grid2(int a, int b, int c) { return dim3((a + 63) / 64, (b + 3) / 4, c); }
-
 static bool dims_ok(int ni, int nj, int nk, const char *op)
 {
     if (ni < 1 || nj < 1 || nk < 1) { latch(FL_ERR_BAD_ARGUMENT, op, "non-positive grid dims"); return false; }
@@ -1544,7 +1542,6 @@ static bool dims_ok(int ni, int nj, int nk, const char *op)
 // per-context state of this file (bq_host.h: Runtime::project_state), behind the names it always had
 struct SweepSpan { hipEvent_t a, b; long long launches, sweeps; };
 struct ProjectState {
-    int klo = 0, khi = 1 << 30;             // plane range of the next sweep launches (gpu_jacobi_sweep_range)
     const char *last_pair_kernel = "";      // name of the fused sweep kernel launched last; gpu_jacobi_sweeps: of the one it launched most (fl_jacobi_kernel_name)
     std::vector<SweepSpan> spans;           // FL_OPT_PROFILE_JACOBI
 };
@@ -1554,8 +1551,6 @@ static ProjectState &ps()
     if (!r.project_state) r.project_state = new ProjectState();
     return *static_cast<ProjectState *>(r.project_state);
 }
-#define g_klo (ps().klo)
-#define g_khi (ps().khi)
 #define g_last_pair_kernel (ps().last_pair_kernel)
 #define g_spans (ps().spans)
 void project_release_state(Runtime &r)
@@ -1567,26 +1562,33 @@ void project_release_state(Runtime &r)
     r.project_state = nullptr;
 }
 
-static inline Slab slab_of(int nk)
+// [klo, khi): the local planes a stencil launch is restricted to; default: the whole array
+static inline Slab slab_of(int nk, int klo = 0, int khi = 1 << 30)
 {
     const Runtime &r = rt();
-    if (r.slab_on) return Slab{r.slab_koff, r.slab_nkg, g_klo, g_khi};
-    return Slab{0, nk, g_klo, g_khi};
+    if (r.slab_on) return Slab{r.slab_koff, r.slab_nkg, klo, khi};
+    return Slab{0, nk, klo, khi};
+}
+// the kernel argument and the chunk count of a launch that marches the ranges `pr` in chunks of kc planes
+struct RangeLaunch { PairRanges rg; int nbz; };
+static inline RangeLaunch range_launch(const geom::PlaneRanges &pr, int kc)
+{
+    const geom::PlaneRanges::Chunks c = pr.chunks(kc);
+    return RangeLaunch{PairRanges{c.k0a, c.k1a, c.k0b, c.k1b, c.nchA}, c.nbz};
 }
 
-static inline bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
-
-// One Jacobi sweep in -> out on the compute stream.
-static void jacobi_sweep(const float *in, const float *div, float *out, int ni, int nj, int nk, float alpha, float beta)
+// One Jacobi sweep in -> out on the compute stream, on the local planes [klo, khi) (default: the whole array).
+static void jacobi_sweep(const float *in, const float *div, float *out, int ni, int nj, int nk, float alpha, float beta,
+                         int klo = 0, int khi = 1 << 30)
 {
     if (ni < 3 || nj < 3 || nk < 3) return;         // no interior
     int variant = rt().opt_jacobi_variant;
-    const bool tile_ok = (ni % 4 == 0) && ni >= 32 && aligned16(in) && aligned16(div) && aligned16(out);
+    const bool tile_ok = (ni % 4 == 0) && ni >= 32 && aligned16(in, div, out);
     if (variant == 0) variant = tile_ok ? 3 : 1;
     if (variant != 1 && !tile_ok) variant = 1;
     hipStream_t st = rt().compute;
     if (variant == 1) {
-        jacobi_generic_kernel<<<grid2(ni, nj, nk), kBlock2, 0, st>>>(in, div, out, ni, nj, nk, alpha, beta, slab_of(nk));
+        jacobi_generic_kernel<<<grid_for(ni, nj, nk), kBlock, 0, st>>>(in, div, out, ni, nj, nk, alpha, beta, slab_of(nk, klo, khi));
         BQ_LAUNCH_CHECK("jacobi_generic_kernel");
         return;
     }
@@ -1594,8 +1596,7 @@ static void jacobi_sweep(const float *in, const float *div, float *out, int ni, 
         int waves = rt().opt_jacobi_rows;
         if (waves != 4 && waves != 8 && waves != 16) waves = 4;
         const int threads = waves * 64;
-        int cw = 16;                                     // float4 columns per tile row: pow2 >= ni/4
-        while (cw * 4 < ni && cw < threads) cw *= 2;
+        const int cw = geom::pow2_lanes(ni, 4, threads);     // float4 columns per tile row: pow2 >= ni/4
         const int rows = threads / cw;
         const int nbx = (ni / 4 + cw - 1) / cw, nby = (nj + rows - 1) / rows;
         // k-chunk: measured optimum at 256^3 is 16 planes (tools/jacobi_tune.py: 4/8/16/32 planes ->
@@ -1606,7 +1607,7 @@ static void jacobi_sweep(const float *in, const float *div, float *out, int ni, 
         if (rt().opt_jacobi_kchunk > 0) kchunk = rt().opt_jacobi_kchunk;
         const int nbz = (nk + kchunk - 1) / kchunk;
         const int nblk = nbx * nby * nbz;
-#define BQ_JM(W) jacobi_march_kernel<W><<<nblk, W * 64, 0, st>>>(in, div, out, ni, nj, nk, cw, nbx, nby, kchunk, alpha, beta, slab_of(nk))
+#define BQ_JM(W) jacobi_march_kernel<W><<<nblk, W * 64, 0, st>>>(in, div, out, ni, nj, nk, cw, nbx, nby, kchunk, alpha, beta, slab_of(nk, klo, khi))
         if (waves == 4) BQ_JM(4); else if (waves == 8) BQ_JM(8); else BQ_JM(16);
 #undef BQ_JM
         BQ_LAUNCH_CHECK("jacobi_march_kernel");
@@ -1625,31 +1626,12 @@ static void jacobi_sweep(const float *in, const float *div, float *out, int ni, 
     if (rt().opt_jacobi_kchunk > 0) kchunk = rt().opt_jacobi_kchunk;
     const int bz = (nk + kchunk - 1) / kchunk;
     dim3 grid(bx, by, bz);
-#define BQ_JT(TXV, RR) jacobi_tile_kernel<TXV, RR><<<grid, 256, 0, st>>>(in, div, out, ni, nj, nk, kchunk, alpha, beta, slab_of(nk))
+#define BQ_JT(TXV, RR) jacobi_tile_kernel<TXV, RR><<<grid, 256, 0, st>>>(in, div, out, ni, nj, nk, kchunk, alpha, beta, slab_of(nk, klo, khi))
     if (wide) { if (R == 4) BQ_JT(64, 4); else if (R == 2) BQ_JT(64, 2); else BQ_JT(64, 1); }
     else      { if (R == 4) BQ_JT(32, 4); else if (R == 2) BQ_JT(32, 2); else BQ_JT(32, 1); }
 #undef BQ_JT
     BQ_LAUNCH_CHECK("jacobi_tile_kernel");
 }
-
-// How many k-chunks a fused launch cuts `nkr` planes into when the compute stream does not own the whole chip
-// (FL_OPT_RESERVE_CUS): the rules below fill 256 CUs in whole rounds; with another CU count no chunk count divides evenly, so
-// take the one that minimises rounds x planes marched per block (chunk + `warm` warm-up planes), nearest to the target
-// chunk length among near-equal candidates.  per_cu: resident blocks per CU.
-static int chunks_for_cus(int nkr, int nrow, int target, int warm, int ncus, int per_cu)
-{
-    double best = 1e30; int best_n = 1, best_gap = 1 << 30;
-    for (int n = 1; n <= std::max(1, nkr / 4); n++) {
-        const int kc = (nkr + n - 1) / n;
-        const long blocks = (long)nrow * ((nkr + kc - 1) / kc);
-        const long rounds = (blocks + (long)ncus * per_cu - 1) / ((long)ncus * per_cu);
-        const double cost = (double)rounds * (kc + warm);
-        const int gap = std::abs(kc - target);
-        if (cost < best * 0.97 || (cost <= best * 1.03 && gap < best_gap)) { best = std::min(best, cost); best_n = n; best_gap = gap; }
-    }
-    return best_n;
-}
-
 
 // Two sweeps in one launch (in -> out holds iterate +2) when the fused kernel applies; returns false
 // (nothing launched) otherwise.  The caller guarantees that both buffers carry the same boundary layer.
@@ -1660,15 +1642,12 @@ static bool jacobi_sweep_pair(const float *in, const float *div, float *out, int
     if (ni < 3 || nj < 3 || nk < 3) return false;
     const int variant = rt().opt_jacobi_variant;
     if (variant != 0 && variant != 3) return false;
-    if (!((ni % 4 == 0) && ni >= 32 && ni <= 1024 && aligned16(in) && aligned16(div) && aligned16(out))) return false;
-    k0a = std::max(k0a, 0); k1a = std::min(k1a, nk); k0b = std::max(k0b, 0); k1b = std::min(k1b, nk);
-    const int lenA = std::max(k1a - k0a, 0), lenB = std::max(k1b - k0b, 0);
-    if (lenA + lenB == 0) return true;
-    const bool whole = lenB == 0 && lenA == nk;
-    const int nkr = lenA + lenB;                         // planes this launch produces
-    auto chunks_of = [](int len, int kc) { return len > 0 ? (len + kc - 1) / kc : 0; };
-    int cw = 16;
-    while (cw * 4 < ni) cw *= 2;                         // float4 lanes per row: <= 64 one wave, 128/256 = 2/4 waves
+    if (!((ni % 4 == 0) && ni >= 32 && ni <= 1024 && aligned16(in, div, out))) return false;
+    const geom::PlaneRanges pr(k0a, k1a, k0b, k1b, nk);
+    if (pr.planes == 0) return true;
+    const bool whole = pr.whole;
+    const int nkr = pr.planes;                           // planes this launch produces
+    const int cw = geom::pow2_lanes(ni, 4);              // float4 lanes per row: <= 64 one wave, 128/256 = 2/4 waves
     const bool wide = cw > 64;
     const int rows = 256 / cw;
     const int nby = (nj + rows - 1) / rows;
@@ -1681,16 +1660,12 @@ static bool jacobi_sweep_pair(const float *in, const float *div, float *out, int
     // the ghost planes): one chunk per range.
     if (nj >= 4 && rt().opt_jacobi_rows != 1) {
         const int nby2 = (nj + 2 * rows - 1) / (2 * rows);
-        int gcd = nby2, rem = 256;
-        while (rem) { const int t = gcd % rem; gcd = rem; rem = t; }
-        const int quantum = 256 / gcd;                              // chunk counts that make nby2 * nbz a multiple of 256
         // ~32 planes per chunk for rows of one wave; rows of 2-4 waves (WIDE) like longer marches: 512^3 runs 201 us per
         // sweep with 6 chunks of 86 planes, 203-214 with 8 of 64, 226 with 48, 211 with 128 (one-row kernel: 228-238)
         const int target2 = wide ? 80 : 32;
-        int nchunks = ((2 * nkr + target2) / (2 * target2) + quantum / 2) / quantum * quantum;
-        if (nchunks < quantum) nchunks = quantum;
+        int nchunks = geom::whole_round_chunks(nby2, nkr, target2, 256);
         const int ncus = rt().num_cus;
-        if (ncus != 256) nchunks = chunks_for_cus(nkr, nby2, target2, 2, ncus, 1);
+        if (ncus != 256) nchunks = geom::chunks_for_cus(nkr, nby2, target2, 2, ncus, 1);
         int kc = (nkr + nchunks - 1) / nchunks;
         // Grids too small to give every CU a chunk of 16 planes (128^3: 8 row blocks): the two-row kernel still wins with the
         // short chunks that fill the chip exactly once -- 128^3: 32 chunks of 4 planes = 256 blocks, 2.99 us per sweep against
@@ -1701,19 +1676,16 @@ static bool jacobi_sweep_pair(const float *in, const float *div, float *out, int
         // 256 x 256 x 64 5.49 / 6.74; gpurun_out/r03h/jacobi_small.txt): whole arrays always take the two-row kernel,
         // chunks down to two planes.
         bool pays = kc >= 16 || whole;
-        if (!whole && std::max(lenA, lenB) <= 48) {
+        if (!whole && pr.longest <= 48) {
             // short ranges (the ends of a split launch): as many chunks as fill the 256 CUs once -- a block marches its
             // chunk plus two warm-up planes, so 2 ranges x 32 row blocks x 4 chunks of 3 planes beat 2 x 32 x 1 of 10
-            const int nranges = (lenA > 0) + (lenB > 0);
-            const int per_range = std::max(1, ncus / std::max(1, nby2 * nranges));
-            kc = std::max(2, (std::max(lenA, lenB) + per_range - 1) / per_range);
+            kc = std::max(2, geom::once_per_cu_len(pr.longest, nby2, pr.nranges, ncus));
             pays = true;
         }
         if (rt().opt_jacobi_kchunk2 > 0) kc = rt().opt_jacobi_kchunk2;
         if (kc < 2) kc = 2;
         if (pays || rt().opt_jacobi_rows == 2) {
-            const PairRanges rg{k0a, k1a, k0b, k1b, chunks_of(lenA, kc)};
-            const int nbz2 = rg.nchA + chunks_of(lenB, kc);
+            const auto [rg, nbz2] = range_launch(pr, kc);
             if (rt().opt_jacobi_rows != 3) {
                 // the lean rendering of the same kernel; FL_OPT_JACOBI_ROWS = 3 keeps the older one for A/B timing
                 // loads run one plane ahead while p, p', div sit in the 256 MiB Infinity Cache, two planes ahead when they
@@ -1747,19 +1719,14 @@ static bool jacobi_sweep_pair(const float *in, const float *div, float *out, int
     int kchunk = rt().opt_jacobi_kchunk2;
     if (kchunk <= 0) {
         const int target = wide ? 64 : 32;
-        int gcd = nby, rem = 512;
-        while (rem) { const int t = gcd % rem; gcd = rem; rem = t; }
-        const int quantum = 512 / gcd;                          // chunk counts that make nby * nbz a multiple of 512
-        int nchunks = ((2 * nkr + target) / (2 * target) + quantum / 2) / quantum * quantum;
-        if (nchunks < quantum) nchunks = quantum;
-        if (rt().num_cus != 256) nchunks = chunks_for_cus(nkr, nby, target, 2, rt().num_cus, 2);
+        int nchunks = geom::whole_round_chunks(nby, nkr, target, 512);
+        if (rt().num_cus != 256) nchunks = geom::chunks_for_cus(nkr, nby, target, 2, rt().num_cus, 2);
         kchunk = (nkr + nchunks - 1) / nchunks;
         if (kchunk < 16) kchunk = target;                       // small grids: no whole round to fill anyway
-        if (!whole && std::max(lenA, lenB) <= 48) kchunk = std::max(lenA, lenB);
+        if (!whole && pr.longest <= 48) kchunk = pr.longest;
     }
     while (whole && kchunk > 8 && (long)nby * ((nk + kchunk - 1) / kchunk) < 512) kchunk /= 2;
-    const PairRanges rg{k0a, k1a, k0b, k1b, chunks_of(lenA, kchunk)};
-    const int nbz = rg.nchA + chunks_of(lenB, kchunk);
+    const auto [rg, nbz] = range_launch(pr, kchunk);
     // (loads two planes ahead instead of one measured no better at 256^3: 19.4 vs 19.1 us per sweep)
     if (wide) jacobi_march2_kernel<4, true><<<nby * nbz, 256, 0, rt().compute>>>(in, div, out, ni, nj, nk, cw, nby, kchunk, alpha, beta, slab_of(nk), rg);
     else      jacobi_march2_kernel<4, false><<<nby * nbz, 256, 0, rt().compute>>>(in, div, out, ni, nj, nk, cw, nby, kchunk, alpha, beta, slab_of(nk), rg);
@@ -1775,21 +1742,15 @@ static bool jacobi_sweep_pair(const float *in, const float *div, float *out, int
 static bool jacobi_sweep_lds(const float *in, const float *div, float *out, int ni, int nj, int nk, float alpha, float beta, int S,
                              int k0a = 0, int k1a = 1 << 30, int k0b = 0, int k1b = 0, const SweepMask *mask = nullptr, int min_kc = 0)
 {
-    k0a = std::max(k0a, 0); k1a = std::min(k1a, nk); k0b = std::max(k0b, 0); k1b = std::min(k1b, nk);
-    const int lenA = std::max(k1a - k0a, 0), lenB = std::max(k1b - k0b, 0);
-    if (lenA + lenB == 0) return true;
-    const bool whole = lenB == 0 && lenA == nk;
-    auto chunks_of = [](int len, int kc) { return len > 0 ? (len + kc - 1) / kc : 0; };
+    const geom::PlaneRanges pr(k0a, k1a, k0b, k1b, nk);
+    if (pr.planes == 0) return true;
     // chunk length: whole arrays -- as many chunks as fill the CUs once (one block per CU: LDS, registers), refused below 24
     // planes per chunk (2 (S - 1) warm-up planes: the two-sweep kernel wins there) unless the length is forced; plane ranges
     // (a slab chunk's ends and interiors) -- whatever fills the CUs once, down to 2 planes per chunk
     auto chunk_len = [&](int nby, bool &ok) {
-        const int ncus = rt().num_cus;
-        const int nranges = (lenA > 0) + (lenB > 0);
-        const int per_range = std::max(1, ncus / std::max(1, nby * nranges));
-        int kc = std::max(2, (std::max(lenA, lenB) + per_range - 1) / per_range);
+        int kc = std::max(2, geom::once_per_cu_len(pr.longest, nby, pr.nranges, rt().num_cus));
         if (rt().opt_jacobi_kchunk2 > 0) kc = rt().opt_jacobi_kchunk2;
-        ok = (!whole || kc >= (rt().opt_jacobi_kchunk2 > 0 ? 8 : 24)) && kc >= min_kc;
+        ok = (!pr.whole || kc >= (rt().opt_jacobi_kchunk2 > 0 ? 8 : 24)) && kc >= min_kc;
         return kc;
     };
     // block shape: FL_OPT_JACOBI_KCHUNK = 10 R + W selects R rows per wave and W output waves per block for A/B timing
@@ -1807,15 +1768,14 @@ static bool jacobi_sweep_lds(const float *in, const float *div, float *out, int 
     // rows of 260 .. 512 floats: the two-segment kernel (three sweeps only), 8 output rows per block
     if (mask && !(S == 3 && ni <= 256 && rt().opt_jacobi_kchunk != 24 && rt().opt_jacobi_kchunk != 25 && rt().opt_jacobi_kchunk != 26 &&
                   rt().opt_jacobi_kchunk != 19)) return false;           // masked: the default three-sweep shape only
-    if (S == 3 && ni > 256 && ni <= 512 && ni % 4 == 0 && nj >= 8 && nk >= 12 && aligned16(in) && aligned16(div) && aligned16(out) &&
-        g_klo == 0 && g_khi >= nk && (double)ni * nj * nk * 4.0 < 2147483648.0) {
+    if (S == 3 && ni > 256 && ni <= 512 && ni % 4 == 0 && nj >= 8 && nk >= 12 && aligned16(in, div, out) &&
+        (double)ni * nj * nk * 4.0 < 2147483648.0) {
         constexpr int LW = 8;
         const int nby = (nj + LW - 1) / LW;
         bool ok;
         const int kc = chunk_len(nby, ok);
         if (!ok) return false;
-        const PairRanges rg{k0a, k1a, k0b, k1b, chunks_of(lenA, kc)};
-        const int nbz = rg.nchA + chunks_of(lenB, kc);
+        const auto [rg, nbz] = range_launch(pr, kc);
         const int nblk = nby * nbz, grid = 8 * ((nblk + 7) / 8);
         jacobi_lds2seg_kernel<LW><<<grid, (LW + 4) * 64, 0, rt().compute>>>(in, div, out, ni, nj, nk, nby, nblk, kc, alpha, beta, slab_of(nk), rg);
         BQ_LAUNCH_CHECK("jacobi_lds2seg_kernel");
@@ -1827,16 +1787,14 @@ static bool jacobi_sweep_lds(const float *in, const float *div, float *out, int 
     if (S == 4 && shape != 24 && shape != 18) shape = 24;        // (row pairs, 6 of them: 10 waves at 168 registers spill)
     const int R = shape / 10, W = shape == 19 ? 12 : (S == 4 && shape == 18 ? 6 : shape % 10);        // (19: single rows, 12 of them: 16 waves per block)
     const int rows_per_block = W * R;
-    if (!((ni % 4 == 0) && ni >= 32 && ni <= 256 && nj >= rows_per_block && nk >= 12 && aligned16(in) && aligned16(div) && aligned16(out))) return false;
-    if (g_klo != 0 || g_khi < nk) return false;              // plane ranges: the two-sweep kernels
+    if (!((ni % 4 == 0) && ni >= 32 && ni <= 256 && nj >= rows_per_block && nk >= 12 && aligned16(in, div, out))) return false;
     const int nby = (nj + rows_per_block - 1) / rows_per_block;
     // 2 (S - 1) warm-up planes per chunk and one block per CU: below ~24 planes per chunk the short-march two-row kernel wins
     // on whole arrays (128^3: 4.5 us per sweep with chunks of 8 against 3.1); a forced chunk length (tests, tuning) may go down to 8
     bool ok;
     const int kc = chunk_len(nby, ok);
     if (!ok) return false;
-    const PairRanges rg{k0a, k1a, k0b, k1b, chunks_of(lenA, kc)};
-    const int nbz = rg.nchA + chunks_of(lenB, kc);
+    const auto [rg, nbz] = range_launch(pr, kc);
     const int nblk = nby * nbz, grid = 8 * ((nblk + 7) / 8);
     hipStream_t st = rt().compute;
 #define BQ_LDS(WV, RV, SV) jacobi_lds_kernel<WV, RV, SV><<<grid, (WV + 2 * ((SV - 1 + RV - 1) / RV)) * 64, 0, st>>>(in, div, out, ni, nj, nk, nby, nblk, kc, alpha, beta, slab_of(nk), rg, SweepMask{})
@@ -1891,19 +1849,13 @@ static bool jacobi_sweep_triple(const float *in, const float *div, float *out, i
         jacobi_sweep_lds(in, div, out, ni, nj, nk, alpha, beta, 3)) return true;
     const int variant = rt().opt_jacobi_variant;
     if ((variant != 0 && variant != 3) || rt().opt_jacobi_rows == 1 || rt().opt_jacobi_rows == 3) return false;
-    if (!((ni % 4 == 0) && ni >= 32 && ni <= 256 && aligned16(in) && aligned16(div) && aligned16(out))) return false;
-    if (g_klo != 0 || g_khi < nk) return false;              // plane ranges: the two-sweep kernels
-    int cw = 16;
-    while (cw * 4 < ni) cw *= 2;
+    if (!((ni % 4 == 0) && ni >= 32 && ni <= 256 && aligned16(in, div, out))) return false;
+    const int cw = geom::pow2_lanes(ni, 4);
     const int rows = 256 / cw;
     const int nby2 = (nj + 2 * rows - 1) / (2 * rows);
-    int gcd = nby2, rem = 256;
-    while (rem) { const int t = gcd % rem; gcd = rem; rem = t; }
-    const int quantum = 256 / gcd;                           // chunk counts that fill the 256 CUs in whole rounds
     const int target = 32;
-    int nchunks = ((2 * nk + target) / (2 * target) + quantum / 2) / quantum * quantum;
-    if (nchunks < quantum) nchunks = quantum;
-    if (rt().num_cus != 256) nchunks = chunks_for_cus(nk, nby2, target, 4, rt().num_cus, 1);
+    int nchunks = geom::whole_round_chunks(nby2, nk, target, 256);
+    if (rt().num_cus != 256) nchunks = geom::chunks_for_cus(nk, nby2, target, 4, rt().num_cus, 1);
     int kc = (nk + nchunks - 1) / nchunks;
     if (rt().opt_jacobi_kchunk2 > 0) kc = rt().opt_jacobi_kchunk2;
     if (kc < 16 && rt().opt_jacobi_rows != 2) return false;  // chunks too short to pay for four warm-up planes
@@ -1977,7 +1929,7 @@ extern "C" {
 void gpu_divergence(const float *u, const float *v, const float *w, float *div, int ni, int nj, int nk, float halfrdx)
 {
     BQ_ENTER("gpu_divergence", u, v, w, div)
-    divergence_kernel<<<grid2(ni, nj, nk), kBlock2, 0, rt().compute>>>(u, v, w, div, ni, nj, nk, halfrdx, slab_of(nk));
+    divergence_kernel<<<grid_for(ni, nj, nk), kBlock, 0, rt().compute>>>(u, v, w, div, ni, nj, nk, halfrdx, slab_of(nk));
     BQ_LAUNCH_CHECK("divergence_kernel");
 }
 
@@ -2029,9 +1981,7 @@ void gpu_jacobi_sweep_range(const float *in, const float *div, float *out, int n
     BQ_ENTER("gpu_jacobi_sweep_range", in, div, out)
     BQ_REQUIRE(in != out, "gpu_jacobi_sweep_range");
     if (k_begin >= k_end) return;
-    g_klo = k_begin; g_khi = k_end;
-    jacobi_sweep(in, div, out, ni, nj, nk, alpha, beta);
-    g_klo = 0; g_khi = 1 << 30;
+    jacobi_sweep(in, div, out, ni, nj, nk, alpha, beta, k_begin, k_end);
 }
 
 // Two sweeps in one launch, `out` written on the planes [k0a, k1a) and [k0b, k1b) only (either may be empty): the
@@ -2064,7 +2014,7 @@ int gpu_jacobi_sweep_triple_ranges(const float *in, const float *div, float *out
 void gpu_gradient(float *u, float *v, float *w, const float *p, int ni, int nj, int nk, float halfrdx)
 {
     BQ_ENTER("gpu_gradient", u, v, w, p)
-    gradient_kernel<<<grid2(ni, nj, nk), kBlock2, 0, rt().compute>>>(u, v, w, p, ni, nj, nk, halfrdx, slab_of(nk));
+    gradient_kernel<<<grid_for(ni, nj, nk), kBlock, 0, rt().compute>>>(u, v, w, p, ni, nj, nk, halfrdx, slab_of(nk));
     BQ_LAUNCH_CHECK("gradient_kernel");
 }
 
@@ -2072,7 +2022,7 @@ void gpu_gradient_delta(float *u, float *v, float *w, const float *p, float *du,
                         int ni, int nj, int nk, float halfrdx)
 {
     BQ_ENTER("gpu_gradient_delta", u, v, w, p, du, dv, dw)
-    gradient_delta_kernel<<<grid2(ni + 1, nj + 1, nk + 1), kBlock2, 0, rt().compute>>>(u, v, w, p, du, dv, dw, ni, nj, nk, halfrdx, slab_of(nk));
+    gradient_delta_kernel<<<grid_for(ni + 1, nj + 1, nk + 1), kBlock, 0, rt().compute>>>(u, v, w, p, du, dv, dw, ni, nj, nk, halfrdx, slab_of(nk));
     BQ_LAUNCH_CHECK("gradient_delta_kernel");
 }
 
@@ -2143,7 +2093,7 @@ void gpu_projection_jacobi(float *u, float *v, float *w, float *div, float *p, f
     BQ_ENTER("gpu_projection_jacobi", u, v, w, div, p, p_temp)
     BQ_REQUIRE(p != p_temp && iter >= 0, "gpu_projection_jacobi");
     hipStream_t st = rt().compute;
-    divergence_kernel<<<grid2(ni, nj, nk), kBlock2, 0, st>>>(u, v, w, div, ni, nj, nk, halfrdx, slab_of(nk));
+    divergence_kernel<<<grid_for(ni, nj, nk), kBlock, 0, st>>>(u, v, w, div, ni, nj, nk, halfrdx, slab_of(nk));
     BQ_LAUNCH_CHECK("divergence_kernel");
     const int stride = rt().opt_residual_stride;
     const bool dbg = debugParam != nullptr && stride > 0;
@@ -2182,7 +2132,7 @@ void gpu_projection_jacobi(float *u, float *v, float *w, float *div, float *p, f
     if (dbg && iter > 0 && (iter - 1) % stride == 0 && iter - 1 < 2000)
         residual_norms_async(div, in, ni, nj, nk, nullptr, nullptr, debugParam + iter - 1, debugParam + 2000 + iter - 1);
     if (in != p) fl_memcpy_d2d(p, in, (size_t)ni * nj * nk * sizeof(float));
-    gradient_kernel<<<grid2(ni, nj, nk), kBlock2, 0, st>>>(u, v, w, p, ni, nj, nk, halfrdx, slab_of(nk));
+    gradient_kernel<<<grid_for(ni, nj, nk), kBlock, 0, st>>>(u, v, w, p, ni, nj, nk, halfrdx, slab_of(nk));
     BQ_LAUNCH_CHECK("gradient_kernel");
 }
 
@@ -2217,7 +2167,7 @@ void gpu_diffuse_field(float *field, float *fieldTemp0, float *filedTemp1, int n
     if (rt().slab_on) dsl.nkg += nk - rt().slab_nkl;
     fl_memcpy_d2d(in, field, bytes);
     for (int it = 0; it < iter; it++) {
-        diffuse_kernel<<<grid2(ni, nj, nk), kBlock2, 0, rt().compute>>>(field, in, out, ni, nj, nk, coef, dsl.koff, dsl.nkg);
+        diffuse_kernel<<<grid_for(ni, nj, nk), kBlock, 0, rt().compute>>>(field, in, out, ni, nj, nk, coef, dsl.koff, dsl.nkg);
         BQ_LAUNCH_CHECK("diffuse_kernel");
         float *t = out; out = in; in = t;
     }
@@ -2237,7 +2187,7 @@ int gpu_diffuse_sweeps(const float *field, float *in, float *out, int ni, int nj
     if (rt().slab_on) dsl.nkg += nk - rt().slab_nkl;        // nk is a BUFFER dim (nk+1 for w)
     float *a = in, *b = out;
     for (int it = 0; it < sweeps; it++) {
-        diffuse_kernel<<<grid2(ni, nj, nk), kBlock2, 0, rt().compute>>>(field, a, b, ni, nj, nk, coef, dsl.koff, dsl.nkg);
+        diffuse_kernel<<<grid_for(ni, nj, nk), kBlock, 0, rt().compute>>>(field, a, b, ni, nj, nk, coef, dsl.koff, dsl.nkg);
         float *t = a; a = b; b = t;
     }
     BQ_LAUNCH_CHECK("diffuse_kernel");

@@ -14,8 +14,6 @@ namespace bq {
 
 static_assert(BQ_MAX_SOURCES == BQ_MAX_BOUNDARIES, "sources travel in the obstacle list's ObsSet / LsSet");
 
-static const dim3 kBlockS(64, 4, 1);
-
 // what the entries write
 struct SrcVal {
     float density[BQ_MAX_SOURCES], temperature[BQ_MAX_SOURCES];
@@ -175,8 +173,8 @@ extern "C" void gpu_emit_sources(float *u, float *v, float *w, float *rho, float
     if (planes > 65535) { latch(FL_ERR_BAD_ARGUMENT, op, "source boxes hold more than 65535 planes"); return; }
     const dim3 grid(gx, gy, planes);
     if (any_ls)
-        emit_sources_kernel<LsSet><<<grid, kBlockS, 0, rt().compute>>>(u, v, w, rho, T, make_obs(shapes, n, h), make_ls(shapes, ls, n), sv, bx, h, ni, nj, nk, koff, nkg);
+        emit_sources_kernel<LsSet><<<grid, kBlock, 0, rt().compute>>>(u, v, w, rho, T, make_obs(shapes, n, h), make_ls(shapes, ls, n), sv, bx, h, ni, nj, nk, koff, nkg);
     else
-        emit_sources_kernel<><<<grid, kBlockS, 0, rt().compute>>>(u, v, w, rho, T, make_obs(shapes, n, h), sv, bx, h, ni, nj, nk, koff, nkg);
+        emit_sources_kernel<><<<grid, kBlock, 0, rt().compute>>>(u, v, w, rho, T, make_obs(shapes, n, h), sv, bx, h, ni, nj, nk, koff, nkg);
     BQ_LAUNCH_CHECK("emit_sources_kernel");
 }

@@ -4,6 +4,7 @@ GPU tests as references.  Test infrastructure.
   build()            tests/_build/libbimocq_host_cpu.so: tests/cpu_abi/oracle_abi.c + the oracle
   build_obstacles()  ..._obstacles.so: + the obstacle operators (tests/cpu_abi/obstacle_abi.c)
   build_levelsets()  ..._levelsets.so: + the level-set operators (tests/cpu_abi/levelset_abi.c)
+  build_launch_geom() tests/_build/liblaunch_geom.so: csrc/bq_launch_geom.h behind tests/cpu_abi/launch_geom_shim.cpp
 A stand-in without some operators leaves the host solver's weak references to them null: set_boundary refuses there."""
 import glob
 import os
@@ -56,5 +57,17 @@ def build_levelsets():
     return _build(os.path.join(OUT, "libbimocq_host_cpu_levelsets.so"), ["obstacle_abi.c", "levelset_abi.c"])
 
 
+def build_launch_geom():
+    """the launchers' integer geometry rules (a host-only header of the product) as a C library for ctypes"""
+    os.makedirs(OUT, exist_ok=True)
+    so = os.path.join(OUT, "liblaunch_geom.so")
+    deps = [os.path.join(ABI, "launch_geom_shim.cpp"), os.path.join(CSRC, "bq_launch_geom.h")]
+    if os.path.exists(so) and all(os.path.getmtime(d) <= os.path.getmtime(so) for d in deps):
+        return so
+    flags = ["-O1", *SAN_FLAGS] if SANITIZE else ["-O2"]
+    subprocess.check_call(["g++", "-std=c++17", *flags, "-fPIC", "-Wall", "-Wextra", "-shared", "-I" + CSRC, deps[0], "-o", so])
+    return so
+
+
 if __name__ == "__main__":
-    print(build(), build_obstacles(), build_levelsets())
+    print(build(), build_obstacles(), build_levelsets(), build_launch_geom())
