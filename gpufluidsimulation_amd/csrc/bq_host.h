@@ -98,6 +98,10 @@ void mgcg_pcg_coarse(const SCoarseLevelInfo *L, int levelnum, double *temp, int 
 void halo_release_state(Runtime &r);    // bq_halo.hip
 void halo_abandon_comm(Runtime &r);     // bq_halo.hip: forget the communicator without destroying it (process exit)
 void project_release_state(Runtime &r); // bq_project.hip
+// bq_project.hip: FL_OPT_JACOBI_VARIANT / _ROWS / _KCHUNK / _KCHUNK2 / _FUSE of the current context, decoded (bq_jacobi_plan.h); the
+// launchers call it once per entry-point call and read the named fields, never the raw integers
+namespace plan { struct JacobiTuning; }
+plan::JacobiTuning jacobi_tuning();
 // bq_project.hip: FL_OPT_PROFILE_JACOBI spans -- an event pair around a loop of sweep launches on the compute
 // stream, summed by fl_jacobi_profile().  profile_begin returns false when profiling is off.
 struct ProfileSpan { hipEvent_t a = nullptr, b = nullptr; };

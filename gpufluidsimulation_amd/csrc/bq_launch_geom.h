@@ -1,7 +1,7 @@
 // bq_launch_geom.h -- launch geometry shared by the marching stencil kernels: the fp32 Jacobi sweeps (bq_project.hip) and the
 // fp64 multigrid smoothers (bq_mgcg.hip, bq_mgcg_fused.hip.inc).  Pure integer arithmetic on the host: no HIP, no runtime
 // state, so that tests/test_launch_geom_cpu.py can compile it with a plain C++ compiler and check every rule without a GPU.
-// The clamps, overrides and refusals that differ between the launchers stay with the launchers.
+// The clamps, overrides and refusals that differ between the launchers: bq_jacobi_plan.h for the fp32 sweeps, the launchers for fp64.
 #pragma once
 #include <algorithm>
 #include <cstdlib>

@@ -24,7 +24,7 @@
 #include "bq_buffer.hip.h"
 #include <type_traits>
 #include "bq_host.h"
-#include "bq_launch_geom.h"
+#include "bq_jacobi_plan.h"
 
 #include <cstdint>
 
@@ -1369,26 +1369,27 @@ static void mg_smooth(double *x, const double *b, double *temp, double alpha, do
     const bool big = (long long)ni * nj * nk >= (1ll << 21);
     // the lean two-row kernel also pays one level down (127^3: 2.05 M cells)
     const bool mid = (long long)ni * nj * nk >= (1ll << 20);
-    if (((rt().opt_jacobi_fuse == 1 && (big || mid)) || rt().opt_jacobi_fuse >= 2) && ni >= 8) {
+    const plan::JacobiTuning tun = jacobi_tuning();
+    const bool vouched = tun.trust == plan::Trust::kVouched;
+    if (((tun.trust == plan::Trust::kChecked && (big || mid)) || vouched) && ni >= 8) {
         const int vec = (ni % 2 == 0 && aligned16(x, temp, b)) ? 2 : 1;
         // the lean two-row kernel: double2 columns, rows of at most 4 waves, arrays below 2 GiB (32-bit byte offsets).
         // FL_OPT_JACOBI_ROWS = 3 / 8 keep mg_smooth2_kernel (A/B timing)
         // (odd rows: 16-byte loads at 8-byte-aligned addresses, which the memory pipeline splits -- the same mode the
         // gather kernels' dwordx2 loads at 4-byte alignment rely on)
         if ((vec == 2 || ni % 2 == 1) && ni >= 8 && ni <= 512 && nj >= 4 && (double)ni * nj * nk * 8.0 < 2147483648.0 &&
-            rt().opt_jacobi_rows != 3 && rt().opt_jacobi_rows != 8) {
+            !tun.mg_keep_smooth2) {
             const int cw = geom::pow2_lanes(ni, 2);
             const bool wide = cw > 64;
             const int rows2 = 256 / cw;
             const int nby2 = (nj + 2 * rows2 - 1) / (2 * rows2);
             const int nchunks = geom::whole_round_chunks(nby2, nk, wide ? 80 : 32, 256);
             int kc = (nk + nchunks - 1) / nchunks;
-            if (rt().opt_jacobi_kchunk2 > 0) kc = rt().opt_jacobi_kchunk2;
+            if (tun.fused_kchunk > 0) kc = tun.fused_kchunk;
             if (kc < 4) kc = 4;
             const int nbz = (nk + kc - 1) / kc;
             const bool in_cache = 24.0 * (double)ni * nj * nk <= 256.0 * 1048576.0;
-            const int forced = rt().opt_jacobi_kchunk;
-            const int pf = forced == 1 || forced == 2 ? forced : (in_cache ? 1 : 2);
+            const int pf = tun.prefetch ? tun.prefetch : (in_cache ? 1 : 2);
             bool zin = false;
             if (!cleared && iter >= 4) {
                 if (clear & 1) mg_zero_shell(temp, ni, nj, nk);
@@ -1401,26 +1402,17 @@ static void mg_smooth(double *x, const double *b, double *temp, double alpha, do
             long long launches = 0;
             bool planned = false;
             // three (and two) sweeps per launch through mg_lds3_kernel where it applies (rows of 130 .. 256 doubles, chunks of >= 24
-            // planes at one block per CU; FL_OPT_JACOBI_ROWS = 5 keeps it off for A/B timing): as many triples as leave an even
-            // number of launches in total, so that the newest iterate still ends in x, the rest as pairs through the same
-            // kernel -- 4 sweeps = 2 pairs.  A call that starts from a cleared x (V_Cycle's way down) is free of the parity rule:
-            // its first launch does not read its input, so with an odd number of launches it writes straight into x --
-            // 32 sweeps = 10 triples + 1 pair.
-            if (vec == 2 && ni >= 130 && ni <= 256 && nj >= 4 && nk >= 12 && rt().opt_jacobi_rows != 5 && cleared) {
-                // FL_OPT_JACOBI_KCHUNK = 14: blocks of 4 output rows (8 waves) instead of 8 (12 waves), for A/B timing
-                const int LW = rt().opt_jacobi_kchunk == 14 ? 4 : 8;
+            // planes at one block per CU; FL_OPT_JACOBI_ROWS = 5 keeps it off for A/B timing), split into triples and pairs by
+            // plan::mg_lds3_split so that the newest iterate still ends in x
+            if (vec == 2 && ni >= 130 && ni <= 256 && nj >= 4 && nk >= 12 && !tun.mg_lds3_off && cleared) {
+                const int LW = tun.mg_lds3_rows;
                 const int nbyl = (nj + LW - 1) / LW;
                 int kcl = geom::once_per_cu_len(nk, nbyl, 1, rt().num_cus);
-                if (rt().opt_jacobi_kchunk2 > 0) kcl = rt().opt_jacobi_kchunk2;
-                int triples = -1;
-                if (kcl >= (rt().opt_jacobi_kchunk2 > 0 ? 8 : 24))
-                    for (int a = (iter - s) / 3; a >= 0 && triples < 0; a--) {
-                        const int rest = iter - s - 3 * a;
-                        if (rest % 2 == 0 && (zin || (rest / 2 + a) % 2 == 0)) triples = a;
-                    }
-                if (triples >= 0) {
-                    const int pairs = (iter - s - 3 * triples) / 2;
-                    if (zin && (pairs + triples) % 2 == 1) { double *t2 = in; in = out; out = t2; }
+                if (tun.fused_kchunk > 0) kcl = tun.fused_kchunk;
+                const plan::MgLds3Split split = kcl >= tun.lds_min_kc ? plan::mg_lds3_split(iter, s, zin) : plan::MgLds3Split{-1, 0, false};
+                if (split.triples >= 0) {
+                    const int triples = split.triples, pairs = split.pairs;
+                    if (split.swap_first) { double *t2 = in; in = out; out = t2; }
                     const int nbzl = (nk + kcl - 1) / kcl;
                     const int nblk = nbyl * nbzl, gridl = 8 * ((nblk + 7) / 8);
                     for (int t = 0; t < triples + pairs; t++) {
@@ -1474,11 +1466,11 @@ static void mg_smooth(double *x, const double *b, double *temp, double alpha, do
         if (!cleared) { if (clear & 1) mg_zero(temp, cells); if (clear & 2) mg_zero(x, cells); cleared = true; }
         const int lanes = (ni + vec - 1) / vec;
         const int lpr = ((lanes + 63) / 64) * 64;
-        const int threads = rt().opt_jacobi_rows == 8 ? 512 : 256;      // FL_OPT_JACOBI_ROWS: waves per block (4 or 8)
-        if (lpr <= threads && (big || rt().opt_jacobi_fuse >= 2)) {      // (slower than one launch per sweep below 2 M cells)
+        const int threads = tun.mg_smooth2_threads;
+        if (lpr <= threads && (big || vouched)) {      // (slower than one launch per sweep below 2 M cells)
             const int rows = threads / lpr;
             const int nby = (nj + rows - 1) / rows;
-            int kchunk = rt().opt_jacobi_kchunk2 > 0 ? rt().opt_jacobi_kchunk2 : 64;
+            int kchunk = tun.fused_kchunk > 0 ? tun.fused_kchunk : 64;
             while (kchunk > 4 && (long)nby * ((nk + kchunk - 1) / kchunk) < 512) kchunk /= 2;
             const int nbz = (nk + kchunk - 1) / kchunk;
             // launches come in pairs (x -> temp -> x) so that the newest iterate still ends where the

@@ -4,6 +4,7 @@
 // The band semi-Lagrangian pass lives beside semilag_kernel in bq_advect.hip.
 #include "bq_device.hip.h"
 #include "bq_host.h"
+#include "bq_jacobi_plan.h"
 #include "bq_obstacle.hip.h"
 
 namespace bq {
@@ -208,7 +209,7 @@ static void obstacle_blend(float *u, float *v, float *w, float *rho, float *T, c
     BQ_LAUNCH_CHECK("obstacle_blend_kernel");
 }
 
-bool jacobi_sweep_triple_masked(const float *in, const float *div, float *out, int ni, int nj, int nk, float alpha,
+bool jacobi_sweep_triple_masked(const plan::JacobiTuning &tun, const float *in, const float *div, float *out, int ni, int nj, int nk, float alpha,
                                 const unsigned char *solid, const unsigned char *rows, const float betas[7]);   // bq_project.hip
 
 } // namespace bq
@@ -264,8 +265,9 @@ int gpu_jacobi_sweeps_masked(float *p, const float *div, float *p_temp, const un
     const bool prof = sweeps > 0 && profile_begin(span);      // FL_OPT_PROFILE_JACOBI, like gpu_jacobi_sweeps
     int s = 0;
     long long launches = 0;
-    while (rt().opt_jacobi_fuse >= 2 && rt().opt_jacobi_fuse != 4 && s + 3 <= sweeps &&
-           jacobi_sweep_triple_masked(in, div, out, ni, nj, nk, alpha, solid, rows, bt.b)) {
+    const plan::JacobiTuning tun = jacobi_tuning();
+    while (tun.sweeps_fuse == plan::SweepsFuse::kAll && s + 3 <= sweeps &&
+           jacobi_sweep_triple_masked(tun, in, div, out, ni, nj, nk, alpha, solid, rows, bt.b)) {
         float *t = in; in = out; out = t;
         s += 3; launches++;
     }

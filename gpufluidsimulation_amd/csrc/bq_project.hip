@@ -10,7 +10,7 @@
 #include "bq_buffer.hip.h"
 #include <type_traits>
 #include "bq_host.h"
-#include "bq_launch_geom.h"
+#include "bq_jacobi_plan.h"
 #include <algorithm>
 #include <vector>
 
@@ -1551,8 +1551,6 @@ static ProjectState &ps()
     if (!r.project_state) r.project_state = new ProjectState();
     return *static_cast<ProjectState *>(r.project_state);
 }
-#define g_last_pair_kernel (ps().last_pair_kernel)
-#define g_spans (ps().spans)
 void project_release_state(Runtime &r)
 {
     ProjectState *st = static_cast<ProjectState *>(r.project_state);
@@ -1577,296 +1575,137 @@ static inline RangeLaunch range_launch(const geom::PlaneRanges &pr, int kc)
     return RangeLaunch{PairRanges{c.k0a, c.k1a, c.k0b, c.k1b, c.nchA}, c.nbz};
 }
 
-// One Jacobi sweep in -> out on the compute stream, on the local planes [klo, khi) (default: the whole array).
-static void jacobi_sweep(const float *in, const float *div, float *out, int ni, int nj, int nk, float alpha, float beta,
-                         int klo = 0, int khi = 1 << 30)
+// The Jacobi tuning options of the current context, decoded (bq_jacobi_plan.h).  Once per entry-point call: the options are per
+// context and may change between two calls.
+plan::JacobiTuning jacobi_tuning()
 {
-    if (ni < 3 || nj < 3 || nk < 3) return;         // no interior
-    int variant = rt().opt_jacobi_variant;
-    const bool tile_ok = (ni % 4 == 0) && ni >= 32 && aligned16(in, div, out);
-    if (variant == 0) variant = tile_ok ? 3 : 1;
-    if (variant != 1 && !tile_ok) variant = 1;
+    const Runtime &r = rt();
+    return plan::decode_jacobi_tuning(r.opt_jacobi_variant, r.opt_jacobi_rows, r.opt_jacobi_kchunk, r.opt_jacobi_kchunk2, r.opt_jacobi_fuse);
+}
+
+// The launchers below ask bq_jacobi_plan.h which kernel, template arguments and geometry apply, switch on the answer and launch on
+// the compute stream; every rule and the measurements behind it live with the planners.
+
+// One Jacobi sweep in -> out, on the local planes [klo, khi) (default: the whole array).
+static void jacobi_sweep(const plan::JacobiTuning &tun, const float *in, const float *div, float *out, int ni, int nj, int nk, float alpha,
+                         float beta, int klo = 0, int khi = 1 << 30)
+{
+    const plan::LaunchPlan pl = plan::plan_single(ni, nj, nk, aligned16(in, div, out), tun);
     hipStream_t st = rt().compute;
-    if (variant == 1) {
-        jacobi_generic_kernel<<<grid_for(ni, nj, nk), kBlock, 0, st>>>(in, div, out, ni, nj, nk, alpha, beta, slab_of(nk, klo, khi));
+    const Slab sl = slab_of(nk, klo, khi);
+    switch (pl.kernel) {
+    case plan::Kernel::kGeneric:
+        jacobi_generic_kernel<<<grid_for(ni, nj, nk), kBlock, 0, st>>>(in, div, out, ni, nj, nk, alpha, beta, sl);
         BQ_LAUNCH_CHECK("jacobi_generic_kernel");
         return;
-    }
-    if (variant == 3) {
-        int waves = rt().opt_jacobi_rows;
-        if (waves != 4 && waves != 8 && waves != 16) waves = 4;
-        const int threads = waves * 64;
-        const int cw = geom::pow2_lanes(ni, 4, threads);     // float4 columns per tile row: pow2 >= ni/4
-        const int rows = threads / cw;
-        const int nbx = (ni / 4 + cw - 1) / cw, nby = (nj + rows - 1) / rows;
-        // k-chunk: measured optimum at 256^3 is 16 planes (tools/jacobi_tune.py: 4/8/16/32 planes ->
-        // 34.2/34.5/31.8/34.0 us); shorter chunks re-read more planes, longer ones leave CUs idle.
-        // Keep >= ~1024 blocks when the grid is small in x/y.
-        int kchunk = 16;
-        while (kchunk > 4 && (long)nbx * nby * ((nk + kchunk - 1) / kchunk) < 1024) kchunk /= 2;
-        if (rt().opt_jacobi_kchunk > 0) kchunk = rt().opt_jacobi_kchunk;
-        const int nbz = (nk + kchunk - 1) / kchunk;
-        const int nblk = nbx * nby * nbz;
-#define BQ_JM(W) jacobi_march_kernel<W><<<nblk, W * 64, 0, st>>>(in, div, out, ni, nj, nk, cw, nbx, nby, kchunk, alpha, beta, slab_of(nk, klo, khi))
-        if (waves == 4) BQ_JM(4); else if (waves == 8) BQ_JM(8); else BQ_JM(16);
+    case plan::Kernel::kMarch:
+#define BQ_JM(W) jacobi_march_kernel<W><<<pl.grid, W * 64, 0, st>>>(in, div, out, ni, nj, nk, pl.cw, pl.col_blocks, pl.row_blocks, pl.kc, alpha, beta, sl)
+        if (pl.W == 4) BQ_JM(4); else if (pl.W == 8) BQ_JM(8); else BQ_JM(16);
 #undef BQ_JM
         BQ_LAUNCH_CHECK("jacobi_march_kernel");
         return;
-    }
-    // tile geometry: 256-wide rows when the row is long enough, else 128-wide; R float4 per thread
-    const bool wide = ni > 128;
-    int R = rt().opt_jacobi_rows;
-    if (R != 1 && R != 2 && R != 4) R = 4;
-    const int TX = wide ? 256 : 128, TY = (wide ? 4 : 8) * R;
-    const int bx = (ni + TX - 1) / TX, by = (nj + TY - 1) / TY;
-    // k-chunks: enough blocks to fill 256 CUs x 2 resident blocks, at least 8 planes per chunk
-    int want = (1024 + bx * by - 1) / (bx * by);
-    int kchunk = (nk + want - 1) / want;
-    if (kchunk < 8) kchunk = 8;
-    if (rt().opt_jacobi_kchunk > 0) kchunk = rt().opt_jacobi_kchunk;
-    const int bz = (nk + kchunk - 1) / kchunk;
-    dim3 grid(bx, by, bz);
-#define BQ_JT(TXV, RR) jacobi_tile_kernel<TXV, RR><<<grid, 256, 0, st>>>(in, div, out, ni, nj, nk, kchunk, alpha, beta, slab_of(nk, klo, khi))
-    if (wide) { if (R == 4) BQ_JT(64, 4); else if (R == 2) BQ_JT(64, 2); else BQ_JT(64, 1); }
-    else      { if (R == 4) BQ_JT(32, 4); else if (R == 2) BQ_JT(32, 2); else BQ_JT(32, 1); }
+    case plan::Kernel::kTile: {
+        const dim3 grid(pl.col_blocks, pl.row_blocks, pl.nbz);
+#define BQ_JT(TXV, RR) jacobi_tile_kernel<TXV, RR><<<grid, 256, 0, st>>>(in, div, out, ni, nj, nk, pl.kc, alpha, beta, sl)
+        if (pl.wide) { if (pl.R == 4) BQ_JT(64, 4); else if (pl.R == 2) BQ_JT(64, 2); else BQ_JT(64, 1); }
+        else         { if (pl.R == 4) BQ_JT(32, 4); else if (pl.R == 2) BQ_JT(32, 2); else BQ_JT(32, 1); }
 #undef BQ_JT
-    BQ_LAUNCH_CHECK("jacobi_tile_kernel");
+        BQ_LAUNCH_CHECK("jacobi_tile_kernel");
+        return;
+    }
+    default: return;                                // no interior
+    }
 }
 
-// Two sweeps in one launch (in -> out holds iterate +2) when the fused kernel applies; returns false
-// (nothing launched) otherwise.  The caller guarantees that both buffers carry the same boundary layer.
-// k0a..k1b: output plane ranges (see PairRanges); the default is the whole array
-static bool jacobi_sweep_pair(const float *in, const float *div, float *out, int ni, int nj, int nk, float alpha, float beta,
-                              int k0a = 0, int k1a = 1 << 30, int k0b = 0, int k1b = 0)
+// The fused launch that `pl` describes: in -> out holds iterate + pl.S on the output planes `pr`.  false: the plan does not apply,
+// nothing launched.  Records the kernel's name for fl_jacobi_kernel_name.  The caller guarantees that both buffers carry the same
+// boundary layer.
+static bool launch_fused(const plan::LaunchPlan &pl, const float *in, const float *div, float *out, int ni, int nj, int nk, float alpha,
+                         float beta, const geom::PlaneRanges &pr, const SweepMask *mask = nullptr)
 {
-    if (ni < 3 || nj < 3 || nk < 3) return false;
-    const int variant = rt().opt_jacobi_variant;
-    if (variant != 0 && variant != 3) return false;
-    if (!((ni % 4 == 0) && ni >= 32 && ni <= 1024 && aligned16(in, div, out))) return false;
-    const geom::PlaneRanges pr(k0a, k1a, k0b, k1b, nk);
-    if (pr.planes == 0) return true;
-    const bool whole = pr.whole;
-    const int nkr = pr.planes;                           // planes this launch produces
-    const int cw = geom::pow2_lanes(ni, 4);              // float4 lanes per row: <= 64 one wave, 128/256 = 2/4 waves
-    const bool wide = cw > 64;
-    const int rows = 256 / cw;
-    const int nby = (nj + rows - 1) / rows;
-    // Two rows per thread (jacobi_march2r_kernel; rows of one wave only).  It has half as many row blocks, runs one
-    // 4-wave block per CU best, and like the one-row kernel only pays when the blocks fill the 256 CUs in whole
-    // rounds: 256^3 17.1 us per sweep with 8 chunks of 32 planes (256 blocks) against 19.0-19.7 for the one-row
-    // kernel, but 21-23 us with chunks of 24-28 and 28 us with chunks of 64; 272 planes 18.0 (8 chunks of 34) against
-    // 20.0; 128^3 is slower with it (5.5 vs 4.6: the chunks get too short).  FL_OPT_JACOBI_ROWS: 0 = this rule,
-    // 1 = one row, 2 = two rows whenever the kernel applies.  Short plane ranges (the parts of a split launch next to
-    // the ghost planes): one chunk per range.
-    if (nj >= 4 && rt().opt_jacobi_rows != 1) {
-        const int nby2 = (nj + 2 * rows - 1) / (2 * rows);
-        // ~32 planes per chunk for rows of one wave; rows of 2-4 waves (WIDE) like longer marches: 512^3 runs 201 us per
-        // sweep with 6 chunks of 86 planes, 203-214 with 8 of 64, 226 with 48, 211 with 128 (one-row kernel: 228-238)
-        const int target2 = wide ? 80 : 32;
-        int nchunks = geom::whole_round_chunks(nby2, nkr, target2, 256);
-        const int ncus = rt().num_cus;
-        if (ncus != 256) nchunks = geom::chunks_for_cus(nkr, nby2, target2, 2, ncus, 1);
-        int kc = (nkr + nchunks - 1) / nchunks;
-        // Grids too small to give every CU a chunk of 16 planes (128^3: 8 row blocks): the two-row kernel still wins with the
-        // short chunks that fill the chip exactly once -- 128^3: 32 chunks of 4 planes = 256 blocks, 2.99 us per sweep against
-        // 4.41 for the one-row kernel with chunks of 8 (chunks of 2 / 3 / 5 planes: 3.34 / 3.73 / 3.24; the three-sweep kernel
-        // with chunks of 4: 3.21; gpurun_out/r03f/jacobi_tune_128.txt) -- a march this short is bound by the latency of its
-        // 6 plane steps at one wave per SIMD, so what counts is that no CU waits for a second round.
-        // Smaller still (64^3 2.21 against 4.11 us per sweep, 96^3 3.15 / 4.28, 160^3 7.34 / 9.85, 192^3 8.30 / 12.95,
-        // 256 x 256 x 64 5.49 / 6.74; gpurun_out/r03h/jacobi_small.txt): whole arrays always take the two-row kernel,
-        // chunks down to two planes.
-        bool pays = kc >= 16 || whole;
-        if (!whole && pr.longest <= 48) {
-            // short ranges (the ends of a split launch): as many chunks as fill the 256 CUs once -- a block marches its
-            // chunk plus two warm-up planes, so 2 ranges x 32 row blocks x 4 chunks of 3 planes beat 2 x 32 x 1 of 10
-            kc = std::max(2, geom::once_per_cu_len(pr.longest, nby2, pr.nranges, ncus));
-            pays = true;
-        }
-        if (rt().opt_jacobi_kchunk2 > 0) kc = rt().opt_jacobi_kchunk2;
-        if (kc < 2) kc = 2;
-        if (pays || rt().opt_jacobi_rows == 2) {
-            const auto [rg, nbz2] = range_launch(pr, kc);
-            if (rt().opt_jacobi_rows != 3) {
-                // the lean rendering of the same kernel; FL_OPT_JACOBI_ROWS = 3 keeps the older one for A/B timing
-                // loads run one plane ahead while p, p', div sit in the 256 MiB Infinity Cache, two planes ahead when they
-                // come from HBM (512^3: 199.8 -> 195.6 us per sweep; 256^3 15.75 vs 15.95 the other way round).
-                // FL_OPT_JACOBI_KCHUNK = 1 / 2 forces a distance (it has no other meaning for the fused kernels)
-                const bool in_cache = 12.0 * (double)ni * (double)nj * (double)nk <= 256.0 * 1048576.0;
-                const int forced = rt().opt_jacobi_kchunk;
-                const int pf = forced == 1 || forced == 2 ? forced : (in_cache ? 1 : 2);
-                const dim3 gr(nby2 * nbz2);
-                hipStream_t st = rt().compute;
-#define BQ_LEAN2R(W, F) jacobi_lean2r_kernel<W, F><<<gr, 256, 0, st>>>(in, div, out, ni, nj, nk, cw, nby2, kc, alpha, beta, slab_of(nk), rg)
-                if (wide) { if (pf == 1) BQ_LEAN2R(true, 1); else BQ_LEAN2R(true, 2); }
-                else      { if (pf == 1) BQ_LEAN2R(false, 1); else BQ_LEAN2R(false, 2); }
-#undef BQ_LEAN2R
-                BQ_LAUNCH_CHECK("jacobi_lean2r_kernel");
-                g_last_pair_kernel = "jacobi_lean2r_kernel";
-                return true;
-            }
-            if (wide) jacobi_march2r_kernel<4, true><<<nby2 * nbz2, 256, 0, rt().compute>>>(in, div, out, ni, nj, nk, cw, nby2, kc, alpha, beta, slab_of(nk), rg);
-            else      jacobi_march2r_kernel<4, false><<<nby2 * nbz2, 256, 0, rt().compute>>>(in, div, out, ni, nj, nk, cw, nby2, kc, alpha, beta, slab_of(nk), rg);
-            BQ_LAUNCH_CHECK("jacobi_march2r_kernel");
-            g_last_pair_kernel = "jacobi_march2r_kernel";
-            return true;
-        }
-    }
-    // planes per block: ~32 measured best at 256^3 (one wave per row), ~64 at 512^3 (248 vs 254 us per sweep).  What
-    // matters more is that the blocks fill the 256 CUs in whole rounds of two blocks per CU: at 256^3, 512 blocks
-    // (chunks of 32) run 19.1 us per sweep, 576 or 448 blocks (chunks of 28 or 40) 22.7; a z-slab rank with 272
-    // planes runs 25.4 us with chunks of 32 (9 of them) and 20.0 with chunks of 34 (8).  So: the number of chunks is
-    // the multiple of 512 / gcd(row blocks, 512) closest to planes / target.
-    int kchunk = rt().opt_jacobi_kchunk2;
-    if (kchunk <= 0) {
-        const int target = wide ? 64 : 32;
-        int nchunks = geom::whole_round_chunks(nby, nkr, target, 512);
-        if (rt().num_cus != 256) nchunks = geom::chunks_for_cus(nkr, nby, target, 2, rt().num_cus, 2);
-        kchunk = (nkr + nchunks - 1) / nchunks;
-        if (kchunk < 16) kchunk = target;                       // small grids: no whole round to fill anyway
-        if (!whole && pr.longest <= 48) kchunk = pr.longest;
-    }
-    while (whole && kchunk > 8 && (long)nby * ((nk + kchunk - 1) / kchunk) < 512) kchunk /= 2;
-    const auto [rg, nbz] = range_launch(pr, kchunk);
-    // (loads two planes ahead instead of one measured no better at 256^3: 19.4 vs 19.1 us per sweep)
-    if (wide) jacobi_march2_kernel<4, true><<<nby * nbz, 256, 0, rt().compute>>>(in, div, out, ni, nj, nk, cw, nby, kchunk, alpha, beta, slab_of(nk), rg);
-    else      jacobi_march2_kernel<4, false><<<nby * nbz, 256, 0, rt().compute>>>(in, div, out, ni, nj, nk, cw, nby, kchunk, alpha, beta, slab_of(nk), rg);
-    BQ_LAUNCH_CHECK("jacobi_march2_kernel");
-    g_last_pair_kernel = "jacobi_march2_kernel";
-    return true;
-}
-
-// Three or four sweeps in one launch through jacobi_lds_kernel (neighbour rows of the intermediate levels via LDS); false = not applicable.
-// FL_OPT_JACOBI_ROWS: 4 forces it wherever it applies, 5 keeps it off (A/B timing); auto: see jacobi_sweep_triple.
-// k0a .. k1b: the OUTPUT planes as up to two ranges (gpu_jacobi_sweep_triple_ranges: the pieces of a z-slab chunk); default: the whole array.
-// min_kc > 0: refused when the chunks come out shorter than that, a forced chunk length included (jacobi_sweep_quad's auto rule).
-static bool jacobi_sweep_lds(const float *in, const float *div, float *out, int ni, int nj, int nk, float alpha, float beta, int S,
-                             int k0a = 0, int k1a = 1 << 30, int k0b = 0, int k1b = 0, const SweepMask *mask = nullptr, int min_kc = 0)
-{
-    const geom::PlaneRanges pr(k0a, k1a, k0b, k1b, nk);
-    if (pr.planes == 0) return true;
-    // chunk length: whole arrays -- as many chunks as fill the CUs once (one block per CU: LDS, registers), refused below 24
-    // planes per chunk (2 (S - 1) warm-up planes: the two-sweep kernel wins there) unless the length is forced; plane ranges
-    // (a slab chunk's ends and interiors) -- whatever fills the CUs once, down to 2 planes per chunk
-    auto chunk_len = [&](int nby, bool &ok) {
-        int kc = std::max(2, geom::once_per_cu_len(pr.longest, nby, pr.nranges, rt().num_cus));
-        if (rt().opt_jacobi_kchunk2 > 0) kc = rt().opt_jacobi_kchunk2;
-        ok = (!pr.whole || kc >= (rt().opt_jacobi_kchunk2 > 0 ? 8 : 24)) && kc >= min_kc;
-        return kc;
-    };
-    // block shape: FL_OPT_JACOBI_KCHUNK = 10 R + W selects R rows per wave and W output waves per block for A/B timing
-    // (24 / 25 / 26: row pairs, 4 / 5 / 6 of them; 18 / 19: single rows, 8 / 12 of them); default 18 for three sweeps, 24 for four.
-    // 256^3, three sweeps, us per sweep (gpurun_out/r03l, r03m): 18 with chunks of 32 planes 10.79, 24 11.06, 25 11.59, 26 with
-    // chunks of 26 11.88, 19 11.23 -- against 13.1-13.6 for jacobi_lean3r_kernel and 15.6 for the two-sweep kernel.  A launch
-    // then takes 32.4 us for 201 MB of compulsory traffic = 6.2 TB/s: like the two-sweep kernel (31.4 us per launch) it sits on
-    // the fabric, so what is left is more sweeps per launch, not a better schedule -- hence S = 4.
-    // Later in round 3 (gpurun_out/r03r .. r03v): the l + r stage through v_add_f32_dpp 10.79 -> 10.71; input rings of 5 / 6
-    // planes (loads one / two steps further ahead) 11.00 / 11.19; the step's prefetch issued last 11.11, the first level ahead
-    // of the LDS reads 10.76; blocks of 4 single rows, two per CU 11.83; halo waves that skip the levels nobody needs: S = 3
-    // 10.69, S = 4 in row pairs 11.40 -> 9.98 (39.9 us per launch).  SQ counters: a wave issues 24-28 % of its cycles, is
-    // parked on waitcnt / barrier 40 % and stalled at issue 33 % (the L1 path: with the prefetch last the stall moves to the
-    // barrier) -- VALU, LDS and L1 path are each 25-40 % busy but take turns between the barriers.
-    // rows of 260 .. 512 floats: the two-segment kernel (three sweeps only), 8 output rows per block
-    if (mask && !(S == 3 && ni <= 256 && rt().opt_jacobi_kchunk != 24 && rt().opt_jacobi_kchunk != 25 && rt().opt_jacobi_kchunk != 26 &&
-                  rt().opt_jacobi_kchunk != 19)) return false;           // masked: the default three-sweep shape only
-    if (S == 3 && ni > 256 && ni <= 512 && ni % 4 == 0 && nj >= 8 && nk >= 12 && aligned16(in, div, out) &&
-        (double)ni * nj * nk * 4.0 < 2147483648.0) {
-        constexpr int LW = 8;
-        const int nby = (nj + LW - 1) / LW;
-        bool ok;
-        const int kc = chunk_len(nby, ok);
-        if (!ok) return false;
-        const auto [rg, nbz] = range_launch(pr, kc);
-        const int nblk = nby * nbz, grid = 8 * ((nblk + 7) / 8);
-        jacobi_lds2seg_kernel<LW><<<grid, (LW + 4) * 64, 0, rt().compute>>>(in, div, out, ni, nj, nk, nby, nblk, kc, alpha, beta, slab_of(nk), rg);
-        BQ_LAUNCH_CHECK("jacobi_lds2seg_kernel");
-        g_last_pair_kernel = "jacobi_lds2seg_kernel";
-        return true;
-    }
-    int shape = rt().opt_jacobi_kchunk;
-    if (shape != 24 && shape != 25 && shape != 26 && shape != 18 && shape != 19) shape = S == 4 ? 24 : 18;
-    if (S == 4 && shape != 24 && shape != 18) shape = 24;        // (row pairs, 6 of them: 10 waves at 168 registers spill)
-    const int R = shape / 10, W = shape == 19 ? 12 : (S == 4 && shape == 18 ? 6 : shape % 10);        // (19: single rows, 12 of them: 16 waves per block)
-    const int rows_per_block = W * R;
-    if (!((ni % 4 == 0) && ni >= 32 && ni <= 256 && nj >= rows_per_block && nk >= 12 && aligned16(in, div, out))) return false;
-    const int nby = (nj + rows_per_block - 1) / rows_per_block;
-    // 2 (S - 1) warm-up planes per chunk and one block per CU: below ~24 planes per chunk the short-march two-row kernel wins
-    // on whole arrays (128^3: 4.5 us per sweep with chunks of 8 against 3.1); a forced chunk length (tests, tuning) may go down to 8
-    bool ok;
-    const int kc = chunk_len(nby, ok);
-    if (!ok) return false;
-    const auto [rg, nbz] = range_launch(pr, kc);
-    const int nblk = nby * nbz, grid = 8 * ((nblk + 7) / 8);
+    using plan::Kernel;
+    if (pl.kernel == Kernel::kNone) return false;
+    if (pl.kernel == Kernel::kEmpty) return true;
     hipStream_t st = rt().compute;
-#define BQ_LDS(WV, RV, SV) jacobi_lds_kernel<WV, RV, SV><<<grid, (WV + 2 * ((SV - 1 + RV - 1) / RV)) * 64, 0, st>>>(in, div, out, ni, nj, nk, nby, nblk, kc, alpha, beta, slab_of(nk), rg, SweepMask{})
-    if (mask) {
-        jacobi_lds_kernel<8, 1, 3, true><<<grid, (8 + 2 * 2) * 64, 0, st>>>(in, div, out, ni, nj, nk, nby, nblk, kc, alpha, beta, slab_of(nk), rg, *mask);
-        BQ_LAUNCH_CHECK("jacobi_lds_kernel<masked>");
-        g_last_pair_kernel = "jacobi_lds3_masked_kernel";
-        return true;
-    }
-    if (S == 4) {
-        if (shape == 24) BQ_LDS(4, 2, 4); else BQ_LDS(6, 1, 4);      // (18 with four sweeps: 6 single rows + 6 halo waves)
-    } else {
-        if (shape == 24) BQ_LDS(4, 2, 3); else if (shape == 25) BQ_LDS(5, 2, 3); else if (shape == 26) BQ_LDS(6, 2, 3);
-        else if (shape == 19) BQ_LDS(12, 1, 3);
-        else BQ_LDS(8, 1, 3);
-    }
+    const Slab sl = slab_of(nk);
+    const PairRanges rg = range_launch(pr, pl.kc).rg;
+    const char *name = "", *what = nullptr;             // the name reported, and the one an error message carries where it differs
+    switch (pl.kernel) {
+    case Kernel::kLean2r:
+#define BQ_LEAN2R(W, F) jacobi_lean2r_kernel<W, F><<<pl.grid, 256, 0, st>>>(in, div, out, ni, nj, nk, pl.cw, pl.row_blocks, pl.kc, alpha, beta, sl, rg)
+        if (pl.wide) { if (pl.pf == 1) BQ_LEAN2R(true, 1); else BQ_LEAN2R(true, 2); }
+        else         { if (pl.pf == 1) BQ_LEAN2R(false, 1); else BQ_LEAN2R(false, 2); }
+#undef BQ_LEAN2R
+        name = "jacobi_lean2r_kernel";
+        break;
+    case Kernel::kMarch2r:
+        if (pl.wide) jacobi_march2r_kernel<4, true><<<pl.grid, 256, 0, st>>>(in, div, out, ni, nj, nk, pl.cw, pl.row_blocks, pl.kc, alpha, beta, sl, rg);
+        else         jacobi_march2r_kernel<4, false><<<pl.grid, 256, 0, st>>>(in, div, out, ni, nj, nk, pl.cw, pl.row_blocks, pl.kc, alpha, beta, sl, rg);
+        name = "jacobi_march2r_kernel";
+        break;
+    case Kernel::kMarch2:
+        if (pl.wide) jacobi_march2_kernel<4, true><<<pl.grid, 256, 0, st>>>(in, div, out, ni, nj, nk, pl.cw, pl.row_blocks, pl.kc, alpha, beta, sl, rg);
+        else         jacobi_march2_kernel<4, false><<<pl.grid, 256, 0, st>>>(in, div, out, ni, nj, nk, pl.cw, pl.row_blocks, pl.kc, alpha, beta, sl, rg);
+        name = "jacobi_march2_kernel";
+        break;
+    case Kernel::kLds2seg:
+        jacobi_lds2seg_kernel<8><<<pl.grid, pl.block, 0, st>>>(in, div, out, ni, nj, nk, pl.row_blocks, pl.nblk, pl.kc, alpha, beta, sl, rg);
+        name = "jacobi_lds2seg_kernel";
+        break;
+    case Kernel::kLds:
+        if (mask) {
+            jacobi_lds_kernel<8, 1, 3, true><<<pl.grid, pl.block, 0, st>>>(in, div, out, ni, nj, nk, pl.row_blocks, pl.nblk, pl.kc, alpha, beta, sl, rg, *mask);
+            name = "jacobi_lds3_masked_kernel"; what = "jacobi_lds_kernel<masked>";
+            break;
+        }
+#define BQ_LDS(WV, RV, SV) jacobi_lds_kernel<WV, RV, SV><<<pl.grid, pl.block, 0, st>>>(in, div, out, ni, nj, nk, pl.row_blocks, pl.nblk, pl.kc, alpha, beta, sl, rg, SweepMask{})
+        if (pl.S == 4) {
+            if (pl.R == 2) BQ_LDS(4, 2, 4); else BQ_LDS(6, 1, 4);
+        } else if (pl.R == 2) {
+            if (pl.W == 4) BQ_LDS(4, 2, 3); else if (pl.W == 5) BQ_LDS(5, 2, 3); else BQ_LDS(6, 2, 3);
+        } else {
+            if (pl.W == 12) BQ_LDS(12, 1, 3); else BQ_LDS(8, 1, 3);
+        }
 #undef BQ_LDS
-    BQ_LAUNCH_CHECK("jacobi_lds_kernel");
-    g_last_pair_kernel = S == 4 ? "jacobi_lds_kernel<4 sweeps>" : "jacobi_lds3_kernel";
+        name = pl.S == 4 ? "jacobi_lds_kernel<4 sweeps>" : "jacobi_lds3_kernel"; what = "jacobi_lds_kernel";
+        break;
+    case Kernel::kLean3r:
+        if (pl.pf == 2) jacobi_lean3r_kernel<2><<<pl.grid, 256, 0, st>>>(in, div, out, ni, nj, nk, pl.cw, pl.row_blocks, pl.kc, alpha, beta, sl);
+        else            jacobi_lean3r_kernel<1><<<pl.grid, 256, 0, st>>>(in, div, out, ni, nj, nk, pl.cw, pl.row_blocks, pl.kc, alpha, beta, sl);
+        name = "jacobi_lean3r_kernel";
+        break;
+    default: return false;                          // (a one-sweep plan: jacobi_sweep's)
+    }
+    BQ_LAUNCH_CHECK(what ? what : name);
+    ps().last_pair_kernel = name;
     return true;
+}
+
+static inline geom::PlaneRanges whole_array(int nk) { return geom::PlaneRanges(0, 1 << 30, 0, 0, nk); }
+
+// Two, three (LDS kernels, else the lean triple) or four sweeps in one launch on the whole array; false = not applicable
+static bool jacobi_sweep_pair(const plan::JacobiTuning &tun, const float *in, const float *div, float *out, int ni, int nj, int nk, float alpha, float beta)
+{
+    const geom::PlaneRanges pr = whole_array(nk);
+    return launch_fused(plan::plan_pair(ni, nj, nk, aligned16(in, div, out), pr, tun, rt().num_cus), in, div, out, ni, nj, nk, alpha, beta, pr);
+}
+static bool jacobi_sweep_triple(const plan::JacobiTuning &tun, const float *in, const float *div, float *out, int ni, int nj, int nk, float alpha, float beta)
+{
+    return launch_fused(plan::plan_triple(ni, nj, nk, aligned16(in, div, out), tun, rt().num_cus), in, div, out, ni, nj, nk, alpha, beta, whole_array(nk));
+}
+static bool jacobi_sweep_quad(const plan::JacobiTuning &tun, const float *in, const float *div, float *out, int ni, int nj, int nk, float alpha, float beta)
+{
+    return launch_fused(plan::plan_quad(ni, nj, nk, aligned16(in, div, out), tun, rt().num_cus, rt().slab_on), in, div, out, ni, nj, nk, alpha, beta,
+                        whole_array(nk));
 }
 
 // Three MASKED sweeps in one launch (bq_obstacle.hip: gpu_jacobi_sweeps_masked); false = not applicable, nothing launched
-bool jacobi_sweep_triple_masked(const float *in, const float *div, float *out, int ni, int nj, int nk, float alpha,
+bool jacobi_sweep_triple_masked(const plan::JacobiTuning &tun, const float *in, const float *div, float *out, int ni, int nj, int nk, float alpha,
                                 const unsigned char *solid, const unsigned char *rows, const float betas[7])
 {
-    if (ni < 3 || nj < 4 || nk < 3 || rt().slab_on) return false;
     const SweepMask mk{solid, rows, betas[0], betas[1], betas[2], betas[3], betas[4], betas[5], betas[6]};
-    return jacobi_sweep_lds(in, div, out, ni, nj, nk, alpha, betas[0], 3, 0, 1 << 30, 0, 0, &mk);
-}
-
-// Four sweeps in one launch (jacobi_lds_kernel<.., 4>), whole unmasked arrays.  FL_OPT_JACOBI_ROWS = 6 forces it wherever the
-// kernel applies.  Auto (0): where the chunk rule gives at least 24 planes per chunk (six of a chunk's planes are warm-up; a forced
-// chunk length below that keeps the triples) and the process is not a z-slab rank (nothing measures those) -- 256^3: 49 quads + 1
-// triple for the projection's 199 sweeps instead of 66 triples + 1 single sweep (EXPERIMENTS section 10).  128^3 (chunks of 8),
-// rows of 260 .. 512 floats (two-segment kernel), masked sweeps and plane ranges never come here or are refused below.
-// FL_OPT_JACOBI_ROWS = 7: auto without this kernel, the launch sequence from before it became the default (A/B timing).
-static bool jacobi_sweep_quad(const float *in, const float *div, float *out, int ni, int nj, int nk, float alpha, float beta)
-{
-    const int rows = rt().opt_jacobi_rows;
-    if ((rows != 6 && rows != 0) || (rt().opt_jacobi_variant != 0 && rt().opt_jacobi_variant != 3)) return false;
-    if (rows == 6) return jacobi_sweep_lds(in, div, out, ni, nj, nk, alpha, beta, 4);
-    if (rt().slab_on) return false;
-    return jacobi_sweep_lds(in, div, out, ni, nj, nk, alpha, beta, 4, 0, 1 << 30, 0, 0, nullptr, 24);
-}
-
-// Three sweeps in one launch (in -> out holds iterate +3), whole array, rows of one wave; false = not applicable
-static bool jacobi_sweep_triple(const float *in, const float *div, float *out, int ni, int nj, int nk, float alpha, float beta)
-{
-    if (ni < 3 || nj < 4 || nk < 3) return false;
-    if ((rt().opt_jacobi_rows == 4 || rt().opt_jacobi_rows == 6 || rt().opt_jacobi_rows == 0 || rt().opt_jacobi_rows == 7) && (rt().opt_jacobi_variant == 0 || rt().opt_jacobi_variant == 3) &&
-        jacobi_sweep_lds(in, div, out, ni, nj, nk, alpha, beta, 3)) return true;
-    const int variant = rt().opt_jacobi_variant;
-    if ((variant != 0 && variant != 3) || rt().opt_jacobi_rows == 1 || rt().opt_jacobi_rows == 3) return false;
-    if (!((ni % 4 == 0) && ni >= 32 && ni <= 256 && aligned16(in, div, out))) return false;
-    const int cw = geom::pow2_lanes(ni, 4);
-    const int rows = 256 / cw;
-    const int nby2 = (nj + 2 * rows - 1) / (2 * rows);
-    const int target = 32;
-    int nchunks = geom::whole_round_chunks(nby2, nk, target, 256);
-    if (rt().num_cus != 256) nchunks = geom::chunks_for_cus(nk, nby2, target, 4, rt().num_cus, 1);
-    int kc = (nk + nchunks - 1) / nchunks;
-    if (rt().opt_jacobi_kchunk2 > 0) kc = rt().opt_jacobi_kchunk2;
-    if (kc < 16 && rt().opt_jacobi_rows != 2) return false;  // chunks too short to pay for four warm-up planes
-    if (kc < 4) kc = 4;
-    const int nbz = (nk + kc - 1) / kc;
-    // FL_OPT_JACOBI_KCHUNK = 1 / 2: how many planes ahead the loads run
-    if (rt().opt_jacobi_kchunk == 2) jacobi_lean3r_kernel<2><<<nby2 * nbz, 256, 0, rt().compute>>>(in, div, out, ni, nj, nk, cw, nby2, kc, alpha, beta, slab_of(nk));
-    else                             jacobi_lean3r_kernel<1><<<nby2 * nbz, 256, 0, rt().compute>>>(in, div, out, ni, nj, nk, cw, nby2, kc, alpha, beta, slab_of(nk));
-    BQ_LAUNCH_CHECK("jacobi_lean3r_kernel");
-    g_last_pair_kernel = "jacobi_lean3r_kernel";
-    return true;
+    return launch_fused(plan::plan_triple_masked(ni, nj, nk, aligned16(in, div, out), tun, rt().num_cus, rt().slab_on), in, div, out, ni, nj, nk,
+                        alpha, betas[0], whole_array(nk), &mk);
 }
 
 static const int kResidualBlocks = 1024;
@@ -1908,7 +1747,7 @@ void profile_end(ProfileSpan &sp, long long launches, long long sweeps)
 {
     if (!sp.a || !sp.b) return;
     BQ_HIP(hipEventRecord(sp.b, rt().compute));
-    g_spans.push_back(SweepSpan{sp.a, sp.b, launches, sweeps});
+    ps().spans.push_back(SweepSpan{sp.a, sp.b, launches, sweeps});
 }
 
 } // namespace bq
@@ -1938,35 +1777,32 @@ int gpu_jacobi_sweeps(float *p, const float *div, float *p_temp, int ni, int nj,
     if (!ensure_ready("gpu_jacobi_sweeps")) return 0;
     if (!dims_ok(ni, nj, nk, "gpu_jacobi_sweeps")) return 0;
     if (!p || !div || !p_temp || p == p_temp) { latch(FL_ERR_BAD_ARGUMENT, "gpu_jacobi_sweeps", "null or aliased buffers"); return 0; }
+    const plan::JacobiTuning tun = jacobi_tuning();
     float *in = p, *out = p_temp;
     int s = 0;
     long long launches = 0;
     ProfileSpan span;
     const bool prof = sweeps > 0 && profile_begin(span);      // FL_OPT_PROFILE_JACOBI (the z-slab projection runs through here)
-    // FL_OPT_JACOBI_FUSE == 2: the caller vouches that p and p_temp carry the same boundary layer
-    // (FL_OPT_JACOBI_FUSE: 2 = pairs and triples, 4 = pairs only)
-    // four sweeps per launch where jacobi_sweep_quad's rule admits them (FL_OPT_JACOBI_ROWS: 0 auto, 6 always, 7 never)
+    // FL_OPT_JACOBI_FUSE >= 2: the caller vouches that p and p_temp carry the same boundary layer, so sweeps may share a launch:
+    // four where plan_quad admits them, then three, then two (FL_OPT_JACOBI_FUSE = 4: two only), the rest one by one
+    using Launcher = bool (*)(const plan::JacobiTuning &, const float *, const float *, float *, int, int, int, float, float);
+    const bool all = tun.sweeps_fuse == plan::SweepsFuse::kAll;
+    const struct { int sweeps; bool on; Launcher launch; } stages[] = {
+        {4, all, jacobi_sweep_quad}, {3, all, jacobi_sweep_triple}, {2, tun.sweeps_fuse != plan::SweepsFuse::kNone, jacobi_sweep_pair}};
     // fl_jacobi_kernel_name: the fused kernel this call launched most often (more sweeps per launch first on a tie)
     const char *most_name = nullptr;
-    long long most = 0, n_here = 0;
-    auto counted = [&]() { if (++n_here > most) { most = n_here; most_name = g_last_pair_kernel; } };
-    while (rt().opt_jacobi_fuse >= 2 && rt().opt_jacobi_fuse != 4 && s + 4 <= sweeps && jacobi_sweep_quad(in, div, out, ni, nj, nk, alpha, beta)) {
-        s += 4; launches++; counted();             // iterate +4 sits in `out`: swap
-        float *t = in; in = out; out = t;
+    long long most = 0;
+    for (const auto &stage : stages) {
+        long long n_here = 0;
+        while (stage.on && s + stage.sweeps <= sweeps && stage.launch(tun, in, div, out, ni, nj, nk, alpha, beta)) {
+            float *t = in; in = out; out = t;          // the newest iterate sits in the former `out`
+            s += stage.sweeps; launches++;
+            if (++n_here > most) { most = n_here; most_name = ps().last_pair_kernel; }
+        }
     }
-    n_here = 0;
-    while (rt().opt_jacobi_fuse >= 2 && rt().opt_jacobi_fuse != 4 && s + 3 <= sweeps && jacobi_sweep_triple(in, div, out, ni, nj, nk, alpha, beta)) {
-        float *t = in; in = out; out = t;          // iterate +3 sits in the former `out`
-        s += 3; launches++; counted();
-    }
-    n_here = 0;
-    while (rt().opt_jacobi_fuse >= 2 && s + 2 <= sweeps && jacobi_sweep_pair(in, div, out, ni, nj, nk, alpha, beta)) {
-        float *t = in; in = out; out = t;          // iterate +2 sits in the former `out`
-        s += 2; launches++; counted();
-    }
-    if (most_name) g_last_pair_kernel = most_name;
+    if (most_name) ps().last_pair_kernel = most_name;
     for (; s < sweeps; s++) {
-        jacobi_sweep(in, div, out, ni, nj, nk, alpha, beta);
+        jacobi_sweep(tun, in, div, out, ni, nj, nk, alpha, beta);
         float *t = in; in = out; out = t;
         launches++;
     }
@@ -1981,7 +1817,7 @@ void gpu_jacobi_sweep_range(const float *in, const float *div, float *out, int n
     BQ_ENTER("gpu_jacobi_sweep_range", in, div, out)
     BQ_REQUIRE(in != out, "gpu_jacobi_sweep_range");
     if (k_begin >= k_end) return;
-    jacobi_sweep(in, div, out, ni, nj, nk, alpha, beta, k_begin, k_end);
+    jacobi_sweep(jacobi_tuning(), in, div, out, ni, nj, nk, alpha, beta, k_begin, k_end);
 }
 
 // Two sweeps in one launch, `out` written on the planes [k0a, k1a) and [k0b, k1b) only (either may be empty): the
@@ -1993,8 +1829,10 @@ int gpu_jacobi_sweep_pair_ranges(const float *in, const float *div, float *out, 
 {
     if (!ensure_ready("gpu_jacobi_sweep_pair_ranges") || !dims_ok(ni, nj, nk, "gpu_jacobi_sweep_pair_ranges")) return 0;
     if (!in || !div || !out || in == out) { latch(FL_ERR_BAD_ARGUMENT, "gpu_jacobi_sweep_pair_ranges", "null or aliased buffers"); return 0; }
-    if (rt().opt_jacobi_fuse == 0) return 0;
-    return jacobi_sweep_pair(in, div, out, ni, nj, nk, alpha, beta, k0a, k1a, k0b, k1b) ? 1 : 0;
+    const plan::JacobiTuning tun = jacobi_tuning();
+    if (!tun.pair_ranges) return 0;
+    const geom::PlaneRanges pr(k0a, k1a, k0b, k1b, nk);
+    return launch_fused(plan::plan_pair(ni, nj, nk, aligned16(in, div, out), pr, tun, rt().num_cus), in, div, out, ni, nj, nk, alpha, beta, pr) ? 1 : 0;
 }
 
 // Three sweeps in -> out on the output planes [k0a, k1a) and [k0b, k1b) (either may be empty) through the LDS-exchanged
@@ -2005,10 +1843,9 @@ int gpu_jacobi_sweep_triple_ranges(const float *in, const float *div, float *out
 {
     if (!ensure_ready("gpu_jacobi_sweep_triple_ranges") || !dims_ok(ni, nj, nk, "gpu_jacobi_sweep_triple_ranges")) return 0;
     if (!in || !div || !out || in == out) { latch(FL_ERR_BAD_ARGUMENT, "gpu_jacobi_sweep_triple_ranges", "null or aliased buffers"); return 0; }
-    if (rt().opt_jacobi_fuse == 0 || rt().opt_jacobi_fuse == 4 || rt().opt_jacobi_rows == 5) return 0;
-    if (rt().opt_jacobi_variant != 0 && rt().opt_jacobi_variant != 3) return 0;
-    if (ni < 3 || nj < 4 || nk < 3) return 0;
-    return jacobi_sweep_lds(in, div, out, ni, nj, nk, alpha, beta, 3, k0a, k1a, k0b, k1b) ? 1 : 0;
+    const geom::PlaneRanges pr(k0a, k1a, k0b, k1b, nk);
+    const plan::LaunchPlan pl = plan::plan_triple_ranges(ni, nj, nk, aligned16(in, div, out), pr, jacobi_tuning(), rt().num_cus);
+    return launch_fused(pl, in, div, out, ni, nj, nk, alpha, beta, pr) ? 1 : 0;
 }
 
 void gpu_gradient(float *u, float *v, float *w, const float *p, int ni, int nj, int nk, float halfrdx)
@@ -2102,8 +1939,9 @@ void gpu_projection_jacobi(float *u, float *v, float *w, float *div, float *p, f
     SweepSpan span{nullptr, nullptr, 0, (long long)(iter - 1)};
     if (prof && BQ_HIP(hipEventCreate(&span.a)) && BQ_HIP(hipEventCreate(&span.b))) BQ_HIP(hipEventRecord(span.a, st));
     long long launches = 0;
-    const bool may_fuse = iter > 2 && (rt().opt_jacobi_fuse >= 2 ||
-                                      (rt().opt_jacobi_fuse == 1 && !rt().slab_on && shells_match(p, p_temp, ni, nj, nk)));
+    const plan::JacobiTuning tun = jacobi_tuning();
+    const bool may_fuse = iter > 2 && (tun.trust == plan::Trust::kVouched ||
+                                      (tun.trust == plan::Trust::kChecked && !rt().slab_on && shells_match(p, p_temp, ni, nj, nk)));
     if (iter == 0) {
         // the reference's swap loop does not run: p_out is still p_temp, which is copied over p (:1876-1879) and used
         // by the gradient (:1883-1891)
@@ -2115,20 +1953,20 @@ void gpu_projection_jacobi(float *u, float *v, float *w, float *div, float *p, f
         // equal boundary shells (checked above): two sweeps may share a launch -- unless residual norms are wanted
         // for the iterate in between
         const bool pair_ok = may_fuse && it + 2 < iter && !(dbg && (it + 1) % stride == 0);
-        const bool triple_ok = pair_ok && it + 3 < iter && !(dbg && (it + 2) % stride == 0) && rt().opt_jacobi_fuse != 4;
-        if (triple_ok && jacobi_sweep_triple(in, div, out, ni, nj, nk, alpha, beta)) {
+        const bool triple_ok = pair_ok && it + 3 < iter && !(dbg && (it + 2) % stride == 0) && tun.beyond_pairs;
+        if (triple_ok && jacobi_sweep_triple(tun, in, div, out, ni, nj, nk, alpha, beta)) {
             it += 3;
-        } else if (pair_ok && jacobi_sweep_pair(in, div, out, ni, nj, nk, alpha, beta)) {
+        } else if (pair_ok && jacobi_sweep_pair(tun, in, div, out, ni, nj, nk, alpha, beta)) {
             it += 2;
         } else {
-            jacobi_sweep(in, div, out, ni, nj, nk, alpha, beta);
+            jacobi_sweep(tun, in, div, out, ni, nj, nk, alpha, beta);
             it += 1;
         }
         launches++;
         float *t = in; in = out; out = t;
     }
     span.launches = launches;
-    if (prof && span.a && span.b) { BQ_HIP(hipEventRecord(span.b, st)); g_spans.push_back(span); }
+    if (prof && span.a && span.b) { BQ_HIP(hipEventRecord(span.b, st)); ps().spans.push_back(span); }
     if (dbg && iter > 0 && (iter - 1) % stride == 0 && iter - 1 < 2000)
         residual_norms_async(div, in, ni, nj, nk, nullptr, nullptr, debugParam + iter - 1, debugParam + 2000 + iter - 1);
     if (in != p) fl_memcpy_d2d(p, in, (size_t)ni * nj * nk * sizeof(float));
@@ -2141,19 +1979,20 @@ void fl_jacobi_profile(double *total_ms, long long *launches, long long *sweeps)
 {
     double ms = 0.0;
     long long n = 0, sw = 0;
-    for (SweepSpan &sp : g_spans) {
+    std::vector<SweepSpan> &spans = ps().spans;
+    for (SweepSpan &sp : spans) {
         float t = 0.f;
         if (BQ_HIP(hipEventSynchronize(sp.b)) && BQ_HIP(hipEventElapsedTime(&t, sp.a, sp.b))) { ms += t; n += sp.launches; sw += sp.sweeps; }
         (void)hipEventDestroy(sp.a);
         (void)hipEventDestroy(sp.b);
     }
-    g_spans.clear();
+    spans.clear();
     if (total_ms) *total_ms = ms;
     if (launches) *launches = n;
     if (sweeps) *sweeps = sw;
 }
 
-const char *fl_jacobi_kernel_name(void) { return g_last_pair_kernel; }
+const char *fl_jacobi_kernel_name(void) { return ps().last_pair_kernel; }
 
 // GPU_kernel.cu:855-876
 void gpu_diffuse_field(float *field, float *fieldTemp0, float *filedTemp1, int ni, int nj, int nk, int iter, float coef)

@@ -292,22 +292,47 @@ enum {
     FL_OPT_SKIP_UNIT_BLEND = 2, /* gpu_advect_*_double with blend==1 (field*1 + 0*prev): 1 (default) = no launch, the
                                    values cannot change for finite prev; 2 = one-pass field+0 kernel (turns -0
                                    into +0 like the reference); 0 = the full two-level kernel               */
-    FL_OPT_JACOBI_VARIANT  = 3, /* 0 = auto, 1 = generic scalar kernel, 2 = LDS-tiled kernel      */
+    /* The five Jacobi tuning options below are decoded in one place, csrc/bq_jacobi_plan.h (JacobiTuning); one line per code,
+     * saying what it does to each reader.  "fused" = the kernels that run two to four sweeps per launch. */
+    FL_OPT_JACOBI_VARIANT  = 3, /* 0 (default): one sweep = jacobi_march_kernel on 16-byte aligned rows of 4 k >= 32 floats, else the generic kernel; fused kernels allowed
+                                 * 1: one sweep = jacobi_generic_kernel; no fused kernel; gpu_clamp_extrema_box*: the one-thread-per-cell kernel instead of the marching one
+                                 * 3: one sweep = jacobi_march_kernel (generic where float4 rows do not apply); fused kernels allowed, as with 0
+                                 * any other value (2): one sweep = jacobi_tile_kernel (generic where float4 rows do not apply); no fused kernel */
     FL_OPT_PROFILE_JACOBI  = 4, /* record a hipEvent pair around each projection's sweep loop      */
-    FL_OPT_JACOBI_KCHUNK   = 5, /* planes marched per block in the tiled kernel (0 = auto); for the fused kernels (which take
-                                   their chunk length from FL_OPT_JACOBI_KCHUNK2): 1 / 2 = loads run one / two planes ahead */
-    FL_OPT_JACOBI_ROWS     = 6, /* float4 rows per thread: tiled kernel 1, 2, 4; fused kernels 1, 2 (0 = auto); 4 = the three-sweep kernel
-                                   that exchanges the intermediate levels' neighbour rows through LDS wherever it applies (auto: whole
-                                   arrays with chunks of >= 24 planes), 5 = never that kernel (A/B timing), 6 = its four-sweep form
-                                   wherever it applies (auto: whole unmasked arrays with chunks of >= 24 planes, not on a z-slab rank --
-                                   256^3: 49 launches of four sweeps + 1 of three for 199 sweeps,
-                                   10.1 instead of 11.0 us per sweep inside whole steps, 11.40 instead of 11.56 ms per step), 7 = auto without the four-sweep form:
-                                   the launch sequence from before it became the default (A/B timing) */
+    FL_OPT_JACOBI_KCHUNK   = 5, /* 0 (default, negative values count as 0): every reader's own rule
+                                 * k > 0, every code below included: jacobi_march_kernel and jacobi_tile_kernel march chunks of k planes (24 is also a 24-plane chunk)
+                                 * 1 / 2: the loads of jacobi_lean2r_kernel, jacobi_lean3r_kernel and mg_lean2r_kernel (fp64) run one / two planes ahead
+                                 *        (auto: one while the arrays fit the Infinity Cache, else two; jacobi_lean3r_kernel: one)
+                                 * 14: mg_lds3_kernel (fp64) in blocks of 4 output rows (8 waves) instead of 8 (12 waves)
+                                 * 18 / 19: jacobi_lds_kernel, three sweeps, in blocks of 8 / 12 single rows (18 is the default); four sweeps: 18 = 6 single rows, 19 = default
+                                 * 24 / 25 / 26: jacobi_lds_kernel, three sweeps, in blocks of 4 / 5 / 6 row pairs; four sweeps: always 4 row pairs (the default)
+                                 * 19 / 24 / 25 / 26: gpu_jacobi_sweeps_masked launches no three-sweep kernel (it has the default shape only) */
+    FL_OPT_JACOBI_ROWS     = 6, /* 0 (default): every reader's own rule -- two-row pair kernel where it pays; triples through the LDS kernels, else jacobi_lean3r_kernel;
+                                 *    four sweeps per launch (jacobi_lds_kernel<.., 4>) on whole unmasked arrays with chunks of >= 24 planes, not on a z-slab
+                                 *    rank -- 256^3: 49 launches of four sweeps + 1 of three for 199 sweeps, 10.1 instead of 11.0 us per sweep inside whole
+                                 *    steps, 11.40 instead of 11.56 ms per step
+                                 * 1: tile kernel 1 row per thread; never the two-row pair kernel (jacobi_march2_kernel); no three- or four-sweep launch
+                                 * 2: tile kernel 2 rows per thread; always the two-row pair kernel; no LDS triple, no four-sweep launch; jacobi_lean3r_kernel also with chunks below 16 planes
+                                 * 3: jacobi_march2r_kernel instead of jacobi_lean2r_kernel; no three- or four-sweep launch; fp64: mg_smooth2_kernel instead of mg_lean2r_kernel (A/B timing)
+                                 * 4: tile kernel 4 rows per thread and jacobi_march_kernel 4 waves per block (both the default); LDS triple wherever it applies, no four-sweep launch
+                                 * 5: never the LDS triple (jacobi_lean3r_kernel instead), no four-sweep launch, gpu_jacobi_sweep_triple_ranges returns 0; fp64: never mg_lds3_kernel (A/B timing)
+                                 * 6: the four-sweep kernel wherever it applies (a z-slab rank and forced chunks below 24 planes included)
+                                 * 7: 0 without the four-sweep kernel: the launch sequence from before it became the default (A/B timing)
+                                 * 8 / 16: jacobi_march_kernel 8 / 16 waves per block; fused kernels: as any other value, below; 8 on fp64: mg_smooth2_kernel, in blocks of 512 threads
+                                 * the masked triple ignores this option; gpu_jacobi_sweep_triple_ranges honours 5 only; any other value: as 0 without the LDS triple and the four-sweep kernel */
     FL_OPT_STRUCTURED_MAPS = 7, /* 9-point kernels: compile-time taps when h is a power of two (1)  */
-    FL_OPT_JACOBI_FUSE     = 8, /* two or three sweeps per launch (4: at most two): 0 never, 1 in gpu_projection_jacobi after it has checked that p and
-                                   p_temp carry the same boundary shell (default), 2 there without the check and also in
-                                   gpu_jacobi_sweeps (caller vouches for equal boundary shells) */
-    FL_OPT_JACOBI_KCHUNK2  = 9, /* planes marched per block in the fused kernel (0 = auto)           */
+    FL_OPT_JACOBI_FUSE     = 8, /* 0: one sweep per launch everywhere; gpu_jacobi_sweep_pair_ranges / _triple_ranges return 0; fp64: one sweep per launch
+                                 * 1 (default): gpu_projection_jacobi fuses after it has checked that p and p_temp carry the same boundary shell (never on a z-slab rank);
+                                 *    gpu_jacobi_sweeps and gpu_jacobi_sweeps_masked do not fuse; the *_ranges entry points launch; fp64: fused smoothers from 2^20 cells
+                                 *    (mg_smooth2_kernel from 2^21)
+                                 * 2 and above (but 4): gpu_projection_jacobi fuses without the check, gpu_jacobi_sweeps and gpu_jacobi_sweeps_masked fuse too (the caller
+                                 *    vouches for equal boundary shells); fp64: fused smoothers at every size
+                                 * 4: as 2 with at most two sweeps per launch; gpu_jacobi_sweep_triple_ranges returns 0
+                                 * negative: as 0, except that the *_ranges entry points launch */
+    FL_OPT_JACOBI_KCHUNK2  = 9, /* 0 (default, negative values count as 0): every fused kernel's own chunk rule
+                                 * k > 0: planes marched per block of every fused kernel, fp64 smoothers included (pair kernels at least 2, jacobi_lean3r_kernel and
+                                 *    mg_lean2r_kernel at least 4, the fused mgcg passes at least 4); the LDS kernels then take whole arrays from 8 planes per chunk
+                                 *    instead of 24, and the four-sweep auto rule still wants 24 */
     FL_OPT_MGCG_GRAPH      = 10,/* 1 (default): the multigrid V-cycle is captured into a hipGraph once and
                                  * replayed in every outer iteration; 0: plain launches                */
     FL_OPT_FUSED_HOUSEKEEPING = 12, /* bit mask, default 0 (the reference's operator semantics).  Lets a caller drop the clears

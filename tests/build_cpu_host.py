@@ -5,6 +5,7 @@ GPU tests as references.  Test infrastructure.
   build_obstacles()  ..._obstacles.so: + the obstacle operators (tests/cpu_abi/obstacle_abi.c)
   build_levelsets()  ..._levelsets.so: + the level-set operators (tests/cpu_abi/levelset_abi.c)
   build_launch_geom() tests/_build/liblaunch_geom.so: csrc/bq_launch_geom.h behind tests/cpu_abi/launch_geom_shim.cpp
+  build_jacobi_plan() tests/_build/libjacobi_plan.so: csrc/bq_jacobi_plan.h behind tests/cpu_abi/jacobi_plan_shim.cpp
 A stand-in without some operators leaves the host solver's weak references to them null: set_boundary refuses there."""
 import glob
 import os
@@ -57,11 +58,11 @@ def build_levelsets():
     return _build(os.path.join(OUT, "libbimocq_host_cpu_levelsets.so"), ["obstacle_abi.c", "levelset_abi.c"])
 
 
-def build_launch_geom():
-    """the launchers' integer geometry rules (a host-only header of the product) as a C library for ctypes"""
+def _build_header_shim(so_name, shim, headers):
+    """a host-only header of the product behind its C shim (tests/cpu_abi) as a library for ctypes"""
     os.makedirs(OUT, exist_ok=True)
-    so = os.path.join(OUT, "liblaunch_geom.so")
-    deps = [os.path.join(ABI, "launch_geom_shim.cpp"), os.path.join(CSRC, "bq_launch_geom.h")]
+    so = os.path.join(OUT, so_name)
+    deps = [os.path.join(ABI, shim)] + [os.path.join(CSRC, h) for h in headers]
     if os.path.exists(so) and all(os.path.getmtime(d) <= os.path.getmtime(so) for d in deps):
         return so
     flags = ["-O1", *SAN_FLAGS] if SANITIZE else ["-O2"]
@@ -69,5 +70,15 @@ def build_launch_geom():
     return so
 
 
+def build_launch_geom():
+    """the launchers' integer geometry rules"""
+    return _build_header_shim("liblaunch_geom.so", "launch_geom_shim.cpp", ["bq_launch_geom.h"])
+
+
+def build_jacobi_plan():
+    """the decoder of the Jacobi tuning options and the planners of the sweep launches"""
+    return _build_header_shim("libjacobi_plan.so", "jacobi_plan_shim.cpp", ["bq_jacobi_plan.h", "bq_launch_geom.h"])
+
+
 if __name__ == "__main__":
-    print(build(), build_obstacles(), build_levelsets(), build_launch_geom())
+    print(build(), build_obstacles(), build_levelsets(), build_launch_geom(), build_jacobi_plan())

@@ -2,14 +2,15 @@
 """The kernel launches of the stencil launchers over a table of shapes and option settings, for comparing two builds of the
 library launch by launch (a refactor of the launchers must leave the list unchanged).
 
-    rocprofv3 --kernel-trace --output-format csv -d <dir> -- python tools/launch_sequence.py run [--log calls.txt]
+    rocprofv3 --kernel-trace --output-format csv -d <dir> -- python tools/launch_sequence.py run [--log calls.txt] [--extended]
     python tools/launch_sequence.py reduce <dir> > launches.txt
 
 `run` calls each launcher once per case through the C-ABI of the tree this file sits in (zeroed buffers: no launcher reads a
 value back, so the sequence does not depend on the data) and writes what every call returned and which fused kernel it
 reports to --log.  `reduce` turns the kernel trace into the ordered list of launches -- kernel name with its template
 arguments, grid size, workgroup size -- written as a table of the distinct launches and the sequence of their numbers.
-Two builds agree when both files are equal line for line.
+Two builds agree when both files are equal line for line.  --extended adds the shape and the option combinations of EXTENDED below
+to the table (the lists without it are those of profiles/launch_geom_launches_*.txt, with it of profiles/jacobi_plan_launches_*.txt).
 """
 import argparse
 import csv
@@ -28,6 +29,14 @@ FP32_SETTINGS = ([[(ROWS, r)] for r in range(1, 8)] + [[(VARIANT, v)] for v in (
                  [[(KCHUNK, k)] for k in (1, 2, 18, 19, 24, 25, 26)] + [[(KCHUNK2, 8)], [(RESERVE_CUS, 8)]])
 FP64_SETTINGS = [[], [(FUSE, 0)], [(FUSE, 2)], [(FUSE, 2), (ROWS, 3)], [(ROWS, 5)], [(FUSE, 2), (ROWS, 8)], [(KCHUNK, 14)],
                  [(KCHUNK, 1)], [(KCHUNK, 2)], [(KCHUNK2, 8)], [(RESERVE_CUS, 8)]]
+# --extended: what the tests and tools set and the table above lacks -- a shape on which only jacobi_lean3r_kernel takes the triples, the
+# marching one-sweep kernel and both one-sweep kernels' readings of ROWS, the LDS block shapes and the four-sweep kernel under a forced
+# chunk length, ROWS = 8 on fp32, and FUSE = 4 (last: resetting it leaves FL_OPT_JACOBI_FUSE at its default of 1)
+EXTENDED_SHAPES = [(256, 256, 128)]
+EXTENDED_SETTINGS = ([[(VARIANT, 3)]] + [[(VARIANT, 2), (ROWS, r)] for r in (1, 2, 4)] + [[(VARIANT, 3), (ROWS, r)] for r in (8, 16)] +
+                     [[(ROWS, 4), (KCHUNK, k), (KCHUNK2, 8)] for k in (24, 26, 18, 19)] +
+                     [[(ROWS, 6), (KCHUNK, k), (KCHUNK2, 8)] for k in (18, 24)] + [[(ROWS, 8)]] +
+                     [[(FUSE, 4), (ROWS, 2), (KCHUNK, k)] for k in (1, 2)])
 
 
 class Level(C.Structure):
@@ -35,7 +44,11 @@ class Level(C.Structure):
                 ("beta", C.c_double), ("b", C.c_void_p), ("x", C.c_void_p), ("r", C.c_void_p)]
 
 
-def run(log_path):
+def run(log_path, extended=False):
+    if extended:
+        FP32_SHAPES.extend(EXTENDED_SHAPES)
+        FP64_SHAPES.extend(EXTENDED_SHAPES)
+        FP32_SETTINGS.extend(EXTENDED_SETTINGS)
     sys.path.insert(0, ROOT)
     import gpufluidsimulation_amd as bq
     lib = bq.hip_lib()
@@ -215,8 +228,9 @@ if __name__ == "__main__":
     ap.add_argument("mode", choices=["run", "reduce"])
     ap.add_argument("trace_dir", nargs="?")
     ap.add_argument("--log", default="")
+    ap.add_argument("--extended", action="store_true")
     args = ap.parse_args()
     if args.mode == "run":
-        run(args.log)
+        run(args.log, args.extended)
     else:
         reduce(args.trace_dir)
