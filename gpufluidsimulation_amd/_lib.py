@@ -83,6 +83,10 @@ HIP_SIGS = {
     "fl_map_guard_reset": (None, [c_i]),
     "fl_map_guard_read": (None, [C.POINTER(c_i)]),
     "fl_nonfinite_seen": (c_i, [c_i]),
+    "gpu_solve_forward_hint": (None, [VP] * 6 + _G + [c_f, c_f, C.c_uint]),
+    "gpu_solve_backwardDMC_hint": (None, [VP] * 9 + _G + [c_f, C.c_uint]),
+    "fl_map_kernel_name": (C.c_char_p, [c_i]),
+    "fl_map_kernels_seen": (c_i, [c_i]),
     "gpu_max_abs3": (c_f, [VP, VP, VP, c_i, c_i, c_i]),
     "gpu_divergence": (None, [VP] * 4 + [c_i, c_i, c_i, c_f]),
     "gpu_jacobi_sweeps": (c_i, [VP, VP, VP, c_i, c_i, c_i, c_i, c_f, c_f]),
@@ -162,6 +166,7 @@ FL_OPT_JACOBI_FUSE, FL_OPT_JACOBI_KCHUNK2, FL_OPT_MGCG_GRAPH, FL_OPT_FAST_LERP =
 FL_OPT_FUSED_HOUSEKEEPING = 12
 FL_OPT_MAP_QUARTER_FP32 = 13
 FL_OPT_MGCG_TILE = 14
+FL_MAP_HINT_FINITE, FL_MAP_HINT_IDENTITY = 1, 2
 FL_OPT_PROFILE_COMM = 15
 FL_OPT_RESERVE_CUS = 16
 FL_OPT_MGCG_BOTTOM = 17

@@ -82,17 +82,24 @@ __device__ __forceinline__ void guard_map_values(int *guard, f3 r, float h)
         atomicOr(guard, 1);
 }
 
-template <bool P2>
+// IDSTART (power-of-two spacing, one GPU, finite velocity): the caller vouches that the map still holds what gpu_init_maps
+// wrote -- node (i, j, k) holds ((float)i h, (float)j h, (float)k h), the node's own position.  The start of the trace is
+// computed by that very expression instead of loaded, and the first velocity look-up of the first RK3 sub-step is the
+// node look-up (bq_device.hip.h: node_velocity, trace).
+template <bool P2, bool IDSTART = false>
 __global__ __launch_bounds__(256) void forward_kernel(const float *u, const float *v, const float *w,
                                                       float *xf, float *yf, float *zf,
                                                       Spacing sp, Grid g, float cfldt, float dt, int *guard)
 {
+    static_assert(P2 || !IDSTART, "the node look-up exists for power-of-two spacing only");
     BQ_IJK(g.ni, g.nj, g.nk)
     if (!(i > 1 && i < g.ni - 2 && j > 1 && j < g.nj - 2 && kg > 1 && kg < g.nkg - 2)) return;
     Vel3 vel{make_field(u, g.ni + 1, g.nj, g.nk, g.koff), make_field(v, g.ni, g.nj + 1, g.nk, g.koff), make_field(w, g.ni, g.nj, g.nk + 1, g.koff)};
     f3 hi = mk3((float)g.ni * sp.h - sp.h, (float)g.nj * sp.h - sp.h, (float)g.nkg * sp.h - sp.h);
     size_t id = (size_t)i + (size_t)g.ni * j + (size_t)g.ni * g.nj * k;
-    f3 q = trace<P2>(vel, sp, hi, cfldt, dt, mk3(xf[id], yf[id], zf[id]));
+    f3 q;
+    if constexpr (IDSTART) q = trace<P2, true>(vel, sp, hi, cfldt, dt, mk3((float)i * sp.h, (float)j * sp.h, (float)kg * sp.h), i, j, k);
+    else q = trace<P2>(vel, sp, hi, cfldt, dt, mk3(xf[id], yf[id], zf[id]));
     xf[id] = q.x; yf[id] = q.y; zf[id] = q.z;
     guard_map_values(guard, q, sp.h);
 }
@@ -104,12 +111,21 @@ __device__ __forceinline__ float dmc_axis(float p, float vel, float a, float s)
     return p - vel * s;
 }
 
-template <bool P2>
+// NODE (power-of-two spacing, finite velocity): pt is the grid node (i, j, kg) and tp = pt -+ h, exact in fp32, is its
+// upwind neighbour node, so both velocity look-ups are node look-ups (bq_device.hip.h: node_velocity) -- 12 loads and 6
+// lerps instead of 48 and 42.  They equal get_velocity's samples in value; the sign of a zero sample cannot reach an output:
+// `vl.x > 0` is false for both zeros, vl - tv with one operand +-0 is the other operand or +-0, and dmc_axis returns
+// p - (+-0) = p in both of its branches because p = h i with i >= 2 is strictly positive.
+// IDIN (with NODE, one GPU): the caller vouches that the input map still holds what gpu_init_maps wrote; the map look-up
+// at the departure point computes its corners (map_at_identity), falling back to the buffers wave by wave.
+template <bool P2, bool NODE = false, bool IDIN = false>
 __global__ __launch_bounds__(256) void dmc_kernel(const float *u, const float *v, const float *w,
                                                   const float *xi, const float *yi, const float *zi,
                                                   float *xo, float *yo, float *zo,
                                                   Spacing sp, Grid g, float substep, int border, int *guard)
 {
+    static_assert(P2 || !NODE, "the node look-up exists for power-of-two spacing only");
+    static_assert(NODE || !IDIN, "the identity input comes with the node look-ups");
     BQ_IJK(g.ni, g.nj, g.nk)
     if (!(i > 1 && i < g.ni - 2 && j > 1 && j < g.nj - 2 && kg > 1 && kg < g.nkg - 2)) {
         // border nodes are not updated (GPU_kernel.cu:175).  FL_OPT_FUSED_HOUSEKEEPING bits 4 / 8: the kernel itself
@@ -130,14 +146,20 @@ __global__ __launch_bounds__(256) void dmc_kernel(const float *u, const float *v
     // the node (indices >= 2 inside the window) and its upwind neighbour are at least h away from the origin on every
     // axis: q >= 1 for both velocity look-ups (sample's GE1 form); the DMC departure point below is not bounded
     f3 pt = mk3(h * (float)i, h * (float)j, h * (float)kg);
-    f3 vl = get_velocity<P2, true>(vel, sp, pt);
+    f3 vl;
+    if constexpr (NODE) vl = node_velocity(vel, i, j, k);
+    else vl = get_velocity<P2, true>(vel, sp, pt);
     f3 tp = mk3((vl.x > 0) ? pt.x - h : pt.x + h, (vl.y > 0) ? pt.y - h : pt.y + h, (vl.z > 0) ? pt.z - h : pt.z + h);
-    f3 tv = get_velocity<P2, true>(vel, sp, tp);
+    f3 tv;
+    if constexpr (NODE) tv = node_velocity(vel, (vl.x > 0) ? i - 1 : i + 1, (vl.y > 0) ? j - 1 : j + 1, (vl.z > 0) ? k - 1 : k + 1);
+    else tv = get_velocity<P2, true>(vel, sp, tp);
     float ax = (vl.x - tv.x) / (pt.x - tp.x);
     float ay = (vl.y - tv.y) / (pt.y - tp.y);
     float az = (vl.z - tv.z) / (pt.z - tp.z);
     f3 pn = mk3(dmc_axis(pt.x, vl.x, ax, substep), dmc_axis(pt.y, vl.y, ay, substep), dmc_axis(pt.z, vl.z, az, substep));
-    f3 r = map_at<P2>(in, sp, pn);
+    f3 r;
+    if constexpr (IDIN) r = map_at_identity<P2>(in, sp, pn, g.ni, g.nj, g.nk);
+    else r = map_at<P2>(in, sp, pn);
     size_t id = (size_t)i + (size_t)g.ni * j + (size_t)g.ni * g.nj * k;
     xo[id] = r.x; yo[id] = r.y; zo[id] = r.z;
     guard_map_values(guard, r, sp.h);
@@ -1067,32 +1089,89 @@ using namespace bq;
             if (!p_) { latch(FL_ERR_BAD_ARGUMENT, op, "null device pointer"); return; } \
     }
 
+// ---- the two map updates; hints: FL_MAP_HINT_* promises of the caller (include/bimocq_gpu.h) ------------------------------------
+// A promise is used only where the closed forms hold: power-of-two spacing, the whole buffer in one launch (no plane
+// window), one GPU (no slab context).  Everything else runs the plain instance, whatever the caller promised.
+static inline bool hints_usable(const Spacing &sp) { return sp.pow2 && !rt().win_on && !rt().slab_on; }
+static inline void note_map_kernel(int which, const char *name, int bit)
+{
+    rt().map_kernel_name[which] = name;
+    rt().map_kernels_seen |= bit;
+}
+
+static void solve_forward(const char *op, float *u, float *v, float *w, float *x_fwd, float *y_fwd, float *z_fwd,
+                          float h, int ni, int nj, int nk, float cfldt, float dt, unsigned hints)
+{
+    BQ_ENTER(op, u, v, w, x_fwd, y_fwd, z_fwd)
+    BQ_REQUIRE(cfldt > 0.f || dt == 0.f, op);     // cfldt <= 0 would never terminate
+    int planes;
+    Spacing sp = make_spacing(h); Grid g = mk_grid_win(ni, nj, nk, 0, &planes);
+    if (planes <= 0) return;
+    int *guard = rt().map_guard_on ? rt().map_guard + 1 : nullptr;
+    const unsigned both = FL_MAP_HINT_FINITE | FL_MAP_HINT_IDENTITY;
+    if (hints_usable(sp) && (hints & both) == both) {
+        forward_kernel<true, true><<<grid_for(ni, nj, planes), kBlock, 0, rt().compute>>>(u, v, w, x_fwd, y_fwd, z_fwd, sp, g, cfldt, dt, guard);
+        BQ_LAUNCH_CHECK("forward_kernel");
+        note_map_kernel(1, "forward_identity_kernel", 16);
+        return;
+    }
+    BQ_DISPATCH1(forward_kernel, sp.pow2, grid_for(ni, nj, planes), u, v, w, x_fwd, y_fwd, z_fwd, sp, g, cfldt, dt, guard);
+    note_map_kernel(1, "forward_kernel", 8);
+}
+
+static void solve_backward_dmc(const char *op, float *u, float *v, float *w, float *x_in, float *y_in, float *z_in,
+                               float *x_out, float *y_out, float *z_out,
+                               float h, int ni, int nj, int nk, float substep, unsigned hints)
+{
+    BQ_ENTER(op, u, v, w, x_in, y_in, z_in, x_out, y_out, z_out)
+    BQ_REQUIRE(x_in != x_out && y_in != y_out && z_in != z_out, op);
+    int planes;
+    Spacing sp = make_spacing(h); Grid g = mk_grid_win(ni, nj, nk, 0, &planes);
+    if (planes <= 0) return;
+    const int border = (rt().opt_fused_housekeeping & 8) ? 2 : (rt().opt_fused_housekeeping & 4) ? 1 : 0;
+    int *guard = rt().map_guard_on ? rt().map_guard : nullptr;
+    if (hints_usable(sp) && (hints & FL_MAP_HINT_FINITE)) {
+        const dim3 grid = grid_for(ni, nj, planes);
+        hipStream_t st = rt().compute;
+        if (hints & FL_MAP_HINT_IDENTITY)
+            dmc_kernel<true, true, true><<<grid, kBlock, 0, st>>>(u, v, w, x_in, y_in, z_in, x_out, y_out, z_out, sp, g, substep, border, guard);
+        else
+            dmc_kernel<true, true, false><<<grid, kBlock, 0, st>>>(u, v, w, x_in, y_in, z_in, x_out, y_out, z_out, sp, g, substep, border, guard);
+        BQ_LAUNCH_CHECK("dmc_kernel");
+        if (hints & FL_MAP_HINT_IDENTITY) note_map_kernel(0, "dmc_node_identity_kernel", 4);
+        else note_map_kernel(0, "dmc_node_kernel", 2);
+        return;
+    }
+    BQ_DISPATCH1(dmc_kernel, sp.pow2, grid_for(ni, nj, planes), u, v, w, x_in, y_in, z_in, x_out, y_out, z_out, sp, g, substep, border, guard);
+    note_map_kernel(0, "dmc_kernel", 1);
+}
+
 extern "C" {
 
 BQ_ENTRY(gpu_solve_forward, (float *u, float *v, float *w, float *x_fwd, float *y_fwd, float *z_fwd,
                        float h, int ni, int nj, int nk, float cfldt, float dt), (u, v, w, x_fwd, y_fwd, z_fwd, h, ni, nj, nk, cfldt, dt))
 {
-    BQ_ENTER("gpu_solve_forward", u, v, w, x_fwd, y_fwd, z_fwd)
-    BQ_REQUIRE(cfldt > 0.f || dt == 0.f, "gpu_solve_forward");     // cfldt <= 0 would never terminate
-    int planes;
-    Spacing sp = make_spacing(h); Grid g = mk_grid_win(ni, nj, nk, 0, &planes);
-    if (planes <= 0) return;
-    int *guard = rt().map_guard_on ? rt().map_guard + 1 : nullptr;
-    BQ_DISPATCH1(forward_kernel, sp.pow2, grid_for(ni, nj, planes), u, v, w, x_fwd, y_fwd, z_fwd, sp, g, cfldt, dt, guard);
+    solve_forward("gpu_solve_forward", u, v, w, x_fwd, y_fwd, z_fwd, h, ni, nj, nk, cfldt, dt, 0u);
+}
+
+BQ_ENTRY(gpu_solve_forward_hint, (float *u, float *v, float *w, float *x_fwd, float *y_fwd, float *z_fwd,
+                       float h, int ni, int nj, int nk, float cfldt, float dt, unsigned hints), (u, v, w, x_fwd, y_fwd, z_fwd, h, ni, nj, nk, cfldt, dt, hints))
+{
+    solve_forward("gpu_solve_forward_hint", u, v, w, x_fwd, y_fwd, z_fwd, h, ni, nj, nk, cfldt, dt, hints);
 }
 
 BQ_ENTRY(gpu_solve_backwardDMC, (float *u, float *v, float *w, float *x_in, float *y_in, float *z_in,
                            float *x_out, float *y_out, float *z_out,
                            float h, int ni, int nj, int nk, float substep), (u, v, w, x_in, y_in, z_in, x_out, y_out, z_out, h, ni, nj, nk, substep))
 {
-    BQ_ENTER("gpu_solve_backwardDMC", u, v, w, x_in, y_in, z_in, x_out, y_out, z_out)
-    BQ_REQUIRE(x_in != x_out && y_in != y_out && z_in != z_out, "gpu_solve_backwardDMC");
-    int planes;
-    Spacing sp = make_spacing(h); Grid g = mk_grid_win(ni, nj, nk, 0, &planes);
-    if (planes <= 0) return;
-    const int border = (rt().opt_fused_housekeeping & 8) ? 2 : (rt().opt_fused_housekeeping & 4) ? 1 : 0;
-    int *guard = rt().map_guard_on ? rt().map_guard : nullptr;
-    BQ_DISPATCH1(dmc_kernel, sp.pow2, grid_for(ni, nj, planes), u, v, w, x_in, y_in, z_in, x_out, y_out, z_out, sp, g, substep, border, guard);
+    solve_backward_dmc("gpu_solve_backwardDMC", u, v, w, x_in, y_in, z_in, x_out, y_out, z_out, h, ni, nj, nk, substep, 0u);
+}
+
+BQ_ENTRY(gpu_solve_backwardDMC_hint, (float *u, float *v, float *w, float *x_in, float *y_in, float *z_in,
+                           float *x_out, float *y_out, float *z_out,
+                           float h, int ni, int nj, int nk, float substep, unsigned hints), (u, v, w, x_in, y_in, z_in, x_out, y_out, z_out, h, ni, nj, nk, substep, hints))
+{
+    solve_backward_dmc("gpu_solve_backwardDMC_hint", u, v, w, x_in, y_in, z_in, x_out, y_out, z_out, h, ni, nj, nk, substep, hints);
 }
 
 BQ_ENTRY(gpu_advect_velocity, (float *u, float *v, float *w, float *u_init, float *v_init, float *w_init,
@@ -1466,6 +1545,17 @@ void fl_map_guard_read(int ok[2])
         bad[0] = hf[0] != 0.f; bad[1] = hf[1] != 0.f;
     }
     ok[0] = !bad[0]; ok[1] = !bad[1];
+}
+
+// which map-update instance ran last (which: 0 the DMC sub-step, 1 the forward update), "" before the first; and which
+// have run since the last reset, as bits: 1 dmc_kernel, 2 dmc_node_kernel, 4 dmc_node_identity_kernel, 8 forward_kernel,
+// 16 forward_identity_kernel
+const char *fl_map_kernel_name(int which) { return (which == 0 || which == 1) ? rt().map_kernel_name[which] : ""; }
+int fl_map_kernels_seen(int reset)
+{
+    const int v = rt().map_kernels_seen;
+    if (reset) rt().map_kernels_seen = 0;
+    return v;
 }
 
 // 1 when every value of the three map arrays is 0 or lies in [h/256, 1024 h] (tile_value_ok): the precondition of

@@ -536,6 +536,63 @@ __device__ __forceinline__ f3 get_velocity(const Vel3 &vel, const Spacing &sp, f
                sample<P2, GE1>(vel.w, sp, mk3(0.f, 0.f, mh), pos));
 }
 
+// ---- the same look-up AT A GRID NODE, power-of-two spacing, finite velocity ---------------------------------------------------
+// At pos = (h i, h j, h k) with h = 2^-m, locate() returns compile-time cells and weights: cell (i, j, k) for all three
+// components (q = i + 1/2 along the component's own axis, an integer along the other two), weights (1/2, 0, 0) for u,
+// (0, 1/2, 0) for v, (0, 0, 1/2) for w.  Six of gather()'s seven lerps then have weight 0 and one has weight 1/2:
+//   * a weight-0 lerp is 1*a + 0*b, which is `a` in value for a finite b (only the sign of a zero can differ);
+//   * the weight-1/2 lerp is lerp_q's case c = 1/2: fmaf(0.5f, a, 0.5f * b) is bit-identical to the contract's
+//     (float)(0.5 * (double)a + (double)(0.5f * b)) (proof at lerp_q).
+// So for FINITE corner values the whole chain equals lerp_q(a, b, 0.5f) of the two values adjacent along the component's
+// own axis -- 2 loads and 2 instructions per component instead of 8 loads and ~30 -- in value; the sign of a zero
+// result may differ (checked on 2e8 random 8-tuples with denormals, every exponent and both zeros: 0 value mismatches).
+// A discarded corner that is an Inf or a NaN makes the contract's result NaN, hence "finite": the caller vouches for it.
+// Written with lerp_q, the BQ_FAST_LERP twin evaluates fmaf(0.5f, b - a, a), the first lerp of ITS chain; its weight-0
+// lerps fmaf(0, b - a, a) additionally want b - a finite, i.e. values below 2^126 in magnitude.
+// (i, j, kl): node indices in the buffers' LOCAL index space, all >= 0 and inside the cell grid.
+__device__ __forceinline__ f3 node_velocity(const Vel3 &vel, int i, int j, int kl)
+{
+    const unsigned bu = (unsigned)(i + vel.u.nx * (j + vel.u.ny * kl)) * 4u;
+    const unsigned bv = (unsigned)(i + vel.v.nx * (j + vel.v.ny * kl)) * 4u;
+    const unsigned bw = (unsigned)(i + vel.w.nx * (j + vel.w.ny * kl)) * 4u;
+    const unsigned sj = (unsigned)vel.v.nx * 4u, sk = (unsigned)vel.w.nx * (unsigned)vel.w.ny * 4u;
+    return mk3(lerp_q(ldf(vel.u, bu), ldf(vel.u, bu + 4u), 0.5f),
+               lerp_q(ldf(vel.v, bv), ldf(vel.v, bv + sj), 0.5f),
+               lerp_q(ldf(vel.w, bw), ldf(vel.w, bw + sk), 0.5f));
+}
+
+// ---- map_at() on the IDENTITY map (what gpu_init_maps stores: node (a, b, c) holds ((float)a h, (float)b h, (float)c h)) ---
+// Cell and weights come from the same locate() arithmetic; the corner values are computed instead of loaded.  Corners that
+// hold equal values make several of gather()'s lerps the same operation on the same operands -- each is evaluated once:
+//   x map: the four x-lerps coincide, then the two y-lerps                          -> 3 lerps
+//   y map: x-lerps of rows j and j + 1 (two distinct), one y-lerp, then equal z operands -> 4 lerps
+//   z map: x- and y-lerps of planes k and k + 1 (two each), one z-lerp                -> 5 lerps
+// 12 lerps and no loads instead of 21 lerps and 24 loads.  (lerp(a, a, c) is NOT a in the contract's double-rounded form,
+// so those lerps stay.)  This holds only where all eight corners are real nodes of the grid: 0 <= cell <= n - 2 on every
+// axis.  A DMC departure point is unbounded (cells out of range, negative bases, row wraps near the walls), so one vote
+// per wave decides: a wave with any lane outside -- or with a NaN position -- runs map_at on the real buffers.
+// Single GPU only (the node values along z are global indices times h; m.x.koff must be 0).
+template <bool P2>
+__device__ __forceinline__ f3 map_at_identity(const Map3 &m, const Spacing &sp, f3 pos, int ni, int nj, int nk)
+{
+    const float qx = div_h<P2>(pos.x - 0.f, sp), qy = div_h<P2>(pos.y - 0.f, sp), qz = div_h<P2>(pos.z - 0.f, sp);
+    const bool inside = qx >= 0.f && qx < (float)(ni - 1) && qy >= 0.f && qy < (float)(nj - 1) && qz >= 0.f && qz < (float)(nk - 1);
+    if (!__all(inside)) return map_at<P2>(m, sp, pos);
+    const int i = floor_to_int(qx), j = floor_to_int(qy), k = floor_to_int(qz);
+    const float fx = qx - (float)i, fy = qy - (float)j, fz = qz - (float)k;
+    const double ox = 1.0 - (double)fx, oy = 1.0 - (double)fy, oz = 1.0 - (double)fz;
+    const float x0 = (float)i * sp.h, x1 = (float)(i + 1) * sp.h;
+    const float y0 = (float)j * sp.h, y1 = (float)(j + 1) * sp.h;
+    const float z0 = (float)k * sp.h, z1 = (float)(k + 1) * sp.h;
+    const float xl = lerp_w(x0, x1, fx, ox);
+    const float xm = lerp_w(xl, xl, fy, oy);
+    const float yl0 = lerp_w(y0, y0, fx, ox), yl1 = lerp_w(y1, y1, fx, ox);
+    const float ym = lerp_w(yl0, yl1, fy, oy);
+    const float zl0 = lerp_w(z0, z0, fx, ox), zl1 = lerp_w(z1, z1, fx, ox);
+    const float zm0 = lerp_w(zl0, zl0, fy, oy), zm1 = lerp_w(zl1, zl1, fy, oy);
+    return mk3(lerp_w(xm, xm, fz, oz), lerp_w(ym, ym, fz, oz), lerp_w(zm0, zm1, fz, oz));
+}
+
 // The same look-up at a position that is not known to be inside the grid: one test per wave decides between the short
 // form (every lane at least h from the origin on every axis: q >= 1) and the general one.  A NaN fails the test.
 template <bool P2>
@@ -547,13 +604,13 @@ __device__ __forceinline__ f3 get_velocity_auto(const Vel3 &vel, const Spacing &
 }
 
 // GPU_kernel.cu:74-90 traceRK3
+// v1: the velocity at pos
 template <bool P2>
-__device__ __forceinline__ f3 trace_rk3(const Vel3 &vel, const Spacing &sp, f3 hi, float dt, f3 pos)
+__device__ __forceinline__ f3 trace_rk3_from(const Vel3 &vel, const Spacing &sp, f3 hi, float dt, f3 pos, f3 v1)
 {
     float c1 = (float)(2.0 / 9.0 * (double)dt);
     float c2 = (float)(3.0 / 9.0 * (double)dt);
     float c3 = (float)(4.0 / 9.0 * (double)dt);
-    f3 v1 = get_velocity_auto<P2>(vel, sp, pos);
     double hdt = 0.5 * (double)dt;
     f3 m1 = mk3((float)((double)pos.x + hdt * (double)v1.x),
                 (float)((double)pos.y + hdt * (double)v1.y),
@@ -569,15 +626,29 @@ __device__ __forceinline__ f3 trace_rk3(const Vel3 &vel, const Spacing &sp, f3 h
                  pos.z + c1 * v1.z + c2 * v2.z + c3 * v3.z);
     return clamp3(out, mk3(sp.h, sp.h, sp.h), hi);
 }
+template <bool P2>
+__device__ __forceinline__ f3 trace_rk3(const Vel3 &vel, const Spacing &sp, f3 hi, float dt, f3 pos)
+{
+    return trace_rk3_from<P2>(vel, sp, hi, dt, pos, get_velocity_auto<P2>(vel, sp, pos));
+}
 
 // GPU_kernel.cu:92-125 trace
-template <bool P2>
-__device__ __forceinline__ f3 trace(const Vel3 &vel, const Spacing &sp, f3 hi, float cfldt, float dt, f3 pos)
+// NODE0: the caller vouches that pos is the grid node (i, j, kl) (local indices, all >= 2), that the spacing is a power
+// of two and that the velocity is finite: the first look-up of the first sub-step is node_velocity().  The sign of a zero
+// sample cannot reach the result: pos + hdt * (+-0) and pos + c1 * (+-0) are pos, because pos >= 2h > 0.
+template <bool P2, bool NODE0 = false>
+__device__ __forceinline__ f3 trace(const Vel3 &vel, const Spacing &sp, f3 hi, float cfldt, float dt, f3 pos,
+                                    int i = 0, int j = 0, int kl = 0)
 {
     const bool fwd = dt > 0;
     float T = fwd ? dt : -dt;
     float t = 0.f, substep = cfldt;
     f3 p = pos;
+    if (NODE0 && t < T) {
+        if (t + substep > T) substep = T - t;
+        p = trace_rk3_from<P2>(vel, sp, hi, fwd ? substep : -substep, p, node_velocity(vel, i, j, kl));
+        t += substep;
+    }
     while (t < T) {
         if (t + substep > T) substep = T - t;
         p = trace_rk3<P2>(vel, sp, hi, fwd ? substep : -substep, p);

@@ -70,6 +70,8 @@ struct Runtime {
     float  map_tab_h = 0.f;
     int    map_tab_dims[3] = {0, 0, 0}, map_tab_stride = 0, map_tab_ok = 0;
     int    nonfinite_seen = 0;          // sticky: a gpu_max_abs3 met a NaN or an Inf (fl_nonfinite_seen)
+    const char *map_kernel_name[2] = { "", "" };    // the DMC / forward instance launched last (fl_map_kernel_name)
+    int    map_kernels_seen = 0;        // instances launched since the last reset, as bits (fl_map_kernels_seen)
     long long   mg_fused_launches = 0;  // fl_mg_fused_launches
     const char *mg_smooth_kernel = ""; // the fused kernel the last fp64 smoothing call launched first (fl_mg_smooth_kernel_name)
 };

@@ -314,6 +314,9 @@ void BimocqGPUSolver::advanceReflection(int framenum, float dt)
 float BimocqGPUSolver::getCFL()
 {
     MaxVelocity = gpu_max_abs3(VelocityU, VelocityV, VelocityW, g.ni, g.nj, g.nk);    // includes the 1e-4 floor
+    // what the map updates of this step may promise their kernels (gpuMapper::mapHints): the reduction has just read every
+    // value they will read.  The library's flag is sticky, so once a NaN or an Inf has been met the plain kernels stay.
+    GpuSolver->velocity_finite = !GpuSolver->slab.on && fl_nonfinite_seen && fl_nonfinite_seen(0) == 0 && MaxVelocity < 1.0e30f;
     return CellSize / MaxVelocity;
 }
 

@@ -19,6 +19,12 @@
 #include "bimocq_gpu.h"
 #include "wall_sheets.hpp"
 
+// Weak references, like the obstacle operators in fluid_solver.cpp: a CPU stand-in of the operator ABI need not provide
+// them (they resolve to null there) and the reference entry points run instead.
+#pragma weak gpu_solve_forward_hint
+#pragma weak gpu_solve_backwardDMC_hint
+#pragma weak fl_nonfinite_seen
+
 namespace bqhost {
 
 // untyped zero-filled device allocation (the fp64 arrays of the multigrid projection), RAII
@@ -254,6 +260,16 @@ public:
     bool jacobi_ends_first = true;          // BQ_OPT_JACOBI_ENDS_FIRST
     bool jacobi_triples = true;             // BQ_OPT_JACOBI_TRIPLES
     bool concurrent_maps = false;           // BQ_OPT_CONCURRENT_MAPS (measured: no gain, EXPERIMENTS.md section 9)
+    bool node_lookups = true;               // BQ_OPT_NODE_LOOKUPS
+    // the solver's last getCFL() ran on the velocity arrays the map updates are about to read and met no NaN, no Inf and
+    // nothing near the top of the fp32 range: what FL_MAP_HINT_FINITE promises.  Never set on slab ranks.
+    bool velocity_finite = false;
+    // the FL_MAP_HINT_* promises a map update may pass: none unless the option is on, this is one GPU and the velocity is finite
+    unsigned mapHints(bool identity) const
+    {
+        if (!node_lookups || slab.on || !velocity_finite) return 0u;
+        return FL_MAP_HINT_FINITE | (identity ? (unsigned)FL_MAP_HINT_IDENTITY : 0u);
+    }
     int shallow_blocking = 0;               // BQ_OPT_SHALLOW_BLOCKING_EXCHANGE: 1 require(), 2 also withGhosts() move only the planes asked for
     static bool trace_require() { static const bool on = getenv("BQ_TRACE_REQUIRE") && atoi(getenv("BQ_TRACE_REQUIRE")) != 0; return on; }
     // record that an operator just rewrote `f` from inputs whose reach left `valid` correct ghost planes
@@ -283,13 +299,20 @@ public:
     void startEventRecord();
     float endEventRecord();
 
-    void solveForward(float *u, float *v, float *w, float *xf, float *yf, float *zf, float cfldt, float dt) const
-    { gpu_solve_forward(u, v, w, xf, yf, zf, g.h, g.ni, g.nj, g.nk, cfldt, dt); }
+    // hints: FL_MAP_HINT_* (mapHints); an operator library without the _hint entry points runs the reference ones
+    void solveForward(float *u, float *v, float *w, float *xf, float *yf, float *zf, float cfldt, float dt, unsigned hints = 0u) const
+    {
+        if (hints && gpu_solve_forward_hint) gpu_solve_forward_hint(u, v, w, xf, yf, zf, g.h, g.ni, g.nj, g.nk, cfldt, dt, hints);
+        else gpu_solve_forward(u, v, w, xf, yf, zf, g.h, g.ni, g.nj, g.nk, cfldt, dt);
+    }
 
     // one DMC sub-step in -> out (GPU_Advection.h:460-470 without the copy-back; the caller swaps)
     void solveBackwardDMC(float *u, float *v, float *w, float *xi, float *yi, float *zi,
-                          float *xo, float *yo, float *zo, float substep) const
-    { gpu_solve_backwardDMC(u, v, w, xi, yi, zi, xo, yo, zo, g.h, g.ni, g.nj, g.nk, substep); }
+                          float *xo, float *yo, float *zo, float substep, unsigned hints = 0u) const
+    {
+        if (hints && gpu_solve_backwardDMC_hint) gpu_solve_backwardDMC_hint(u, v, w, xi, yi, zi, xo, yo, zo, g.h, g.ni, g.nj, g.nk, substep, hints);
+        else gpu_solve_backwardDMC(u, v, w, xi, yi, zi, xo, yo, zo, g.h, g.ni, g.nj, g.nk, substep);
+    }
 
     void advectVelocity(float *u, float *v, float *w, float *ui, float *vi, float *wi,
                         float *bx, float *by, float *bz, bool is_point) const;

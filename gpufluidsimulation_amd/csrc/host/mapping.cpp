@@ -48,6 +48,7 @@ bool MapperBaseGPU::init(int ni, int nj, int nk, float h, float coeff, gpuMapper
     m.ForwardX.copy_from(m.InitX); m.ForwardY.copy_from(m.InitY); m.ForwardZ.copy_from(m.InitZ);
     m.BackwardX.copy_from(m.InitX); m.BackwardY.copy_from(m.InitY); m.BackwardZ.copy_from(m.InitZ);
     m.BackwardXPrev.copy_from(m.InitX); m.BackwardYPrev.copy_from(m.InitY); m.BackwardZPrev.copy_from(m.InitZ);
+    m.fwdIdentity = m.backIdentity = true;
     return true;
 }
 
@@ -111,8 +112,11 @@ void MapperBaseGPU::updateBackward(DeviceField &U, DeviceField &V, DeviceField &
         FusedScope fused(gs.fuse_housekeeping, keepDmcBorder ? 8 : 4);
         swap_result = fused.on;
         if (keepDmcBorder && !fused.on) { out[0]->copy_from(*in[0]); out[1]->copy_from(*in[1]); out[2]->copy_from(*in[2]); }
+        // (the first sub-step after a re-initialisation reads the identity map; every sub-step looks the velocity up at nodes)
+        const unsigned hints = gs.mapHints(m.backIdentity);
+        m.backIdentity = false;
         gs.withGhosts({ { { &U, &V, &W, in[0], in[1], in[2] }, kReachDMC } }, [&] {
-            gs.solveBackwardDMC(U, V, W, *in[0], *in[1], *in[2], *out[0], *out[1], *out[2], substep);
+            gs.solveBackwardDMC(U, V, W, *in[0], *in[1], *in[2], *out[0], *out[1], *out[2], substep, hints);
         }, gs.validAfter({ &U, &V, &W, in[0], in[1], in[2] }, kReachDMC) - kReachDMC, { out[0], out[1], out[2] });
         const int v = gpuMapper::minValid({ &U, &V, &W, in[0], in[1], in[2] }) - kReachDMC;
         gs.producedAll({ out[0], out[1], out[2] }, v);
@@ -138,8 +142,9 @@ void MapperBaseGPU::updateForward(DeviceField &U, DeviceField &V, DeviceField &W
     MapSet &m = *maps;
     gpuMapper &gs = *gpuSolver;
     const int reach = reachField(m.Dfwd + dcells);
+    const unsigned hints = m.fwdIdentity ? gs.mapHints(true) : 0u;      // (the forward update has no use for finiteness alone)
     gs.withGhosts({ { { &U, &V, &W }, reach } }, [&] {
-        gs.solveForward(U, V, W, m.ForwardX, m.ForwardY, m.ForwardZ, cfldt, dt);
+        gs.solveForward(U, V, W, m.ForwardX, m.ForwardY, m.ForwardZ, cfldt, dt, hints);
     }, std::min(gpuMapper::minValid({ &m.ForwardX, &m.ForwardY, &m.ForwardZ }), gs.validAfter({ &U, &V, &W }, reach) - reach),
        { &m.ForwardX, &m.ForwardY, &m.ForwardZ });
     const int v = std::min(gpuMapper::minValid({ &m.ForwardX, &m.ForwardY, &m.ForwardZ }),
@@ -469,7 +474,7 @@ void MapperBaseGPU::reinitializeMapping()
     m.DbackPrev = m.Dback;
     m.Dback = 0;
     m.Dfwd = 0;
-    m.fwdIdentity = true;
+    m.fwdIdentity = m.backIdentity = true;
     m.backQ4 = m.fwdQ4 = true;          // identity maps: 0 or n*h with 1 <= n <= 1024 (planes outside the global grid: 0)
 }
 

@@ -90,6 +90,16 @@ class GpuMapper:
         for dst, src in ((x, self.x_out), (y, self.y_out), (z, self.z_out)):
             self.lib.fl_memcpy_d2d(dst.ptr, src.ptr, dst.nbytes)
 
+    # the same two updates with FL_MAP_HINT_* promises of the caller (include/bimocq_gpu.h): bit-identical when they hold
+    def solveForwardHint(self, u, v, w, x_fwd, y_fwd, z_fwd, cfldt, dt, hints):
+        self.lib.gpu_solve_forward_hint(u.ptr, v.ptr, w.ptr, x_fwd.ptr, y_fwd.ptr, z_fwd.ptr, *self._g(), cfldt, dt, hints)
+
+    def solveBackwardDMCHint(self, u, v, w, x, y, z, substep, hints):
+        self.lib.gpu_solve_backwardDMC_hint(u.ptr, v.ptr, w.ptr, x.ptr, y.ptr, z.ptr,
+                                            self.x_out.ptr, self.y_out.ptr, self.z_out.ptr, *self._g(), substep, hints)
+        for dst, src in ((x, self.x_out), (y, self.y_out), (z, self.z_out)):
+            self.lib.fl_memcpy_d2d(dst.ptr, src.ptr, dst.nbytes)
+
     # GPU_Advection.h:472-482
     def advectVelocity(self, u, v, w, u_init, v_init, w_init, bx, by, bz, is_point=False):
         for f in (u, v, w):

@@ -426,6 +426,27 @@ void fl_map_guard_reset(int which);
 void fl_map_guard_read(int ok[2]);
 /* maps <- (i*h, j*h, k*h): the host loop + H2D of MapperBaseGPU::init (Mapping.cpp:306-328) */
 void gpu_init_maps(float *x, float *y, float *z, float h, int ni, int nj, int nk);
+/* gpu_solve_backwardDMC / gpu_solve_forward with promises of the caller (`hints`, FL_MAP_HINT_* or-ed) that let the
+ * kernels skip work the result does not need.  Results are bit-identical to the plain entry points whenever the promises
+ * are true; a false promise gives wrong maps.  A promise the library cannot use (spacing not a power of two, a plane
+ * window, a slab context) is ignored: the plain kernel runs.
+ *   FL_MAP_HINT_FINITE    every value of u, v, w is finite (and below 2^126 in magnitude): both velocity look-ups of a DMC
+ *                         sub-step are at grid nodes, where the trilinear sample is the mean of two values -- but only in
+ *                         value, and only while the six discarded corners are finite.  gpu_max_abs3 tells (fl_nonfinite_seen).
+ *   FL_MAP_HINT_IDENTITY  (with _FINITE) x/y/z_in resp. x/y/z_fwd hold what gpu_init_maps wrote for these dims: the DMC
+ *                         sub-step computes the map corners it would load, the forward trace its start, whose first velocity
+ *                         look-up is then a node look-up too. */
+enum { FL_MAP_HINT_FINITE = 1, FL_MAP_HINT_IDENTITY = 2 };
+void gpu_solve_forward_hint(float *u, float *v, float *w, float *x_fwd, float *y_fwd, float *z_fwd,
+                            float h, int ni, int nj, int nk, float cfldt, float dt, unsigned hints);
+void gpu_solve_backwardDMC_hint(float *u, float *v, float *w, float *x_in, float *y_in, float *z_in,
+                                float *x_out, float *y_out, float *z_out,
+                                float h, int ni, int nj, int nk, float substep, unsigned hints);
+/* which map-update kernel ran last (which: 0 DMC sub-step, 1 forward update; "" before the first): "dmc_kernel",
+ * "dmc_node_kernel", "dmc_node_identity_kernel", "forward_kernel", "forward_identity_kernel" -- and which have run since
+ * the last reset, as bits 1, 2, 4, 8, 16 in that order (reset != 0 clears).  For reports and tests. */
+const char *fl_map_kernel_name(int which);
+int  fl_map_kernels_seen(int reset);
 /* device getCFL (BimocqGPUSolver.cpp:348-373): max(1e-4, max|u|,|v|,|w|); blocking */
 float gpu_max_abs3(const float *u, const float *v, const float *w, int ni, int nj, int nk);
 /* the three stages of gpu_projection_jacobi, separately launchable */

@@ -132,7 +132,13 @@ enum {
      * exact as long as no node within a cell of the outermost window nodes is carried more than 3/4 of a cell towards a wall
      * between two re-initialisations (reads outside the slab return 0 otherwise).  get: 2 = copies are in use.  Costs five
      * whole-grid float arrays per rank. */
-    BQ_OPT_WHOLE_GRID_PREV = 13
+    BQ_OPT_WHOLE_GRID_PREV = 13,
+    /* one GPU, power-of-two spacing, 1 (default): the map updates tell their kernels what the solver knows -- that getCFL()
+     * has just found the velocity finite, and that a map still is the identity gpu_init_maps wrote (always at the first DMC
+     * sub-step and the forward update after a re-initialisation) -- through gpu_solve_backwardDMC_hint / gpu_solve_forward_hint
+     * (include/bimocq_gpu.h).  The kernels then look the velocity up at grid nodes as the mean of two values and compute
+     * identity-map corners instead of loading them.  Same bits.  0: the reference entry points, for A/B runs. */
+    BQ_OPT_NODE_LOOKUPS = 14
 };
 /* BQ_OPT_PROFILE_PHASES: milliseconds per phase summed over the steps since the last reset -- map update (DMC + RK3,
  * BimocqGPUSolver.cpp:136-139), advection with error compensation (:143-145), sources and forces (:157-177), projection
