@@ -8,7 +8,7 @@
 // rings blown along x by the reference's emitter velocity formula (main.cpp:52-73, emiter = +1 for both: the rear
 // ring catches up and threads the front one -- leapfrogging), no buoyancy, density dumped every frame.
 //
-//   make example && build/bimocq3d [N=128] [frames=20] [outdir=out] [scheme=0|3] [projection=0|1] [async=1] [scene=0|1]
+//   make example && build/bimocq3d [N=128] [frames=20] [outdir=out] [scheme=0|2|3] [projection=0|1] [async=1] [scene=0|1]
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -24,12 +24,12 @@ int main(int argc, char **argv)
     const int n = argc > 1 ? std::atoi(argv[1]) : 128;
     const int total_frame = argc > 2 ? std::atoi(argv[2]) : 20;
     const std::string filepath = argc > 3 ? argv[3] : "out";
-    const int scheme = argc > 4 ? std::atoi(argv[4]) : 0;            // 0 BIMOCQ, 3 MAC_REFLECTION (main.cpp:51 ships 3)
+    const int scheme = argc > 4 ? std::atoi(argv[4]) : 0;            // 0 BIMOCQ, 2 MACCORMACK, 3 MAC_REFLECTION (main.cpp:51 ships 3)
     const int projection = argc > 5 ? std::atoi(argv[5]) : 0;        // 0 Jacobi, 1 multigrid-CG (what the binary ships)
     const bool async_dump = argc > 6 ? std::atoi(argv[6]) != 0 : true;
     const int scene = argc > 7 ? std::atoi(argv[7]) : 0;             // 0 rising smoke, 1 leapfrogging vortex rings, 2 box-shaped plume source
-    if (n < 8 || total_frame < 1 || (scene == 1 && n % 2)) {
-        std::fprintf(stderr, "usage: %s [N>=8] [frames] [outdir] [scheme] [projection] [async] [scene]\n", argv[0]); return 2;
+    if (n < 8 || total_frame < 1 || (scene == 1 && n % 2) || (scheme != 0 && scheme != 2 && scheme != 3)) {
+        std::fprintf(stderr, "usage: %s [N>=8] [frames] [outdir] [scheme: 0 BiMocq, 2 MacCormack, 3 reflection] [projection] [async] [scene]\n", argv[0]); return 2;
     }
 
     const int ni = n, nj = n, nk = scene == 1 ? n / 2 : n;
@@ -39,7 +39,8 @@ int main(int argc, char **argv)
 
     if (fl_init(0) != FL_OK) { std::fprintf(stderr, "%s\n", fl_last_error_string()); return 1; }
     auto *myGPUmapper = new gpuMapper(/*device*/0, ni, nj, nk, h);
-    BimocqGPUSolver mysolver(ni, nj, nk, L, viscosity, mapping_blend_coeff, scheme == 3 ? MAC_REFLECTION : BIMOCQ, myGPUmapper);
+    BimocqGPUSolver mysolver(ni, nj, nk, L, viscosity, mapping_blend_coeff, scheme == 3 ? MAC_REFLECTION : scheme == 2 ? MACCORMACK : BIMOCQ,
+                             myGPUmapper);
     if (!myGPUmapper->ok() || !mysolver.ok()) { std::fprintf(stderr, "%s\n", fl_last_error_string()); return 1; }
 
     if (scene == 1) {

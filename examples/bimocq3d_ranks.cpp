@@ -11,6 +11,7 @@
 // Each rank dumps the planes it owns: <outdir>/density_render_%04d.k%05d.bqd (the slab files stitch to the global grid).
 //
 //   build/bimocq3d_ranks [NX=512] [NY=512] [NZ=512] [frames=20] [outdir=out] [scene=0 smoke|1 leapfrog] [ghost=8] [jacobi=200]
+//                      [scheme=0 BiMocq|2 MacCormack|3 reflection]
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -68,9 +69,12 @@ int main(int argc, char **argv)
     const int scene = argc > 6 ? std::atoi(argv[6]) : 0;
     const int ghost = argc > 7 ? std::atoi(argv[7]) : 8;
     const int jacobi = argc > 8 ? std::atoi(argv[8]) : 200;
+    const int scheme = argc > 9 ? std::atoi(argv[9]) : 0;
     const int rank = env_int("RANK", 0), world = env_int("WORLD_SIZE", 1), local = env_int("LOCAL_RANK", rank);
-    if (ni < 8 || nj < 8 || nk < 8 || total_frame < 1 || world < 1 || rank < 0 || rank >= world || nk % world != 0) {
-        std::fprintf(stderr, "usage: RANK=r WORLD_SIZE=n %s [NX] [NY] [NZ divisible by n] [frames] [outdir] [scene] [ghost] [jacobi]\n", argv[0]);
+    if (ni < 8 || nj < 8 || nk < 8 || total_frame < 1 || world < 1 || rank < 0 || rank >= world || nk % world != 0 ||
+        (scheme != 0 && scheme != 2 && scheme != 3)) {
+        std::fprintf(stderr, "usage: RANK=r WORLD_SIZE=n %s [NX] [NY] [NZ divisible by n] [frames] [outdir] [scene] [ghost] [jacobi] "
+                             "[scheme: 0 BiMocq, 2 MacCormack, 3 reflection]\n", argv[0]);
         return 2;
     }
     ::mkdir(filepath.c_str(), 0777);
@@ -89,7 +93,7 @@ int main(int argc, char **argv)
     }
     auto *myGPUmapper = new gpuMapper(local, ni, nj, nk, h, slab);
     if (!myGPUmapper->ok()) { std::fprintf(stderr, "[rank %d] %s\n", rank, fl_last_error_string()); return 1; }
-    BimocqGPUSolver mysolver(ni, nj, nk, L, 0.f, 1.f, BIMOCQ, myGPUmapper);
+    BimocqGPUSolver mysolver(ni, nj, nk, L, 0.f, 1.f, scheme == 3 ? MAC_REFLECTION : scheme == 2 ? MACCORMACK : BIMOCQ, myGPUmapper);
     if (!mysolver.ok()) { std::fprintf(stderr, "[rank %d] %s\n", rank, fl_last_error_string()); return 1; }
 
     float zc = 0.5f * (float)nk * h;

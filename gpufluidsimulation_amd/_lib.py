@@ -32,6 +32,7 @@ HIP_SIGS = {
     "gpu_compensate_velocity": (None, [VP] * 15 + _G + [c_b]),
     "gpu_compensate_field": (None, [VP] * 9 + _G + [c_b]),
     "gpu_semilag": (None, [VP] * 5 + [c_i, c_i, c_i] + _G + [c_f, c_f]),
+    "gpu_maccormack": (None, [VP] * 7 + [c_i, c_i, c_i] + _G + [c_f, c_f, c_f]),
     "gpu_emit_smoke": (None, [VP] * 5 + _G + [c_f] * 7),
     "gpu_add_buoyancy": (None, [VP] * 3 + [c_i, c_i, c_i, c_f, c_f, c_f]),
     "gpu_diffuse_field": (None, [VP] * 3 + [c_i, c_i, c_i, c_i, c_f]),

@@ -622,6 +622,53 @@ __global__ __launch_bounds__(256) void clamp_extrema_kernel(const float *field, 
     if (t < mn || t > mx) field_temp[id] = gather(src, c);
 }
 
+// ---- MacCormack correction + limiter in one pass (include/bimocq_gpu.h: gpu_maccormack) ----------------------
+// What semilag_kernel(+dt) of f1 into a cleared field, two add_kernels (-0.5 back, +0.5 f_adv) and clamp_extrema_kernel
+// against f_lim leave at a node, evaluated at that node: the correction reads the node's own f1 / f_adv and ONE sample of
+// f1 at the end of the forward trace, the limiter reads f_lim only -- no thread reads what another one writes, so `out`
+// needs no clear and the intermediate fields are never stored.  Both halves are the statements of the two kernels above
+// (same device functions, same order); the node's position is the one expression both of them evaluate.
+template <bool P2>
+__global__ __launch_bounds__(256) void maccormack_kernel(float *out, const float *f1, const float *f_adv, const float *f_lim,
+                                                         const float *u, const float *v, const float *w,
+                                                         Spacing sp, Grid g, int dx, int dy, int dz,
+                                                         float cfldt, float dt, float dt_clamp)
+{
+    const int bi = g.ni + dx, bj = g.nj + dy, bk = g.nk + dz;
+    BQ_IJK(bi, bj, bk)
+    const float h = sp.h;
+    Vel3 vel{make_field(u, g.ni + 1, g.nj, g.nk, g.koff), make_field(v, g.ni, g.nj + 1, g.nk, g.koff), make_field(w, g.ni, g.nj, g.nk + 1, g.koff)};
+    const f3 org = mk3(-(float)dx * 0.5f * h, -(float)dy * 0.5f * h, -(float)dz * 0.5f * h);
+    const f3 hi = mk3((float)g.ni * h - h, (float)g.nj * h - h, (float)g.nkg * h - h);
+    const f3 pt = mk3(h * (float)i + org.x, h * (float)j + org.y, h * (float)kg + org.z);
+    const size_t id = (size_t)i + (size_t)bi * j + (size_t)bi * bj * k;
+    // semilag_kernel: the forward pass of the first pass's result; 0 (the cleared field) outside its window
+    float back = 0.f;
+    if (i > 1 && i < bi - 2 - dx && j > 1 && j < bj - 2 - dy && kg > 1 && kg < g.nkg - 2) {
+        const Field first = make_field(f1, bi, bj, bk, g.koff);
+        back = sample<P2>(first, sp, org, trace<P2>(vel, sp, hi, cfldt, dt, pt));
+    }
+    // the two add_kernels: each a rounded product and a rounded sum
+    float t = f1[id];
+    t += -0.5f * back;
+    t += 0.5f * f_adv[id];
+    // clamp_extrema_kernel at every node of the buffer
+    const Field lim = make_field(f_lim, bi, bj, bk, g.koff);
+    const f3 lo = mk3(h, h, h);
+    const float halfdt = 0.5f * dt_clamp;
+    f3 vl = get_velocity<P2>(vel, sp, pt);
+    f3 px = mk3(pt.x - vl.x * halfdt, pt.y - vl.y * halfdt, pt.z - vl.z * halfdt);
+    vl = get_velocity<P2>(vel, sp, px);
+    px = clamp3(mk3(pt.x - vl.x * dt_clamp, pt.y - vl.y * dt_clamp, pt.z - vl.z * dt_clamp), lo, hi);
+    const Cell c = locate<P2>(lim, sp, org, px);
+    float cv[8];
+    corners(lim, c, cv);
+    const float mn = fminf(cv[0], fminf(cv[1], fminf(cv[2], fminf(cv[3], fminf(cv[4], fminf(cv[5], fminf(cv[6], cv[7])))))));
+    const float mx = fmaxf(cv[0], fmaxf(cv[1], fmaxf(cv[2], fmaxf(cv[3], fmaxf(cv[4], fmaxf(cv[5], fmaxf(cv[6], cv[7])))))));
+    if (t < mn || t > mx) t = gather(lim, c);
+    out[id] = t;
+}
+
 // ---- map-value scan behind FL_OPT_MAP_QUARTER_FP32 (bq_device.hip.h: tile_value_ok) ------------------------
 __global__ __launch_bounds__(256) void maps_quarter_safe_kernel(const float *__restrict__ x, const float *__restrict__ y,
                                                                 const float *__restrict__ z, size_t n, float lo, float hi,
@@ -1444,6 +1491,19 @@ BQ_ENTRY(gpu_clamp_extrema, (float *field, float *fieldTemp, float *u, float *v,
     const Grid g = mk_grid(ni - dimx, nj - dimy, nk - dimz);          // the slab context (single GPU: koff 0, nkg = cell planes)
     BQ_DISPATCH1(clamp_extrema_kernel, sp.pow2, grid_for(ni, nj, nk), field, fieldTemp, u, v, w, sp, ni, nj, nk,
                  dimx, dimy, dimz, ox, oy, oz, dt, g.koff, g.nkg);
+}
+
+BQ_ENTRY(gpu_maccormack, (float *out, const float *f1, const float *f_adv, const float *f_lim, float *u, float *v, float *w,
+                          int dim_x, int dim_y, int dim_z, float h, int ni, int nj, int nk, float cfldt, float dt, float dt_clamp),
+         (out, f1, f_adv, f_lim, u, v, w, dim_x, dim_y, dim_z, h, ni, nj, nk, cfldt, dt, dt_clamp))
+{
+    BQ_ENTER("gpu_maccormack", out, f1, f_adv, f_lim, u, v, w)
+    BQ_REQUIRE(out != f1 && out != f_adv && out != f_lim && out != u && out != v && out != w, "gpu_maccormack");
+    BQ_REQUIRE(cfldt > 0.f || dt == 0.f, "gpu_maccormack");
+    BQ_REQUIRE((unsigned)dim_x <= 1u && (unsigned)dim_y <= 1u && (unsigned)dim_z <= 1u && dim_x + dim_y + dim_z <= 1, "gpu_maccormack");
+    Spacing sp = make_spacing(h); Grid g = mk_grid(ni, nj, nk);
+    BQ_DISPATCH1(maccormack_kernel, sp.pow2, grid_for(ni + dim_x, nj + dim_y, nk + dim_z), out, f1, f_adv, f_lim, u, v, w, sp, g,
+                 dim_x, dim_y, dim_z, cfldt, dt, dt_clamp);
 }
 
 BQ_ENTRY(gpu_clamp_extrema_box, (const float *before, float *after, int ni, int nj, int nk), (before, after, ni, nj, nk))

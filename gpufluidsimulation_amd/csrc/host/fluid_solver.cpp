@@ -35,6 +35,7 @@
 #pragma weak gpu_pcg_solve
 #pragma weak gpu_pcg_gradient
 #pragma weak gpu_emit_sources
+#pragma weak gpu_maccormack
 
 namespace bqhost {
 
@@ -183,7 +184,8 @@ void BimocqGPUSolver::advance(int framenum, float dt)
     switch (myscheme) {
     case BIMOCQ: advanceBimocq(framenum, dt); break;
     case MAC_REFLECTION: advanceReflection(framenum, dt); break;
-    default: break;                                      // the reference's GPU solver has no other scheme (:112-122)
+    case MACCORMACK: advanceMacCormack(framenum, dt); break;      // (the CPU solver's scheme, BimocqSolver.cpp:282-364)
+    default: break;                                      // SEMILAG: refused by bq_solver_create
     }
     // FL_OPT_COMM_CHECK (debugging aid for the first runs on real links): every rank has issued this step's communicator
     // calls; compare the ledgers (include/bimocq_gpu.h: fl_comm_check)
@@ -192,118 +194,204 @@ void BimocqGPUSolver::advance(int framenum, float dt)
     if (verbose) printf("[Bimocq GPU Time: %gms ]\n", last_ms);
 }
 
-// :232-337 advanceReflection (SURVEY 8f N3): MacCormack advection of rho, T and of the velocity (half step),
-// sources, projection, reflection 2 u_proj - u advected another half step, sources, projection.  The
-// limiter is the corrected gpu_clamp_extrema (include/bimocq_gpu.h).
+// ---- the pieces the MacCormack and the reflection scheme are made of -------------------------------------------------
 // z-slab ranks (Jacobi projection): every look-up states how far it reaches along z -- the trace travels at most
 // |t| * max|u| (getCFL) and the sample adds its cell and the half-cell stagger -- so gpuMapper::require refreshes ghost
 // planes exactly when an input's correct depth no longer covers that reach, and produced() records what is left of it.
+// step_cfldt_ / step_vmax_: getCFL()'s step bound and the speed bound of the velocity field the traces run through (max|u|
+// of getCFL() until a projection has changed the field, a fresh maximum after it; single-GPU runs never look at it).
+int BimocqGPUSolver::reach(float t) const
+{
+    return (int)std::ceil(std::fabs((double)t) * (double)step_vmax_ / (double)CellSize) + 3;
+}
+
+int BimocqGPUSolver::velValid() const { return gpuMapper::minValid({ &VelocityU, &VelocityV, &VelocityW }); }
+
+// semilagAdvectField / semilagAdvectVelocity (GPU_Advection.h:530-551) clear their outputs first
+void BimocqGPUSolver::semilagScalar(DeviceField &dst, DeviceField &src, float t)
+{
+    gpuMapper &gs = *GpuSolver;
+    const int r = reach(t);
+    gs.require({ &src, &VelocityU, &VelocityV, &VelocityW }, r);
+    fl_memset(dst, 0, g.n() * sizeof(float));
+    gpu_semilag(dst, src, VelocityU, VelocityV, VelocityW, 0, 0, 0, CellSize, g.ni, g.nj, g.nk, step_cfldt_, t);
+    gs.produced(dst, std::min(src.valid, velValid()) - r);
+}
+
+void BimocqGPUSolver::semilagVelocity(DeviceField &uo, DeviceField &vo, DeviceField &wo, DeviceField &us, DeviceField &vs,
+                                      DeviceField &ws, float t)
+{
+    gpuMapper &gs = *GpuSolver;
+    const float h = CellSize;
+    const int ni = g.ni, nj = g.nj, nk = g.nk;
+    const int r = reach(t);
+    gs.require({ &us, &vs, &ws, &VelocityU, &VelocityV, &VelocityW }, r);
+    uo.zero(); vo.zero(); wo.zero();
+    gpu_semilag(uo, us, VelocityU, VelocityV, VelocityW, 1, 0, 0, h, ni, nj, nk, step_cfldt_, t);
+    gpu_semilag(vo, vs, VelocityU, VelocityV, VelocityW, 0, 1, 0, h, ni, nj, nk, step_cfldt_, t);
+    gpu_semilag(wo, ws, VelocityU, VelocityV, VelocityW, 0, 0, 1, h, ni, nj, nk, step_cfldt_, t);
+    const int vv = velValid();
+    gs.produced(uo, std::min(us.valid, vv) - r); gs.produced(vo, std::min(vs.valid, vv) - r); gs.produced(wo, std::min(ws.valid, vv) - r);
+}
+
+// the limiter reads `field` around the departure point of a trace over dtc and rewrites `temp` at the node itself
+void BimocqGPUSolver::limiter(DeviceField &field, DeviceField &temp, int dx, int dy, int dz, float dtc)
+{
+    gpuMapper &gs = *GpuSolver;
+    const int r = reach(dtc);
+    gs.require({ &field, &VelocityU, &VelocityV, &VelocityW }, r);
+    gpu_clamp_extrema(field, temp, VelocityU, VelocityV, VelocityW, g.ni + dx, g.nj + dy, g.nk + dz, dx, dy, dz,
+                      0.5f * dx, 0.5f * dy, 0.5f * dz, CellSize, dtc);
+    gs.produced(temp, std::min(temp.valid, std::min(field.valid, velValid()) - r));
+}
+
+// f1 += coeff * f2
+void BimocqGPUSolver::axpy(DeviceField &f1, DeviceField &f2, float coeff, size_t count)
+{
+    GpuSolver->add(f1, f2, coeff, count);
+    GpuSolver->produced(f1, std::min(f1.valid, f2.valid));
+}
+
+// emission over dt_emit (legacy emitters and the source list), buoyancy and viscous diffusion over dt_forces
+void BimocqGPUSolver::applySources(bool emit, int framenum, float dt_emit, float dt_forces)
+{
+    const gpuMapper &gs = *GpuSolver;
+    const int ni = g.ni, nj = g.nj, nk = g.nk;
+    if (emit) emitSmoke(framenum, dt_emit);
+    addBuoyancy(dt_forces);
+    if (Viscosity) {
+        if (gs.slab.on && gs.slab.nranks > 1) {
+            diffuseFieldSlab(VelocityU, VelocityUTemp, TempSrcU, ni + 1, nj, nk, 20, Viscosity, dt_forces);
+            diffuseFieldSlab(VelocityV, VelocityVTemp, TempSrcV, ni, nj + 1, nk, 20, Viscosity, dt_forces);
+            diffuseFieldSlab(VelocityW, VelocityWTemp, TempSrcW, ni, nj, nk + 1, 20, Viscosity, dt_forces);
+        } else {
+            diffuseField(VelocityU, VelocityUTemp, TempSrcU, ni + 1, nj, nk, 20, Viscosity, dt_forces);
+            diffuseField(VelocityV, VelocityVTemp, TempSrcV, ni, nj + 1, nk, 20, Viscosity, dt_forces);
+            diffuseField(VelocityW, VelocityWTemp, TempSrcW, ni, nj, nk + 1, 20, Viscosity, dt_forces);
+        }
+    }
+}
+
+bool BimocqGPUSolver::fusedMacCormack() const
+{
+    return gpu_maccormack && fused_maccormack >= (myscheme == MACCORMACK ? 1 : 2);
+}
+
+// MacCormack advection of one scalar (count 1) or of three velocity-like components (count 3) through the step's
+// velocity: f.field <- limit(first + 0.5 (f.adv - semilag(first, +t))), first = semilag(f.adv, -t), the limiter looking at
+// f.field over dt_clamp (BimocqSolver.cpp:293-304 / :324-348, BimocqGPUSolver.cpp:237-287).
+//   unfused: memset + semilag(-t), memset + semilag(+t), two adds, the limiter and a copy per field;
+//   fused (fusedMacCormack()): memset + semilag(-t), then gpu_maccormack into a scratch field that becomes the field by a
+//   swap (DeviceField::swap carries the ghost validity along) -- for the velocity after all three components exist, since
+//   every trace reads all of them.
+// Scratch: the scalars' *Temp fields and TempSrcU, the velocity's *Temp and TempSrc* fields; their contents afterwards
+// differ between the two bodies and nothing reads them.
+void BimocqGPUSolver::macCormack(const MacCormackFields &f, float t, float dt_clamp)
+{
+    gpuMapper &gs = *GpuSolver;
+    const float h = CellSize;
+    const int ni = g.ni, nj = g.nj, nk = g.nk;
+    const bool fused = fusedMacCormack();
+    // what the fused operator leaves of its inputs' ghost planes: the sample of `first` after a trace over t, the
+    // limiter's corners of `lim` after one over dt_clamp, adv at the node itself
+    auto fusedCall = [&](DeviceField &out, DeviceField &first, DeviceField &adv, DeviceField &lim, int dx, int dy, int dz) {
+        const int rt = reach(t), rc = reach(dt_clamp);
+        gs.require({ &first, &VelocityU, &VelocityV, &VelocityW }, rt);
+        gs.require({ &lim, &VelocityU, &VelocityV, &VelocityW }, rc);
+        gpu_maccormack(out, first, adv, lim, VelocityU, VelocityV, VelocityW, dx, dy, dz, h, ni, nj, nk, step_cfldt_, t, dt_clamp);
+        const int vv = velValid();
+        gs.produced(out, std::min({ std::min(first.valid, vv) - rt, std::min(lim.valid, vv) - rc, adv.valid }));
+    };
+    if (f.count == 1) {
+        DeviceField &field = *f.field[0], &adv = *f.adv[0];
+        if (fused) {
+            semilagScalar(DensityTemp, adv, -t);
+            fusedCall(TemperatureTemp, DensityTemp, adv, field, 0, 0, 0);
+            field.swap(TemperatureTemp);
+            return;
+        }
+        DeviceField &tmp = &field == &Temperature ? TemperatureTemp : DensityTemp;
+        semilagScalar(tmp, adv, -t);
+        semilagScalar(TempSrcU, tmp, t);
+        axpy(tmp, TempSrcU, -0.5f, g.n());
+        axpy(tmp, adv, 0.5f, g.n());
+        limiter(field, tmp, 0, 0, 0, dt_clamp);
+        fl_memcpy_d2d(field, tmp, g.n() * sizeof(float));
+        gs.produced(field, tmp.valid);
+        return;
+    }
+    semilagVelocity(VelocityUTemp, VelocityVTemp, VelocityWTemp, *f.adv[0], *f.adv[1], *f.adv[2], -t);
+    if (fused) {
+        fusedCall(TempSrcU, VelocityUTemp, *f.adv[0], *f.field[0], 1, 0, 0);
+        fusedCall(TempSrcV, VelocityVTemp, *f.adv[1], *f.field[1], 0, 1, 0);
+        fusedCall(TempSrcW, VelocityWTemp, *f.adv[2], *f.field[2], 0, 0, 1);
+        f.field[0]->swap(TempSrcU); f.field[1]->swap(TempSrcV); f.field[2]->swap(TempSrcW);
+        return;
+    }
+    semilagVelocity(TempSrcU, TempSrcV, TempSrcW, VelocityUTemp, VelocityVTemp, VelocityWTemp, t);
+    axpy(VelocityUTemp, TempSrcU, -0.5f, g.nu()); axpy(VelocityVTemp, TempSrcV, -0.5f, g.nv()); axpy(VelocityWTemp, TempSrcW, -0.5f, g.nw());
+    axpy(VelocityUTemp, *f.adv[0], 0.5f, g.nu()); axpy(VelocityVTemp, *f.adv[1], 0.5f, g.nv()); axpy(VelocityWTemp, *f.adv[2], 0.5f, g.nw());
+    limiter(*f.field[0], VelocityUTemp, 1, 0, 0, dt_clamp);
+    limiter(*f.field[1], VelocityVTemp, 0, 1, 0, dt_clamp);
+    limiter(*f.field[2], VelocityWTemp, 0, 0, 1, dt_clamp);
+    f.field[0]->copy_from(VelocityUTemp); f.field[1]->copy_from(VelocityVTemp); f.field[2]->copy_from(VelocityWTemp);
+}
+
+// the scratch scalars of both schemes and the step's bounds; false: allocation failed
+bool BimocqGPUSolver::beginSchemeStep()
+{
+    for (DeviceField *f : { &DensityTemp, &TemperatureTemp })
+        if (!f->get() && !GpuSolver->allocField(*f, FIELD_S)) return false;
+    step_cfldt_ = last_cfldt = getCFL();
+    step_vmax_ = MaxVelocity;
+    return true;
+}
+
+// BimocqSolver.cpp:282-364 advanceMacCormack on device buffers: MacCormack advection of rho, T (:293-320) and of the
+// velocity (:324-348) over the whole step through the step's old velocity, one getCFL() (:291), clearBoundary (:351),
+// sources and forces (:352-361), projection (:363).  The limiter is the corrected gpu_clamp_extrema, as in the reflection
+// scheme; emitters, setSources, the projection kinds and obstacles come with the shared emitSmoke / projection().
+void BimocqGPUSolver::advanceMacCormack(int framenum, float dt)
+{
+    if (!beginSchemeStep()) return;
+    macCormack({ 1, { &Density }, { &Density } }, dt, dt);
+    macCormack({ 1, { &Temperature }, { &Temperature } }, dt, dt);
+    macCormack({ 3, { &VelocityU, &VelocityV, &VelocityW }, { &VelocityU, &VelocityV, &VelocityW } }, dt, dt);
+    if (!boundaries.empty()) blendBoundary(false);        // clearBoundary(_rho) (:351)
+    applySources(true, framenum, dt, dt);
+    projection();
+    steps_taken++;
+}
+
+// :232-337 advanceReflection (SURVEY 8f N3): MacCormack advection of rho, T and of the velocity (half step),
+// sources, projection, reflection 2 u_proj - u advected another half step, sources, projection.  The
+// limiter is the corrected gpu_clamp_extrema (include/bimocq_gpu.h).
 void BimocqGPUSolver::advanceReflection(int framenum, float dt)
 {
     gpuMapper &gs = *GpuSolver;
     const bool slabs = gs.slab.on && gs.slab.nranks > 1;
-    DeviceField *extra[] = { &DensityTemp, &TemperatureTemp };
-    for (DeviceField *f : extra)
-        if (!f->get() && !gs.allocField(*f, FIELD_S)) return;
-    const float cfldt = getCFL();                        // :234
-    last_cfldt = cfldt;
-    const float h = CellSize;
-    const int ni = g.ni, nj = g.nj, nk = g.nk;
-    const size_t n = g.n(), nu = g.nu(), nv = g.nv(), nw = g.nw();
-    // ghost planes a look-up after a trace over time t can touch
-    // (vmax: the speed bound of the velocity field the traces run through -- max|u| of getCFL() until the first
-    // projection has changed the field, a fresh maximum after it; single-GPU runs never look at it)
-    float vmax = MaxVelocity;
-    auto reach = [&](float t) { return (int)std::ceil(std::fabs((double)t) * (double)vmax / (double)h) + 3; };
-    auto vel_valid = [&]() { return gpuMapper::minValid({ &VelocityU, &VelocityV, &VelocityW }); };
+    if (!beginSchemeStep()) return;                      // :234
+    const size_t nu = g.nu(), nv = g.nv(), nw = g.nw();
 
-    // semilagAdvectField / semilagAdvectVelocity (GPU_Advection.h:530-551) clear their outputs first
-    auto semilagScalar = [&](DeviceField &dst, DeviceField &src, float t) {
-        const int r = reach(t);
-        gs.require({ &src, &VelocityU, &VelocityV, &VelocityW }, r);
-        fl_memset(dst, 0, n * sizeof(float));
-        gpu_semilag(dst, src, VelocityU, VelocityV, VelocityW, 0, 0, 0, h, ni, nj, nk, cfldt, t);
-        gs.produced(dst, std::min(src.valid, vel_valid()) - r);
-    };
-    auto semilagVelocity = [&](DeviceField &uo, DeviceField &vo, DeviceField &wo, DeviceField &us, DeviceField &vs, DeviceField &ws, float t) {
-        const int r = reach(t);
-        gs.require({ &us, &vs, &ws, &VelocityU, &VelocityV, &VelocityW }, r);
-        uo.zero(); vo.zero(); wo.zero();
-        gpu_semilag(uo, us, VelocityU, VelocityV, VelocityW, 1, 0, 0, h, ni, nj, nk, cfldt, t);
-        gpu_semilag(vo, vs, VelocityU, VelocityV, VelocityW, 0, 1, 0, h, ni, nj, nk, cfldt, t);
-        gpu_semilag(wo, ws, VelocityU, VelocityV, VelocityW, 0, 0, 1, h, ni, nj, nk, cfldt, t);
-        const int vv = vel_valid();
-        gs.produced(uo, std::min(us.valid, vv) - r); gs.produced(vo, std::min(vs.valid, vv) - r); gs.produced(wo, std::min(ws.valid, vv) - r);
-    };
-    // the limiter reads `field` around the departure point of a trace over dtc and rewrites `temp` at the node itself
-    auto limiter = [&](DeviceField &field, DeviceField &temp, int bi, int bj, int bk, int dx, int dy, int dz, float dtc) {
-        const int r = reach(dtc);
-        gs.require({ &field, &VelocityU, &VelocityV, &VelocityW }, r);
-        gpu_clamp_extrema(field, temp, VelocityU, VelocityV, VelocityW, bi, bj, bk, dx, dy, dz, 0.5f * dx, 0.5f * dy, 0.5f * dz, h, dtc);
-        gs.produced(temp, std::min(temp.valid, std::min(field.valid, vel_valid()) - r));
-    };
-    auto clampVelocity = [&]() {                         // :283-285, :323-325: source field = VelocityU/V/W
-        limiter(VelocityU, VelocityUTemp, ni + 1, nj, nk, 1, 0, 0, 0.5f * dt);
-        limiter(VelocityV, VelocityVTemp, ni, nj + 1, nk, 0, 1, 0, 0.5f * dt);
-        limiter(VelocityW, VelocityWTemp, ni, nj, nk + 1, 0, 0, 1, 0.5f * dt);
-    };
-    // f1 += coeff * f2
-    auto axpy = [&](DeviceField &f1, DeviceField &f2, float coeff, size_t count) {
-        gs.add(f1, f2, coeff, count);
-        gs.produced(f1, std::min(f1.valid, f2.valid));
-    };
-    auto sources = [&](bool emit) {                      // :289-297 / :330-337
-        if (emit) emitSmoke(framenum, dt);
-        addBuoyancy(0.5f * dt);
-        if (Viscosity) {
-            if (slabs) {
-                diffuseFieldSlab(VelocityU, VelocityUTemp, TempSrcU, ni + 1, nj, nk, 20, Viscosity, 0.5f * dt);
-                diffuseFieldSlab(VelocityV, VelocityVTemp, TempSrcV, ni, nj + 1, nk, 20, Viscosity, 0.5f * dt);
-                diffuseFieldSlab(VelocityW, VelocityWTemp, TempSrcW, ni, nj, nk + 1, 20, Viscosity, 0.5f * dt);
-            } else {
-                diffuseField(VelocityU, VelocityUTemp, TempSrcU, ni + 1, nj, nk, 20, Viscosity, 0.5f * dt);
-                diffuseField(VelocityV, VelocityVTemp, TempSrcV, ni, nj + 1, nk, 20, Viscosity, 0.5f * dt);
-                diffuseField(VelocityW, VelocityWTemp, TempSrcW, ni, nj, nk + 1, 20, Viscosity, 0.5f * dt);
-            }
-        }
-    };
-
-    DeviceField *scal[2] = { &Density, &Temperature }, *tmp[2] = { &DensityTemp, &TemperatureTemp };
-    for (int a = 0; a < 2; a++) {                        // :237-263
-        semilagScalar(*tmp[a], *scal[a], -dt);
-        semilagScalar(TempSrcU, *tmp[a], dt);
-        axpy(*tmp[a], TempSrcU, -0.5f, n);
-        axpy(*tmp[a], *scal[a], 0.5f, n);
-        limiter(*scal[a], *tmp[a], ni, nj, nk, 0, 0, 0, dt);
-        fl_memcpy_d2d(*scal[a], *tmp[a], n * sizeof(float));
-        gs.produced(*scal[a], tmp[a]->valid);
-    }
+    macCormack({ 1, { &Density }, { &Density } }, dt, dt);                  // :237-263
+    macCormack({ 1, { &Temperature }, { &Temperature } }, dt, dt);
     if (!boundaries.empty()) blendBoundary(false);        // clearBoundary (BimocqSolver.cpp:406)
     // :267-287
-    semilagVelocity(VelocityUTemp, VelocityVTemp, VelocityWTemp, VelocityU, VelocityV, VelocityW, -0.5f * dt);
-    semilagVelocity(TempSrcU, TempSrcV, TempSrcW, VelocityUTemp, VelocityVTemp, VelocityWTemp, 0.5f * dt);
-    axpy(VelocityUTemp, TempSrcU, -0.5f, nu); axpy(VelocityVTemp, TempSrcV, -0.5f, nv); axpy(VelocityWTemp, TempSrcW, -0.5f, nw);
-    axpy(VelocityUTemp, VelocityU, 0.5f, nu); axpy(VelocityVTemp, VelocityV, 0.5f, nv); axpy(VelocityWTemp, VelocityW, 0.5f, nw);
-    clampVelocity();
-    VelocityU.copy_from(VelocityUTemp); VelocityV.copy_from(VelocityVTemp); VelocityW.copy_from(VelocityWTemp);
+    macCormack({ 3, { &VelocityU, &VelocityV, &VelocityW }, { &VelocityU, &VelocityV, &VelocityW } }, 0.5f * dt, 0.5f * dt);
 
-    sources(true);
+    applySources(true, framenum, dt, 0.5f * dt);              // :289-297
     VelocityUTemp.copy_from(VelocityU); VelocityVTemp.copy_from(VelocityV); VelocityWTemp.copy_from(VelocityW);   // :299-303
     projection();                                        // :305
-    if (slabs) vmax = std::max(vmax, gpu_max_abs3(VelocityU, VelocityV, VelocityW, g.ni, g.nj, g.nk));
+    if (slabs) step_vmax_ = std::max(step_vmax_, gpu_max_abs3(VelocityU, VelocityV, VelocityW, g.ni, g.nj, g.nk));
     gpu_mad(duProj, VelocityU, VelocityUTemp, 2.f, -1.f, (int)nu);      // :307-309
     gpu_mad(dvProj, VelocityV, VelocityVTemp, 2.f, -1.f, (int)nv);
     gpu_mad(dwProj, VelocityW, VelocityWTemp, 2.f, -1.f, (int)nw);
     gs.produced(duProj, std::min(VelocityU.valid, VelocityUTemp.valid));
     gs.produced(dvProj, std::min(VelocityV.valid, VelocityVTemp.valid));
     gs.produced(dwProj, std::min(VelocityW.valid, VelocityWTemp.valid));
-    semilagVelocity(VelocityUTemp, VelocityVTemp, VelocityWTemp, duProj, dvProj, dwProj, -0.5f * dt);             // :311
-    semilagVelocity(TempSrcU, TempSrcV, TempSrcW, VelocityUTemp, VelocityVTemp, VelocityWTemp, 0.5f * dt);        // :313
-    axpy(VelocityUTemp, TempSrcU, -0.5f, nu); axpy(VelocityVTemp, TempSrcV, -0.5f, nv); axpy(VelocityWTemp, TempSrcW, -0.5f, nw);
-    axpy(VelocityUTemp, duProj, 0.5f, nu); axpy(VelocityVTemp, dvProj, 0.5f, nv); axpy(VelocityWTemp, dwProj, 0.5f, nw);
-    clampVelocity();
-    VelocityU.copy_from(VelocityUTemp); VelocityV.copy_from(VelocityVTemp); VelocityW.copy_from(VelocityWTemp);
-    sources(false);
+    // :311-325: d*Proj is advected, the limiter looks at Velocity*, which the result replaces
+    macCormack({ 3, { &duProj, &dvProj, &dwProj }, { &VelocityU, &VelocityV, &VelocityW } }, 0.5f * dt, 0.5f * dt);
+    applySources(false, framenum, dt, 0.5f * dt);             // :330-337
     projection();
     steps_taken++;
 }

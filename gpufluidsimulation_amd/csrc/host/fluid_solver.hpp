@@ -36,6 +36,23 @@ public:
     void advance(int framenum, float dt);
     void advanceBimocq(int framenum, float dt);
     void advanceReflection(int framenum, float dt);
+    void advanceMacCormack(int framenum, float dt);
+    // MacCormack advection, the building block of both schemes above (fluid_solver.cpp).  adv: what is advected; field: what
+    // the limiter looks at and the result replaces (the two differ in the reflection scheme's second half only).
+    struct MacCormackFields { int count; DeviceField *adv[3]; DeviceField *field[3]; };   // count 1: a scalar, 3: u, v, w
+    void macCormack(const MacCormackFields &f, float t, float dt_clamp);
+    // BQ_OPT_FUSED_MACCORMACK: 0 the separate launches everywhere, 1 (default) gpu_maccormack in the MACCORMACK scheme,
+    // 2 in MAC_REFLECTION too.  An operator library without gpu_maccormack runs the separate launches.
+    int  fused_maccormack = 1;
+    bool fusedMacCormack() const;
+    bool beginSchemeStep();
+    int  reach(float t) const;              // ghost planes a look-up after a trace over t can touch
+    int  velValid() const;
+    void semilagScalar(DeviceField &dst, DeviceField &src, float t);
+    void semilagVelocity(DeviceField &uo, DeviceField &vo, DeviceField &wo, DeviceField &us, DeviceField &vs, DeviceField &ws, float t);
+    void limiter(DeviceField &field, DeviceField &temp, int dx, int dy, int dz, float dtc);
+    void axpy(DeviceField &f1, DeviceField &f2, float coeff, size_t count);
+    void applySources(bool emit, int framenum, float dt_emit, float dt_forces);
     float getCFL();
     void emitSmoke(int framenum, float dt);
     void addBuoyancy(float dt);
@@ -92,6 +109,7 @@ public:
     GridDims g;
     float CellSize, MaxVelocity = 0.f, Viscosity;
     float last_cfldt = 0.f, last_ms = 0.f;
+    float step_cfldt_ = 0.f, step_vmax_ = 0.f;      // MacCormack / reflection step: getCFL()'s bound, speed bound of the traces
 
     DeviceField VelocityU, VelocityV, VelocityW;
     DeviceField VelocityUInit, VelocityVInit, VelocityWInit;

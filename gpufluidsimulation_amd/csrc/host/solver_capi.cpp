@@ -25,7 +25,7 @@ bq_solver *bq_solver_create(int device, int nx, int ny, int nz, float L, float v
 bq_solver *bq_solver_create_slab(int device, int nx, int ny, int nz, float L, float viscosity, float blend, int scheme,
                                  int rank, int nranks, int ghost)
 {
-    if (nx < 8 || ny < 8 || nz < 8 || (scheme != BQ_SCHEME_BIMOCQ && scheme != BQ_SCHEME_MAC_REFLECTION)) return nullptr;
+    if (nx < 8 || ny < 8 || nz < 8 || (scheme != BQ_SCHEME_BIMOCQ && scheme != BQ_SCHEME_MACCORMACK && scheme != BQ_SCHEME_MAC_REFLECTION)) return nullptr;
     SlabCtx sl;
     if (nranks > 1 || ghost > 0) {
         // even z-slabs: rank r owns planes [r*nz/nranks, (r+1)*nz/nranks); each must be deeper than the ghost zone
@@ -40,7 +40,8 @@ bq_solver *bq_solver_create_slab(int device, int nx, int ny, int nz, float L, fl
     s->ctx = fl_context_current();
     s->mapper = std::make_unique<gpuMapper>(device, nx, ny, nz, L / nx, sl);   // main.cpp:151 / :37 (h = L/ni)
     if (!s->mapper->ok()) return nullptr;
-    s->solver = std::make_unique<BimocqGPUSolver>(nx, ny, nz, L, viscosity, blend, scheme == BQ_SCHEME_MAC_REFLECTION ? MAC_REFLECTION : BIMOCQ, s->mapper.get());
+    s->solver = std::make_unique<BimocqGPUSolver>(nx, ny, nz, L, viscosity, blend, scheme == BQ_SCHEME_MAC_REFLECTION ? MAC_REFLECTION : scheme == BQ_SCHEME_MACCORMACK ? MACCORMACK : BIMOCQ,
+                                                  s->mapper.get());
     if (!s->solver->ok()) return nullptr;
     return s.release();
 }
@@ -143,6 +144,9 @@ void bq_solver_set_option(bq_solver *s, int option, int value)
         s->solver->setTravelLimit(value);
     } else if (option == BQ_OPT_PROFILE_PHASES) {
         s->solver->profile_phases = value != 0;
+    } else if (option == BQ_OPT_FUSED_MACCORMACK) {
+        if (value < 0 || value > 2) { fl_report_error(FL_ERR_BAD_ARGUMENT, "BQ_OPT_FUSED_MACCORMACK: 0, 1 or 2"); return; }
+        s->solver->fused_maccormack = value;
     } else if (option == BQ_OPT_REINIT_POLICY) {
         s->solver->setReinitPolicy(value);
         s->solver->ScalarAdvector.keepDmcBorder = s->solver->VelocityAdvector.keepDmcBorder;
@@ -167,6 +171,7 @@ int bq_solver_get_option(const bq_solver *s, int option)
     case BQ_OPT_SHALLOW_BLOCKING_EXCHANGE: return s->solver->GpuSolver->shallow_blocking;
     case BQ_OPT_PROFILE_PHASES:      return s->solver->profile_phases ? 1 : 0;
     case BQ_OPT_REINIT_MAX_TRAVEL:   return s->solver->travel_limit;
+    case BQ_OPT_FUSED_MACCORMACK:    return s->solver->fused_maccormack;
     default:                         return -1;
     }
 }

@@ -211,6 +211,10 @@ HOST_SIGS = {
     "bq_solver_pcg_pressure": (C.c_long, [C.c_void_p, C.POINTER(C.c_double), C.c_long]),
 }
 PROJECTION_JACOBI, PROJECTION_MGCG, PROJECTION_PCG = 0, 1, 2
+# enum Scheme of the reference (BimocqSolver.h:29) as far as it is built: SEMILAG (1) is refused
+SCHEME_BIMOCQ, SCHEME_MACCORMACK, SCHEME_MAC_REFLECTION = 0, 2, 3
+# setOption(OPT_FUSED_MACCORMACK, v): 0 separate launches, 1 (default) gpu_maccormack in scheme 2, 2 in scheme 3 too
+OPT_FUSED_MACCORMACK = 15
 PCG_STOP = {0: "converged", 1: "iteration limit", 2: "breakdown"}
 PHASES = ("maps", "advect_compensate", "forces", "projection", "accumulate_reinit")
 
@@ -242,7 +246,8 @@ class BimocqGPUSolver:
     def __init__(self, nx, ny, nz, L=1.0, viscosity=0.0, blend=1.0, device=0, lib=None, errlib=None,
                  rank=0, nranks=1, ghost=0, scheme=0):
         """nz is the GLOBAL plane count; with nranks > 1 (or ghost > 0) this object is one z-slab rank
-        (set the communicator up first: gpufluidsimulation_amd.transport)."""
+        (set the communicator up first: gpufluidsimulation_amd.transport).  scheme: SCHEME_BIMOCQ, SCHEME_MACCORMACK or
+        SCHEME_MAC_REFLECTION."""
         self.lib = lib or host_lib()
         self.errlib = errlib or (_lib.hip_lib() if lib is None else lib)
         self.nx, self.ny, self.nz = nx, ny, nz
@@ -315,7 +320,8 @@ class BimocqGPUSolver:
     def setOption(self, option, value):
         """option 1 = BQ_OPT_KEEP_DMC_BORDER, 2 = BQ_OPT_REINIT_POLICY (0 every frame, 1 distortion-driven),
         3 = BQ_OPT_FULL_STATE, 4 = BQ_OPT_FUSED_HOUSEKEEPING, 5 = BQ_OPT_OVERLAP_EXCHANGES, 6 = BQ_OPT_SHALLOW_BLOCKING_EXCHANGE,
-        7 = BQ_OPT_JACOBI_ENDS_FIRST, 8 = BQ_OPT_PROFILE_PHASES, 9 = BQ_OPT_REINIT_MAX_TRAVEL, 10 = BQ_OPT_JACOBI_TRIPLES, 14 = BQ_OPT_NODE_LOOKUPS (include/bimocq_solver.h)"""
+        7 = BQ_OPT_JACOBI_ENDS_FIRST, 8 = BQ_OPT_PROFILE_PHASES, 9 = BQ_OPT_REINIT_MAX_TRAVEL, 10 = BQ_OPT_JACOBI_TRIPLES, 14 = BQ_OPT_NODE_LOOKUPS,
+        15 = BQ_OPT_FUSED_MACCORMACK (include/bimocq_solver.h)"""
         self.lib.bq_solver_set_option(self.s, option, value)
         self._check()
 

@@ -179,6 +179,23 @@ void gpu_clamp_extrema(float *field, float *fieldTemp, float *u, float *v, float
                        int ni, int nj, int nk, int dimx, int dimy, int dimz,
                        float ox, float oy, float oz, float h, float dt);
 
+/* (ours) The MacCormack correction and its limiter in one launch: what the reflection scheme issues after its first
+ * semi-Lagrangian pass (BimocqGPUSolver.cpp:240-262), for one field.  `out` receives, value for value, what
+ *     back = 0;  gpu_semilag(back, f1, u, v, w, dim_x, dim_y, dim_z, h, ni, nj, nk, cfldt, dt);
+ *     out = f1;  gpu_add(out, back, -0.5f, n);  gpu_add(out, f_adv, 0.5f, n);
+ *     gpu_clamp_extrema(f_lim, out, u, v, w, ni + dim_x, nj + dim_y, nk + dim_z, dim_x, dim_y, dim_z,
+ *                       0.5f * dim_x, 0.5f * dim_y, 0.5f * dim_z, h, dt_clamp);
+ * leaves there (n = the buffer's element count): two separately rounded products and sums, back = 0 at the nodes
+ * outside gpu_semilag's window.  f1: the caller's first pass, gpu_semilag(..., -dt) of f_adv into a cleared buffer;
+ * f_adv: the field that was advected; f_lim: the field the limiter looks at (f_adv itself, except in the reflection
+ * scheme's second half).  ni, nj, nk: CELL dims as in gpu_semilag; every buffer holds (ni + dim_x)(nj + dim_y)(nk + dim_z)
+ * floats and EVERY node of `out` is written: it needs no clear.  The inputs are read only.  Honours the z-slab context.
+ * FL_ERR_BAD_ARGUMENT, nothing launched: `out` aliasing f1, f_adv, f_lim, u, v or w; cfldt <= 0 with dt != 0; a stagger
+ * triple other than (0,0,0), (1,0,0), (0,1,0), (0,0,1). */
+void gpu_maccormack(float *out, const float *f1, const float *f_adv, const float *f_lim,
+                    float *u, float *v, float *w, int dim_x, int dim_y, int dim_z,
+                    float h, int ni, int nj, int nk, float cfldt, float dt, float dt_clamp);
+
 /* GPU_Advection.h:103 / GPU_kernel.cu:959-964.  field = c1*field1 + c2*field2. */
 void gpu_mad(float *field, float *field1, float *field2, float coeff1, float coeff2, int number);
 
@@ -202,7 +219,7 @@ void gpu_multi_grid_conjugate_gradient(float *u, float *v, float *w, double *div
 
 /* ---- Limits of the operators above (part of the ABI contract; each violation latches an error, nothing is launched) ----
  *   * ONE field must stay below 2 GiB: 4 (ni+1)(nj+1)(nk+1) < 2^31 bytes.  The gather kernels (gpu_solve_*, gpu_advect_*,
- *     gpu_compensate_*, gpu_accumulate_*, gpu_semilag, gpu_clamp_extrema, gpu_estimate_distortion) address a field through
+ *     gpu_compensate_*, gpu_accumulate_*, gpu_semilag, gpu_clamp_extrema, gpu_maccormack, gpu_estimate_distortion) address a field through
  *     a buffer resource descriptor with 32-bit byte offsets, and the offset 2 GiB is where a cell whose base index is
  *     negative is parked so that the descriptor's range check zeroes its corners (FL_ERR_BAD_ARGUMENT "field larger than
  *     2 GiB").  512^3 is 0.5 GiB; BASELINE config 5 (1024 x 1024 x 512 = 2.0 GiB per field) needs >= 2 z-slab ranks --

@@ -26,8 +26,10 @@ typedef struct bq_emitter {
 } bq_emitter;
 
 /* enum Scheme, BimocqSolver.h:29.  The reference's GPU solver implements BIMOCQ and MAC_REFLECTION
- * (BimocqGPUSolver.cpp:112-122); the reflection scheme runs with the corrected limiter (gpu_clamp_extrema). */
-enum { BQ_SCHEME_BIMOCQ = 0, BQ_SCHEME_MAC_REFLECTION = 3 };
+ * (BimocqGPUSolver.cpp:112-122); MACCORMACK is its CPU solver's advanceMacCormack (BimocqSolver.cpp:282-364) on device
+ * buffers.  Both MacCormack schemes run with the corrected limiter (gpu_clamp_extrema).  SEMILAG
+ * (1) is not built: bq_solver_create returns NULL for it. */
+enum { BQ_SCHEME_BIMOCQ = 0, BQ_SCHEME_MACCORMACK = 2, BQ_SCHEME_MAC_REFLECTION = 3 };
 enum {
     BQ_PROJECTION_JACOBI = 0,           /* the `#if 0` branch of BimocqGPUSolver::projection (:408-417); iters = sweeps      */
     BQ_PROJECTION_MGCG = 1,             /* the `#else` branch (:443-446): fp64 multigrid-CG; iters = outer iterations (50)  */
@@ -138,7 +140,13 @@ enum {
      * sub-step and the forward update after a re-initialisation) -- through gpu_solve_backwardDMC_hint / gpu_solve_forward_hint
      * (include/bimocq_gpu.h).  The kernels then look the velocity up at grid nodes as the mean of two values and compute
      * identity-map corners instead of loading them.  Same bits.  0: the reference entry points, for A/B runs. */
-    BQ_OPT_NODE_LOOKUPS = 14
+    BQ_OPT_NODE_LOOKUPS = 14,
+    /* The MacCormack advection of a field (schemes MACCORMACK and MAC_REFLECTION) after its first semi-Lagrangian pass: 0 =
+     * the reference's launches (clear + second pass, two adds, the limiter, a copy); 1 (default) = one gpu_maccormack launch
+     * (include/bimocq_gpu.h) in the MACCORMACK scheme, whose result becomes the field by a buffer swap; 2 = in MAC_REFLECTION
+     * too.  With 0 and 1 the reflection scheme issues the launches it always did.  Same values in every field either way.
+     * An operator library without gpu_maccormack runs the separate launches whatever the value. */
+    BQ_OPT_FUSED_MACCORMACK = 15
 };
 /* BQ_OPT_PROFILE_PHASES: milliseconds per phase summed over the steps since the last reset -- map update (DMC + RK3,
  * BimocqGPUSolver.cpp:136-139), advection with error compensation (:143-145), sources and forces (:157-177), projection
