@@ -10,6 +10,7 @@
 //
 // RCCL is dlopen'ed on first use, so single-GPU runs never load it.
 #include "bq_host.h"
+#include "bq_box_chunk.h"
 
 #include <dlfcn.h>
 #include <cstdlib>
@@ -453,14 +454,7 @@ void fl_halo_exchange(int n, float *const *fields, const size_t *plane_elems, co
 } // extern "C"
 
 // ---- wall sheets (include/bimocq_gpu.h, section 4): box gather / scatter and point-to-point messages -------------
-namespace {
-constexpr int kBoxChunk = 64;
-struct BoxChunk {
-    int n;
-    int x0[kBoxChunk], y0[kBoxChunk], z0[kBoxChunk], wx[kBoxChunk], wy[kBoxChunk];
-    long long off[kBoxChunk + 1];       // element offset of each box inside this chunk's packed range
-};
-}
+using bq::box::BoxChunk;     // bq_box_chunk.h: the chunk a launch takes by value, and the rule that fills it
 
 // one thread per packed element; MODE 0: packed <- field, 1: field <- packed, 2: field <- NaN,
 // 3: packed[same global cell] <- field, `packed` being a second field that holds the planes [koff2, ...)
@@ -491,22 +485,18 @@ static void box_copy(float *field, int nbi, int nbj, int nk_field, int koff, con
     if (!ensure_ready(op)) return;
     if (nboxes <= 0) return;
     if (!field || !boxes || (MODE != 2 && !packed) || nbi < 1 || nbj < 1 || nk_field < 1) { latch(FL_ERR_BAD_ARGUMENT, op, "null pointer or bad dims"); return; }
-    long long base = 0;
-    for (int first = 0; first < nboxes; first += kBoxChunk) {
-        BoxChunk c;
-        c.n = 0; c.off[0] = 0;
-        for (int b = first; b < nboxes && c.n < kBoxChunk; b++) {
-            const fl_box &q = boxes[b];
-            if (q.x0 < 0 || q.y0 < 0 || q.z0 < koff || q.x1 > nbi || q.y1 > nbj || q.z1 > koff + nk_field || q.x1 < q.x0 || q.y1 < q.y0 || q.z1 < q.z0) {
-                latch(FL_ERR_BAD_ARGUMENT, op, "box outside the field"); return;
-            }
-            if (MODE == 3 && (q.z0 < koff2 || q.z1 > koff2 + nk2)) { latch(FL_ERR_BAD_ARGUMENT, op, "box outside the destination"); return; }
-            const long long vol = (long long)(q.x1 - q.x0) * (q.y1 - q.y0) * (q.z1 - q.z0);
-            if (vol == 0) continue;
-            c.x0[c.n] = q.x0; c.y0[c.n] = q.y0; c.z0[c.n] = q.z0; c.wx[c.n] = q.x1 - q.x0; c.wy[c.n] = q.y1 - q.y0;
-            c.off[c.n + 1] = c.off[c.n] + vol;
-            c.n++;
+    // every box is checked before the first launch: a refused list leaves the buffers as they were
+    for (int b = 0; b < nboxes; b++) {
+        const fl_box &q = boxes[b];
+        if (q.x0 < 0 || q.y0 < 0 || q.z0 < koff || q.x1 > nbi || q.y1 > nbj || q.z1 > koff + nk_field || q.x1 < q.x0 || q.y1 < q.y0 || q.z1 < q.z0) {
+            latch(FL_ERR_BAD_ARGUMENT, op, "box outside the field"); return;
         }
+        if (MODE == 3 && (q.z0 < koff2 || q.z1 > koff2 + nk2)) { latch(FL_ERR_BAD_ARGUMENT, op, "box outside the destination"); return; }
+    }
+    long long base = 0;
+    for (int first = 0; first < nboxes;) {
+        BoxChunk c;
+        first = box::fill_chunk(boxes, nboxes, first, c);       // continues where the previous chunk stopped
         const long long total = c.off[c.n];
         if (total == 0) continue;
         const int blocks = (int)std::min<long long>((total + 255) / 256, 4096);

@@ -49,14 +49,15 @@ __global__ __launch_bounds__(256) void gradient_kernel(float *__restrict__ u, fl
 {
     const int i = blockIdx.x * 64 + threadIdx.x, j = blockIdx.y * 4 + threadIdx.y, k = blockIdx.z;
     const int kg = k + sl.koff;
-    if (i < 2 || i >= ni || j < 2 || j >= nj || kg < 2 || kg >= sl.nkg || k < 1) return;
+    if (i < 2 || i >= ni || j < 2 || j >= nj || kg < 2 || kg >= sl.nkg) return;
     const size_t ic = (size_t)i + (size_t)ni * ((size_t)j + (size_t)nj * k);
     const float p0 = p[ic];
     const size_t iu = (size_t)i + (size_t)(ni + 1) * ((size_t)j + (size_t)nj * k);
     const size_t iv = (size_t)i + (size_t)ni * ((size_t)j + (size_t)(nj + 1) * k);
     u[iu] -= halfrdx * (p0 - p[ic - 1]);
     v[iv] -= halfrdx * (p0 - p[ic - ni]);
-    w[ic] -= halfrdx * (p0 - p[ic - (size_t)ni * nj]);
+    // a slab rank's first local plane can lie inside the global window (kg >= 2): u and v need no plane below it, w does
+    if (k >= 1) w[ic] -= halfrdx * (p0 - p[ic - (size_t)ni * nj]);
 }
 
 // The same update that also hands out what it changed: d = u_new - u_old on the window, 0 elsewhere -- exactly
@@ -71,18 +72,21 @@ __global__ __launch_bounds__(256) void gradient_delta_kernel(float *__restrict__
     const int i = blockIdx.x * 64 + threadIdx.x, j = blockIdx.y * 4 + threadIdx.y, k = blockIdx.z;
     if (i > ni || j > nj || k > nk) return;
     const int kg = k + sl.koff;
-    const bool win = !(i < 2 || i >= ni || j < 2 || j >= nj || kg < 2 || kg >= sl.nkg || k < 1 || k >= nk);
+    const bool win = !(i < 2 || i >= ni || j < 2 || j >= nj || kg < 2 || kg >= sl.nkg || k >= nk);
     const size_t iu = (size_t)i + (size_t)(ni + 1) * ((size_t)j + (size_t)nj * k);
     const size_t iv = (size_t)i + (size_t)ni * ((size_t)j + (size_t)(nj + 1) * k);
     const size_t ic = (size_t)i + (size_t)ni * ((size_t)j + (size_t)nj * k);
     if (win) {
         const float p0 = p[ic];
-        const float uo = u[iu], vo = v[iv], wo = w[ic];
+        const float uo = u[iu], vo = v[iv];
         const float un = uo - halfrdx * (p0 - p[ic - 1]);
         const float vn = vo - halfrdx * (p0 - p[ic - ni]);
-        const float wn = wo - halfrdx * (p0 - p[ic - (size_t)ni * nj]);
-        u[iu] = un; v[iv] = vn; w[ic] = wn;
-        du[iu] = un - uo; dv[iv] = vn - vo; dw[ic] = wn - wo;
+        u[iu] = un; v[iv] = vn;
+        du[iu] = un - uo; dv[iv] = vn - vo;
+        if (k >= 1) {       // as in gradient_kernel: w alone needs the plane below
+            const float wo = w[ic], wn = wo - halfrdx * (p0 - p[ic - (size_t)ni * nj]);
+            w[ic] = wn; dw[ic] = wn - wo;
+        } else dw[ic] = 0.f;
     } else {
         if (j < nj && k < nk) du[iu] = 0.f;                  // the u buffer has ni+1 columns
         if (i < ni && k < nk) dv[iv] = 0.f;                  // the v buffer has nj+1 rows

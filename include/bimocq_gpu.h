@@ -473,6 +473,11 @@ void gpu_divergence(const float *u, const float *v, const float *w, float *div,
  * iterate ends in p, 1 if it ends in p_temp.  Boundary cells are never written. */
 int  gpu_jacobi_sweeps(float *p, const float *div, float *p_temp,
                        int ni, int nj, int nk, int sweeps, float alpha, float beta);
+/* window: cells 2 <= i < ni, 2 <= j < nj, 2 <= kg < nk_global (kg the GLOBAL plane on a z-slab rank).  A slab rank's first
+ * local plane may lie inside it: u and v are updated there too, w -- which reads the plane below -- is not.  The rule of
+ * gpu_gradient, gpu_gradient_delta and the gradient stage of gpu_projection_jacobi alike (the oracle's orc_gradient).
+ * gpu_multi_grid_conjugate_gradient_slab differs on purpose: it keeps its pressure on its own plane range and promises the
+ * projected velocity on the owned planes and 7 ghost planes only, so it leaves the whole first stored plane alone. */
 void gpu_gradient(float *u, float *v, float *w, const float *p,
                   int ni, int nj, int nk, float halfrdx);
 /* gpu_gradient that also returns what it changed: (du, dv, dw) = new - old on the update window, 0 elsewhere --
@@ -654,6 +659,9 @@ void fl_comm_set_null(int rank, int nranks);
  * ranks that own them into a copy of the sampled field that spans the needed global planes, and re-evaluates the wall
  * layers from that copy.  Pieces (host computes WHICH boxes; csrc/host/wall_sheets.*): */
 typedef struct fl_box { int x0, x1, y0, y1, z0, z1; } fl_box;   /* half-open, GLOBAL indices of the field's buffer */
+/* All three box calls: a box that leaves the field (fl_box_copy: the source's or the destination's planes) or is inverted
+ * (x1 < x0, ...) latches FL_ERR_BAD_ARGUMENT for the whole list before anything is written; zero-volume boxes are legal and
+ * take no room in `packed`; nboxes == 0 is a no-op. */
 /* packed <- the boxes of `field`, one after the other, x fastest.  `field` holds the global planes [koff, koff + nk_field)
  * of a buffer with rows of nbi and planes of nbi*nbj floats; every box must lie inside them.  `boxes` is a HOST array. */
 void fl_box_pack(const float *field, int nbi, int nbj, int nk_field, int koff, const fl_box *boxes, int nboxes, float *packed);
@@ -680,7 +688,9 @@ void fl_comm_set_custom_p2p(fl_p2p_cb p2p);
  * GLOBAL plane in zlist (host arrays, at most 8 entries each), the source read from `src`, which holds the global
  * planes [src_koff, src_koff + src_nk) of the sampled field:  dst = before + blend9(coeff * src(map(x))), `before`
  * being dst's value ahead of the stage (gpu_compensate_*'s stage-2 copy).  axis: -1 scalar, 0/1/2 = u/v/w buffers.
- * The maps and before/dst are local slab buffers (slab context, plane window honoured). */
+ * The maps and before/dst are local slab buffers (slab context, plane window honoured).  A node of a slab's FIRST local plane
+ * looks its map up in cells that start one plane below the buffer: where that plane lies inside the global window its listed
+ * nodes are written, but with unspecified ghost data (as with every nine-point operator there; no host reads that plane). */
 void gpu_accumulate_wall_fixup(const float *src, int src_koff, int src_nk, const float *before, float *dst,
                                const float *mx, const float *my, const float *mz,
                                float h, int ni, int nj, int nk, int axis, float coeff,

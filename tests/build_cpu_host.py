@@ -6,6 +6,7 @@ GPU tests as references.  Test infrastructure.
   build_levelsets()  ..._levelsets.so: + the level-set operators (tests/cpu_abi/levelset_abi.c)
   build_launch_geom() tests/_build/liblaunch_geom.so: csrc/bq_launch_geom.h behind tests/cpu_abi/launch_geom_shim.cpp
   build_jacobi_plan() tests/_build/libjacobi_plan.so: csrc/bq_jacobi_plan.h behind tests/cpu_abi/jacobi_plan_shim.cpp
+  build_box_chunk()  tests/_build/libbox_chunk.so: csrc/bq_box_chunk.h behind tests/cpu_abi/box_chunk_shim.cpp
 A stand-in without some operators leaves the host solver's weak references to them null: set_boundary refuses there."""
 import glob
 import os
@@ -80,5 +81,10 @@ def build_jacobi_plan():
     return _build_header_shim("libjacobi_plan.so", "jacobi_plan_shim.cpp", ["bq_jacobi_plan.h", "bq_launch_geom.h"])
 
 
+def build_box_chunk():
+    """how the box copies cut a box list into launches"""
+    return _build_header_shim("libbox_chunk.so", "box_chunk_shim.cpp", ["bq_box_chunk.h"])
+
+
 if __name__ == "__main__":
-    print(build(), build_obstacles(), build_levelsets(), build_launch_geom(), build_jacobi_plan())
+    print(build(), build_obstacles(), build_levelsets(), build_launch_geom(), build_jacobi_plan(), build_box_chunk())

@@ -218,9 +218,14 @@ void fl_p2p_exchange_begin(int n, const int *peers, float *const *send, const si
 static void box_copy(float *field, int nbi, int nbj, int nk_field, int koff, const fl_box *boxes, int nboxes, float *packed, int mode)
 {
     size_t t = 0;
+    for (int b = 0; b < nboxes; b++) {      /* a refused list leaves the buffers as they were */
+        const fl_box q = boxes[b];
+        if (q.x0 < 0 || q.y0 < 0 || q.z0 < koff || q.x1 > nbi || q.y1 > nbj || q.z1 > koff + nk_field || q.x1 < q.x0 || q.y1 < q.y0 || q.z1 < q.z0) {
+            latch(FL_ERR_BAD_ARGUMENT, "fl_box_*: box outside the field"); return;
+        }
+    }
     for (int b = 0; b < nboxes; b++) {
         const fl_box q = boxes[b];
-        if (q.x0 < 0 || q.y0 < 0 || q.z0 < koff || q.x1 > nbi || q.y1 > nbj || q.z1 > koff + nk_field) { latch(FL_ERR_BAD_ARGUMENT, "fl_box_*: box outside the field"); return; }
         for (int z = q.z0; z < q.z1; z++)
             for (int y = q.y0; y < q.y1; y++)
                 for (int x = q.x0; x < q.x1; x++, t++) {
@@ -240,9 +245,13 @@ void fl_box_copy(const float *src, int nbi, int nbj, int nk_src, int koff_src, f
 {
     for (int b = 0; b < nboxes; b++) {
         const fl_box q = boxes[b];
-        if (q.x0 < 0 || q.y0 < 0 || q.z0 < koff_src || q.z0 < koff_dst || q.x1 > nbi || q.y1 > nbj || q.z1 > koff_src + nk_src || q.z1 > koff_dst + nk_dst) {
+        if (q.x0 < 0 || q.y0 < 0 || q.z0 < koff_src || q.z0 < koff_dst || q.x1 > nbi || q.y1 > nbj || q.z1 > koff_src + nk_src || q.z1 > koff_dst + nk_dst ||
+            q.x1 < q.x0 || q.y1 < q.y0 || q.z1 < q.z0) {
             latch(FL_ERR_BAD_ARGUMENT, "fl_box_copy: box outside a field"); return;
         }
+    }
+    for (int b = 0; b < nboxes; b++) {
+        const fl_box q = boxes[b];
         for (int z = q.z0; z < q.z1; z++)
             for (int y = q.y0; y < q.y1; y++)
                 for (int x = q.x0; x < q.x1; x++)
@@ -254,7 +263,10 @@ void gpu_accumulate_wall_fixup(const float *src, int src_koff, int src_nk, const
                                const float *mx, const float *my, const float *mz,
                                float h, int ni, int nj, int nk, int axis, float coeff,
                                const int *xlist, int nxl, const int *ylist, int nyl, const int *zlist, int nzl)
-{ orc_accumulate_wall_fixup(src, src_koff, src_nk, before, dst, mx, my, mz, h, ni, nj, nk, axis, coeff, xlist, nxl, ylist, nyl, zlist, nzl); }
+{
+    if (axis < -1 || axis > 2 || nxl < 0 || nyl < 0 || nzl < 0 || nxl > 8 || nyl > 8 || nzl > 8) { latch(FL_ERR_BAD_ARGUMENT, "gpu_accumulate_wall_fixup"); return; }
+    orc_accumulate_wall_fixup(src, src_koff, src_nk, before, dst, mx, my, mz, h, ni, nj, nk, axis, coeff, xlist, nxl, ylist, nyl, zlist, nzl);
+}
 
 /* the stand-in has one arithmetic path: the precondition checks may simply say no */
 void fl_map_guard_reset(int which) { (void)which; }
@@ -314,6 +326,7 @@ void gpu_accumulate_velocity2(float *u1, float *v1, float *w1, float k1, float *
 void gpu_accumulate_component(float *c1, float k1, float *c2, float k2, float *d, float *fx, float *fy, float *fz,
                               float h, int ni, int nj, int nk, int axis, bool pt)
 {
+    if (axis < 0 || axis > 2) { latch(FL_ERR_BAD_ARGUMENT, "gpu_accumulate_component"); return; }
     orc_accumulate_component(c1, d, fx, fy, fz, h, ni, nj, nk, axis, pt, k1);
     if (c2) orc_accumulate_component(c2, d, fx, fy, fz, h, ni, nj, nk, axis, pt, k2);
 }

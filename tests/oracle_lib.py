@@ -12,6 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORACLE_DIR = os.path.join(ROOT, "oracle")
 
 FP = C.POINTER(C.c_float)
+IP = C.POINTER(C.c_int)
 c_f, c_i = C.c_float, C.c_int
 
 
@@ -106,6 +107,12 @@ _SIGS = {
     "orc_advect_field_double": (None, [FP] * 8 + [c_f, c_i, c_i, c_i, c_i, c_f]),
     "orc_accumulate_velocity": (None, [FP] * 9 + [c_f, c_i, c_i, c_i, c_i, c_f]),
     "orc_accumulate_field": (None, [FP] * 5 + [c_f, c_i, c_i, c_i, c_i, c_f]),
+    "orc_accumulate_component": (None, [FP] * 5 + [c_f, c_i, c_i, c_i, c_i, c_i, c_f]),
+    "orc_accumulate_wall_fixup": (None, [FP, c_i, c_i] + [FP] * 5 + [c_f, c_i, c_i, c_i, c_i, c_f] + [IP, c_i] * 3),
+    "orc_clamp_extrema_box_w": (None, [FP, FP, c_i, c_i, c_i]),
+    "orc_diffuse_sweeps": (c_i, [FP] * 3 + [c_i, c_i, c_i, c_i, c_f]),
+    "orc_set_slab": (None, [c_i] * 5),
+    "orc_set_plane_window": (None, [c_i] * 3),
     "orc_estimate_distortion": (None, [FP] * 7 + [c_f, c_i, c_i, c_i]),
     "orc_add": (None, [FP, FP, c_f, c_i]),
     "orc_compensate_velocity": (None, [FP] * 15 + [c_f, c_i, c_i, c_i, c_i]),

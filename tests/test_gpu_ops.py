@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import fields as F
+from host_entry_case import wild_maps
 from oracle_lib import fp, lib as oracle
 
 pytestmark = pytest.mark.gpu
@@ -461,34 +462,6 @@ def test_clamp_extrema_corrected(gm, ni, nj, nk, h):
         assert F.same(ref, dc.numpy()), (dx, dy, dz)
         assert F.same(field, df.numpy())
     bq.check()
-
-
-def wild_maps(ni, nj, nk, h, phase):
-    """Maps that leave the comfortable range on purpose: the zero border the DMC update leaves behind,
-    positions inside the first cell (q < 1: the lerps must take the contract's two-rounding form), exact zeros,
-    positions outside the domain on both sides, tiny values next to large ones (the 3/4*a midpoint case of the
-    constant-weight lerps), infinities and NaNs.  Deterministic (no RNG)."""
-    maps = F.warped_maps(ni, nj, nk, h, 0.9, phase)
-    n = ni * nj * nk
-    idx = np.arange(n)
-    k, j, i = idx // (ni * nj), (idx // ni) % nj, idx % ni
-    border = (i <= 1) | (i >= ni - 2) | (j <= 1) | (j >= nj - 2) | (k <= 1) | (k >= nk - 2)
-    out = []
-    for c, m in enumerate(maps):
-        m = m.copy()
-        m[border] = 0.0                                                  # Q13
-        sel = (idx * 7 + c * 3) % 23
-        m[sel == 0] *= np.float32(0.01)                                  # inside the first cell
-        m[sel == 1] = np.float32(h) * np.float32(0.999)
-        m[sel == 2] = -m[sel == 2]                                       # below the domain
-        m[sel == 3] *= np.float32(3.0)                                   # possibly above it
-        m[sel == 4] = np.float32(1e-30)                                  # tiny next to O(1)
-        m[sel == 5] = np.float32(2.0 ** -60)
-        m[(idx % 997) == 5 + c] = np.nan
-        m[(idx % 1013) == 7 + c] = np.inf
-        m[(idx % 1019) == 11 + c] = -np.inf
-        out.append(np.ascontiguousarray(m.astype(np.float32)))
-    return out
 
 
 @pytest.mark.parametrize("ni,nj,nk,h", GRIDS + [(40, 24, 16, 1.0 / 64)])
