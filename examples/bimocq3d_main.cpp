@@ -8,7 +8,8 @@
 // rings blown along x by the reference's emitter velocity formula (main.cpp:52-73, emiter = +1 for both: the rear
 // ring catches up and threads the front one -- leapfrogging), no buoyancy, density dumped every frame.
 //
-//   make example && build/bimocq3d [N=128] [frames=20] [outdir=out] [scheme=0|2|3] [projection=0|1] [async=1] [scene=0|1]
+//   make example && build/bimocq3d [N=128] [frames=20] [outdir=out] [scheme=0|2|3] [projection=0|1] [async=1] [scene=0|1] [walls=0]
+// walls: the closed sides (BQ_WALL_* bits of include/bimocq_gpu.h; 55 = the reference CPU solver's container, open at the top)
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -28,8 +29,9 @@ int main(int argc, char **argv)
     const int projection = argc > 5 ? std::atoi(argv[5]) : 0;        // 0 Jacobi, 1 multigrid-CG (what the binary ships)
     const bool async_dump = argc > 6 ? std::atoi(argv[6]) != 0 : true;
     const int scene = argc > 7 ? std::atoi(argv[7]) : 0;             // 0 rising smoke, 1 leapfrogging vortex rings, 2 box-shaped plume source
+    const int walls = argc > 8 ? std::atoi(argv[8]) : BQ_WALLS_NONE; // closed sides, BQ_WALL_* bits: 55 = the reference's container (open top)
     if (n < 8 || total_frame < 1 || (scene == 1 && n % 2) || (scheme != 0 && scheme != 2 && scheme != 3)) {
-        std::fprintf(stderr, "usage: %s [N>=8] [frames] [outdir] [scheme: 0 BiMocq, 2 MacCormack, 3 reflection] [projection] [async] [scene]\n", argv[0]); return 2;
+        std::fprintf(stderr, "usage: %s [N>=8] [frames] [outdir] [scheme: 0 BiMocq, 2 MacCormack, 3 reflection] [projection] [async] [scene] [walls]\n", argv[0]); return 2;
     }
 
     const int ni = n, nj = n, nk = scene == 1 ? n / 2 : n;
@@ -72,6 +74,7 @@ int main(int argc, char **argv)
     }
     if (projection == 1) { mysolver.projection_kind = BQ_PROJECTION_MGCG; mysolver.mg_iters = 50; }
     else                 { mysolver.jacobi_iters = 200; }
+    if (!mysolver.setWalls(walls)) { std::fprintf(stderr, "%s\n", fl_last_error_string()); return 1; }   // (not with projection 1)
     mysolver.verbose = true;                                         // "[Bimocq GPU Time: ...ms ]" like the reference
 
     const auto t0 = std::chrono::steady_clock::now();

@@ -152,6 +152,13 @@ HIP_SIGS = {
     "gpu_pcg_gradient": (None, [VP] * 5 + [c_i, c_i, c_i, c_d]),
     "gpu_semilag_band": (None, [VP] * 5 + [c_i, c_i, c_i] + _G + [c_f, c_f, VP, c_i]),
     "gpu_obstacle_blend": (None, [VP] * 11 + [VP, c_i] + _G),
+    # closed domain walls
+    "gpu_wall_flags": (None, [VP, VP, c_i, c_i, c_i, c_i]),
+    "gpu_wall_faces": (None, [VP] * 7 + [c_i, c_i, c_i]),
+    "gpu_jacobi_sweep_masked_walls": (None, [VP] * 5 + [c_i, c_i, c_i, c_i, c_f, c_f]),
+    "gpu_jacobi_sweeps_masked_walls": (c_i, [VP] * 5 + [c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
+    "gpu_gradient_masked_walls": (None, [VP] * 8 + [c_i, c_i, c_i, c_i, c_f]),
+    "gpu_pcg_gradient_walls": (None, [VP] * 5 + [c_i, c_i, c_i, c_i, c_d]),
     # level-set obstacles (the bq_levelset array travels as a HOST pointer, its phi device pointers: solver.LevelSetDesc)
     "gpu_obstacle_flags_ls": (None, [VP, VP, VP, c_i, VP] + _G),
     "gpu_semilag_band_ls": (None, [VP] * 5 + [c_i, c_i, c_i] + _G + [c_f, c_f, VP, c_i, VP]),

@@ -250,7 +250,7 @@ inline LaunchPlan plan_pair(int ni, int nj, int nk, bool aligned16, const geom::
 // parked on waitcnt / barrier 40 % and stalled at issue 33 % (the L1 path: with the prefetch last the stall moves to the
 // barrier) -- VALU, LDS and L1 path are each 25-40 % busy but take turns between the barriers.
 inline LaunchPlan plan_lds(int ni, int nj, int nk, bool aligned16, const geom::PlaneRanges &pr, const JacobiTuning &tun, int num_cus,
-                           int S, bool masked = false, int min_kc = 0)
+                           int S, bool masked = false, int min_kc = 0, bool walled = false)
 {
     LaunchPlan p;
     if (pr.planes == 0) { p.kernel = Kernel::kEmpty; return p; }
@@ -269,7 +269,9 @@ inline LaunchPlan plan_lds(int ni, int nj, int nk, bool aligned16, const geom::P
     // interiors) -- whatever fills the CUs once, down to 2 planes per chunk
     p.kc = std::max(2, geom::once_per_cu_len(pr.longest, p.row_blocks, pr.nranges, num_cus));
     if (tun.fused_kchunk > 0) p.kc = tun.fused_kchunk;
-    if ((pr.whole && p.kc < tun.lds_min_kc) || p.kc < min_kc) return p;
+    // (the walled launch has no shorter-march kernel to lose to: what it refuses runs one masked sweep per launch, so it takes
+    // whole arrays at whatever length fills the CUs, down to the 2 planes the kernel marches on plane ranges -- 256 x 128 x 40: 3)
+    if ((pr.whole && p.kc < (walled ? 2 : tun.lds_min_kc)) || p.kc < min_kc) return p;
     p.kernel = two_seg ? Kernel::kLds2seg : Kernel::kLds;
     p.nbz = pr.chunks(p.kc).nbz;
     p.nblk = p.row_blocks * p.nbz;
@@ -322,11 +324,12 @@ inline LaunchPlan plan_triple(int ni, int nj, int nk, bool aligned16, const Jaco
     return plan_lean_triple(ni, nj, nk, aligned16, tun, num_cus);
 }
 
-// Three MASKED sweeps in one launch (gpu_jacobi_sweeps_masked): whole array, never on a z-slab rank.
-inline LaunchPlan plan_triple_masked(int ni, int nj, int nk, bool aligned16, const JacobiTuning &tun, int num_cus, bool slab_on)
+// Three MASKED sweeps in one launch (gpu_jacobi_sweeps_masked; walled: gpu_jacobi_sweeps_masked_walls): whole array, never on a
+// z-slab rank.  The walled launch takes the shapes of the masked one, and short chunks too.
+inline LaunchPlan plan_triple_masked(int ni, int nj, int nk, bool aligned16, const JacobiTuning &tun, int num_cus, bool slab_on, bool walled = false)
 {
     if (ni < 3 || nj < 4 || nk < 3 || slab_on) return LaunchPlan{};
-    return plan_lds(ni, nj, nk, aligned16, geom::PlaneRanges(0, 1 << 30, 0, 0, nk), tun, num_cus, 3, true);
+    return plan_lds(ni, nj, nk, aligned16, geom::PlaneRanges(0, 1 << 30, 0, 0, nk), tun, num_cus, 3, true, 0, walled);
 }
 
 // Three sweeps on plane ranges (gpu_jacobi_sweep_triple_ranges): the LDS kernels only.

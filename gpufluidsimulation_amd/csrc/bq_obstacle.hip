@@ -92,15 +92,96 @@ __global__ __launch_bounds__(256) void jacobi_masked_kernel(const float *__restr
     out[id] = s == 6 ? 0.f : sum * bt.b[s];
 }
 
-// ---- masked gradient (gradient_delta_kernel / gradient_kernel with solid faces left alone) ----------------------------
-__global__ __launch_bounds__(256) void gradient_masked_kernel(float *__restrict__ u, float *__restrict__ v, float *__restrict__ w,
-                                                              const float *__restrict__ p,
-                                                              float *__restrict__ du, float *__restrict__ dv, float *__restrict__ dw,
-                                                              const unsigned char *__restrict__ solid, int ni, int nj, int nk, float halfrdx)
+// ---- closed domain walls (BimocqSolver.cpp:938-948) --------------------------------------------------
+// a border cell of a closed side
+__device__ __forceinline__ bool wall_cell(int walls, int i, int j, int k, int ni, int nj, int nk)
+{
+    return ((walls & BQ_WALL_XLO) && i == 0) || ((walls & BQ_WALL_XHI) && i == ni - 1) || ((walls & BQ_WALL_YLO) && j == 0) ||
+           ((walls & BQ_WALL_YHI) && j == nj - 1) || ((walls & BQ_WALL_ZLO) && k == 0) || ((walls & BQ_WALL_ZHI) && k == nk - 1);
+}
+// the solid neighbours of the interior cell (i, j, k) of a grid without obstacles nearby: the closed sides it touches
+__device__ __forceinline__ int wall_neighbours(int walls, int i, int j, int k, int ni, int nj, int nk)
+{
+    return (int)((walls & BQ_WALL_XLO) && i == 1) + (int)((walls & BQ_WALL_XHI) && i == ni - 2) + (int)((walls & BQ_WALL_YLO) && j == 1) +
+           (int)((walls & BQ_WALL_YHI) && j == nj - 2) + (int)((walls & BQ_WALL_ZLO) && k == 1) + (int)((walls & BQ_WALL_ZHI) && k == nk - 2);
+}
+
+// solidw = solid (or 0) with BQ_FLAG_WALL in the wall cells no obstacle covers: one thread per cell
+__global__ __launch_bounds__(256) void wall_flags_kernel(unsigned char *__restrict__ solidw, const unsigned char *__restrict__ solid,
+                                                         int walls, int ni, int nj, int nk)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x, j = blockIdx.y * 4 + threadIdx.y, k = blockIdx.z;
+    if (i >= ni || j >= nj) return;
+    const size_t id = (size_t)i + (size_t)ni * ((size_t)j + (size_t)nj * k);
+    const unsigned char f = solid ? solid[id] : (unsigned char)0;
+    solidw[id] = f ? f : (wall_cell(walls, i, j, k, ni, nj, nk) ? (unsigned char)BQ_FLAG_WALL : (unsigned char)0);
+}
+
+// wall faces: one thread per node of the (ni+1, nj+1, nk+1) super-grid; a face takes 0 when one of its cells is a wall cell
+// and neither is an obstacle cell (those faces are gpu_obstacle_faces')
+__device__ __forceinline__ bool wall_face(int a, int b)
+{
+    return (a == BQ_FLAG_WALL || b == BQ_FLAG_WALL) && (a == 0 || a == BQ_FLAG_WALL) && (b == 0 || b == BQ_FLAG_WALL);
+}
+__global__ __launch_bounds__(256) void wall_faces_kernel(float *__restrict__ u, float *__restrict__ v, float *__restrict__ w,
+                                                         float *__restrict__ du, float *__restrict__ dv, float *__restrict__ dw,
+                                                         const unsigned char *__restrict__ solidw, int ni, int nj, int nk)
 {
     const int i = blockIdx.x * 64 + threadIdx.x, j = blockIdx.y * 4 + threadIdx.y, k = blockIdx.z;
     if (i > ni || j > nj || k > nk) return;
-    const bool win = !(i < 2 || i >= ni || j < 2 || j >= nj || k < 2 || k >= nk);
+    const int c = flag_at(solidw, i, j, k, ni, nj, nk);
+    if (j < nj && k < nk && wall_face(flag_at(solidw, i - 1, j, k, ni, nj, nk), c)) {
+        const size_t id = (size_t)i + (size_t)(ni + 1) * ((size_t)j + (size_t)nj * k);
+        if (du) du[id] = 0.f - u[id];
+        u[id] = 0.f;
+    }
+    if (i < ni && k < nk && wall_face(flag_at(solidw, i, j - 1, k, ni, nj, nk), c)) {
+        const size_t id = (size_t)i + (size_t)ni * ((size_t)j + (size_t)(nj + 1) * k);
+        if (dv) dv[id] = 0.f - v[id];
+        v[id] = 0.f;
+    }
+    if (i < ni && j < nj && wall_face(flag_at(solidw, i, j, k - 1, ni, nj, nk), c)) {
+        const size_t id = (size_t)i + (size_t)ni * ((size_t)j + (size_t)nj * k);
+        if (dw) dw[id] = 0.f - w[id];
+        w[id] = 0.f;
+    }
+}
+
+// jacobi_masked_kernel with walls: a cell whose (obstacle) rows summary is clean counts its solid neighbours by position and
+// reads no flag; the others read the flags of solid + walls
+__global__ __launch_bounds__(256) void jacobi_masked_walls_kernel(const float *__restrict__ p, const float *__restrict__ div,
+                                                                  float *__restrict__ out, const unsigned char *__restrict__ solidw,
+                                                                  const unsigned char *__restrict__ rows, int walls,
+                                                                  int ni, int nj, int nk, float alpha, BetaTab bt)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x, j = blockIdx.y * 4 + threadIdx.y, k = blockIdx.z;
+    if (!(i > 0 && i < ni - 1 && j > 0 && j < nj - 1 && k > 0 && k < nk - 1)) return;
+    const size_t sj = ni, sk = (size_t)ni * nj;
+    const size_t id = (size_t)i + sj * j + sk * k;
+    int s;
+    if (!rows[(size_t)j + (size_t)nj * k]) {
+        s = wall_neighbours(walls, i, j, k, ni, nj, nk);
+    } else {
+        if (solidw[id]) return;
+        s = (solidw[id - 1] != 0) + (solidw[id + 1] != 0) + (solidw[id - sj] != 0) + (solidw[id + sj] != 0)
+          + (solidw[id - sk] != 0) + (solidw[id + sk] != 0);
+    }
+    const float sum = p[id - 1] + p[id + 1] + p[id - sj] + p[id + sj] + p[id - sk] + p[id + sk] + alpha * div[id];
+    out[id] = s == 6 ? 0.f : sum * bt.b[s];
+}
+
+// ---- masked gradient (gradient_delta_kernel / gradient_kernel with solid faces left alone) ----------------------------
+// i0, j0, k0: the first cell index of the window on each axis -- 2 (the open-boundary window of gradient_kernel), or 1 behind a
+// closed wall (gradient_masked_walls_kernel), where the faces between the cells of the first interior layer are projected too
+__device__ __forceinline__ void gradient_masked_body(float *__restrict__ u, float *__restrict__ v, float *__restrict__ w,
+                                                     const float *__restrict__ p,
+                                                     float *__restrict__ du, float *__restrict__ dv, float *__restrict__ dw,
+                                                     const unsigned char *__restrict__ solid, int ni, int nj, int nk, float halfrdx,
+                                                     int i0, int j0, int k0)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x, j = blockIdx.y * 4 + threadIdx.y, k = blockIdx.z;
+    if (i > ni || j > nj || k > nk) return;
+    const bool win = !(i < i0 || i >= ni || j < j0 || j >= nj || k < k0 || k >= nk);
     const size_t iu = (size_t)i + (size_t)(ni + 1) * ((size_t)j + (size_t)nj * k);
     const size_t iv = (size_t)i + (size_t)ni * ((size_t)j + (size_t)(nj + 1) * k);
     const size_t ic = (size_t)i + (size_t)ni * ((size_t)j + (size_t)nj * k);
@@ -130,6 +211,24 @@ __global__ __launch_bounds__(256) void gradient_masked_kernel(float *__restrict_
         if (hv && !sv) dv[iv] = 0.f;
         if (hw && !sw) dw[ic] = 0.f;
     }
+}
+__global__ __launch_bounds__(256) void gradient_masked_kernel(float *__restrict__ u, float *__restrict__ v, float *__restrict__ w,
+                                                              const float *__restrict__ p,
+                                                              float *__restrict__ du, float *__restrict__ dv, float *__restrict__ dw,
+                                                              const unsigned char *__restrict__ solid, int ni, int nj, int nk, float halfrdx)
+{
+    gradient_masked_body(u, v, w, p, du, dv, dw, solid, ni, nj, nk, halfrdx, 2, 2, 2);
+}
+// closed domain walls: the window starts at cell 1 behind a closed low side (BimocqSolver.cpp:1288-1335
+// updates every face between two fluid cells); the faces of the wall cells themselves are solid faces and stay alone
+__global__ __launch_bounds__(256) void gradient_masked_walls_kernel(float *__restrict__ u, float *__restrict__ v, float *__restrict__ w,
+                                                                    const float *__restrict__ p,
+                                                                    float *__restrict__ du, float *__restrict__ dv, float *__restrict__ dw,
+                                                                    const unsigned char *__restrict__ solidw, int walls,
+                                                                    int ni, int nj, int nk, float halfrdx)
+{
+    gradient_masked_body(u, v, w, p, du, dv, dw, solidw, ni, nj, nk, halfrdx, (walls & BQ_WALL_XLO) ? 1 : 2, (walls & BQ_WALL_YLO) ? 1 : 2,
+                         (walls & BQ_WALL_ZLO) ? 1 : 2);
 }
 
 // ---- band blend + density clear: one thread per super-grid node -------------------------------------------------------
@@ -210,7 +309,7 @@ static void obstacle_blend(float *u, float *v, float *w, float *rho, float *T, c
 }
 
 bool jacobi_sweep_triple_masked(const plan::JacobiTuning &tun, const float *in, const float *div, float *out, int ni, int nj, int nk, float alpha,
-                                const unsigned char *solid, const unsigned char *rows, const float betas[7]);   // bq_project.hip
+                                const unsigned char *solid, const unsigned char *rows, const float betas[7], int walls = 0);   // bq_project.hip
 
 } // namespace bq
 
@@ -281,6 +380,69 @@ int gpu_jacobi_sweeps_masked(float *p, const float *div, float *p_temp, const un
     return in == p ? 0 : 1;
 }
 
+static bool walls_ok(int walls, const char *op)
+{
+    if (walls >= 0 && walls < 63) return true;
+    latch(FL_ERR_BAD_ARGUMENT, op, "walls: BQ_WALL_* bits, at least one side open");
+    return false;
+}
+
+void gpu_wall_flags(unsigned char *solidw, const unsigned char *solid, int walls, int ni, int nj, int nk)
+{
+    if (!obs_args_ok(nullptr, 0, ni, nj, nk, "gpu_wall_flags") || !walls_ok(walls, "gpu_wall_flags")) return;
+    if (!solidw || solidw == solid) { latch(FL_ERR_BAD_ARGUMENT, "gpu_wall_flags", "null or aliased buffers"); return; }
+    wall_flags_kernel<<<grid_for(ni, nj, nk), kBlock, 0, rt().compute>>>(solidw, solid, walls, ni, nj, nk);
+    BQ_LAUNCH_CHECK("wall_flags_kernel");
+}
+
+void gpu_wall_faces(float *u, float *v, float *w, float *du, float *dv, float *dw, const unsigned char *solidw, int ni, int nj, int nk)
+{
+    if (!obs_args_ok(nullptr, 0, ni, nj, nk, "gpu_wall_faces")) return;
+    if (!u || !v || !w || !solidw || (!du) != (!dv) || (!du) != (!dw)) { latch(FL_ERR_BAD_ARGUMENT, "gpu_wall_faces", "null device pointer"); return; }
+    wall_faces_kernel<<<grid_for(ni + 1, nj + 1, nk + 1), kBlock, 0, rt().compute>>>(u, v, w, du, dv, dw, solidw, ni, nj, nk);
+    BQ_LAUNCH_CHECK("wall_faces_kernel");
+}
+
+void gpu_jacobi_sweep_masked_walls(const float *in, const float *div, float *out, const unsigned char *solidw,
+                                   const unsigned char *rows, int walls, int ni, int nj, int nk, float alpha, float beta)
+{
+    if (walls == 0) { gpu_jacobi_sweep_masked(in, div, out, solidw, rows, ni, nj, nk, alpha, beta); return; }
+    if (!obs_args_ok(nullptr, 0, ni, nj, nk, "gpu_jacobi_sweep_masked_walls") || !walls_ok(walls, "gpu_jacobi_sweep_masked_walls")) return;
+    if (!in || !div || !out || !solidw || !rows || in == out) { latch(FL_ERR_BAD_ARGUMENT, "gpu_jacobi_sweep_masked_walls", "null or aliased buffers"); return; }
+    jacobi_masked_walls_kernel<<<grid_for(ni, nj, nk), kBlock, 0, rt().compute>>>(in, div, out, solidw, rows, walls, ni, nj, nk, alpha, beta_table(beta));
+    BQ_LAUNCH_CHECK("jacobi_masked_walls_kernel");
+}
+
+// gpu_jacobi_sweeps_masked's loop with the walled kernels (FL_OPT_JACOBI_FUSE >= 2: three sweeps per launch where
+// plan_triple_masked admits the shape)
+int gpu_jacobi_sweeps_masked_walls(float *p, const float *div, float *p_temp, const unsigned char *solidw, const unsigned char *rows,
+                                   int walls, int ni, int nj, int nk, int sweeps, float alpha, float beta)
+{
+    if (walls == 0) return gpu_jacobi_sweeps_masked(p, div, p_temp, solidw, rows, ni, nj, nk, sweeps, alpha, beta);
+    if (!obs_args_ok(nullptr, 0, ni, nj, nk, "gpu_jacobi_sweeps_masked_walls") || !walls_ok(walls, "gpu_jacobi_sweeps_masked_walls")) return 0;
+    if (!p || !div || !p_temp || !solidw || !rows || p == p_temp) { latch(FL_ERR_BAD_ARGUMENT, "gpu_jacobi_sweeps_masked_walls", "null or aliased buffers"); return 0; }
+    const BetaTab bt = beta_table(beta);
+    float *in = p, *out = p_temp;
+    ProfileSpan span;
+    const bool prof = sweeps > 0 && profile_begin(span);
+    int s = 0;
+    long long launches = 0;
+    const plan::JacobiTuning tun = jacobi_tuning();
+    while (tun.sweeps_fuse == plan::SweepsFuse::kAll && s + 3 <= sweeps &&
+           jacobi_sweep_triple_masked(tun, in, div, out, ni, nj, nk, alpha, solidw, rows, bt.b, walls)) {
+        float *t = in; in = out; out = t;
+        s += 3; launches++;
+    }
+    for (; s < sweeps; s++) {
+        jacobi_masked_walls_kernel<<<grid_for(ni, nj, nk), kBlock, 0, rt().compute>>>(in, div, out, solidw, rows, walls, ni, nj, nk, alpha, bt);
+        if (!BQ_LAUNCH_CHECK("jacobi_masked_walls_kernel")) break;
+        float *t = in; in = out; out = t;
+        launches++;
+    }
+    if (prof) profile_end(span, launches, sweeps);
+    return in == p ? 0 : 1;
+}
+
 void gpu_gradient_masked(float *u, float *v, float *w, const float *p, float *du, float *dv, float *dw,
                          const unsigned char *solid, int ni, int nj, int nk, float halfrdx)
 {
@@ -288,6 +450,16 @@ void gpu_gradient_masked(float *u, float *v, float *w, const float *p, float *du
     if (!u || !v || !w || !p || !solid || (!du) != (!dv) || (!du) != (!dw)) { latch(FL_ERR_BAD_ARGUMENT, "gpu_gradient_masked", "null device pointer"); return; }
     gradient_masked_kernel<<<grid_for(ni + 1, nj + 1, nk + 1), kBlock, 0, rt().compute>>>(u, v, w, p, du, dv, dw, solid, ni, nj, nk, halfrdx);
     BQ_LAUNCH_CHECK("gradient_masked_kernel");
+}
+
+void gpu_gradient_masked_walls(float *u, float *v, float *w, const float *p, float *du, float *dv, float *dw,
+                               const unsigned char *solidw, int walls, int ni, int nj, int nk, float halfrdx)
+{
+    if (walls == 0) { gpu_gradient_masked(u, v, w, p, du, dv, dw, solidw, ni, nj, nk, halfrdx); return; }
+    if (!obs_args_ok(nullptr, 0, ni, nj, nk, "gpu_gradient_masked_walls") || !walls_ok(walls, "gpu_gradient_masked_walls")) return;
+    if (!u || !v || !w || !p || !solidw || (!du) != (!dv) || (!du) != (!dw)) { latch(FL_ERR_BAD_ARGUMENT, "gpu_gradient_masked_walls", "null device pointer"); return; }
+    gradient_masked_walls_kernel<<<grid_for(ni + 1, nj + 1, nk + 1), kBlock, 0, rt().compute>>>(u, v, w, p, du, dv, dw, solidw, walls, ni, nj, nk, halfrdx);
+    BQ_LAUNCH_CHECK("gradient_masked_walls_kernel");
 }
 
 void gpu_obstacle_blend(float *u, float *v, float *w, float *rho, float *T, const float *us, const float *vs,

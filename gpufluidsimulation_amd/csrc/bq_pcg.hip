@@ -264,18 +264,32 @@ __global__ __launch_bounds__(256) void pcg_divergence_kernel(const float *__rest
 }
 
 // mg_gradient_kernel's window and expression on the faces whose two cells are fluid
-__global__ __launch_bounds__(256) void pcg_gradient_kernel(float *__restrict__ u, float *__restrict__ v, float *__restrict__ w,
-                                                           const double *__restrict__ p, const unsigned char *__restrict__ solid,
-                                                           int ni, int nj, int nk, double halfrdx)
+// i0, j0, k0: the first cell index of the window on each axis (2, or 1 behind a closed wall: DESIGN.md section 18)
+__device__ __forceinline__ void pcg_gradient_body(float *__restrict__ u, float *__restrict__ v, float *__restrict__ w,
+                                                  const double *__restrict__ p, const unsigned char *__restrict__ solid,
+                                                  int ni, int nj, int nk, double halfrdx, int i0, int j0, int k0)
 {
     const int i = blockIdx.x * 64 + threadIdx.x, j = blockIdx.y * 4 + threadIdx.y, k = blockIdx.z;
-    if (!(i > 1 && i < ni && j > 1 && j < nj && k > 1 && k < nk)) return;
+    if (!(i >= i0 && i < ni && j >= j0 && j < nj && k >= k0 && k < nk)) return;
     const size_t sj = ni, sk = (size_t)ni * nj, id = (size_t)i + sj * j + sk * k;
     const double p0 = p[id];
     const bool fc = !solid || solid[id] == 0;
     if (fc && (!solid || solid[id - 1] == 0))  u[(size_t)i + (size_t)(ni + 1) * (j + (size_t)nj * k)] -= (float)(halfrdx * (p0 - p[id - 1]));
     if (fc && (!solid || solid[id - sj] == 0)) v[(size_t)i + (size_t)ni * (j + (size_t)(nj + 1) * k)] -= (float)(halfrdx * (p0 - p[id - sj]));
     if (fc && (!solid || solid[id - sk] == 0)) w[id] -= (float)(halfrdx * (p0 - p[id - sk]));
+}
+__global__ __launch_bounds__(256) void pcg_gradient_kernel(float *__restrict__ u, float *__restrict__ v, float *__restrict__ w,
+                                                           const double *__restrict__ p, const unsigned char *__restrict__ solid,
+                                                           int ni, int nj, int nk, double halfrdx)
+{
+    pcg_gradient_body(u, v, w, p, solid, ni, nj, nk, halfrdx, 2, 2, 2);
+}
+__global__ __launch_bounds__(256) void pcg_gradient_walls_kernel(float *__restrict__ u, float *__restrict__ v, float *__restrict__ w,
+                                                                 const double *__restrict__ p, const unsigned char *__restrict__ solidw,
+                                                                 int walls, int ni, int nj, int nk, double halfrdx)
+{
+    pcg_gradient_body(u, v, w, p, solidw, ni, nj, nk, halfrdx, (walls & BQ_WALL_XLO) ? 1 : 2, (walls & BQ_WALL_YLO) ? 1 : 2,
+                      (walls & BQ_WALL_ZLO) ? 1 : 2);
 }
 
 inline unsigned blocks_of(size_t n) { return (unsigned)((n + 255) / 256); }
@@ -307,6 +321,17 @@ void gpu_pcg_gradient(float *u, float *v, float *w, const double *p, const unsig
     if (!ensure_ready(op)) return;
     BQ_REQUIRE(u && v && w && p && ni >= 1 && nj >= 1 && nk >= 1 && nk < 65535, op);
     pcg_gradient_kernel<<<dim3((ni + 1 + 63) / 64, (nj + 1 + 3) / 4, nk + 1), dim3(64, 4, 1), 0, rt().compute>>>(u, v, w, p, solid, ni, nj, nk, halfrdx);
+    BQ_LAUNCH_CHECK(op);
+}
+
+void gpu_pcg_gradient_walls(float *u, float *v, float *w, const double *p, const unsigned char *solidw, int walls,
+                            int ni, int nj, int nk, double halfrdx)
+{
+    const char *op = "gpu_pcg_gradient_walls";
+    if (walls == 0) { gpu_pcg_gradient(u, v, w, p, solidw, ni, nj, nk, halfrdx); return; }
+    if (!ensure_ready(op)) return;
+    BQ_REQUIRE(u && v && w && p && solidw && walls > 0 && walls < 63 && ni >= 3 && nj >= 3 && nk >= 3 && nk < 65535, op);
+    pcg_gradient_walls_kernel<<<dim3((ni + 1 + 63) / 64, (nj + 1 + 3) / 4, nk + 1), dim3(64, 4, 1), 0, rt().compute>>>(u, v, w, p, solidw, walls, ni, nj, nk, halfrdx);
     BQ_LAUNCH_CHECK(op);
 }
 

@@ -1036,6 +1036,10 @@ __global__ __launch_bounds__(256) void jacobi_lean3r_kernel(const float *__restr
 // Obstacles (MASK = true; bq_obstacle.hip).  solid: one byte per cell, 0 = fluid; rows: one byte per
 // (row, plane), 1 when a solid cell lies in rows j-1 .. j+1 of planes k-1 .. k+1; b0 .. b6: beta_s for s solid neighbours.
 struct SweepMask { const unsigned char *solid = nullptr, *rows = nullptr; float b0 = 0.f, b1 = 0.f, b2 = 0.f, b3 = 0.f, b4 = 0.f, b5 = 0.f, b6 = 0.f; };
+// Closed domain walls (WALLS = true).  solid: the obstacle flags plus BQ_FLAG_WALL in the wall cells; rows:
+// still the summary of the OBSTACLE flags; walls: the closed sides (BQ_WALL_* bits).
+struct SweepMaskWalls : SweepMask { int walls = 0; };
+template <bool WALLS, typename M> __device__ __forceinline__ int walls_of(const M &m) { if constexpr (WALLS) return m.walls; else return 0; }
 
 // Per cell of a float4 column a code byte: 7 = solid, else s = the number of solid neighbours.  own / lw / rw: the flag words
 // (one byte per cell) of the column, of the column to the left (lane - 1) and to the right (lane + 1); yl, yh, zl, zh: of
@@ -1093,13 +1097,18 @@ __device__ __forceinline__ R4 mask_finish(R4 sum, R4 ce, unsigned code, const Sw
 // A halo wave whose nearest row lies dn rows outside the block owes the block levels 1 .. S - dn only: the march is instantiated
 // once per level count and a block's waves run different code between the same barriers (S = 4 in row pairs: 11.4 -> 10.0 us
 // per sweep at 256^3; S = 3 unchanged, 10.7 -- its waves wait for each other, not for the VALU).
-template <int W, int R, int S, bool MASK = false>
+// WALLS (with MASK): a block the rows summary finds clean still has wall cells next to its first and last
+// interior column, row and plane.  Their number is a function of the position alone: such a block reads no flag and scales the
+// unscaled sum by beta_s with s = [x wall] + [y wall] (per row: wave-uniform) + [z wall] (per plane) -- the floats mask_finish
+// gives for the same s.  A dirty block takes the flag words (of solid + walls) as before.
+template <int W, int R, int S, bool MASK = false, bool WALLS = false>
 __global__ __launch_bounds__((W + 2 * ((S - 1 + R - 1) / R)) * 64) void jacobi_lds_kernel(const float *__restrict__ p, const float *__restrict__ div,
                                                                   float *__restrict__ out, int nx, int ny, int nz,
                                                                   int nby, int nblk, int kchunk, float alpha, float beta, Slab sl, PairRanges rg,
-                                                                  SweepMask mk)
+                                                                  std::conditional_t<WALLS, SweepMaskWalls, SweepMask> mk)
 {
     static_assert((R == 1 || R == 2) && (S == 3 || S == 4), "one or two rows per wave, three or four sweeps per launch");
+    static_assert(MASK || !WALLS, "walls are a state of the masked kernel");
     constexpr int H = (S - 1 + R - 1) / R, NW = W + 2 * H, NS = NW * R, P = 4, A = P - 2;   // A: the plane loaded in step q is q + A
     __shared__ v4f lds[S - 1][2][NS][64];                           // [level - 1][plane parity][row slot][lane]
     // XCD-contiguous block order: the grid is padded to a multiple of 8 blocks (nblk real ones), XCD x = blockIdx % 8 works
@@ -1158,13 +1167,36 @@ __global__ __launch_bounds__((W + 2 * ((S - 1 + R - 1) / R)) * 64) void jacobi_l
     };
     auto run = [&](auto EDGE_T, auto SM_T, auto MASK_T) __attribute__((always_inline)) {
     constexpr bool EDGE = decltype(EDGE_T)::value;
-    constexpr bool MK = decltype(MASK_T)::value;                    // this block lies near a solid cell
+    constexpr bool MK = decltype(MASK_T)::value == 1;               // this block lies near a solid cell
+    constexpr bool PW = decltype(MASK_T)::value == 2;               // clean, walls on: solid neighbours by position
     constexpr int SM = decltype(SM_T)::value;                       // the levels this wave evaluates (halo waves: fewer than S)
     R4 L0[P][R + 2], D[P][R], Lv[S][P][R];                          // Lv[s]: level s (1 .. S-1) on the wave's own rows
     // masked blocks: flag words of rows j-1 .. j+R in the same ring as L0 (loaded with it, A planes ahead), and the code
     // words (mask_code) of the own rows per plane, formed with level 1 and reused by the later levels of that plane
     unsigned Fw[P][R + 2], Cd[P][R];
     const R4 zero = R4{v2f{0.f, 0.f}, v2f{0.f, 0.f}};
+    // PW: the y term of the own rows (wave-uniform), the z term of a plane, and the finish of a level from its unscaled sum --
+    // component .y of the xlo lane is cell 1, component .z of the xhi lane cell nx - 2; s <= 3 (nj >= 8, nk >= 12)
+    int wy[R];
+    bool wxl = false, wxh = false;
+    int wzl = 0, wzh = 0;
+    if constexpr (PW) {
+        const int wl = walls_of<WALLS>(mk);
+#pragma unroll
+        for (int a = 0; a < R; a++) wy[a] = (int)((wl & 4) != 0 && j + a == 1) + (int)((wl & 8) != 0 && j + a == ny - 2);
+        wxl = xlo && (wl & 1) != 0; wxh = xhi && (wl & 2) != 0;
+        wzl = (wl & 16) != 0 ? 1 : -8; wzh = (wl & 32) != 0 ? nz - 2 : -8;      // the plane with a closed z side below / above it
+    }
+    auto pw_finish = [&](R4 sum, R4 ce, int a, int pl) -> R4 {
+        const int n = wy[a] + (int)(pl == wzl) + (int)(pl == wzh);
+        const float bu = n == 0 ? mk.b0 : n == 1 ? mk.b1 : mk.b2, bx = n == 0 ? mk.b1 : n == 1 ? mk.b2 : mk.b3;
+        R4 o;
+        o.a.x = xlo ? ce.a.x : sum.a.x * bu;
+        o.a.y = sum.a.y * (wxl ? bx : bu);
+        o.b.x = sum.b.x * (wxh ? bx : bu);
+        o.b.y = xhi ? ce.b.y : sum.b.y * bu;
+        return o;
+    };
     if (MK) {
 #pragma unroll
         for (int a = 0; a < P; a++)
@@ -1217,6 +1249,7 @@ __global__ __launch_bounds__((W + 2 * ((S - 1 + R - 1) / R)) * 64) void jacobi_l
             _Pragma("unroll") for (int a = 0; a < R; a++) {                                                          \
                 D[ic][a].a = alpha * D[ic][a].a; D[ic][a].b = alpha * D[ic][a].b;                                   \
                 if (MK) Lv[1][ic][a] = mask_finish(jac_r4<false, true, true>(L0[ic][a + 1], L0[ic][a], L0[ic][a + 2], L0[im][a + 1], L0[in_][a + 1], D[ic][a], alpha, 1.0f, false, false), L0[ic][a + 1], Cd[ic][a], mk, xlo, xhi); \
+                else if (PW) Lv[1][ic][a] = pw_finish(jac_r4<false, true, true>(L0[ic][a + 1], L0[ic][a], L0[ic][a + 2], L0[im][a + 1], L0[in_][a + 1], D[ic][a], alpha, 1.0f, false, false), L0[ic][a + 1], a, q); \
                 else Lv[1][ic][a] = jac_r4<false, true, true>(L0[ic][a + 1], L0[ic][a], L0[ic][a + 2], L0[im][a + 1], L0[in_][a + 1], D[ic][a], alpha, beta, xlo, xhi); \
                 if (EDGE && rowb[a]) Lv[1][ic][a] = L0[ic][a + 1];                                                  \
             }                                                                                                       \
@@ -1232,6 +1265,7 @@ __global__ __launch_bounds__((W + 2 * ((S - 1 + R - 1) / R)) * 64) void jacobi_l
                     const R4 ce = Lv[s - 1][cs][a];                                                                 \
                     const R4 fr = a == 0 ? nlo[s] : Lv[s - 1][cs][a == 0 ? 0 : a - 1], bk = a == R - 1 ? nhi[s] : Lv[s - 1][cs][a == R - 1 ? a : a + 1]; \
                     R4 v = MK ? mask_finish(jac_r4<false, true, true>(ce, fr, bk, Lv[s - 1][ds][a], Lv[s - 1][us][a], D[cs][a], alpha, 1.0f, false, false), ce, Cd[cs][a], mk, xlo, xhi) \
+                         : PW ? pw_finish(jac_r4<false, true, true>(ce, fr, bk, Lv[s - 1][ds][a], Lv[s - 1][us][a], D[cs][a], alpha, 1.0f, false, false), ce, a, ps) \
                               : jac_r4<false, true, true>(ce, fr, bk, Lv[s - 1][ds][a], Lv[s - 1][us][a], D[cs][a], alpha, beta, xlo, xhi); \
                     if (keep || (EDGE && rowb[a])) v = ce;                                                          \
                     if (s < S) { Lv[s][cs][a] = v; put(lds[s - 1][ps & 1], a, v); }                                 \
@@ -1270,11 +1304,15 @@ __global__ __launch_bounds__((W + 2 * ((S - 1 + R - 1) / R)) * 64) void jacobi_l
         for (int t = (int)threadIdx.x; t < cnt; t += (int)blockDim.x)
             any |= mk.rows[(size_t)(r0 + t % nr) + (size_t)ny * (size_t)(k0 + t / nr)];
         if (__syncthreads_or(any)) {
-            if (edge_block) go(std::true_type{}, std::true_type{}); else go(std::false_type{}, std::true_type{});
+            if (edge_block) go(std::true_type{}, std::integral_constant<int, 1>{}); else go(std::false_type{}, std::integral_constant<int, 1>{});
+            return;
+        }
+        if constexpr (WALLS) {                                      // clean, but never wall-free: the positional state
+            if (edge_block) go(std::true_type{}, std::integral_constant<int, 2>{}); else go(std::false_type{}, std::integral_constant<int, 2>{});
             return;
         }
     }
-    if (edge_block) go(std::true_type{}, std::false_type{}); else go(std::false_type{}, std::false_type{});
+    if (edge_block) go(std::true_type{}, std::integral_constant<int, 0>{}); else go(std::false_type{}, std::integral_constant<int, 0>{});
 #undef BQ_LDS_PHASE
 #undef BQ_SL4
 }
@@ -1625,7 +1663,7 @@ static void jacobi_sweep(const plan::JacobiTuning &tun, const float *in, const f
 // nothing launched.  Records the kernel's name for fl_jacobi_kernel_name.  The caller guarantees that both buffers carry the same
 // boundary layer.
 static bool launch_fused(const plan::LaunchPlan &pl, const float *in, const float *div, float *out, int ni, int nj, int nk, float alpha,
-                         float beta, const geom::PlaneRanges &pr, const SweepMask *mask = nullptr)
+                         float beta, const geom::PlaneRanges &pr, const SweepMaskWalls *mask = nullptr)
 {
     using plan::Kernel;
     if (pl.kernel == Kernel::kNone) return false;
@@ -1657,8 +1695,13 @@ static bool launch_fused(const plan::LaunchPlan &pl, const float *in, const floa
         name = "jacobi_lds2seg_kernel";
         break;
     case Kernel::kLds:
+        if (mask && mask->walls) {
+            jacobi_lds_kernel<8, 1, 3, true, true><<<pl.grid, pl.block, 0, st>>>(in, div, out, ni, nj, nk, pl.row_blocks, pl.nblk, pl.kc, alpha, beta, sl, rg, *mask);
+            name = "jacobi_lds3_walls_kernel"; what = "jacobi_lds_kernel<walls>";
+            break;
+        }
         if (mask) {
-            jacobi_lds_kernel<8, 1, 3, true><<<pl.grid, pl.block, 0, st>>>(in, div, out, ni, nj, nk, pl.row_blocks, pl.nblk, pl.kc, alpha, beta, sl, rg, *mask);
+            jacobi_lds_kernel<8, 1, 3, true><<<pl.grid, pl.block, 0, st>>>(in, div, out, ni, nj, nk, pl.row_blocks, pl.nblk, pl.kc, alpha, beta, sl, rg, SweepMask(*mask));
             name = "jacobi_lds3_masked_kernel"; what = "jacobi_lds_kernel<masked>";
             break;
         }
@@ -1703,12 +1746,15 @@ static bool jacobi_sweep_quad(const plan::JacobiTuning &tun, const float *in, co
                         whole_array(nk));
 }
 
-// Three MASKED sweeps in one launch (bq_obstacle.hip: gpu_jacobi_sweeps_masked); false = not applicable, nothing launched
+// Three MASKED sweeps in one launch (bq_obstacle.hip: gpu_jacobi_sweeps_masked; walls != 0: gpu_jacobi_sweeps_masked_walls, solid then
+// being solid + walls); false = not applicable, nothing launched
 bool jacobi_sweep_triple_masked(const plan::JacobiTuning &tun, const float *in, const float *div, float *out, int ni, int nj, int nk, float alpha,
-                                const unsigned char *solid, const unsigned char *rows, const float betas[7])
+                                const unsigned char *solid, const unsigned char *rows, const float betas[7], int walls)
 {
-    const SweepMask mk{solid, rows, betas[0], betas[1], betas[2], betas[3], betas[4], betas[5], betas[6]};
-    return launch_fused(plan::plan_triple_masked(ni, nj, nk, aligned16(in, div, out), tun, rt().num_cus, rt().slab_on), in, div, out, ni, nj, nk,
+    SweepMaskWalls mk;
+    mk.solid = solid; mk.rows = rows; mk.walls = walls;
+    mk.b0 = betas[0]; mk.b1 = betas[1]; mk.b2 = betas[2]; mk.b3 = betas[3]; mk.b4 = betas[4]; mk.b5 = betas[5]; mk.b6 = betas[6];
+    return launch_fused(plan::plan_triple_masked(ni, nj, nk, aligned16(in, div, out), tun, rt().num_cus, rt().slab_on, walls != 0), in, div, out, ni, nj, nk,
                         alpha, betas[0], whole_array(nk), &mk);
 }
 

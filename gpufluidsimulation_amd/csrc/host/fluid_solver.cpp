@@ -36,6 +36,11 @@
 #pragma weak gpu_pcg_gradient
 #pragma weak gpu_emit_sources
 #pragma weak gpu_maccormack
+#pragma weak gpu_wall_flags
+#pragma weak gpu_wall_faces
+#pragma weak gpu_jacobi_sweeps_masked_walls
+#pragma weak gpu_gradient_masked_walls
+#pragma weak gpu_pcg_gradient_walls
 
 namespace bqhost {
 
@@ -702,7 +707,7 @@ bool BimocqGPUSolver::setBoundary(const bq_boundary *b, const bq_levelset *ls, i
     }
     if (n == 0) {
         dropBoundaries();
-        return true;
+        return buildWallFlags();
     }
     if (GpuSolver->slab.on) {
         fl_report_error(FL_ERR_UNSUPPORTED, "setBoundary: obstacles are not supported on z-slab ranks");
@@ -757,7 +762,7 @@ bool BimocqGPUSolver::setBoundary(const bq_boundary *b, const bq_levelset *ls, i
     boundaries.swap(list);
     levelsets.swap(descs);
     lsgrids = std::move(grids);
-    return true;
+    return buildWallFlags();
 }
 
 // no obstacles: the list, the flags, the rows summary and the level-set grids released
@@ -777,6 +782,7 @@ bool BimocqGPUSolver::buildFlags(const std::vector<bq_boundary> &list, const bq_
     obstacle_flags(solid.u8(), rows.u8(), list.data(), (int)list.size(), ls, CellSize, g.ni, g.nj, g.nk);
     if (fl_last_error() == FL_OK) return true;
     dropBoundaries();
+    dropWalls();                                    // (solidw held the flags of the list that is gone)
     return false;
 }
 
@@ -793,7 +799,80 @@ bool BimocqGPUSolver::updateBoundary(int /*framenum*/, float dt)
     }
     if (!buildFlags(list, levelsetList())) return false;
     boundaries.swap(list);
+    return buildWallFlags();
+}
+
+bool BimocqGPUSolver::wallOperators()
+{
+    return gpu_wall_flags && gpu_wall_faces && gpu_jacobi_sweeps_masked_walls && gpu_gradient_masked_walls &&
+           (!pcgOperators() || gpu_pcg_gradient_walls);
+}
+
+// setWalls (BimocqSolver.cpp:938-948 as an opt-in): the closed sides; 0 releases solidw and the step is exactly the one without
+// this feature.  A refused mask leaves the previous one in place.
+bool BimocqGPUSolver::setWalls(int mask)
+{
+    if (mask < 0 || mask > 63) {
+        fl_report_error(FL_ERR_BAD_ARGUMENT, "setWalls: bits outside BQ_WALL_XLO .. BQ_WALL_ZHI");
+        return false;
+    }
+    if (mask == 63) {
+        fl_report_error(FL_ERR_BAD_ARGUMENT, "setWalls: all six sides closed (the pressure needs one open side as its reference)");
+        return false;
+    }
+    if (mask == 0) {
+        dropWalls();
+        return true;
+    }
+    if (GpuSolver->slab.on) {
+        fl_report_error(FL_ERR_UNSUPPORTED, "setWalls: walls are not supported on z-slab ranks");
+        return false;
+    }
+    if (projection_kind == BQ_PROJECTION_MGCG) {
+        fl_report_error(FL_ERR_UNSUPPORTED, "setWalls: walls need the Jacobi or the PCG projection (not BQ_PROJECTION_MGCG)");
+        return false;
+    }
+    if (!wallOperators()) {
+        fl_report_error(FL_ERR_UNSUPPORTED, "setWalls: the operator library has no wall operators");
+        return false;
+    }
+    const size_t nrows = (size_t)g.nj * (size_t)g.nk;
+    DeviceBytes sw, rw;
+    if (!sw.alloc(g.n())) return false;
+    if (boundaries.empty()) {                       // the obstacles' rows summary of an empty list: all zero
+        if (!rw.alloc(nrows)) return false;
+        fl_memset(rw.u8(), 0, nrows);
+        if (fl_last_error() != FL_OK) return false;
+    }
+    gpu_wall_flags(sw.u8(), boundaries.empty() ? nullptr : solid.u8(), mask, g.ni, g.nj, g.nk);
+    if (fl_last_error() != FL_OK) return false;
+    solidw = std::move(sw);
+    if (boundaries.empty()) rows = std::move(rw);
+    walls = mask;
     return true;
+}
+
+void BimocqGPUSolver::dropWalls()
+{
+    walls = 0;
+    solidw.release();
+    if (boundaries.empty()) rows.release();
+}
+
+// solidw from the current obstacle flags (after setBoundary / updateBoundary); nothing to do with walls off
+bool BimocqGPUSolver::buildWallFlags()
+{
+    if (!walls) return true;
+    const size_t nrows = (size_t)g.nj * (size_t)g.nk;
+    bool ok = true;
+    if (boundaries.empty()) {
+        ok = rows.bytes() == nrows || rows.alloc(nrows);
+        if (ok) fl_memset(rows.u8(), 0, nrows);
+    }
+    if (ok) gpu_wall_flags(solidw.u8(), boundaries.empty() ? nullptr : solid.u8(), walls, g.ni, g.nj, g.nk);
+    if (ok && fl_last_error() == FL_OK) return true;
+    dropWalls();
+    return false;
 }
 
 // the semi-Lagrangian values of blendBoundary (BimocqSolver.cpp:106): u, v, w, rho, T traced back over dt, at band nodes only,
@@ -835,16 +914,21 @@ bool BimocqGPUSolver::projectionObstacles(bool with_delta)
     const float alpha = -1.f, beta = (float)(1.0 / 6.0);
     float *du = with_delta ? duProj.get() : nullptr, *dv = with_delta ? dvProj.get() : nullptr, *dw = with_delta ? dwProj.get() : nullptr;
     div.zero(); p.zero(); p_temp.zero();
-    gpu_obstacle_faces(VelocityU, VelocityV, VelocityW, du, dv, dw, solid.u8(), boundaries.data(), (int)boundaries.size(), g.ni, g.nj, g.nk);
+    if (!boundaries.empty())
+        gpu_obstacle_faces(VelocityU, VelocityV, VelocityW, du, dv, dw, solid.u8(), boundaries.data(), (int)boundaries.size(), g.ni, g.nj, g.nk);
+    if (walls) gpu_wall_faces(VelocityU, VelocityV, VelocityW, du, dv, dw, solidw.u8(), g.ni, g.nj, g.nk);   // (disjoint faces: the order is free)
     gpu_divergence(VelocityU, VelocityV, VelocityW, div, g.ni, g.nj, g.nk, halfrdx);
     // p and p_temp carry the same (zero) boundary layer and +0 in every solid cell: three masked sweeps per launch
     const int fuse_was = fl_get_option(FL_OPT_JACOBI_FUSE);
     if (fuse_was == 1) fl_set_option(FL_OPT_JACOBI_FUSE, 2);
-    const int where = jacobi_iters > 1 ? gpu_jacobi_sweeps_masked(p, div, p_temp, solid.u8(), rows.u8(), g.ni, g.nj, g.nk,
-                                                                  jacobi_iters - 1, alpha, beta) : 0;
+    const int where = jacobi_iters <= 1 ? 0
+                    : walls ? gpu_jacobi_sweeps_masked_walls(p, div, p_temp, solidw.u8(), rows.u8(), walls, g.ni, g.nj, g.nk,
+                                                             jacobi_iters - 1, alpha, beta)
+                            : gpu_jacobi_sweeps_masked(p, div, p_temp, solid.u8(), rows.u8(), g.ni, g.nj, g.nk, jacobi_iters - 1, alpha, beta);
     fl_set_option(FL_OPT_JACOBI_FUSE, fuse_was);
     if (where) p.swap(p_temp);
-    gpu_gradient_masked(VelocityU, VelocityV, VelocityW, p, du, dv, dw, solid.u8(), g.ni, g.nj, g.nk, halfrdx);
+    if (walls) gpu_gradient_masked_walls(VelocityU, VelocityV, VelocityW, p, du, dv, dw, solidw.u8(), walls, g.ni, g.nj, g.nk, halfrdx);
+    else       gpu_gradient_masked(VelocityU, VelocityV, VelocityW, p, du, dv, dw, solid.u8(), g.ni, g.nj, g.nk, halfrdx);
     return with_delta;
 }
 
@@ -856,10 +940,11 @@ bool BimocqGPUSolver::projectionPcg()
 {
     if (!allocMgcg()) return false;
     const bool obst = !boundaries.empty();
-    const unsigned char *sol = obst ? solid.u8() : nullptr;
+    const unsigned char *sol = projectionFlags();       // (walls on: solid + walls)
     if (obst)
         gpu_obstacle_faces(VelocityU, VelocityV, VelocityW, nullptr, nullptr, nullptr, solid.u8(), boundaries.data(),
                            (int)boundaries.size(), g.ni, g.nj, g.nk);
+    if (walls) gpu_wall_faces(VelocityU, VelocityV, VelocityW, nullptr, nullptr, nullptr, solidw.u8(), g.ni, g.nj, g.nk);
     gpu_divergence_double(VelocityU, VelocityV, VelocityW, mg.div.f64(), g.ni, g.nj, g.nk, (double)halfrdx);
     SCoarseLevelInfo &L0 = mg.levels[0];
     gpu_pcg_solve(mg.div.f64(), mg.p.f64(), sol, mg.residual.f64(), mg.dir.f64(), mg.temp0.f64(), mg.temp1.f64(), L0.b, L0.r,
@@ -867,7 +952,8 @@ bool BimocqGPUSolver::projectionPcg()
     if (fl_last_error() != FL_OK) return false;
     pcg_projections++;
     if (pcg_stats[3] != BQ_PCG_CONVERGED) pcg_unconverged++;
-    gpu_pcg_gradient(VelocityU, VelocityV, VelocityW, mg.p.f64(), sol, g.ni, g.nj, g.nk, (double)halfrdx);
+    if (walls) gpu_pcg_gradient_walls(VelocityU, VelocityV, VelocityW, mg.p.f64(), sol, walls, g.ni, g.nj, g.nk, (double)halfrdx);
+    else       gpu_pcg_gradient(VelocityU, VelocityV, VelocityW, mg.p.f64(), sol, g.ni, g.nj, g.nk, (double)halfrdx);
     return false;
 }
 
@@ -892,7 +978,7 @@ bool BimocqGPUSolver::projection(bool with_delta)
                                           mg.levels.data(), (int)mg.levels.size(), mg_iters, (double)halfrdx);
         return false;
     }
-    if (!boundaries.empty()) return projectionObstacles(with_delta);   // (setBoundary admits one GPU + Jacobi or PCG only)
+    if (!boundaries.empty() || walls) return projectionObstacles(with_delta);   // (setBoundary / setWalls admit one GPU + Jacobi or PCG only)
     if (!gs.slab.on || gs.slab.nranks <= 1) {
         if (!with_delta) {
             gs.projectionJacobi(VelocityU, VelocityV, VelocityW, div, p, p_temp, debugParam, jacobi_iters, halfrdx, alpha, beta);

@@ -161,6 +161,17 @@ public:
     void dropBoundaries();
     bool buildFlags(const std::vector<bq_boundary> &list, const bq_levelset *ls);
     bool projectionObstacles(bool with_delta);
+    // Closed domain walls (the reference's container, BimocqSolver.cpp:938-948): `walls` the closed sides
+    // (BQ_WALL_* bits), `solidw` = solid + BQ_FLAG_WALL in the wall cells, allocated only while walls are on and rebuilt when the
+    // walls or the obstacle flags change.  solid and rows stay the obstacles' own (rows: all zero while the list is empty).
+    // With walls off a step issues exactly the launches it issues without this feature.
+    int walls = 0;
+    DeviceBytes solidw;
+    bool setWalls(int mask);
+    bool buildWallFlags();                          // on failure the walls are dropped
+    void dropWalls();
+    static bool wallOperators();                    // the operator library has the wall operators
+    const unsigned char *projectionFlags() { return walls ? solidw.u8() : (boundaries.empty() ? nullptr : solid.u8()); }
     void blendBoundary(bool band);                  // band: blendBoundary + clearBoundary, else clearBoundary only
     void semilagBand(float cfldt, float dt);
 

@@ -80,6 +80,10 @@ void bq_solver_set_projection(bq_solver *s, int kind, int iters, float halfrdx)
         fl_report_error(FL_ERR_UNSUPPORTED, "bq_solver_set_projection: obstacles need the Jacobi projection");
         return;
     }
+    if (kind == BQ_PROJECTION_MGCG && s->solver->walls) {
+        fl_report_error(FL_ERR_UNSUPPORTED, "bq_solver_set_projection: walls need the Jacobi or the PCG projection");
+        return;
+    }
     if (kind == BQ_PROJECTION_MGCG) {
         s->solver->projection_kind = kind;
         s->solver->mg_iters = iters;
@@ -268,6 +272,18 @@ int bq_solver_update_boundary(bq_solver *s, int framenum, float dt)
     BQ_ENTER(s);
     if (!s) return -1;
     return s->solver->updateBoundary(framenum, dt) ? 0 : -1;
+}
+
+int bq_solver_set_walls(bq_solver *s, int walls)
+{
+    BQ_ENTER(s);
+    if (!s) return -1;
+    return s->solver->setWalls(walls) ? 0 : -1;
+}
+
+int bq_solver_get_walls(bq_solver *s)
+{
+    return s ? s->solver->walls : 0;
 }
 
 long bq_solver_download_solid(bq_solver *s, unsigned char *host, long capacity)

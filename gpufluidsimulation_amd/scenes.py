@@ -35,6 +35,13 @@ def collision(h):
             (0.16, 0.201, 0.2, 0.015, 1.0, 50.0, -1.0, 10)]
 
 
+def boxed_plume(solver, nz_global, h):
+    """the rising smoke inside the reference CPU solver's container: every side closed but the top"""
+    from .solver import WALLS_REFERENCE_BOX
+    solver.setSmoke(0.0, 1.0, rising_smoke(nz_global, h))
+    solver.setWalls(WALLS_REFERENCE_BOX)
+
+
 def plume(nz_global, h):
     """a shaped source (solver.Source list for BimocqGPUSolver.setSources): a box of half extents
     (0.08, 0.04, 0.08) given as a level set of spacing h, under the rising-smoke position, blowing upwards at 0.5 with a slow

@@ -21,6 +21,10 @@ class Emitter(C.Structure):
 
 
 SHAPE_SPHERE, SHAPE_BOX, SHAPE_LEVELSET = 0, 1, 2
+# closed domain walls (setWalls; include/bimocq_gpu.h): one bit per closed side; the reference's container is open at +y
+WALL_XLO, WALL_XHI, WALL_YLO, WALL_YHI, WALL_ZLO, WALL_ZHI = 1, 2, 4, 8, 16, 32
+WALLS_NONE, WALLS_REFERENCE_BOX = 0, 1 | 2 | 4 | 16 | 32
+FLAG_WALL = 0x80
 MAX_BOUNDARIES = 16
 
 
@@ -204,6 +208,8 @@ HOST_SIGS = {
     "bq_solver_set_boundary_levelsets": (C.c_int, [C.c_void_p, C.POINTER(Boundary), C.POINTER(LevelSetDesc), C.c_int]),
     "bq_solver_update_boundary": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
     "bq_solver_download_solid": (C.c_long, [C.c_void_p, C.c_void_p, C.c_long]),
+    "bq_solver_set_walls": (C.c_int, [C.c_void_p, C.c_int]),
+    "bq_solver_get_walls": (C.c_int, [C.c_void_p]),
     "bq_solver_set_sources": (C.c_int, [C.c_void_p, C.POINTER(SourceDesc), C.POINTER(LevelSetDesc), C.c_int]),
     "bq_solver_source_position": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
     "bq_solver_set_pcg_tolerance": (C.c_int, [C.c_void_p, C.c_double]),
@@ -367,6 +373,19 @@ class BimocqGPUSolver:
         self._check()
         if rc != 0:
             raise _lib.BimocqError("bq_solver_update_boundary failed")
+
+    def setWalls(self, mask):
+        """closes the sides in `mask` (a sum of WALL_* bits; WALLS_REFERENCE_BOX: every side but +y, WALLS_NONE: all open,
+        the default): their border cells become solid cells with velocity 0 for the projection.  One
+        GPU, Jacobi or PCG (kind 2) projection, with or without obstacles; a refused mask leaves the previous one."""
+        rc = self.lib.bq_solver_set_walls(self.s, int(mask))
+        self._check()
+        if rc != 0:
+            raise _lib.BimocqError("bq_solver_set_walls failed")
+
+    def walls(self):
+        """the closed sides in force (WALL_* bits)"""
+        return self.lib.bq_solver_get_walls(self.s)
 
     def setSources(self, sources):
         """replaces the list of shaped sources (Source objects; [] removes them and releases their grids).  Level-set

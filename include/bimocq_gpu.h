@@ -790,6 +790,43 @@ void gpu_obstacle_blend_ls(float *u, float *v, float *w, float *rho, float *T, c
                            const float *ws, const float *rhos, const float *Ts, const unsigned char *solid,
                            const bq_boundary *b, int n, const bq_levelset *ls, float h, int ni, int nj, int nk);
 
+/* ---- closed domain walls (reference: updateBoundary's flag-2 border, BimocqSolver.cpp:938-948, which the
+ * projection treats as obstacle cells with velocity 0, :1157-1164, :1184-1256, :1288-1356) -------------------------------
+ * `walls`: the closed sides, a sum of BQ_WALL_* bits.  A border cell of a closed side that no obstacle covers is a wall
+ * cell: solid, velocity 0.  Open sides keep p = 0 in the border cell.  `solidw`: the obstacle flags plus BQ_FLAG_WALL in
+ * the wall cells; `rows` stays the summary of the OBSTACLE flags (all zero without obstacles).  Single GPU. */
+#ifndef BQ_WALLS_DEFINED
+#define BQ_WALLS_DEFINED
+enum { BQ_WALL_XLO = 1, BQ_WALL_XHI = 2, BQ_WALL_YLO = 4, BQ_WALL_YHI = 8, BQ_WALL_ZLO = 16, BQ_WALL_ZHI = 32 };
+enum { BQ_WALLS_NONE = 0, BQ_WALLS_REFERENCE_BOX = 1 | 2 | 4 | 16 | 32 };   /* every side but +y (:938-948) */
+enum { BQ_FLAG_WALL = 0x80 };
+#endif
+/* solidw = solid (NULL: no obstacles) with BQ_FLAG_WALL in the wall cells (:938-948; an obstacle in the border layer
+ * keeps its own flag, as flag 3 is written over flag 2) */
+void gpu_wall_flags(unsigned char *solidw, const unsigned char *solid, int walls, int ni, int nj, int nk);
+/* a face with a wall cell on at least one side and an obstacle cell on neither takes 0 (:1157-1164: all six faces of a
+ * wall cell); where du/dv/dw are non-NULL they receive 0 - previous value there.  Writes no face gpu_obstacle_faces
+ * writes. */
+void gpu_wall_faces(float *u, float *v, float *w, float *du, float *dv, float *dw, const unsigned char *solidw,
+                    int ni, int nj, int nk);
+/* gpu_jacobi_sweep_masked / gpu_jacobi_sweeps_masked on solidw, value for value (:1184-1256): where the obstacle rows
+ * summary is clean the number of solid neighbours comes from the position alone (a closed side at i = 1, i = ni-2,
+ * j = 1, ...) and no flag is read; elsewhere from the flags of solidw.  walls = 0: the masked operators themselves. */
+void gpu_jacobi_sweep_masked_walls(const float *in, const float *div, float *out, const unsigned char *solidw,
+                                   const unsigned char *rows, int walls, int ni, int nj, int nk, float alpha, float beta);
+int  gpu_jacobi_sweeps_masked_walls(float *p, const float *div, float *p_temp, const unsigned char *solidw,
+                                    const unsigned char *rows, int walls, int ni, int nj, int nk, int sweeps,
+                                    float alpha, float beta);
+/* gpu_gradient_masked / gpu_pcg_gradient on solidw with the window starting at cell 1 instead of 2 on every axis whose
+ * low side is closed (:1288-1335 update every face between two fluid cells): the faces between the cells of the first
+ * interior layer behind a closed wall are projected too, so that those cells end divergence-free; behind an open side
+ * the window is the unchanged one.  The faces of wall cells are solid faces and stay alone.  walls = 0: the operators
+ * without walls. */
+void gpu_gradient_masked_walls(float *u, float *v, float *w, const float *p, float *du, float *dv, float *dw,
+                               const unsigned char *solidw, int walls, int ni, int nj, int nk, float halfrdx);
+void gpu_pcg_gradient_walls(float *u, float *v, float *w, const double *p, const unsigned char *solidw, int walls,
+                            int ni, int nj, int nk, double halfrdx);
+
 /* ---- shaped, moving smoke sources (reference: Emitter and BimocqSolver::emitSmoke of the CPU
  * solver, BimocqSolver.h:31-59, BimocqSolver.cpp:696-813) ----------------------------------------------------------------
  * A source is a shape of section 14 (sphere, box or level set) at a position.  A node belongs to it when the obstacle

@@ -203,6 +203,17 @@ int   bq_solver_set_boundary(bq_solver *s, const bq_boundary *b, int n);
  * obstacles.  Returns 0 on success. */
 int   bq_solver_set_boundary_levelsets(bq_solver *s, const bq_boundary *b, const bq_levelset *ls, int n);
 int   bq_solver_update_boundary(bq_solver *s, int framenum, float dt);
+/* Closed domain walls (the reference's container, BimocqSolver.cpp:938-948): `walls` is a sum of
+ * BQ_WALL_* bits (include/bimocq_gpu.h), BQ_WALLS_NONE (default: every side open, p = 0 in the border cells) or
+ * BQ_WALLS_REFERENCE_BOX (every side closed but +y).  Border cells of a closed side are solid cells with velocity 0 for
+ * the projection; no band, no blend, no density clear, and download_solid keeps reporting obstacle cells only.  One GPU,
+ * Jacobi projection or BQ_PROJECTION_PCG, every scheme, with or without obstacles, in any call order.  Refused through
+ * fl_last_error, the previous setting staying in place: z-slab ranks, BQ_PROJECTION_MGCG (also set_projection(MGCG)
+ * while walls are on) and an operator library without the wall operators with FL_ERR_UNSUPPORTED; bits outside 0 .. 63
+ * and all six sides closed (the pressure needs an open side as its reference) with FL_ERR_BAD_ARGUMENT.
+ * Returns 0 on success; get_walls returns the setting in force. */
+int   bq_solver_set_walls(bq_solver *s, int walls);
+int   bq_solver_get_walls(bq_solver *s);
 /* Shaped, moving smoke sources (Emitter / emitSmoke of the CPU solver, BimocqSolver.h:31-59, BimocqSolver.cpp:696-813;
  * DESIGN.md section 16): a second list next to the emitters of set_smoke, which keep their launches and their bits.
  * set_sources replaces the list (n = 0 releases list and grids; at most BQ_MAX_SOURCES).  ls is an array of n
