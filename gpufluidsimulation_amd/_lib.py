@@ -78,6 +78,9 @@ HIP_SIGS = {
     "fl_jacobi_kernel_name": (C.c_char_p, []),
     "fl_mg_smooth_kernel_name": (C.c_char_p, []),
     "fl_mg_fused_launches": (C.c_longlong, []),
+    "fl_sparse_stats": (None, [C.POINTER(C.c_longlong), c_i]),
+    "fl_sparse_stats_kind": (None, [c_i, C.POINTER(C.c_longlong), c_i]),
+    "gpu_brick_flags": (c_i, [VP, VP, c_i, c_i, c_i, VP, C.POINTER(c_i)]),
     # 3. additive
     "gpu_init_maps": (None, [VP, VP, VP] + _G),
     "gpu_maps_quarter_safe": (c_i, [VP, VP, VP] + _G),
@@ -181,6 +184,7 @@ FL_OPT_MGCG_BOTTOM = 17
 FL_OPT_MGCG_FUSE = 20
 FL_OPT_FIELD_WINDOW = 18
 FL_OPT_COMM_CHECK = 19
+FL_OPT_SKIP_EMPTY_BRICKS = 21
 
 
 class BimocqLibraryMissing(RuntimeError):

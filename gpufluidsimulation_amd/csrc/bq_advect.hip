@@ -8,6 +8,7 @@
 #include "bq_host.h"
 #include "bq_launch_geom.h"
 #include "bq_obstacle.hip.h"
+#include "bq_sparse.hip.h"
 
 #include <algorithm>
 #include <cstdint>
@@ -29,9 +30,11 @@ inline namespace BQ_VARIANT {
 // (bq_device.hip.h: stage_tiles), so every thread of a block has to reach the barrier: the index window
 // ilo < i < ihi, jlo < j < jhi, klo < kg < khi is tested as a predicate, only whole blocks leave early.
 // block_out: no thread of the block is inside the window (block-uniform, so leaving on it skips no barrier).
-#define BQ_IJK_WINDOW(ilo, ihi, jlo, jhi, klo, khi)                                           \
-    const int i0 = blockIdx.x * 64, j0 = blockIdx.y * 4;                                      \
-    const int i = i0 + threadIdx.x, j = j0 + threadIdx.y, k = blockIdx.z + g.kw0;             \
+#define BQ_IJK_WINDOW(ilo, ihi, jlo, jhi, klo, khi) BQ_IJK_WINDOW_AT((int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, ilo, ihi, jlo, jhi, klo, khi)
+// (the same for a workgroup that computes block (bx_, by_, bz_) of the grid, not necessarily its own: bq_sparse.hip.h)
+#define BQ_IJK_WINDOW_AT(bx_, by_, bz_, ilo, ihi, jlo, jhi, klo, khi)                         \
+    const int i0 = (bx_) * 64, j0 = (by_) * 4;                                                \
+    const int i = i0 + threadIdx.x, j = j0 + threadIdx.y, k = (bz_) + g.kw0;                  \
     const int kg = k + g.koff;                                                                \
     const bool block_out = !((klo) < kg && kg < (khi)) || i0 + 63 <= (ilo) || i0 >= (ihi) || j0 + 3 <= (jlo) || j0 >= (jhi); \
     const bool active = !block_out && (ilo) < i && i < (ihi) && (jlo) < j && j < (jhi);
@@ -237,23 +240,52 @@ template <int NF> struct CompensateArgs { const float *src[NF]; float *init[NF];
 
 // ---- A5: advect_kernel (GPU_kernel.cu:312-374) --------------------------------------------
 // Q4: the caller vouches for the map's values (tile_value_ok): the quarter-weight map lerps run in fp32
-template <bool P2, bool PT, int SD, int NF, bool Q4 = false>
+// SPARSE (unstaggered, staged; bq_sparse.hip.h): 1 = the classifying launch of FL_OPT_SKIP_EMPTY_BRICKS -- a block whose taps
+// can only land in empty bricks of the sampled fields takes every gather result as +0.0f and runs the stores below
+// unchanged, every other block goes on the list; 2 = this kernel on the listed blocks.
+template <bool P2, bool PT, int SD, int NF, bool Q4 = false, int SPARSE = 0>
 __global__ __launch_bounds__(256, NF == 1 ? 7 : 5) void advect_kernel(AdvectArgs<NF> a,
                                                      const float *bx, const float *by, const float *bz,
-                                                     Spacing sp, Grid g, int dx, int dy, int dz, int fused, MapTabs tabs)
+                                                     Spacing sp, Grid g, int dx, int dy, int dz, int fused, MapTabs tabs, Sparse sps)
 {
+    static_assert(!SPARSE || (SD == 0 && kStaged<P2, PT, SD>), "the skip exists for unstaggered staged launches only");
     const int nbi = g.ni + dx, nbj = g.nj + dy, nbk = g.nk + dz;
-    BQ_IJK_WINDOW(2 + dx, nbi - 3, 2 + dy, nbj - 3, 2 + dz, g.nkg + dz - 3)
+    int bX = blockIdx.x, bY = blockIdx.y, bZ = blockIdx.z;
+    if constexpr (SPARSE == 1) { if (*sps.word != sps.epoch) return; }         // no empty brick: the second launch is the plain one
+    if constexpr (SPARSE == 2) { if (!listed_block(sps, bX, bY, bZ)) return; }
+    BQ_IJK_WINDOW_AT(bX, bY, bZ, 2 + dx, nbi - 3, 2 + dy, nbj - 3, 2 + dz, g.nkg + dz - 3)
     // FL_OPT_FUSED_HOUSEKEEPING bit 1: nodes outside the window get the zero the caller's clear would have left
-    if ((fused & 1) && !active && i < nbi && j < nbj) {
+    // (SPARSE == 1: only in the blocks this launch finishes -- a listed block is left to the second launch altogether)
+    auto housekeeping = [&] {
+        if ((fused & 1) && !active && i < nbi && j < nbj) {
 #pragma unroll
-        for (int f = 0; f < NF; f++) a.field[f][(size_t)i + (size_t)nbi * j + (size_t)nbi * nbj * k] = 0.f;
-    }
-    if (block_out) return;
+            for (int f = 0; f < NF; f++) a.field[f][(size_t)i + (size_t)nbi * j + (size_t)nbi * nbj * k] = 0.f;
+        }
+    };
+    if constexpr (SPARSE != 1) housekeeping();
+    if (block_out) { if constexpr (SPARSE == 1) housekeeping(); return; }
     const float h = sp.h;
     Map3 back{make_field(bx, g.ni, g.nj, g.nk, g.koff), make_field(by, g.ni, g.nj, g.nk, g.koff), make_field(bz, g.ni, g.nj, g.nk, g.koff)};
     Nine n = nine_setup(h, dx, dy, dz);
     f3 lo = mk3(h, h, h), hi = mk3(h * (float)g.ni - h, h * (float)g.nj - h, h * (float)g.nkg - h);
+    if constexpr (SPARSE == 1) {
+        // (a block that gets here has an active thread -- block_out is exact for boxes -- hence ni, nj, nkg >= 7 and lo <= hi)
+        __shared__ float part[32];
+        const Field mf[3] = {back.x, back.y, back.z};
+        float mn[3], mx[3]; bool bad;
+        tile_range(mf, i0, j0, k, part, 2, nbi - 3, 2, nbj - 3, mn, mx, bad);
+        const bool skip = taps_in_empty_bricks<P2>(sps, mn, mx, bad, lo, hi, sp, nbi, nbj, nbk);
+        count_block(sps, skip);
+        if (!skip) { list_block(sps, bX + gridDim.x * (bY + gridDim.y * bZ)); return; }
+        housekeeping();
+        if (!active) return;
+        // all eight corners of every tap are +0.0f, and a lerp of +0 and +0 is +0 for every weight in [0, 1] in both lerp
+        // forms: sum = 0 + 0.125f * (+0) eight times and value are +0 -- the store of the full path with those operands
+        const float sum = 0.f, value = 0.f;
+#pragma unroll
+        for (int f = 0; f < NF; f++)
+            a.field[f][(size_t)i + (size_t)nbi * j + (size_t)nbi * nbj * k] = 0.5f * sum + 0.5f * value;
+    } else {
     f3 c = nine_centre(n, i, j, kg);
     f3 mp[9];
     if constexpr (kStaged<P2, PT, SD>) {
@@ -279,6 +311,7 @@ __global__ __launch_bounds__(256, NF == 1 ? 7 : 5) void advect_kernel(AdvectArgs
 #pragma unroll
     for (int f = 0; f < NF; f++)
         a.field[f][(size_t)i + (size_t)nbi * j + (size_t)nbi * nbj * k] = 0.5f * sum[f] + 0.5f * value[f];
+    }
 }
 
 // ---- A7: doubleAdvect_kernel (GPU_kernel.cu:236-310) --------------------------------------
@@ -332,13 +365,17 @@ __global__ __launch_bounds__(256) void unit_blend_kernel(float *field, Grid g, i
 
 // ---- A6/A8: cumulate_kernel (GPU_kernel.cu:376-436): dst += blend9(coeff*src(map(x))) ------
 // ID: the map is the identity map of gpu_init_maps (mx/my/mz are not read).
-template <bool P2, bool PT, int SD, int NF, bool ID, bool Q4 = false>
+template <bool P2, bool PT, int SD, int NF, bool ID, bool Q4 = false, int SPARSE = 0>
 __global__ __launch_bounds__(256, NF == 1 ? 7 : 6) void cumulate_kernel(CumulateArgs<NF> a,
                                                        const float *mx, const float *my, const float *mz,
-                                                       Spacing sp, Grid g, int dx, int dy, int dz, MapTabs tabs)
+                                                       Spacing sp, Grid g, int dx, int dy, int dz, MapTabs tabs, Sparse sps)
 {
+    static_assert(!SPARSE || (SD == 0 && !ID && kStaged<P2, PT, SD>), "the skip exists for unstaggered staged launches only");
     const int nbi = g.ni + dx, nbj = g.nj + dy, nbk = g.nk + dz;
-    BQ_IJK_WINDOW(1 + dx, nbi - 2, 1 + dy, nbj - 2, 1 + dz, g.nkg + dz - 2)
+    int bX = blockIdx.x, bY = blockIdx.y, bZ = blockIdx.z;
+    if constexpr (SPARSE == 1) { if (*sps.word != sps.epoch) return; }
+    if constexpr (SPARSE == 2) { if (!listed_block(sps, bX, bY, bZ)) return; }
+    BQ_IJK_WINDOW_AT(bX, bY, bZ, 1 + dx, nbi - 2, 1 + dy, nbj - 2, 1 + dz, g.nkg + dz - 2)
     if (block_out) return;
     const float h = sp.h;
     Map3 m{make_field(mx, g.ni, g.nj, g.nk, g.koff), make_field(my, g.ni, g.nj, g.nk, g.koff), make_field(mz, g.ni, g.nj, g.nk, g.koff)};
@@ -346,8 +383,36 @@ __global__ __launch_bounds__(256, NF == 1 ? 7 : 6) void cumulate_kernel(Cumulate
     f3 lo = mk3(0.f, 0.f, 0.f), hi = mk3(h * (float)g.ni, h * (float)g.nj, h * (float)g.nkg);
     f3 c = nine_centre(n, i, j, kg);
     const size_t id = (size_t)i + (size_t)nbi * j + (size_t)nbi * nbj * k;
-    __shared__ float tile[kStaged<P2, PT, SD> && !ID ? 3 * kTile : 1];
-    (void)tabs;
+    __shared__ float tile[kStaged<P2, PT, SD> && !ID && SPARSE != 1 ? 3 * kTile : 32];
+    (void)tabs; (void)sps;
+    if constexpr (SPARSE == 1) {
+        const Field mf[3] = {m.x, m.y, m.z};
+        float mn[3], mxv[3]; bool bad;
+        // (dst is read ahead of the classification, next to the tile: one wait for memory instead of two)
+        float dst_own[NF];
+#pragma unroll
+        for (int f = 0; f < NF; f++) dst_own[f] = active ? a.dst[f][id] : 0.f;
+        tile_range(mf, i0, j0, k, tile, 1, nbi - 2, 1, nbj - 2, mn, mxv, bad);
+        const bool skip = taps_in_empty_bricks<P2>(sps, mn, mxv, bad, lo, hi, sp, nbi, nbj, nbk);
+        count_block(sps, skip);
+        if (!skip) { list_block(sps, bX + gridDim.x * (bY + gridDim.y * bZ)); return; }
+        if (!active) return;
+        // every gather result is +0.0f: the statements of the full path with that operand -- the products with coeff stay
+        // (a finite w of either sign leaves sum at +0, as +0 + -0 = +0; a w that is not finite makes it NaN, as in the full
+        // path), and dst += ... turns a -0 in dst into +0 as before
+#pragma unroll
+        for (int f = 0; f < NF; f++) {
+            const float w = (PT ? 1.0f : 0.125f) * a.coeff[f];
+            float sum = 0.f;
+#pragma unroll
+            for (int ii = 0; ii < (PT ? 1 : 8); ii++) sum += w * 0.f;
+            const float v = a.coeff[f] * 0.f;
+            // (dst[0] == dst[1] is allowed and applied in order: the second field then starts from what the first stored)
+            const float before = (f > 0 && a.dst[f] == a.dst[0]) ? a.dst[f][id] : dst_own[f];
+            a.dst[f][id] = before + (float)(0.5 * (double)sum + 0.5 * (double)v);
+        }
+        return;
+    }
     if constexpr (ID) {
         // Identity map (node n holds n*h), power-of-two spacing.  A map component then varies along its
         // own axis only; map9's lerps along the other two axes combine equal values (lerp(a, a, c) == a
@@ -443,36 +508,63 @@ __global__ __launch_bounds__(256) void wall_fixup_kernel(const float *src, int s
 }
 
 // ---- A6: compensate_kernel (GPU_kernel.cu:438-499): err = blend9(src(map(x))) - init(x) ----
-template <bool P2, bool PT, int SD, int NF, bool Q4 = false>
+template <bool P2, bool PT, int SD, int NF, bool Q4 = false, int SPARSE = 0>
 __global__ __launch_bounds__(256, NF == 1 ? 7 : 6) void compensate_kernel(CompensateArgs<NF> a,
                                                          const float *mx, const float *my, const float *mz,
-                                                         Spacing sp, Grid g, int dx, int dy, int dz, int fused, MapTabs tabs)
+                                                         Spacing sp, Grid g, int dx, int dy, int dz, int fused, MapTabs tabs, Sparse sps)
 {
+    static_assert(!SPARSE || (SD == 0 && kStaged<P2, PT, SD>), "the skip exists for unstaggered staged launches only");
     const int nbi = g.ni + dx, nbj = g.nj + dy, nbk = g.nk + dz;
-    BQ_IJK_WINDOW(1 + dx, nbi - 2, 1 + dy, nbj - 2, 1 + dz, g.nkg + dz - 2)
+    int bX = blockIdx.x, bY = blockIdx.y, bZ = blockIdx.z;
+    if constexpr (SPARSE == 1) { if (*sps.word != sps.epoch) return; }
+    if constexpr (SPARSE == 2) { if (!listed_block(sps, bX, bY, bZ)) return; }
+    BQ_IJK_WINDOW_AT(bX, bY, bZ, 1 + dx, nbi - 2, 1 + dy, nbj - 2, 1 + dz, g.nkg + dz - 2)
     const size_t id = (size_t)i + (size_t)nbi * j + (size_t)nbi * nbj * k;
     // FL_OPT_FUSED_HOUSEKEEPING.  Bit 2: init <- the uncompensated field, on EVERY node of the buffer (stage 2 of
     // gpu_compensate_*, GPU_kernel.cu:656-658).  A thread reads init only at its own node, before it stores there,
     // and no thread reads init anywhere else or writes src, so doing it here is race-free.  Bit 1: err = 0 outside
     // the window (the caller's clear).
+    // (SPARSE == 1: only in the blocks this launch finishes -- a listed block is left to the second launch altogether,
+    // which has to find init as the caller left it)
     float init_own[NF];
-    if (i < nbi && j < nbj) {
+    auto housekeeping = [&] {
+        if (i < nbi && j < nbj) {
 #pragma unroll
-        for (int f = 0; f < NF; f++) {
-            init_own[f] = a.init[f][id];
-            if (fused & 2) a.init[f][id] = a.src[f][id];
-            if ((fused & 1) && !active) a.err[f][id] = 0.f;
+            for (int f = 0; f < NF; f++) {
+                init_own[f] = a.init[f][id];
+                if (fused & 2) a.init[f][id] = a.src[f][id];
+                if ((fused & 1) && !active) a.err[f][id] = 0.f;
+            }
         }
-    }
-    if (block_out) return;
+    };
+    if constexpr (SPARSE != 1) housekeeping();
+    if (block_out) { if constexpr (SPARSE == 1) housekeeping(); return; }
     const float h = sp.h;
     Map3 m{make_field(mx, g.ni, g.nj, g.nk, g.koff), make_field(my, g.ni, g.nj, g.nk, g.koff), make_field(mz, g.ni, g.nj, g.nk, g.koff)};
     Nine n = nine_setup(h, dx, dy, dz);
     f3 lo = mk3(0.f, 0.f, 0.f), hi = mk3(h * (float)g.ni, h * (float)g.nj, h * (float)g.nkg);
+    if constexpr (SPARSE == 1) {
+        __shared__ float part[32];
+        const Field mf[3] = {m.x, m.y, m.z};
+        float mn[3], mxv[3]; bool bad;
+        tile_range(mf, i0, j0, k, part, 1, nbi - 2, 1, nbj - 2, mn, mxv, bad);
+        const bool skip = taps_in_empty_bricks<P2>(sps, mn, mxv, bad, lo, hi, sp, nbi, nbj, nbk);
+        count_block(sps, skip);
+        if (!skip) { list_block(sps, bX + gridDim.x * (bY + gridDim.y * bZ)); return; }
+        housekeeping();
+        if (!active) return;
+        // every gather result is +0.0f: sum = 0 + 0.125f * (+0) eight times and value are +0 -- the store of the full path
+        // with those operands
+        const float sum = 0.f, value = 0.f;
+#pragma unroll
+        for (int f = 0; f < NF; f++)
+            a.err[f][id] = (float)(0.5 * (double)sum + 0.5 * (double)value) - init_own[f];
+        return;
+    }
     f3 c = nine_centre(n, i, j, kg);
     f3 mp[9];
     if constexpr (kStaged<P2, PT, SD>) {
-        __shared__ float tile[3 * kTile];
+        __shared__ float tile[SPARSE == 1 ? 1 : 3 * kTile];
         const Field mf[3] = {m.x, m.y, m.z};
         stage_tiles<3>(mf, i0, j0, k, tile);
         if (!active) return;
@@ -894,6 +986,53 @@ static bool march_launch(const MarchArgs<NF> &a, const float *mx, const float *m
     return true;
 }
 
+// FL_OPT_SKIP_EMPTY_BRICKS: the flag pass over the NF source arrays (nbi x nbj x nbk) of a launch, issued on the compute stream
+// right in front of that launch, so a flag can never be stale.  Returns what the kernel needs; flags == nullptr: launch
+// without the skip (option off, or the launch is not one the skip is built for -- the caller passes `eligible`).
+// The flag array and the header (pass word, counters) are per-context scratch that grows on demand, like map_tab_dev.
+// kind: whose counters the launch feeds (0 advection, 1 error stage, 2 accumulation).
+template <int NF>
+static Sparse brick_flags(bool eligible, int kind, const float *const (&src)[NF], int nbi, int nbj, int nbk, size_t nblocks, bool force = false)
+{
+    Runtime &r = rt();
+    Sparse none{ nullptr, nullptr, nullptr, nullptr, 0, 0, 0 };
+    // (an open fl_aux_* section runs two streams side by side: they would share the one flag array)
+    if (!eligible || (!r.opt_skip_empty_bricks && !force) || r.compute_main) return none;
+    const int nbx = (nbi + kBrick - 1) >> kBrickShift, nby = (nbj + kBrick - 1) >> kBrickShift, nbz = (nbk + kBrick - 1) >> kBrickShift;
+    if (nby > 65535 || nbz > 65535) return none;
+    // the flags, then (4-byte aligned) the block list of the classifying launch: a count and one entry per block of its grid
+    const size_t nflags = (size_t)nbx * nby * nbz, list_at = (nflags + 255) & ~(size_t)255;
+    const size_t need = list_at + 4 * (nblocks + 1);
+    if (nblocks >= 0x7fffffffu) return none;
+    if (!r.sparse_hdr) {
+        if (!BQ_HIP(hipMalloc((void **)&r.sparse_hdr, 64))) { r.sparse_hdr = nullptr; return none; }
+        if (!BQ_HIP(hipMemsetAsync(r.sparse_hdr, 0, 64, r.compute))) return none;
+        r.sparse_epoch = 0;
+    }
+    if (need > r.sparse_cap) {
+        if (r.sparse_flags) { (void)hipStreamSynchronize(r.compute); (void)hipFree(r.sparse_flags); r.sparse_flags = nullptr; r.sparse_cap = 0; }
+        if (!BQ_HIP(hipMalloc((void **)&r.sparse_flags, need))) { r.sparse_flags = nullptr; return none; }
+        r.sparse_cap = need;
+    }
+    if (r.sparse_epoch == 0x7fffffff) {             // the pass numbers start over
+        if (!BQ_HIP(hipMemsetAsync(r.sparse_hdr, 0, 4, r.compute))) return none;
+        r.sparse_epoch = 0;
+    }
+    const int epoch = ++r.sparse_epoch;
+    BrickSrc<NF> bs;
+    for (int f = 0; f < NF; f++) bs.p[f] = src[f];
+    int *list = reinterpret_cast<int *>(r.sparse_flags + list_at);
+    brick_flags_kernel<NF><<<dim3((nbi + 63) / 64, nby, nbz), kBlock, 0, r.compute>>>(bs, nbi, nbj, nbk, r.sparse_flags, r.sparse_hdr, epoch, list);
+    if (!BQ_LAUNCH_CHECK("brick_flags_kernel")) return none;
+    unsigned long long *stats = (r.opt_skip_empty_bricks == 2 || r.opt_skip_empty_bricks == 4) ? reinterpret_cast<unsigned long long *>(r.sparse_hdr + 2) + 2 * kind : nullptr;
+    return Sparse{ r.sparse_flags, r.sparse_hdr, stats, list, epoch, nbx, nby };
+}
+// the launches the skip is built for: unstaggered, one GPU, the whole array, the staged one-plane kernels
+static inline bool sparse_eligible(const Grid &g, int planes, int dx, int dy, int dz, bool staged)
+{
+    return staged && !dx && !dy && !dz && !rt().slab_on && g.koff == 0 && g.kw0 == 0 && planes == g.nk;
+}
+
 template <int NF>
 static void advect_multi(AdvectArgs<NF> a, const float *bx, const float *by, const float *bz,
                          Spacing sp, Grid g, int dx, int dy, int dz, bool pt)
@@ -911,14 +1050,25 @@ static void advect_multi(AdvectArgs<NF> a, const float *bx, const float *by, con
     }
     int tab_ok = 0;
     const MapTabs tabs = (!sp.pow2 && !pt && rt().opt_structured_maps) ? map_tabs(sp, g, &tab_ok) : MapTabs{ nullptr, nullptr, 0 };
+    const bool tabled = tabs.frac && tabs_cover(tab_ok, stag_axis(dx, dy, dz));
+    const Sparse sps = brick_flags<NF>(sparse_eligible(g, planes, dx, dy, dz, !pt && rt().opt_structured_maps && (sp.pow2 || tabled)), 0,
+                                       a.init, g.ni, g.nj, g.nk, (size_t)grid.x * grid.y * grid.z);
     dispatch_sd(sp.pow2, pt, stag_axis(dx, dy, dz), [&](auto P2, auto PT, auto SD) {
         constexpr bool p2 = decltype(P2)::value, ptc = decltype(PT)::value;
         constexpr int sd = decltype(SD)::value;
-        if constexpr (p2 && kStaged<p2, ptc, sd>) {
-            if (q4) { advect_kernel<p2, ptc, sd, NF, true><<<grid, kBlock, 0, st>>>(a, bx, by, bz, sp, g, dx, dy, dz, rt().opt_fused_housekeeping, tabs); return; }
+        if constexpr (sd == 0 && kStaged<p2, ptc, sd>) {
+            if (sps.flags) {            // classify (and finish the blocks that can be skipped), then the listed blocks
+                advect_kernel<p2, ptc, sd, NF, false, 1><<<grid, kBlock, 0, st>>>(a, bx, by, bz, sp, g, dx, dy, dz, rt().opt_fused_housekeeping, tabs, sps);
+                if (p2 && q4) advect_kernel<p2, ptc, sd, NF, p2, 2><<<grid, kBlock, 0, st>>>(a, bx, by, bz, sp, g, dx, dy, dz, rt().opt_fused_housekeeping, tabs, sps);
+                else advect_kernel<p2, ptc, sd, NF, false, 2><<<grid, kBlock, 0, st>>>(a, bx, by, bz, sp, g, dx, dy, dz, rt().opt_fused_housekeeping, tabs, sps);
+                return;
+            }
         }
-        advect_kernel<p2, ptc, sd, NF, false><<<grid, kBlock, 0, st>>>(a, bx, by, bz, sp, g, dx, dy, dz, rt().opt_fused_housekeeping, tabs);
-    }, tabs.frac && tabs_cover(tab_ok, stag_axis(dx, dy, dz)));
+        if constexpr (p2 && kStaged<p2, ptc, sd>) {
+            if (q4) { advect_kernel<p2, ptc, sd, NF, true><<<grid, kBlock, 0, st>>>(a, bx, by, bz, sp, g, dx, dy, dz, rt().opt_fused_housekeeping, tabs, sps); return; }
+        }
+        advect_kernel<p2, ptc, sd, NF, false><<<grid, kBlock, 0, st>>>(a, bx, by, bz, sp, g, dx, dy, dz, rt().opt_fused_housekeeping, tabs, sps);
+    }, tabled);
     BQ_LAUNCH_CHECK("advect_kernel");
 }
 // identity: the caller vouches that mx/my/mz hold the identity map of gpu_init_maps; the shortcut is
@@ -939,15 +1089,31 @@ static void cumulate_multi(CumulateArgs<NF> a, const float *mx, const float *my,
     }
     int tab_ok = 0;
     const MapTabs tabs = (!sp.pow2 && !pt && rt().opt_structured_maps) ? map_tabs(sp, g, &tab_ok) : MapTabs{ nullptr, nullptr, 0 };
+    const bool tabled = tabs.frac && tabs_cover(tab_ok, stag_axis(dx, dy, dz));
+    // (the identity accumulate reads its nodes directly on the power-of-two path: no staged map, no skip)
+    // Option values 3 / 4 only: the accumulation usually samples through a BACKWARD map, whose zeroed border its
+    // window reaches; at 256^3 half of its blocks then cannot be skipped and the two launches cost more than the one
+    // (EXPERIMENTS section 14), so the default leaves this operator alone.
+    const Sparse sps = brick_flags<NF>(rt().opt_skip_empty_bricks >= 3 &&
+                                       sparse_eligible(g, planes, dx, dy, dz, !pt && rt().opt_structured_maps && (tabled || (sp.pow2 && !identity))), 2,
+                                       a.src, g.ni, g.nj, g.nk, (size_t)grid.x * grid.y * grid.z);
     dispatch_sd(sp.pow2, pt, stag_axis(dx, dy, dz), [&](auto P2, auto PT, auto SD) {
         constexpr bool p2 = decltype(P2)::value, ptc = decltype(PT)::value;
         constexpr int sd = decltype(SD)::value;
-        if constexpr (p2 && !ptc && sd >= 0) {
-            if (identity) { cumulate_kernel<p2, ptc, sd, NF, true><<<grid, kBlock, 0, st>>>(a, mx, my, mz, sp, g, dx, dy, dz, tabs); return; }
-            if (rt().opt_map_quarter_fp32) { cumulate_kernel<p2, ptc, sd, NF, false, true><<<grid, kBlock, 0, st>>>(a, mx, my, mz, sp, g, dx, dy, dz, tabs); return; }
+        if constexpr (sd == 0 && kStaged<p2, ptc, sd>) {
+            if (sps.flags) {
+                cumulate_kernel<p2, ptc, sd, NF, false, false, 1><<<grid, kBlock, 0, st>>>(a, mx, my, mz, sp, g, dx, dy, dz, tabs, sps);
+                if (p2 && rt().opt_map_quarter_fp32) cumulate_kernel<p2, ptc, sd, NF, false, p2, 2><<<grid, kBlock, 0, st>>>(a, mx, my, mz, sp, g, dx, dy, dz, tabs, sps);
+                else cumulate_kernel<p2, ptc, sd, NF, false, false, 2><<<grid, kBlock, 0, st>>>(a, mx, my, mz, sp, g, dx, dy, dz, tabs, sps);
+                return;
+            }
         }
-        cumulate_kernel<p2, ptc, sd, NF, false><<<grid, kBlock, 0, st>>>(a, mx, my, mz, sp, g, dx, dy, dz, tabs);
-    }, tabs.frac && tabs_cover(tab_ok, stag_axis(dx, dy, dz)));
+        if constexpr (p2 && !ptc && sd >= 0) {
+            if (identity) { cumulate_kernel<p2, ptc, sd, NF, true><<<grid, kBlock, 0, st>>>(a, mx, my, mz, sp, g, dx, dy, dz, tabs, sps); return; }
+            if (rt().opt_map_quarter_fp32) { cumulate_kernel<p2, ptc, sd, NF, false, true><<<grid, kBlock, 0, st>>>(a, mx, my, mz, sp, g, dx, dy, dz, tabs, sps); return; }
+        }
+        cumulate_kernel<p2, ptc, sd, NF, false><<<grid, kBlock, 0, st>>>(a, mx, my, mz, sp, g, dx, dy, dz, tabs, sps);
+    }, tabled);
     BQ_LAUNCH_CHECK("cumulate_kernel");
 }
 template <int NF>
@@ -967,14 +1133,25 @@ static void compensate_multi(CompensateArgs<NF> a, const float *mx, const float 
     }
     int tab_ok = 0;
     const MapTabs tabs = (!sp.pow2 && !pt && rt().opt_structured_maps) ? map_tabs(sp, g, &tab_ok) : MapTabs{ nullptr, nullptr, 0 };
+    const bool tabled = tabs.frac && tabs_cover(tab_ok, stag_axis(dx, dy, dz));
+    const Sparse sps = brick_flags<NF>(sparse_eligible(g, planes, dx, dy, dz, !pt && rt().opt_structured_maps && (sp.pow2 || tabled)), 1,
+                                       a.src, g.ni, g.nj, g.nk, (size_t)grid.x * grid.y * grid.z);
     dispatch_sd(sp.pow2, pt, stag_axis(dx, dy, dz), [&](auto P2, auto PT, auto SD) {
         constexpr bool p2 = decltype(P2)::value, ptc = decltype(PT)::value;
         constexpr int sd = decltype(SD)::value;
-        if constexpr (p2 && kStaged<p2, ptc, sd>) {
-            if (q4) { compensate_kernel<p2, ptc, sd, NF, true><<<grid, kBlock, 0, st>>>(a, mx, my, mz, sp, g, dx, dy, dz, rt().opt_fused_housekeeping, tabs); return; }
+        if constexpr (sd == 0 && kStaged<p2, ptc, sd>) {
+            if (sps.flags) {
+                compensate_kernel<p2, ptc, sd, NF, false, 1><<<grid, kBlock, 0, st>>>(a, mx, my, mz, sp, g, dx, dy, dz, rt().opt_fused_housekeeping, tabs, sps);
+                if (p2 && q4) compensate_kernel<p2, ptc, sd, NF, p2, 2><<<grid, kBlock, 0, st>>>(a, mx, my, mz, sp, g, dx, dy, dz, rt().opt_fused_housekeeping, tabs, sps);
+                else compensate_kernel<p2, ptc, sd, NF, false, 2><<<grid, kBlock, 0, st>>>(a, mx, my, mz, sp, g, dx, dy, dz, rt().opt_fused_housekeeping, tabs, sps);
+                return;
+            }
         }
-        compensate_kernel<p2, ptc, sd, NF, false><<<grid, kBlock, 0, st>>>(a, mx, my, mz, sp, g, dx, dy, dz, rt().opt_fused_housekeeping, tabs);
-    }, tabs.frac && tabs_cover(tab_ok, stag_axis(dx, dy, dz)));
+        if constexpr (p2 && kStaged<p2, ptc, sd>) {
+            if (q4) { compensate_kernel<p2, ptc, sd, NF, true><<<grid, kBlock, 0, st>>>(a, mx, my, mz, sp, g, dx, dy, dz, rt().opt_fused_housekeeping, tabs, sps); return; }
+        }
+        compensate_kernel<p2, ptc, sd, NF, false><<<grid, kBlock, 0, st>>>(a, mx, my, mz, sp, g, dx, dy, dz, rt().opt_fused_housekeeping, tabs, sps);
+    }, tabled);
     BQ_LAUNCH_CHECK("compensate_kernel");
 }
 
@@ -1605,6 +1782,53 @@ void fl_map_guard_read(int ok[2])
         bad[0] = hf[0] != 0.f; bad[1] = hf[1] != 0.f;
     }
     ok[0] = !bad[0]; ok[1] = !bad[1];
+}
+
+// FL_OPT_SKIP_EMPTY_BRICKS = 2 or 4: out[0] = blocks whose taps were tested against the brick flags, out[1] = how many of them
+// were skipped, since the last reset (blocking; reset != 0 clears).  fl_sparse_stats_kind: the same per operator
+// (kind 0 advection, 1 error stage, 2 accumulation; reset clears that operator's pair only).
+static void sparse_stats(int kind0, int kind1, long long out[2], int reset)
+{
+    if (!out) return;
+    out[0] = out[1] = 0;
+    Runtime &r = rt();
+    if (!r.ready || !r.sparse_hdr) return;
+    unsigned long long *host = (unsigned long long *)pinned(64);
+    if (!host) return;
+    hipStream_t st = r.compute;
+    const size_t bytes = 16 * (size_t)(kind1 - kind0);
+    unsigned long long *dev = reinterpret_cast<unsigned long long *>(r.sparse_hdr + 2) + 2 * kind0;
+    if (!BQ_HIP(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st))) return;
+    if (reset && !BQ_HIP(hipMemsetAsync(dev, 0, bytes, st))) return;
+    if (!BQ_HIP(hipStreamSynchronize(st))) return;
+    for (int k = 0; k < kind1 - kind0; k++) { out[0] += (long long)(host[2 * k] + host[2 * k + 1]); out[1] += (long long)host[2 * k + 1]; }
+}
+void fl_sparse_stats(long long out[2], int reset) { sparse_stats(0, 3, out, reset); }
+void fl_sparse_stats_kind(int kind, long long out[2], int reset)
+{
+    if (kind < 0 || kind > 2) { latch(FL_ERR_BAD_ARGUMENT, "fl_sparse_stats_kind", "kind must be 0, 1 or 2"); return; }
+    sparse_stats(kind, kind + 1, out, reset);
+}
+
+// The flag pass on its own (for tests and tools/brick_occupancy.py): flags of the 8 x 8 x 8 bricks of one field, or of two
+// taken together (f2 may be NULL), copied to flags_host -- ceil(ni/8) * ceil(nj/8) * ceil(nk/8) bytes, x fastest; *any_empty
+// (may be NULL) = 1 when some brick is empty.  Blocking.  Returns the number of bricks, -1 on an error (latched).
+int gpu_brick_flags(const float *f1, const float *f2, int ni, int nj, int nk, unsigned char *flags_host, int *any_empty)
+{
+    if (!ensure_ready("gpu_brick_flags") || !dims_ok(ni, nj, nk, "gpu_brick_flags")) return -1;
+    if (!f1 || !flags_host) { latch(FL_ERR_BAD_ARGUMENT, "gpu_brick_flags", "null pointer"); return -1; }
+    Sparse s;
+    if (f2) { const float *const src[2] = { f1, f2 }; s = brick_flags<2>(true, 0, src, ni, nj, nk, 0, true); }
+    else { const float *const src[1] = { f1 }; s = brick_flags<1>(true, 0, src, ni, nj, nk, 0, true); }
+    if (!s.flags) { latch(FL_ERR_UNSUPPORTED, "gpu_brick_flags", "no flag pass (an fl_aux_* section is open, or the allocation failed)"); return -1; }
+    const size_t n = (size_t)s.nbx * s.nby * ((nk + kBrick - 1) >> kBrickShift);
+    int *host = (int *)pinned(64);
+    if (!host) return -1;
+    hipStream_t st = rt().compute;
+    if (!BQ_HIP(hipMemcpyAsync(flags_host, s.flags, n, hipMemcpyDeviceToHost, st)) ||
+        !BQ_HIP(hipMemcpyAsync(host, s.word, 4, hipMemcpyDeviceToHost, st)) || !BQ_HIP(hipStreamSynchronize(st))) return -1;
+    if (any_empty) *any_empty = host[0] == s.epoch;
+    return (int)n;
 }
 
 // which map-update instance ran last (which: 0 the DMC sub-step, 1 the forward update), "" before the first; and which

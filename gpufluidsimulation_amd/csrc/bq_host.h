@@ -69,6 +69,13 @@ struct Runtime {
     float *map_tab_dev = nullptr;
     float  map_tab_h = 0.f;
     int    map_tab_dims[3] = {0, 0, 0}, map_tab_stride = 0, map_tab_ok = 0;
+    // FL_OPT_SKIP_EMPTY_BRICKS (bq_advect.hip: brick_flags): one flag per 8^3 brick of the arrays the last flag pass read, and a
+    // header -- word 0: number of the last pass that found an empty brick; bytes 8..55: three pairs of 64-bit block counters (option value 2)
+    unsigned char *sparse_flags = nullptr;
+    size_t sparse_cap = 0;
+    int   *sparse_hdr = nullptr;
+    int    sparse_epoch = 0;            // passes issued so far
+    int    opt_skip_empty_bricks = 1;   // 0 off, 1 on (advection, error stage), 2 = 1 and counting, 3 = 1 plus the accumulation, 4 = 3 and counting
     int    nonfinite_seen = 0;          // sticky: a gpu_max_abs3 met a NaN or an Inf (fl_nonfinite_seen)
     const char *map_kernel_name[2] = { "", "" };    // the DMC / forward instance launched last (fl_map_kernel_name)
     int    map_kernels_seen = 0;        // instances launched since the last reset, as bits (fl_map_kernels_seen)

@@ -206,6 +206,9 @@ void fl_shutdown(void)
     if (g_rt.map_guard) (void)hipFree(g_rt.map_guard);
     if (g_rt.map_tab_dev) (void)hipFree(g_rt.map_tab_dev);
     g_rt.map_tab_dev = nullptr; g_rt.map_tab_h = 0.f; g_rt.map_tab_ok = 0;
+    if (g_rt.sparse_flags) (void)hipFree(g_rt.sparse_flags);
+    if (g_rt.sparse_hdr) (void)hipFree(g_rt.sparse_hdr);
+    g_rt.sparse_flags = nullptr; g_rt.sparse_cap = 0; g_rt.sparse_hdr = nullptr; g_rt.sparse_epoch = 0;
     g_rt.map_guard = nullptr; g_rt.map_guard_on = false;
     if (g_rt.compute_main) { g_rt.compute = g_rt.compute_main; g_rt.compute_main = nullptr; }
     if (g_rt.aux) { (void)hipStreamSynchronize(g_rt.aux); (void)hipStreamDestroy(g_rt.aux); g_rt.aux = nullptr; }
@@ -470,6 +473,7 @@ void fl_set_option(int option, int value)
     case FL_OPT_MGCG_FUSE:       g_rt.opt_mgcg_fuse = value < 0 ? -1 : (value > 3 ? 3 : value); break;
     case FL_OPT_FIELD_WINDOW:    g_rt.opt_field_window = value < 0 ? -1 : value; break;
     case FL_OPT_COMM_CHECK:      g_rt.opt_comm_check = value != 0; break;
+    case FL_OPT_SKIP_EMPTY_BRICKS: g_rt.opt_skip_empty_bricks = (value >= 1 && value <= 4) ? value : 0; break;
     case FL_OPT_RESERVE_CUS: {
         const int k = value < 0 ? 0 : value;
         if (k == g_rt.opt_reserve_cus) break;
@@ -510,6 +514,7 @@ int fl_get_option(int option)
     case FL_OPT_MGCG_FUSE:       return g_rt.opt_mgcg_fuse;
     case FL_OPT_FIELD_WINDOW:    return g_rt.opt_field_window;
     case FL_OPT_COMM_CHECK:      return g_rt.opt_comm_check;
+    case FL_OPT_SKIP_EMPTY_BRICKS: return g_rt.opt_skip_empty_bricks;
     case FL_OPT_RESERVE_CUS:     return g_rt.opt_reserve_cus;
     default: return -1;
     }

@@ -405,6 +405,18 @@ enum {
                                  * scratch).  Hence the default is -1 = off until a caller says so: setting 1 is the caller's
                                  * word that its arrays have that size.  The host solver of this package (csrc/host), which
                                  * allocates them, sets 1 unless the option has been set before.                      */
+    FL_OPT_SKIP_EMPTY_BRICKS = 21,/* nine-point operators on UNSTAGGERED fields, one GPU, whole arrays, the staged structured
+                                 * kernels: 1 (default) puts a streaming pass in front of each advection (gpu_advect_field/_field2)
+                                 * and error-stage launch (gpu_compensate_error_field/_field2, the first stage of
+                                 * gpu_compensate_field) that flags the 8 x 8 x 8 bricks of the sampled fields holding anything but
+                                 * the word 0x00000000, and a block whose taps can only land in empty bricks runs its stores with
+                                 * every gather result taken as +0.0f -- no map look-up, no gathers.  Same bits in every output.
+                                 * 0: the launches without the pass.  2: as 1, and every tested block is counted
+                                 * (fl_sparse_stats).  3: as 1, and the accumulation (gpu_accumulate_field/_field2, the second
+                                 * stage of gpu_compensate_field) takes part too -- not the default: through a backward map with
+                                 * its zeroed border half of that operator's blocks cannot be skipped at 256^3 and it comes out
+                                 * slower.  4: as 3, counting.  Staggered launches, z-slab ranks, plane windows, point mode, the
+                                 * generic path, the identity accumulate and the kernels of FL_OPT_FIELD_WINDOW never take part. */
     FL_OPT_MAP_QUARTER_FP32 = 13 /* 0 (default): every lerp of the structured map look-up follows the double-rounding
                                  * contract.  1: the caller vouches that every value of the map arrays it passes to the
                                  * 9-point operators is 0 or lies in [h/256, 1024 h] (gpu_maps_quarter_safe checks a map
@@ -425,6 +437,16 @@ const char *fl_jacobi_kernel_name(void);
 const char *fl_mg_smooth_kernel_name(void);
 /* launches of the fused level-0 kernels (FL_OPT_MGCG_FUSE) since the previous call (resets the count; for reports and tests) */
 long long fl_mg_fused_launches(void);
+/* FL_OPT_SKIP_EMPTY_BRICKS = 2 or 4: out[0] = blocks tested against the brick flags, out[1] = blocks skipped, since the last reset
+ * (blocking; reset != 0 clears the counters) */
+void fl_sparse_stats(long long out[2], int reset);
+/* the same for one operator: kind 0 = the advection, 1 = the error stage, 2 = the accumulation */
+void fl_sparse_stats_kind(int kind, long long out[2], int reset);
+/* the flag pass of FL_OPT_SKIP_EMPTY_BRICKS on its own (for tests and tools): one byte per 8 x 8 x 8 brick of f1 -- of f1 and
+ * f2 taken together when f2 is not NULL -- into flags_host (HOST memory, ceil(ni/8) ceil(nj/8) ceil(nk/8) bytes, x fastest):
+ * 1 = some word of the brick is not 0x00000000.  *any_empty (may be NULL): 1 when a brick is empty.  Blocking.  Returns the
+ * number of bricks, -1 on an error. */
+int gpu_brick_flags(const float *f1, const float *f2, int ni, int nj, int nk, unsigned char *flags_host, int *any_empty);
 
 /* ------------------------------------------------------------------------------------------
  * 3. Additive entry points (no reference counterpart)
