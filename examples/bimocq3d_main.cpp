@@ -8,7 +8,10 @@
 // rings blown along x by the reference's emitter velocity formula (main.cpp:52-73, emiter = +1 for both: the rear
 // ring catches up and threads the front one -- leapfrogging), no buoyancy, density dumped every frame.
 //
-//   make example && build/bimocq3d [N=128] [frames=20] [outdir=out] [scheme=0|2|3] [projection=0|1] [async=1] [scene=0|1] [walls=0]
+//   make example && build/bimocq3d [N=128] [frames=20] [outdir=out] [scheme=0|2|3] [projection=0|1] [async=1] [scene=0|1] [walls=0] [diag_every=0]
+// diag_every = N > 0: the flow diagnostics of every N-th frame (bq_solver_diagnostics' row: kinetic energy, enstrophy, ...) are
+// sampled on the device while the run goes on, printed one line per sampled frame at the end, and the vorticity magnitude of
+// those frames is dumped next to the density (vorticity_render_%04u.bqd)
 // walls: the closed sides (BQ_WALL_* bits of include/bimocq_gpu.h; 55 = the reference CPU solver's container, open at the top)
 #include <chrono>
 #include <cstdio>
@@ -30,8 +33,9 @@ int main(int argc, char **argv)
     const bool async_dump = argc > 6 ? std::atoi(argv[6]) != 0 : true;
     const int scene = argc > 7 ? std::atoi(argv[7]) : 0;             // 0 rising smoke, 1 leapfrogging vortex rings, 2 box-shaped plume source
     const int walls = argc > 8 ? std::atoi(argv[8]) : BQ_WALLS_NONE; // closed sides, BQ_WALL_* bits: 55 = the reference's container (open top)
-    if (n < 8 || total_frame < 1 || (scene == 1 && n % 2) || (scheme != 0 && scheme != 2 && scheme != 3)) {
-        std::fprintf(stderr, "usage: %s [N>=8] [frames] [outdir] [scheme: 0 BiMocq, 2 MacCormack, 3 reflection] [projection] [async] [scene] [walls]\n", argv[0]); return 2;
+    const int diag_every = argc > 9 ? std::atoi(argv[9]) : 0;        // flow diagnostics and a vorticity dump every N-th frame (0: none)
+    if (n < 8 || total_frame < 1 || diag_every < 0 || (scene == 1 && n % 2) || (scheme != 0 && scheme != 2 && scheme != 3)) {
+        std::fprintf(stderr, "usage: %s [N>=8] [frames] [outdir] [scheme: 0 BiMocq, 2 MacCormack, 3 reflection] [projection] [async] [scene] [walls] [diag_every]\n", argv[0]); return 2;
     }
 
     const int ni = n, nj = n, nk = scene == 1 ? n / 2 : n;
@@ -75,6 +79,7 @@ int main(int argc, char **argv)
     if (projection == 1) { mysolver.projection_kind = BQ_PROJECTION_MGCG; mysolver.mg_iters = 50; }
     else                 { mysolver.jacobi_iters = 200; }
     if (!mysolver.setWalls(walls)) { std::fprintf(stderr, "%s\n", fl_last_error_string()); return 1; }   // (not with projection 1)
+    if (diag_every > 0 && !mysolver.setDiagnosticsEvery(diag_every)) { std::fprintf(stderr, "%s\n", fl_last_error_string()); return 1; }
     mysolver.verbose = true;                                         // "[Bimocq GPU Time: ...ms ]" like the reference
 
     const auto t0 = std::chrono::steady_clock::now();
@@ -83,7 +88,19 @@ int main(int argc, char **argv)
         mysolver.advance(i, dt);
         if (async_dump) mysolver.outputResultAsync((unsigned)i, filepath);      // written while frame i + 1 runs
         else std::printf("[ Valid voxel: %ld ]\n", mysolver.outputResult((unsigned)i, filepath));
+        if (diag_every > 0 && (i + 1) % diag_every == 0)
+            std::printf("[ Vorticity voxel: %ld ]\n", mysolver.outputVorticity((unsigned)i, filepath, 0.1f));
         if (fl_last_error() != FL_OK) { std::fprintf(stderr, "%s\n", fl_last_error_string()); return 1; }
+    }
+    if (diag_every > 0) {                                            // the samples waited in device memory: one download for all of them
+        std::vector<double> rows((size_t)BimocqGPUSolver::kDiagRing * BQ_DIAG_COUNT);
+        const long kept = mysolver.diagnosticsHistory(rows.data(), BimocqGPUSolver::kDiagRing);
+        for (long r = 0; r < kept; r++) {
+            const double *d = rows.data() + (size_t)r * BQ_DIAG_COUNT;
+            std::printf("[diag step %d] kinetic %.9e enstrophy %.9e div_l2 %.3e div_max %.3e rho_sum %.6f centroid %.5f %.5f %.5f vort_max %.5f\n",
+                        (int)d[BQ_DIAG_STEP], d[BQ_DIAG_KINETIC], d[BQ_DIAG_ENSTROPHY], d[BQ_DIAG_DIV_L2], d[BQ_DIAG_DIV_MAX], d[BQ_DIAG_RHO_SUM],
+                        d[BQ_DIAG_CENTROID_X], d[BQ_DIAG_CENTROID_Y], d[BQ_DIAG_CENTROID_Z], d[BQ_DIAG_VORT_MAX]);
+        }
     }
     const long last = async_dump ? mysolver.waitOutput() : 0;
     fl_sync();

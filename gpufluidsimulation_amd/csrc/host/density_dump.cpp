@@ -55,23 +55,23 @@ bool make_dirs(const std::string &path)
 }
 } // namespace
 
-long write_density_dump(unsigned frame, const std::string &filepath, float voxel_size,
-                        const float *density, int nx, int ny, int nz, int k_offset, int nz_global)
+long write_field_dump(unsigned frame, const std::string &filepath, float voxel_size, const float *density, int nx, int ny, int nz,
+                      int k_offset, int nz_global, const char *grid_name, const char *stem, float threshold, double cut)
 {
     if (!make_dirs(filepath)) return -1;       // boost::filesystem::create_directories in main.cpp:138
     char name[512];
     if (k_offset == 0 && nz == nz_global)
-        snprintf(name, sizeof name, "%s/density_render_%04u.bqd", filepath.c_str(), frame);
+        snprintf(name, sizeof name, "%s/%s_%04u.bqd", filepath.c_str(), stem, frame);
     else
-        snprintf(name, sizeof name, "%s/density_render_%04u.k%05d.bqd", filepath.c_str(), frame, k_offset);
+        snprintf(name, sizeof name, "%s/%s_%04u.k%05d.bqd", filepath.c_str(), stem, frame, k_offset);
     FILE *f = fopen(name, "wb");
     if (!f) return -1;
     DumpHeader hd;
     memset(&hd, 0, sizeof hd);
     memcpy(hd.magic, "BQDENS01", 8);
     hd.frame = frame; hd.nx = nx; hd.ny = ny; hd.nz = nz_global; hd.k_offset = k_offset; hd.nz_local = nz;
-    hd.voxel_size = voxel_size; hd.threshold = 1e-4f;
-    strncpy(hd.grid_name, "density", sizeof hd.grid_name - 1);
+    hd.voxel_size = voxel_size; hd.threshold = threshold;
+    strncpy(hd.grid_name, grid_name, sizeof hd.grid_name - 1);
     hd.grid_class = 1;
     if (fwrite(&hd, sizeof hd, 1, f) != 1) { fclose(f); return -1; }
     uint64_t total = 0;
@@ -81,7 +81,7 @@ long write_density_dump(unsigned frame, const std::string &filepath, float voxel
         for (int j = 0; j < ny; j++)
             for (int i = 0; i < nx; i++) {
                 float value = std::fabs(density[(size_t)i + (size_t)nx * ((size_t)j + (size_t)ny * k)]);
-                if ((double)value > 1e-4) {
+                if ((double)value > cut) {
                     buf[nb++] = DumpRecord{ i, j, k + k_offset, value };
                     total++;
                     if (nb == 4096) { if (fwrite(buf, sizeof(DumpRecord), nb, f) != nb) { fclose(f); return -1; } nb = 0; }
@@ -91,10 +91,19 @@ long write_density_dump(unsigned frame, const std::string &filepath, float voxel
     hd.count = total;
     if (fseek(f, 0, SEEK_SET) != 0 || fwrite(&hd, sizeof hd, 1, f) != 1) { fclose(f); return -1; }
     fclose(f);
-#ifdef HAVE_OPENVDB
-    if (write_density_vdb(frame, filepath, voxel_size, density, nx, ny, nz, k_offset, nz_global) < 0) return -1;
-#endif
     return (long)total;
+}
+
+// the density dump: grid "density", density_render_%04u, |rho| against the double literal 1e-4
+long write_density_dump(unsigned frame, const std::string &filepath, float voxel_size,
+                        const float *density, int nx, int ny, int nz, int k_offset, int nz_global)
+{
+    const long total = write_field_dump(frame, filepath, voxel_size, density, nx, ny, nz, k_offset, nz_global, "density",
+                                        "density_render", 1e-4f, 1e-4);
+#ifdef HAVE_OPENVDB
+    if (total >= 0 && write_density_vdb(frame, filepath, voxel_size, density, nx, ny, nz, k_offset, nz_global) < 0) return -1;
+#endif
+    return total;
 }
 
 #ifdef HAVE_OPENVDB

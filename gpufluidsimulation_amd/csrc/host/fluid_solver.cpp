@@ -41,6 +41,7 @@
 #pragma weak gpu_jacobi_sweeps_masked_walls
 #pragma weak gpu_gradient_masked_walls
 #pragma weak gpu_pcg_gradient_walls
+#pragma weak gpu_flow_stats
 
 namespace bqhost {
 
@@ -194,6 +195,7 @@ void BimocqGPUSolver::advance(int framenum, float dt)
     }
     // FL_OPT_COMM_CHECK (debugging aid for the first runs on real links): every rank has issued this step's communicator
     // calls; compare the ledgers (include/bimocq_gpu.h: fl_comm_check)
+    if (diagnostics_every > 0 && steps_taken % diagnostics_every == 0) sampleDiagnostics();     // BQ_OPT_DIAGNOSTICS_EVERY
     if (fl_comm_size() > 1 && fl_get_option(FL_OPT_COMM_CHECK) > 0) (void)fl_comm_check(0);
     last_ms = GpuSolver->endEventRecord();
     if (verbose) printf("[Bimocq GPU Time: %gms ]\n", last_ms);
@@ -1435,6 +1437,108 @@ long BimocqGPUSolver::outputResult(unsigned frame, const std::string &filepath)
     const size_t plane = (size_t)g.ni * g.nj;
     return write_density_dump(frame + 1, filepath, CellSize, host_density.data() + plane * sl.G, g.ni, g.nj,
                               sl.own1 - sl.own0, sl.own0, sl.nkg);
+}
+
+// ---- flow diagnostics ---------------------------------------------------------------------------
+bool BimocqGPUSolver::diagOperator() { return gpu_flow_stats != nullptr; }
+
+// gpu_flow_stats on the current fields into `d_out` (device, BQ_STAT_COUNT doubles); vort: NULL or the scratch field.  A slab
+// rank's centred differences read one ghost plane of the velocity.
+bool BimocqGPUSolver::enqueueStats(float *vort, double *d_out)
+{
+    if (!diagOperator()) { fl_report_error(FL_ERR_UNSUPPORTED, "diagnostics: the operator library has no gpu_flow_stats"); return false; }
+    GpuSolver->require({ &VelocityU, &VelocityV, &VelocityW }, 1);
+    return gpu_flow_stats(VelocityU, VelocityV, VelocityW, Density, Temperature, vort, CellSize, g.ni, g.nj, g.nk, d_out) == FL_OK;
+}
+
+// the raw sums of gpu_flow_stats -> the row a caller sees (include/bimocq_solver.h: BQ_DIAG_*)
+void BimocqGPUSolver::diagRow(const double raw[BQ_STAT_COUNT], int step, double out[BQ_DIAG_COUNT]) const
+{
+    const double h = (double)CellSize, h3 = h * h * h;
+    out[BQ_DIAG_KINETIC] = 0.5 * h3 * raw[BQ_STAT_E2];
+    out[BQ_DIAG_ENSTROPHY] = 0.5 * h3 * raw[BQ_STAT_M2];
+    out[BQ_DIAG_DIV_L2] = std::sqrt(h3 * raw[BQ_STAT_D2]);
+    out[BQ_DIAG_DIV_MAX] = raw[BQ_STAT_DIV_MAX];
+    out[BQ_DIAG_RHO_SUM] = raw[BQ_STAT_RHO];
+    const bool any = raw[BQ_STAT_RHO] != 0.0;
+    out[BQ_DIAG_CENTROID_X] = any ? h * raw[BQ_STAT_RHO_I] / raw[BQ_STAT_RHO] : 0.0;
+    out[BQ_DIAG_CENTROID_Y] = any ? h * raw[BQ_STAT_RHO_J] / raw[BQ_STAT_RHO] : 0.0;
+    out[BQ_DIAG_CENTROID_Z] = any ? h * raw[BQ_STAT_RHO_K] / raw[BQ_STAT_RHO] : 0.0;
+    out[BQ_DIAG_T_SUM] = raw[BQ_STAT_T];
+    out[BQ_DIAG_VORT_MAX] = raw[BQ_STAT_VORT_MAX];
+    out[BQ_DIAG_STEP] = (double)step;
+}
+
+bool BimocqGPUSolver::diagnostics(double out[BQ_DIAG_COUNT])
+{
+    if (!diag_one.f64() && !diag_one.alloc(BQ_STAT_COUNT * sizeof(double))) return false;
+    if (!enqueueStats(nullptr, diag_one.f64())) return false;
+    double raw[BQ_STAT_COUNT];
+    fl_memcpy_d2h(raw, diag_one.f64(), sizeof raw);                 // blocking, after the queued work
+    if (fl_last_error() != FL_OK) return false;
+    diagRow(raw, steps_taken, out);
+    return true;
+}
+
+bool BimocqGPUSolver::setDiagnosticsEvery(int n)
+{
+    if (n < 0) { fl_report_error(FL_ERR_BAD_ARGUMENT, "BQ_OPT_DIAGNOSTICS_EVERY: a step count >= 0"); return false; }
+    if (n > 0) {
+        if (!diagOperator()) { fl_report_error(FL_ERR_UNSUPPORTED, "BQ_OPT_DIAGNOSTICS_EVERY: the operator library has no gpu_flow_stats"); return false; }
+        if (!diag_ring.f64() && !diag_ring.alloc((size_t)kDiagRing * BQ_STAT_COUNT * sizeof(double))) return false;
+        diag_ring_steps.resize(kDiagRing, 0);
+    }
+    diagnostics_every = n;
+    return true;
+}
+
+// after the step: the stats go into the next row of the device ring, in stream order, without a host sync
+void BimocqGPUSolver::sampleDiagnostics()
+{
+    const size_t row = (size_t)(diag_rows % kDiagRing);
+    if (!enqueueStats(nullptr, diag_ring.f64() + row * BQ_STAT_COUNT)) return;
+    diag_ring_steps[row] = steps_taken;
+    diag_rows++;
+}
+
+long BimocqGPUSolver::diagnosticsHistory(double *host, long capacity_rows)
+{
+    const long kept = (long)std::min<long long>(diag_rows, kDiagRing);
+    if (!host || capacity_rows <= 0 || kept == 0) return kept;
+    std::vector<double> raw((size_t)kDiagRing * BQ_STAT_COUNT);
+    fl_memcpy_d2h(raw.data(), diag_ring.f64(), raw.size() * sizeof(double));
+    if (fl_last_error() != FL_OK) return -1;
+    const long long first = diag_rows - kept;                      // oldest retained sample
+    for (long a = 0; a < kept && a < capacity_rows; a++) {
+        const size_t row = (size_t)((first + a) % kDiagRing);
+        diagRow(raw.data() + row * BQ_STAT_COUNT, diag_ring_steps[row], host + (size_t)a * BQ_DIAG_COUNT);
+    }
+    return kept;
+}
+
+// |omega| at the cell centres of the local planes; the scratch field exists from the first call on
+long BimocqGPUSolver::vorticity(float *host, long capacity)
+{
+    const long count = (long)g.n();
+    if (!host || capacity <= 0) return count;
+    if (Vorticity.count() != g.n() && !GpuSolver->allocField(Vorticity, FIELD_S)) return -1;
+    if (!diag_one.f64() && !diag_one.alloc(BQ_STAT_COUNT * sizeof(double))) return -1;
+    if (!enqueueStats(Vorticity, diag_one.f64())) return -1;
+    fl_memcpy_d2h(host, Vorticity.get(), (size_t)std::min(count, capacity) * sizeof(float));
+    return fl_last_error() == FL_OK ? count : -1;
+}
+
+long BimocqGPUSolver::outputVorticity(unsigned frame, const std::string &filepath, float threshold)
+{
+    host_vorticity.resize(g.n());
+    if (vorticity(host_vorticity.data(), (long)host_vorticity.size()) < 0) return -1;
+    const SlabCtx &sl = GpuSolver->slab;
+    if (!sl.on)
+        return write_field_dump(frame + 1, filepath, CellSize, host_vorticity.data(), g.ni, g.nj, g.nk, 0, g.nk,
+                                "vorticity", "vorticity_render", threshold, (double)threshold);
+    const size_t plane = (size_t)g.ni * g.nj;
+    return write_field_dump(frame + 1, filepath, CellSize, host_vorticity.data() + plane * sl.G, g.ni, g.nj, sl.own1 - sl.own0,
+                            sl.own0, sl.nkg, "vorticity", "vorticity_render", threshold, (double)threshold);
 }
 
 } // namespace bqhost

@@ -188,6 +188,26 @@ public:
 
     std::vector<float> host_density, host_u, host_v, host_w;    // outputResult staging (:538-541)
 
+    // Flow diagnostics: kinetic energy, enstrophy, divergence norms, density moments and the vorticity
+    // magnitude from one pass of gpu_flow_stats over the current fields.  Solid cells count as fluid.  With
+    // diagnostics_every == 0 (default) nothing is allocated and a step issues exactly the launches it issues without this.
+    static constexpr int kDiagRing = 1024;          // rows of the device ring of BQ_OPT_DIAGNOSTICS_EVERY
+    static bool diagOperator();                     // the operator library has gpu_flow_stats
+    int  diagnostics_every = 0;                     // BQ_OPT_DIAGNOSTICS_EVERY
+    bool setDiagnosticsEvery(int n);
+    bool diagnostics(double out[BQ_DIAG_COUNT]);    // blocking; every slab rank gets the grid's values
+    long diagnosticsHistory(double *host, long capacity_rows);     // the retained rows, oldest first; blocking
+    long vorticity(float *host, long capacity);     // |omega| of the local planes; blocking
+    long outputVorticity(unsigned frame, const std::string &filepath, float threshold);
+    bool enqueueStats(float *vort, double *d_out);
+    void sampleDiagnostics();
+    void diagRow(const double raw[BQ_STAT_COUNT], int step, double out[BQ_DIAG_COUNT]) const;
+    DeviceBytes diag_one, diag_ring;                // BQ_STAT_COUNT doubles of the blocking calls; kDiagRing rows of them
+    std::vector<int> diag_ring_steps;               // STEP of every ring row
+    long long diag_rows = 0;                        // samples enqueued so far
+    DeviceField Vorticity;                          // scratch of vorticity(), allocated on first use
+    std::vector<float> host_vorticity;
+
     gpuMapper *GpuSolver;
     MapperBaseGPU VelocityAdvector, ScalarAdvector;
     int vel_lastReinit = -11, scalar_lastReinit = -31;          // BimocqGPUSolver.h:109-110
@@ -212,6 +232,10 @@ using FluidSolver = BimocqGPUSolver;
 // number of voxels written or -1.  Defined in density_dump.cpp.
 long write_density_dump(unsigned frame, const std::string &filepath, float voxel_size,
                         const float *density, int nx, int ny, int nz, int k_offset, int nz_global);
+// the same container for any cell-centred field: grid name, file stem (<path>/<stem>_%04u.bqd) and threshold are the
+// caller's; a voxel is kept where (double)|value| > cut, `threshold` is what the header records
+long write_field_dump(unsigned frame, const std::string &filepath, float voxel_size, const float *field, int nx, int ny, int nz,
+                      int k_offset, int nz_global, const char *grid_name, const char *stem, float threshold, double cut);
 #ifdef HAVE_OPENVDB
 long write_density_vdb(unsigned frame, const std::string &filepath, float voxel_size,
                        const float *density, int nx, int ny, int nz, int k_offset, int nz_global);

@@ -151,6 +151,8 @@ void bq_solver_set_option(bq_solver *s, int option, int value)
     } else if (option == BQ_OPT_FUSED_MACCORMACK) {
         if (value < 0 || value > 2) { fl_report_error(FL_ERR_BAD_ARGUMENT, "BQ_OPT_FUSED_MACCORMACK: 0, 1 or 2"); return; }
         s->solver->fused_maccormack = value;
+    } else if (option == BQ_OPT_DIAGNOSTICS_EVERY) {
+        s->solver->setDiagnosticsEvery(value);
     } else if (option == BQ_OPT_REINIT_POLICY) {
         s->solver->setReinitPolicy(value);
         s->solver->ScalarAdvector.keepDmcBorder = s->solver->VelocityAdvector.keepDmcBorder;
@@ -176,6 +178,7 @@ int bq_solver_get_option(const bq_solver *s, int option)
     case BQ_OPT_PROFILE_PHASES:      return s->solver->profile_phases ? 1 : 0;
     case BQ_OPT_REINIT_MAX_TRAVEL:   return s->solver->travel_limit;
     case BQ_OPT_FUSED_MACCORMACK:    return s->solver->fused_maccormack;
+    case BQ_OPT_DIAGNOSTICS_EVERY:   return s->solver->diagnostics_every;
     default:                         return -1;
     }
 }
@@ -360,6 +363,34 @@ long long bq_solver_phase_ms(bq_solver *s, double ms[BQ_PHASE_COUNT], int reset)
     long long steps = 0;
     s->solver->phaseTotals(ms, &steps, reset != 0);
     return steps;
+}
+
+int bq_solver_diagnostics(bq_solver *s, double out[BQ_DIAG_COUNT])
+{
+    BQ_ENTER(s);
+    if (!s || !out) return FL_ERR_BAD_ARGUMENT;
+    if (s->solver->diagnostics(out)) return FL_OK;
+    const int err = fl_last_error();
+    return err != FL_OK ? err : (int)FL_ERR_HIP;
+}
+
+long bq_solver_diagnostics_history(bq_solver *s, double *host, long capacity_rows)
+{
+    BQ_ENTER(s);
+    return s ? s->solver->diagnosticsHistory(host, capacity_rows) : 0;
+}
+
+long bq_solver_vorticity(bq_solver *s, float *host, long capacity)
+{
+    BQ_ENTER(s);
+    return s ? s->solver->vorticity(host, capacity) : 0;
+}
+
+long bq_solver_output_vorticity(bq_solver *s, unsigned frame, const char *path, float threshold)
+{
+    BQ_ENTER(s);
+    if (!s || !path) return -1;
+    return s->solver->outputVorticity(frame, std::string(path), threshold);
 }
 
 float bq_solver_last_cfldt(const bq_solver *s) { return s ? s->solver->last_cfldt : 0.f; }

@@ -215,12 +215,22 @@ HOST_SIGS = {
     "bq_solver_set_pcg_tolerance": (C.c_int, [C.c_void_p, C.c_double]),
     "bq_solver_pcg_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "bq_solver_pcg_pressure": (C.c_long, [C.c_void_p, C.POINTER(C.c_double), C.c_long]),
+    "bq_solver_diagnostics": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "bq_solver_diagnostics_history": (C.c_long, [C.c_void_p, C.POINTER(C.c_double), C.c_long]),
+    "bq_solver_vorticity": (C.c_long, [C.c_void_p, C.c_void_p, C.c_long]),
+    "bq_solver_output_vorticity": (C.c_long, [C.c_void_p, C.c_uint, C.c_char_p, C.c_float]),
 }
 PROJECTION_JACOBI, PROJECTION_MGCG, PROJECTION_PCG = 0, 1, 2
 # enum Scheme of the reference (BimocqSolver.h:29) as far as it is built: SEMILAG (1) is refused
 SCHEME_BIMOCQ, SCHEME_MACCORMACK, SCHEME_MAC_REFLECTION = 0, 2, 3
 # setOption(OPT_FUSED_MACCORMACK, v): 0 separate launches, 1 (default) gpu_maccormack in scheme 2, 2 in scheme 3 too
 OPT_FUSED_MACCORMACK = 15
+# setOption(OPT_DIAGNOSTICS_EVERY, N): after every N-th advance() the flow diagnostics go into a device ring (diagnosticsHistory)
+OPT_DIAGNOSTICS_EVERY = 16
+# the entries of a diagnostics row (BQ_DIAG_* of include/bimocq_solver.h), in order
+DIAG_NAMES = ("kinetic", "enstrophy", "div_l2", "div_max", "rho_sum", "centroid_x", "centroid_y", "centroid_z", "T_sum",
+              "vort_max", "step")
+DIAG_COUNT = len(DIAG_NAMES)
 PCG_STOP = {0: "converged", 1: "iteration limit", 2: "breakdown"}
 PHASES = ("maps", "advect_compensate", "forces", "projection", "accumulate_reinit")
 
@@ -327,7 +337,7 @@ class BimocqGPUSolver:
         """option 1 = BQ_OPT_KEEP_DMC_BORDER, 2 = BQ_OPT_REINIT_POLICY (0 every frame, 1 distortion-driven),
         3 = BQ_OPT_FULL_STATE, 4 = BQ_OPT_FUSED_HOUSEKEEPING, 5 = BQ_OPT_OVERLAP_EXCHANGES, 6 = BQ_OPT_SHALLOW_BLOCKING_EXCHANGE,
         7 = BQ_OPT_JACOBI_ENDS_FIRST, 8 = BQ_OPT_PROFILE_PHASES, 9 = BQ_OPT_REINIT_MAX_TRAVEL, 10 = BQ_OPT_JACOBI_TRIPLES, 14 = BQ_OPT_NODE_LOOKUPS,
-        15 = BQ_OPT_FUSED_MACCORMACK (include/bimocq_solver.h)"""
+        15 = BQ_OPT_FUSED_MACCORMACK, 16 = BQ_OPT_DIAGNOSTICS_EVERY (include/bimocq_solver.h)"""
         self.lib.bq_solver_set_option(self.s, option, value)
         self._check()
 
@@ -419,6 +429,48 @@ class BimocqGPUSolver:
     def outputResult(self, frame, path=None):
         n = self.lib.bq_solver_output_result(self.s, frame, path.encode() if path else None)
         self._check()
+        return n
+
+    def diagnostics(self):
+        """the flow diagnostics of the current fields as a dict over DIAG_NAMES: kinetic energy and
+        enstrophy of the cell-centred velocity, L2 and maximum norm of the divergence, the raw density sum and the density
+        centroid in world units, the temperature sum, the largest vorticity magnitude and the step count.  Blocking; on
+        z-slab ranks collective, every rank gets the whole grid's values."""
+        out = (C.c_double * DIAG_COUNT)()
+        rc = self.lib.bq_solver_diagnostics(self.s, out)
+        self._check()
+        if rc != 0:
+            raise _lib.BimocqError(f"bq_solver_diagnostics failed ({rc})")
+        d = dict(zip(DIAG_NAMES, list(out)))
+        d["step"] = int(d["step"])
+        return d
+
+    def diagnosticsHistory(self):
+        """the samples OPT_DIAGNOSTICS_EVERY retained (at most the last 1024), oldest first: an (n, DIAG_COUNT) float64
+        array whose columns are DIAG_NAMES"""
+        n = self.lib.bq_solver_diagnostics_history(self.s, None, 0)
+        out = np.zeros((max(n, 0), DIAG_COUNT), dtype=np.float64)
+        if n > 0:
+            self.lib.bq_solver_diagnostics_history(self.s, out.ctypes.data_as(C.POINTER(C.c_double)), n)
+        self._check()
+        return out
+
+    def vorticity(self):
+        """the cell-centred vorticity magnitude of the local planes as a (nk_local, ny, nx) float32 array"""
+        count = self.lib.bq_solver_vorticity(self.s, None, 0)
+        out = np.empty(count, dtype=np.float32)
+        rc = self.lib.bq_solver_vorticity(self.s, out.ctypes.data, count)
+        self._check()
+        if rc < 0:
+            raise _lib.BimocqError("bq_solver_vorticity failed")
+        return out.reshape(self.nk_local, self.ny, self.nx)
+
+    def outputVorticity(self, frame, path, threshold=1e-4):
+        """writes <path>/vorticity_render_%04u.bqd for frame + 1 (read_density_dump reads it); returns the voxel count"""
+        n = self.lib.bq_solver_output_vorticity(self.s, frame, path.encode(), threshold)
+        self._check()
+        if n < 0:
+            raise _lib.BimocqError("bq_solver_output_vorticity failed")
         return n
 
     def outputResultAsync(self, frame, path=None):

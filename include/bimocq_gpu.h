@@ -417,6 +417,10 @@ enum {
                                  * its zeroed border half of that operator's blocks cannot be skipped at 256^3 and it comes out
                                  * slower.  4: as 3, counting.  Staggered launches, z-slab ranks, plane windows, point mode, the
                                  * generic path, the identity accumulate and the kernels of FL_OPT_FIELD_WINDOW never take part. */
+    FL_OPT_DIAG_KCHUNK     = 22,/* gpu_flow_stats: 0 (default) = the marching kernel with its own chunk rule (whole rounds of about
+                                 * 16 planes per block, bq_launch_geom.h); k > 0 = chunks of k planes (tests and tuning);
+                                 * negative = the one-thread-per-cell kernel (the A/B partner).  vort_mag and the maxima are
+                                 * the same bits whatever the value; the sums differ in summation order only.        */
     FL_OPT_MAP_QUARTER_FP32 = 13 /* 0 (default): every lerp of the structured map look-up follows the double-rounding
                                  * contract.  1: the caller vouches that every value of the map arrays it passes to the
                                  * 9-point operators is 0 or lies in [h/256, 1024 h] (gpu_maps_quarter_safe checks a map
@@ -902,6 +906,33 @@ void gpu_pcg_solve(const double *div, double *p, const unsigned char *solid, dou
  * window [2, n) whose two cells are fluid (solid == NULL: every face of the window); other faces are left alone */
 void gpu_pcg_gradient(float *u, float *v, float *w, const double *p, const unsigned char *solid, int ni, int nj, int nk,
                       double halfrdx);
+
+/* ---- flow diagnostics -------------------------------------------------------------------------
+ * One pass over the velocity that returns every scalar diagnostic and, on request, the cell-centred vorticity magnitude.
+ * Arrays as everywhere: u (ni+1, nj, nk), v (ni, nj+1, nk), w (ni, nj, nk+1), rho, T and vort_mag (ni, nj, nk), x fastest; on a
+ * z-slab rank kg = k + koff is the global plane and nkg the global plane count.  Per cell (i, j, k), in float, every line one
+ * IEEE operation:
+ *   uc = 0.5f * (u(i,j,k) + u(i+1,j,k));  vc, wc likewise along y and z
+ *   d  = ((u(i+1) - u(i)) + (v(j+1) - v(j)) + (w(k+1) - w(k))) / h          (divergence_kernel's sum order, / h for halfrdx)
+ *   interior cells 1 <= i <= ni-2, 1 <= j <= nj-2, 1 <= kg <= nkg-2, with q = 2.0f * h:
+ *     wx = ((wc(j+1) - wc(j-1)) - (vc(k+1) - vc(k-1))) / q
+ *     wy = ((uc(k+1) - uc(k-1)) - (wc(i+1) - wc(i-1))) / q
+ *     wz = ((vc(i+1) - vc(i-1)) - (uc(j+1) - uc(j-1))) / q              (the mean of the four MAC edge vorticities round the cell)
+ *   border cells: wx = wy = wz = 0 (so does a stored plane whose neighbour plane is not stored; owned planes always have one)
+ *   in double, left to right: m2 = (double)wx*wx + (double)wy*wy + (double)wz*wz,  e2 = (double)uc*uc + (double)vc*vc + (double)wc*wc
+ *   mag = (float)sqrt(m2)                                                   (the double square root: norm3df as restated here)
+ * d_out (DEVICE, BQ_STAT_COUNT doubles) receives, over all cells -- on a slab rank over the owned planes, all-reduced:
+ *   [0] sum e2   [1] sum m2   [2] sum (double)d*d   [3] max |d|   [4] sum rho   [5..7] sum rho*i, rho*j, rho*kg (products in
+ *   double)   [8] sum T   [9] max mag.  Maxima skip NaNs as fmaxf does, sums propagate non-finite values; [4..7] are 0 when rho
+ * is NULL, [8] when T is.  No floating-point atomics: two calls on the same data return the same bits.
+ * vort_mag (may be NULL): every cell of the local buffer is written -- mag, 0 in border cells (no clear needed); cells of ghost
+ * planes take 0 or their computed value.  Asynchronous on the compute stream, nothing synchronises; honours the slab context.
+ * FL_ERR_BAD_ARGUMENT, nothing launched: NULL u, v, w or d_out, a dimension below 3, the size limits above, vort_mag overlapping
+ * an input or d_out.  Returns FL_OK or the error it latched.  Solid cells count as fluid.  FL_OPT_DIAG_KCHUNK picks the kernel. */
+enum { BQ_STAT_E2 = 0, BQ_STAT_M2, BQ_STAT_D2, BQ_STAT_DIV_MAX, BQ_STAT_RHO, BQ_STAT_RHO_I, BQ_STAT_RHO_J, BQ_STAT_RHO_K,
+       BQ_STAT_T, BQ_STAT_VORT_MAX, BQ_STAT_COUNT };
+int gpu_flow_stats(const float *u, const float *v, const float *w, const float *rho, const float *T, float *vort_mag,
+                   float h, int ni, int nj, int nk, double *d_out);
 
 #ifdef __cplusplus
 }

@@ -146,7 +146,12 @@ enum {
      * (include/bimocq_gpu.h) in the MACCORMACK scheme, whose result becomes the field by a buffer swap; 2 = in MAC_REFLECTION
      * too.  With 0 and 1 the reflection scheme issues the launches it always did.  Same values in every field either way.
      * An operator library without gpu_maccormack runs the separate launches whatever the value. */
-    BQ_OPT_FUSED_MACCORMACK = 15
+    BQ_OPT_FUSED_MACCORMACK = 15,
+    /* N > 0: after every N-th advance() the flow diagnostics (gpu_flow_stats, include/bimocq_gpu.h) of the fields the step
+     * left are enqueued into the next row of a device ring of 1024 rows -- in stream order, no host sync; read them with
+     * bq_solver_diagnostics_history.  0 (default): nothing is launched or allocated and a step is exactly what it was.
+     * Refused with FL_ERR_UNSUPPORTED on an operator library without gpu_flow_stats, FL_ERR_BAD_ARGUMENT for N < 0. */
+    BQ_OPT_DIAGNOSTICS_EVERY = 16
 };
 /* BQ_OPT_PROFILE_PHASES: milliseconds per phase summed over the steps since the last reset -- map update (DMC + RK3,
  * BimocqGPUSolver.cpp:136-139), advection with error compensation (:143-145), sources and forces (:157-177), projection
@@ -230,6 +235,27 @@ int   bq_solver_get_walls(bq_solver *s);
 int   bq_solver_set_sources(bq_solver *s, const bq_source *src, const bq_levelset *ls, int n);
 int   bq_solver_source_position(const bq_solver *s, int i, float out[3]);
 long  bq_solver_download_solid(bq_solver *s, unsigned char *host, long capacity);
+/* Flow diagnostics of the current fields, from the raw sums S0..S9 of gpu_flow_stats (cell-centred
+ * velocity, h = L / nx; solid cells count as fluid):
+ *   KINETIC = 0.5 h^3 S0   ENSTROPHY = 0.5 h^3 S1   DIV_L2 = sqrt(h^3 S2)   DIV_MAX = S3   RHO_SUM = S4 (raw: the sum of the cell
+ *   values)   CENTROID_X/Y/Z = h S5..7 / S4 (0 when S4 is 0)   T_SUM = S8   VORT_MAX = S9   STEP = advance() calls so far.
+ * Blocking.  On z-slab ranks collective, and every rank gets the values of the whole grid.  Returns FL_OK, or the error
+ * latched (FL_ERR_UNSUPPORTED on an operator library without gpu_flow_stats). */
+enum { BQ_DIAG_KINETIC = 0, BQ_DIAG_ENSTROPHY, BQ_DIAG_DIV_L2, BQ_DIAG_DIV_MAX, BQ_DIAG_RHO_SUM, BQ_DIAG_CENTROID_X,
+       BQ_DIAG_CENTROID_Y, BQ_DIAG_CENTROID_Z, BQ_DIAG_T_SUM, BQ_DIAG_VORT_MAX, BQ_DIAG_STEP, BQ_DIAG_COUNT };
+int   bq_solver_diagnostics(bq_solver *s, double out[BQ_DIAG_COUNT]);
+/* BQ_OPT_DIAGNOSTICS_EVERY: the retained samples (at most the last 1024), oldest first, as rows of BQ_DIAG_COUNT doubles in
+ * bq_solver_diagnostics' layout with STEP = the step the sample followed.  Blocking.  Returns the number of retained rows
+ * and copies min(rows, capacity_rows) of them when host != NULL. */
+long  bq_solver_diagnostics_history(bq_solver *s, double *host, long capacity_rows);
+/* the cell-centred vorticity magnitude |omega| of the LOCAL planes (nk_local * ny * nx, x fastest; border cells 0) through a
+ * scratch field that is allocated on the first call.  Returns the element count (host == NULL: only that) and copies
+ * min(count, capacity); -1 on error.  Blocking. */
+long  bq_solver_vorticity(bq_solver *s, float *host, long capacity);
+/* |omega| into <path>/vorticity_render_%04u.bqd for frame + 1 (z-slab ranks: .k%05d.bqd with their owned planes) in the
+ * container of bq_solver_output_result: grid "vorticity", voxels whose value exceeds `threshold`.  Returns the number of
+ * voxels written or -1. */
+long  bq_solver_output_vorticity(bq_solver *s, unsigned frame, const char *path, float threshold);
 float bq_solver_last_cfldt(const bq_solver *s);
 float bq_solver_last_ms(const bq_solver *s);          /* event time of the last advance()        */
 int   bq_solver_reinit_count(const bq_solver *s);
