@@ -8,10 +8,12 @@
 // rings blown along x by the reference's emitter velocity formula (main.cpp:52-73, emiter = +1 for both: the rear
 // ring catches up and threads the front one -- leapfrogging), no buoyancy, density dumped every frame.
 //
-//   make example && build/bimocq3d [N=128] [frames=20] [outdir=out] [scheme=0|2|3] [projection=0|1] [async=1] [scene=0|1] [walls=0] [diag_every=0]
+//   make example && build/bimocq3d [N=128] [frames=20] [outdir=out] [scheme=0|2|3] [projection=0|1] [async=1] [scene=0|1] [walls=0] [diag_every=0] [preview_every=0]
 // diag_every = N > 0: the flow diagnostics of every N-th frame (bq_solver_diagnostics' row: kinetic energy, enstrophy, ...) are
 // sampled on the device while the run goes on, printed one line per sampled frame at the end, and the vorticity magnitude of
 // those frames is dumped next to the density (vorticity_render_%04u.bqd)
+// preview_every = N > 0: a shadowed preview of the density of every N-th frame, drawn on the device (view along +z, lit from
+// above), is written next to the density dumps (preview_%04u.pgm)
 // walls: the closed sides (BQ_WALL_* bits of include/bimocq_gpu.h; 55 = the reference CPU solver's container, open at the top)
 #include <chrono>
 #include <cstdio>
@@ -34,8 +36,9 @@ int main(int argc, char **argv)
     const int scene = argc > 7 ? std::atoi(argv[7]) : 0;             // 0 rising smoke, 1 leapfrogging vortex rings, 2 box-shaped plume source
     const int walls = argc > 8 ? std::atoi(argv[8]) : BQ_WALLS_NONE; // closed sides, BQ_WALL_* bits: 55 = the reference's container (open top)
     const int diag_every = argc > 9 ? std::atoi(argv[9]) : 0;        // flow diagnostics and a vorticity dump every N-th frame (0: none)
-    if (n < 8 || total_frame < 1 || diag_every < 0 || (scene == 1 && n % 2) || (scheme != 0 && scheme != 2 && scheme != 3)) {
-        std::fprintf(stderr, "usage: %s [N>=8] [frames] [outdir] [scheme: 0 BiMocq, 2 MacCormack, 3 reflection] [projection] [async] [scene] [walls] [diag_every]\n", argv[0]); return 2;
+    const int preview_every = argc > 10 ? std::atoi(argv[10]) : 0;   // a shadowed preview image every N-th frame (0: none)
+    if (n < 8 || total_frame < 1 || diag_every < 0 || preview_every < 0 || (scene == 1 && n % 2) || (scheme != 0 && scheme != 2 && scheme != 3)) {
+        std::fprintf(stderr, "usage: %s [N>=8] [frames] [outdir] [scheme: 0 BiMocq, 2 MacCormack, 3 reflection] [projection] [async] [scene] [walls] [diag_every] [preview_every]\n", argv[0]); return 2;
     }
 
     const int ni = n, nj = n, nk = scene == 1 ? n / 2 : n;
@@ -90,6 +93,8 @@ int main(int argc, char **argv)
         else std::printf("[ Valid voxel: %ld ]\n", mysolver.outputResult((unsigned)i, filepath));
         if (diag_every > 0 && (i + 1) % diag_every == 0)
             std::printf("[ Vorticity voxel: %ld ]\n", mysolver.outputVorticity((unsigned)i, filepath, 0.1f));
+        if (preview_every > 0 && (i + 1) % preview_every == 0)         // eye looking along +z, light falling along -y
+            std::printf("[ Preview bytes: %ld ]\n", mysolver.outputPreview((unsigned)i, filepath, /*view +z*/4, /*light -y*/3, 12.f, 1.f, 0.1f, 0.f));
         if (fl_last_error() != FL_OK) { std::fprintf(stderr, "%s\n", fl_last_error_string()); return 1; }
     }
     if (diag_every > 0) {                                            // the samples waited in device memory: one download for all of them

@@ -170,6 +170,9 @@ HIP_SIGS = {
     "gpu_emit_sources": (None, [VP] * 5 + [VP, VP, c_i] + _G),
     # flow diagnostics: rho, T and vort_mag may be NULL, d_out is DEVICE memory
     "gpu_flow_stats": (c_i, [VP] * 6 + _G + [VP]),
+    # shadowed density preview: rho, shadow (may be NULL without a light), h, dims, view, light, a HOST
+    # pointer to three floats (sigma, albedo, ambient), d_image in DEVICE memory
+    "gpu_render_density": (c_i, [VP, VP] + _G + [c_i, c_i, VP, VP]),
 }
 
 FL_OK, FL_ERR_NO_DEVICE, FL_ERR_HIP, FL_ERR_BAD_ARGUMENT, FL_ERR_UNSUPPORTED, FL_ERR_COMM = range(6)
@@ -188,6 +191,7 @@ FL_OPT_FIELD_WINDOW = 18
 FL_OPT_COMM_CHECK = 19
 FL_OPT_SKIP_EMPTY_BRICKS = 21
 FL_OPT_DIAG_KCHUNK = 22
+FL_OPT_RENDER_KCHUNK = 23
 # rows of gpu_flow_stats' d_out (BQ_STAT_*)
 STAT_NAMES = ("e2", "m2", "d2", "div_max", "rho", "rho_i", "rho_j", "rho_k", "T", "vort_max")
 STAT_COUNT = len(STAT_NAMES)

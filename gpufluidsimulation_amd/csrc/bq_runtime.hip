@@ -475,6 +475,7 @@ void fl_set_option(int option, int value)
     case FL_OPT_COMM_CHECK:      g_rt.opt_comm_check = value != 0; break;
     case FL_OPT_SKIP_EMPTY_BRICKS: g_rt.opt_skip_empty_bricks = (value >= 1 && value <= 4) ? value : 0; break;
     case FL_OPT_DIAG_KCHUNK:     g_rt.opt_diag_kchunk = value < 0 ? -1 : value; break;
+    case FL_OPT_RENDER_KCHUNK:   g_rt.opt_render_kchunk = value < 0 ? -1 : value; break;
     case FL_OPT_RESERVE_CUS: {
         const int k = value < 0 ? 0 : value;
         if (k == g_rt.opt_reserve_cus) break;
@@ -517,6 +518,7 @@ int fl_get_option(int option)
     case FL_OPT_COMM_CHECK:      return g_rt.opt_comm_check;
     case FL_OPT_SKIP_EMPTY_BRICKS: return g_rt.opt_skip_empty_bricks;
     case FL_OPT_DIAG_KCHUNK:     return g_rt.opt_diag_kchunk;
+    case FL_OPT_RENDER_KCHUNK:   return g_rt.opt_render_kchunk;
     case FL_OPT_RESERVE_CUS:     return g_rt.opt_reserve_cus;
     default: return -1;
     }

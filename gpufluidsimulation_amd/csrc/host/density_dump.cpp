@@ -106,6 +106,31 @@ long write_density_dump(unsigned frame, const std::string &filepath, float voxel
     return total;
 }
 
+long write_preview_pgm(unsigned frame, const std::string &filepath, const float *radiance, const float *transmittance, int w, int h,
+                       float background)
+{
+    if (!make_dirs(filepath)) return -1;
+    char name[512];
+    snprintf(name, sizeof name, "%s/preview_%04u.pgm", filepath.c_str(), frame);
+    FILE *f = fopen(name, "wb");
+    if (!f) return -1;
+    const int head = fprintf(f, "P5\n%d %d\n255\n", w, h);
+    if (head < 0) { fclose(f); return -1; }
+    std::vector<unsigned char> row((size_t)w);
+    for (int r = h - 1; r >= 0; r--) {             // the highest row first: +y or +z points up
+        for (int c = 0; c < w; c++) {
+            const size_t a = (size_t)c + (size_t)w * r;
+            const double prod = (double)transmittance[a] * (double)background;     // exact
+            double v = (double)radiance[a] + prod;
+            v = v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v);
+            row[c] = (unsigned char)std::lrint(v * 255.0);
+        }
+        if (fwrite(row.data(), 1, row.size(), f) != row.size()) { fclose(f); return -1; }
+    }
+    fclose(f);
+    return (long)head + (long)w * h;
+}
+
 #ifdef HAVE_OPENVDB
 // The real thing, for boxes that have OpenVDB: <path>/density_render_%04d.vdb (slab ranks:
 // .k%05d.vdb) holding one float grid "density" -- fog volume, linear transform of the voxel size, active

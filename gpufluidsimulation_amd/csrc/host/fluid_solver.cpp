@@ -42,6 +42,7 @@
 #pragma weak gpu_gradient_masked_walls
 #pragma weak gpu_pcg_gradient_walls
 #pragma weak gpu_flow_stats
+#pragma weak gpu_render_density
 
 namespace bqhost {
 
@@ -1539,6 +1540,96 @@ long BimocqGPUSolver::outputVorticity(unsigned frame, const std::string &filepat
     const size_t plane = (size_t)g.ni * g.nj;
     return write_field_dump(frame + 1, filepath, CellSize, host_vorticity.data() + plane * sl.G, g.ni, g.nj, sl.own1 - sl.own0,
                             sl.own0, sl.nkg, "vorticity", "vorticity_render", threshold, (double)threshold);
+}
+
+// ---- shadowed density preview -------------------------------------------------------------------
+// The oracle's orc_expf / the kernels' exp_portable, operation for operation (no contraction: the products and sums below
+// must round one by one).
+__attribute__((optimize("fp-contract=off"))) float portable_expf(float xf)
+{
+    double x = (double)xf;
+    if (!(x == x)) return xf;
+    if (x > 90.0) x = 90.0;
+    if (x < -110.0) x = -110.0;
+    const double LOG2E = 1.4426950408889634074;
+    const double LN2HI = 6.93147180369123816490e-01;
+    const double LN2LO = 1.90821492927058770002e-10;
+    const double kd = std::floor(x * LOG2E + 0.5);
+    const double r = (x - kd * LN2HI) - kd * LN2LO;
+    double p = 1.0 / 6227020800.0;
+    p = p * r + 1.0 / 479001600.0;
+    p = p * r + 1.0 / 39916800.0;
+    p = p * r + 1.0 / 3628800.0;
+    p = p * r + 1.0 / 362880.0;
+    p = p * r + 1.0 / 40320.0;
+    p = p * r + 1.0 / 5040.0;
+    p = p * r + 1.0 / 720.0;
+    p = p * r + 1.0 / 120.0;
+    p = p * r + 1.0 / 24.0;
+    p = p * r + 1.0 / 6.0;
+    p = p * r + 0.5;
+    p = p * r + 1.0;
+    p = p * r + 1.0;
+    const uint64_t bits = (uint64_t)((int64_t)kd + 1023) << 52;
+    double scale;
+    std::memcpy(&scale, &bits, sizeof scale);
+    return (float)(p * scale);
+}
+
+// att() of include/bimocq_gpu.h: the transmittance behind the fixed-point depth afix
+float render_attenuation(double afix)
+{
+    if (afix >= 128.0 * 4294967296.0) return 0.0f;
+    return portable_expf(-(float)(afix * (1.0 / 4294967296.0)));
+}
+
+bool BimocqGPUSolver::renderOperator() { return gpu_render_density != nullptr; }
+
+bool BimocqGPUSolver::renderSize(int view, int &w, int &h) const
+{
+    if (view < 0 || view > 5) { fl_report_error(FL_ERR_BAD_ARGUMENT, "render: view is a direction code 0..5"); return false; }
+    const int nkg = GpuSolver->slab.on ? GpuSolver->slab.nkg : g.nk;
+    w = view / 2 == 0 ? g.nj : g.ni;
+    h = view / 2 == 2 ? g.nj : nkg;
+    return true;
+}
+
+long BimocqGPUSolver::render(int view, int light, float sigma, float albedo, float ambient, float *radiance, float *transmittance,
+                             long capacity)
+{
+    int w = 0, h = 0;
+    if (!renderSize(view, w, h)) return -1;
+    const long count = (long)w * h;
+    if (!radiance && !transmittance) return count;
+    if (!renderOperator()) { fl_report_error(FL_ERR_UNSUPPORTED, "render: the operator library has no gpu_render_density"); return -1; }
+    const size_t bytes = 2 * (size_t)count * sizeof(double);
+    if (render_image.bytes() != bytes && !render_image.alloc(bytes)) return -1;
+    if (light >= 0 && Shadow.count() != g.n() && !GpuSolver->allocField(Shadow, FIELD_S)) return -1;
+    GpuSolver->require({ &Density }, 0);            // owned planes only: no ghost plane is read
+    const fl_render_params prm = { sigma, albedo, ambient };
+    if (gpu_render_density(Density, light >= 0 ? Shadow.get() : nullptr, CellSize, g.ni, g.nj, g.nk, view, light, &prm,
+                           render_image.f64()) != FL_OK) return -1;
+    host_image.resize(2 * (size_t)count);
+    fl_memcpy_d2h(host_image.data(), render_image.f64(), bytes);    // blocking, after the queued work
+    if (fl_last_error() != FL_OK) return -1;
+    const long n = std::min(count, std::max(capacity, 0L));
+    for (long a = 0; a < n; a++) {
+        if (radiance) radiance[a] = (float)(host_image[a] * (1.0 / 4294967296.0));
+        if (transmittance) transmittance[a] = render_attenuation(host_image[(size_t)count + a]);
+    }
+    return count;
+}
+
+long BimocqGPUSolver::outputPreview(unsigned frame, const std::string &filepath, int view, int light, float sigma, float albedo,
+                                    float ambient, float background)
+{
+    int w = 0, h = 0;
+    if (!renderSize(view, w, h)) return -1;
+    host_radiance.resize((size_t)w * h);
+    host_transmittance.resize((size_t)w * h);
+    if (render(view, light, sigma, albedo, ambient, host_radiance.data(), host_transmittance.data(), (long)w * h) < 0) return -1;
+    if (GpuSolver->slab.on && GpuSolver->slab.rank != 0) return 0;  // every rank holds the whole image; rank 0 writes it
+    return write_preview_pgm(frame + 1, filepath, host_radiance.data(), host_transmittance.data(), w, h, background);
 }
 
 } // namespace bqhost

@@ -208,6 +208,20 @@ public:
     DeviceField Vorticity;                          // scratch of vorticity(), allocated on first use
     std::vector<float> host_vorticity;
 
+    // Shadowed density preview: gpu_render_density on the current density.  The shadow field and the
+    // image buffer are allocated on the first call; advance() never touches any of this.
+    static bool renderOperator();                   // the operator library has gpu_render_density
+    bool renderSize(int view, int &w, int &h) const;
+    // radiance and transmittance of the W x H image (both may be NULL: only the count); blocking; every slab rank gets the
+    // whole image.  Returns W * H or -1.
+    long render(int view, int light, float sigma, float albedo, float ambient, float *radiance, float *transmittance, long capacity);
+    long outputPreview(unsigned frame, const std::string &filepath, int view, int light, float sigma, float albedo, float ambient,
+                       float background);
+    DeviceField Shadow;                             // s per cell, scratch of render()
+    DeviceBytes render_image;                       // 2 W H doubles: Cfix, Afix
+    std::vector<double> host_image;
+    std::vector<float> host_radiance, host_transmittance;
+
     gpuMapper *GpuSolver;
     MapperBaseGPU VelocityAdvector, ScalarAdvector;
     int vel_lastReinit = -11, scalar_lastReinit = -31;          // BimocqGPUSolver.h:109-110
@@ -236,6 +250,13 @@ long write_density_dump(unsigned frame, const std::string &filepath, float voxel
 // caller's; a voxel is kept where (double)|value| > cut, `threshold` is what the header records
 long write_field_dump(unsigned frame, const std::string &filepath, float voxel_size, const float *field, int nx, int ny, int nz,
                       int k_offset, int nz_global, const char *grid_name, const char *stem, float threshold, double cut);
+// <path>/preview_%04u.pgm, binary 8-bit P5, w x h: a pixel is clamp(radiance + transmittance * background, 0, 1) (the sum in
+// double: one rounding) times 255 rounded to nearest; image rows are written highest index first.  Returns the bytes written or -1.
+long write_preview_pgm(unsigned frame, const std::string &filepath, const float *radiance, const float *transmittance, int w, int h,
+                       float background);
+// exp_portable of the operators (the oracle's orc_expf), operation for operation, on the host; att() of gpu_render_density
+float portable_expf(float x);
+float render_attenuation(double afix);
 #ifdef HAVE_OPENVDB
 long write_density_vdb(unsigned frame, const std::string &filepath, float voxel_size,
                        const float *density, int nx, int ny, int nz, int k_offset, int nz_global);

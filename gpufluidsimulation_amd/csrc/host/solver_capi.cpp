@@ -393,6 +393,28 @@ long bq_solver_output_vorticity(bq_solver *s, unsigned frame, const char *path, 
     return s->solver->outputVorticity(frame, std::string(path), threshold);
 }
 
+int bq_solver_render_size(bq_solver *s, int view, int *w, int *h)
+{
+    BQ_ENTER(s);
+    if (!s || !w || !h) return FL_ERR_BAD_ARGUMENT;
+    return s->solver->renderSize(view, *w, *h) ? (int)FL_OK : (int)FL_ERR_BAD_ARGUMENT;
+}
+
+long bq_solver_render(bq_solver *s, int view, int light, float sigma, float albedo, float ambient, float *radiance,
+                      float *transmittance, long capacity)
+{
+    BQ_ENTER(s);
+    return s ? s->solver->render(view, light, sigma, albedo, ambient, radiance, transmittance, capacity) : -1;
+}
+
+long bq_solver_output_preview(bq_solver *s, unsigned frame, const char *path, int view, int light, float sigma, float albedo,
+                              float ambient, float background)
+{
+    BQ_ENTER(s);
+    if (!s || !path) return -1;
+    return s->solver->outputPreview(frame, std::string(path), view, light, sigma, albedo, ambient, background);
+}
+
 float bq_solver_last_cfldt(const bq_solver *s) { return s ? s->solver->last_cfldt : 0.f; }
 float bq_solver_last_ms(const bq_solver *s) { return s ? s->solver->last_ms : 0.f; }
 int   bq_solver_reinit_count(const bq_solver *s) { return s ? (int)s->solver->VelocityAdvector.TotalReinitCount : 0; }

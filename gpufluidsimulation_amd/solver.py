@@ -219,6 +219,10 @@ HOST_SIGS = {
     "bq_solver_diagnostics_history": (C.c_long, [C.c_void_p, C.POINTER(C.c_double), C.c_long]),
     "bq_solver_vorticity": (C.c_long, [C.c_void_p, C.c_void_p, C.c_long]),
     "bq_solver_output_vorticity": (C.c_long, [C.c_void_p, C.c_uint, C.c_char_p, C.c_float]),
+    "bq_solver_render_size": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "bq_solver_render": (C.c_long, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_long]),
+    "bq_solver_output_preview": (C.c_long, [C.c_void_p, C.c_uint, C.c_char_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
+                                            C.c_float]),
 }
 PROJECTION_JACOBI, PROJECTION_MGCG, PROJECTION_PCG = 0, 1, 2
 # enum Scheme of the reference (BimocqSolver.h:29) as far as it is built: SEMILAG (1) is refused
@@ -231,6 +235,8 @@ OPT_DIAGNOSTICS_EVERY = 16
 DIAG_NAMES = ("kinetic", "enstrophy", "div_l2", "div_max", "rho_sum", "centroid_x", "centroid_y", "centroid_z", "T_sum",
               "vort_max", "step")
 DIAG_COUNT = len(DIAG_NAMES)
+# direction codes of render() / outputPreview(): the direction a ray travels (None or "none" as a light: no shadowing)
+DIRECTIONS = {"+x": 0, "-x": 1, "+y": 2, "-y": 3, "+z": 4, "-z": 5}
 PCG_STOP = {0: "converged", 1: "iteration limit", 2: "breakdown"}
 PHASES = ("maps", "advect_compensate", "forces", "projection", "accumulate_reinit")
 
@@ -471,6 +477,51 @@ class BimocqGPUSolver:
         self._check()
         if n < 0:
             raise _lib.BimocqError("bq_solver_output_vorticity failed")
+        return n
+
+    @staticmethod
+    def _direction(d, light=False):
+        """a direction name of DIRECTIONS or its code; as a light also None / "none" / -1 for no shadowing"""
+        if light and (d is None or d == "none" or d == -1):
+            return -1
+        if isinstance(d, str):
+            if d not in DIRECTIONS:
+                raise ValueError(f"direction {d!r}: one of {sorted(DIRECTIONS)}")
+            return DIRECTIONS[d]
+        return int(d)
+
+    def renderSize(self, view="+z"):
+        """(W, H) of the image render() returns for a view"""
+        w, h = C.c_int(0), C.c_int(0)
+        rc = self.lib.bq_solver_render_size(self.s, self._direction(view), C.byref(w), C.byref(h))
+        self._check()
+        if rc != 0:
+            raise _lib.BimocqError(f"bq_solver_render_size failed ({rc})")
+        return w.value, h.value
+
+    def render(self, view="+z", light="-y", sigma=8.0, albedo=1.0, ambient=0.1):
+        """a shadowed emission-absorption preview of the current density, drawn on the device: the
+        orthographic view along `view`, self-shadowed by one directional light travelling along `light` ("+x" ... "-z", or
+        None for no shadowing); sigma is the extinction per unit density and length.  Returns (radiance, transmittance) as
+        float32 arrays of shape (H, W): view +-z gives (ny, nx), +-y (nz, nx), +-x (nz, ny), row index = the higher axis.
+        Blocking; on z-slab ranks collective, every rank gets the whole image."""
+        w, h = self.renderSize(view)
+        rad, tr = np.empty(w * h, dtype=np.float32), np.empty(w * h, dtype=np.float32)
+        n = self.lib.bq_solver_render(self.s, self._direction(view), self._direction(light, True), sigma, albedo, ambient,
+                                      rad.ctypes.data, tr.ctypes.data, w * h)
+        self._check()
+        if n != w * h:
+            raise _lib.BimocqError("bq_solver_render failed")
+        return rad.reshape(h, w), tr.reshape(h, w)
+
+    def outputPreview(self, frame, path, view="+z", light="-y", sigma=8.0, albedo=1.0, ambient=0.1, background=0.0):
+        """writes the preview as <path>/preview_%04u.pgm for frame + 1 (binary 8-bit P5, +y or +z up; on z-slab ranks rank 0
+        writes); returns the bytes written"""
+        n = self.lib.bq_solver_output_preview(self.s, frame, path.encode(), self._direction(view), self._direction(light, True),
+                                              sigma, albedo, ambient, background)
+        self._check()
+        if n < 0:
+            raise _lib.BimocqError("bq_solver_output_preview failed")
         return n
 
     def outputResultAsync(self, frame, path=None):

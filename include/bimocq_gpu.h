@@ -421,6 +421,10 @@ enum {
                                  * 16 planes per block, bq_launch_geom.h); k > 0 = chunks of k planes (tests and tuning);
                                  * negative = the one-thread-per-cell kernel (the A/B partner).  vort_mag and the maxima are
                                  * the same bits whatever the value; the sums differ in summation order only.        */
+    FL_OPT_RENDER_KCHUNK   = 23,/* gpu_render_density, marches along y and z: 0 (default) = the kernels' own rule (bq_render.hip:
+                                 * chunks of about 32 cells in whole rounds of blocks, one chunk where that covers the ray);
+                                 * k > 0 = chunks of k cells along the march (tests and tuning); negative = one sequential march
+                                 * per ray.  Marches along x are a wave-level scan and take no chunks.  Same bits whatever the value. */
     FL_OPT_MAP_QUARTER_FP32 = 13 /* 0 (default): every lerp of the structured map look-up follows the double-rounding
                                  * contract.  1: the caller vouches that every value of the map arrays it passes to the
                                  * 9-point operators is 0 or lies in [h/256, 1024 h] (gpu_maps_quarter_safe checks a map
@@ -933,6 +937,49 @@ enum { BQ_STAT_E2 = 0, BQ_STAT_M2, BQ_STAT_D2, BQ_STAT_DIV_MAX, BQ_STAT_RHO, BQ_
        BQ_STAT_T, BQ_STAT_VORT_MAX, BQ_STAT_COUNT };
 int gpu_flow_stats(const float *u, const float *v, const float *w, const float *rho, const float *T, float *vort_mag,
                    float h, int ni, int nj, int nk, double *d_out);
+
+/* ---- shadowed density preview --------------------------------------------------------------------
+ * An emission-absorption image of the density with single-scattering self-shadowing from one directional light; the view is
+ * orthographic along a grid axis.  Directions are codes 0..5 = +x, -x, +y, -y, +z, -z: the direction a ray TRAVELS.  `view` is
+ * the direction from the eye into the volume, `light` the direction the light travels, light = -1 means no shadowing.
+ * Image axes are the two remaining grid axes in increasing order, columns (fastest) the lower one, rows the higher one:
+ *   view +-z: W x H = ni x nj (x, y)     view +-y: ni x nk (x, z)     view +-x: nj x nk (y, z)
+ * on z-slab ranks nk means the global plane count nkg, and an image row along z is the global plane.
+ * Per cell, every line one IEEE operation (no contraction):
+ *   sh = sigma * h                      (float)
+ *   r  = fmaxf(rho, 0.0f)               (a NaN density is empty, negative undershoots are empty)
+ *   d  = fminf(sh * r, 32.0f)
+ *   D  = trunc((double)d * 2^32)        (an integer <= 2^37)
+ *   a  = 1.0f - exp_portable(-d)        (exp_portable: the oracle's orc_expf, operation for operation)
+ * For a ray through the cells c0, c1, ... in travel order A(c_m) = sum of D(c_n), n < m: the exclusive prefix sum.
+ *   att(A) = 0 when A >= 128 * 2^32, else exp_portable(-(float)((double)A * 2^-32))
+ *   s    = att(A_light(cell))           (light = -1: s = 1.0f)
+ *   q    = a * (albedo * s + ambient)   (three separately rounded float operations)
+ *   Tv   = att(A_view(cell))
+ *   term = trunc((double)Tv * (double)q * 2^32)
+ * d_image (DEVICE, 2 W H doubles) receives per pixel: plane 0 Cfix = sum of term over the pixel's ray, plane 1 Afix = sum of D
+ * over it.  Every pixel is written.  A caller derives radiance = Cfix * 2^-32 and transmittance = att(Afix).
+ * Limits: 1 <= ni, nj, nk <= 65534 next to the operators' size limits above, d <= 32, 0 <= albedo, 0 <= ambient,
+ * albedo + ambient <= 4 (so term <= 2^34): EVERY ACCUMULATED QUANTITY IS AN INTEGER BELOW 2^53.  It is held in doubles, may be
+ * added in any order or grouping and sent through the double-sum all-reduce, and it is the same bits: chunked marches,
+ * wave-level scans along x and slab ranks all give exactly the bits of the plain triple loop.  No floating-point atomics.
+ * Cells with D == 0 contribute term = 0; solid obstacles are not drawn.
+ * shadow: scratch field of ni nj nk floats that receives s per cell (on a z-slab rank: per cell of the OWNED planes; ghost
+ * planes are not touched); NULL only with light = -1.
+ * z-slab ranks (fl_set_slab): only owned planes contribute.  Views and lights along x or y cross no rank boundary: each rank
+ * fills its owned rows of a zero-filled image.  With the view or the light along +-z each rank first leaves its per-column
+ * total of D over its owned planes in its slot of a zero-filled world x ni x nj double buffer, one all-reduce fills every slot
+ * on every rank, and a rank starts its columns at the totals of the ranks before it (after it for -z); one gather serves
+ * view and light.  Last, one all-reduce (double, sum) over the 2 W H doubles gives every rank the whole image.  Both run in
+ * stream order on the communicator of the scalar all-reduces, no host sync.  The gather buffer lives in the library's
+ * scratch: world x ni x nj x 8 bytes, 64 MB at 1024^2 x 8 ranks.
+ * Asynchronous on the compute stream.  FL_ERR_BAD_ARGUMENT, nothing launched: a NULL rho, p or d_image, view outside 0..5,
+ * light outside -1..5, shadow == NULL with light >= 0, d_image or shadow overlapping rho (or each other), a non-finite or
+ * negative sigma, albedo or ambient, albedo + ambient > 4, a non-finite or non-positive h, sizes outside the limits.
+ * Returns FL_OK or the error it latched.  FL_OPT_RENDER_KCHUNK picks the chunking of the marches along y and z. */
+typedef struct { float sigma, albedo, ambient; } fl_render_params;
+int gpu_render_density(const float *rho, float *shadow, float h, int ni, int nj, int nk, int view, int light,
+                       const fl_render_params *p, double *d_image);
 
 #ifdef __cplusplus
 }

@@ -256,6 +256,24 @@ long  bq_solver_vorticity(bq_solver *s, float *host, long capacity);
  * container of bq_solver_output_result: grid "vorticity", voxels whose value exceeds `threshold`.  Returns the number of
  * voxels written or -1. */
 long  bq_solver_output_vorticity(bq_solver *s, unsigned frame, const char *path, float threshold);
+/* Shadowed density preview (the contract of gpu_render_density in include/bimocq_gpu.h): an orthographic
+ * emission-absorption image of the current density along a grid axis, self-shadowed by one directional light.  view and
+ * light are direction codes 0..5 = +x, -x, +y, -y, +z, -z (the direction a ray travels: from the eye into the volume, from
+ * the light into the volume); light = -1: no shadowing.  The image is W x H, columns fastest: view +-z: nx x ny (x, y),
+ * +-y: nx x nz (x, z), +-x: ny x nz (y, z), nz the GLOBAL plane count.  The shadow field and the image buffer are allocated
+ * on the first call; advance() launches nothing for this.  On z-slab ranks the calls are collective and every rank gets the
+ * whole image.  FL_ERR_UNSUPPORTED on an operator library without gpu_render_density.
+ * bq_solver_render_size: W and H of a view; FL_OK or FL_ERR_BAD_ARGUMENT. */
+int   bq_solver_render_size(bq_solver *s, int view, int *w, int *h);
+/* radiance = (float)(Cfix * 2^-32) and transmittance = att(Afix) per pixel.  Blocking.  Returns W * H and copies
+ * min(W * H, capacity) pixels into each non-NULL array; with both NULL it only returns the count; -1 on error. */
+long  bq_solver_render(bq_solver *s, int view, int light, float sigma, float albedo, float ambient, float *radiance,
+                       float *transmittance, long capacity);
+/* the image into <path>/preview_%04u.pgm for frame + 1: binary 8-bit P5, a pixel is clamp(radiance + transmittance *
+ * background, 0, 1) (product and sum in double) times 255, rounded to nearest (ties to even); rows are written highest index
+ * first, so +y or +z points up.  On z-slab ranks only rank 0 writes (the others return 0).  Returns the bytes written or -1. */
+long  bq_solver_output_preview(bq_solver *s, unsigned frame, const char *path, int view, int light, float sigma, float albedo,
+                               float ambient, float background);
 float bq_solver_last_cfldt(const bq_solver *s);
 float bq_solver_last_ms(const bq_solver *s);          /* event time of the last advance()        */
 int   bq_solver_reinit_count(const bq_solver *s);
