@@ -35,8 +35,15 @@ $(OBJDIR)/bq_advect_fast.o: $(CSRC)/bq_advect.hip $(KERNEL_HDRS) include/bimocq_
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -DBQ_FAST_LERP -c $< -o $@
 
-$(PKG)/libbimocq_hip.so: $(KERNEL_OBJS) $(OBJDIR)/bq_advect_fast.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(KERNEL_OBJS) $(OBJDIR)/bq_advect_fast.o $(RCCL_LIB)
+# likewise the two tracer kernels that interpolate (bq_tracers.hip: the launchers of namespace bq::fast)
+$(OBJDIR)/bq_tracers_fast.o: $(CSRC)/bq_tracers.hip $(KERNEL_HDRS) include/bimocq_gpu.h
+	@mkdir -p $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) -DBQ_FAST_LERP -c $< -o $@
+
+FAST_OBJS := $(OBJDIR)/bq_advect_fast.o $(OBJDIR)/bq_tracers_fast.o
+
+$(PKG)/libbimocq_hip.so: $(KERNEL_OBJS) $(FAST_OBJS)
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(KERNEL_OBJS) $(FAST_OBJS) $(RCCL_LIB)
 
 $(OBJDIR)/host_%.o: $(CSRC)/host/%.cpp $(wildcard $(CSRC)/host/*.hpp) $(CSRC)/bq_levelset.h include/bimocq_gpu.h include/bimocq_solver.h
 	@mkdir -p $(OBJDIR)

@@ -8,14 +8,17 @@
 // rings blown along x by the reference's emitter velocity formula (main.cpp:52-73, emiter = +1 for both: the rear
 // ring catches up and threads the front one -- leapfrogging), no buoyancy, density dumped every frame.
 //
-//   make example && build/bimocq3d [N=128] [frames=20] [outdir=out] [scheme=0|2|3] [projection=0|1] [async=1] [scene=0|1] [walls=0] [diag_every=0] [preview_every=0]
+//   make example && build/bimocq3d [N=128] [frames=20] [outdir=out] [scheme=0|2|3] [projection=0|1] [async=1] [scene=0|1] [walls=0] [diag_every=0] [preview_every=0] [tracers_per_cell=0]
 // diag_every = N > 0: the flow diagnostics of every N-th frame (bq_solver_diagnostics' row: kinetic energy, enstrophy, ...) are
 // sampled on the device while the run goes on, printed one line per sampled frame at the end, and the vorticity magnitude of
 // those frames is dumped next to the density (vorticity_render_%04u.bqd)
 // preview_every = N > 0: a shadowed preview of the density of every N-th frame, drawn on the device (view along +z, lit from
 // above), is written next to the density dumps (preview_%04u.pgm)
+// tracers_per_cell = N > 0: N jittered passive tracers in every cell of each emitter's bounding box, moved with every step on the
+// device and dumped with every frame (tracers_%04u.bqp: positions and the density sampled at them)
 // walls: the closed sides (BQ_WALL_* bits of include/bimocq_gpu.h; 55 = the reference CPU solver's container, open at the top)
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -37,8 +40,9 @@ int main(int argc, char **argv)
     const int walls = argc > 8 ? std::atoi(argv[8]) : BQ_WALLS_NONE; // closed sides, BQ_WALL_* bits: 55 = the reference's container (open top)
     const int diag_every = argc > 9 ? std::atoi(argv[9]) : 0;        // flow diagnostics and a vorticity dump every N-th frame (0: none)
     const int preview_every = argc > 10 ? std::atoi(argv[10]) : 0;   // a shadowed preview image every N-th frame (0: none)
-    if (n < 8 || total_frame < 1 || diag_every < 0 || preview_every < 0 || (scene == 1 && n % 2) || (scheme != 0 && scheme != 2 && scheme != 3)) {
-        std::fprintf(stderr, "usage: %s [N>=8] [frames] [outdir] [scheme: 0 BiMocq, 2 MacCormack, 3 reflection] [projection] [async] [scene] [walls] [diag_every] [preview_every]\n", argv[0]); return 2;
+    const int tracers_per_cell = argc > 11 ? std::atoi(argv[11]) : 0; // passive tracers per cell of the emitters' bounding cells (0: none)
+    if (n < 8 || total_frame < 1 || diag_every < 0 || preview_every < 0 || tracers_per_cell < 0 || (scene == 1 && n % 2) || (scheme != 0 && scheme != 2 && scheme != 3)) {
+        std::fprintf(stderr, "usage: %s [N>=8] [frames] [outdir] [scheme: 0 BiMocq, 2 MacCormack, 3 reflection] [projection] [async] [scene] [walls] [diag_every] [preview_every] [tracers_per_cell]\n", argv[0]); return 2;
     }
 
     const int ni = n, nj = n, nk = scene == 1 ? n / 2 : n;
@@ -52,6 +56,16 @@ int main(int argc, char **argv)
                              myGPUmapper);
     if (!myGPUmapper->ok() || !mysolver.ok()) { std::fprintf(stderr, "%s\n", fl_last_error_string()); return 1; }
 
+    // the cells a source of half extents (rx, ry, rz) about (cx, cy, cz) touches get tracers_per_cell tracers each
+    long tracers_seeded = 0;
+    auto seed_box = [&](float cx, float cy, float cz, float rx, float ry, float rz) {
+        if (tracers_per_cell <= 0) return;
+        const float c[3] = { cx, cy, cz }, r[3] = { rx, ry, rz };
+        int lo[3], hi[3];
+        for (int a = 0; a < 3; a++) { lo[a] = (int)std::floor((c[a] - r[a]) / h); hi[a] = (int)std::floor((c[a] + r[a]) / h) + 1; }
+        const long added = mysolver.seedTracers(lo, hi, tracers_per_cell, /*seed*/(unsigned)tracers_seeded);
+        if (added > 0) tracers_seeded += added;
+    };
     if (scene == 1) {
         Emitter a, b;                                                // main.cpp:75-78: 10 frames, density 1, +x velocity ring
         a.emitFrame = b.emitFrame = 10; a.emit_density = b.emit_density = 1.f; a.emit_temperature = b.emit_temperature = 0.f;
@@ -61,6 +75,8 @@ int main(int argc, char **argv)
         a.e_pos[0] = 0.15f; a.e_pos[1] = yc; a.e_pos[2] = zc;
         b.e_pos[0] = 0.35f; b.e_pos[1] = yc; b.e_pos[2] = zc;
         mysolver.setSmoke(smoke_drop, smoke_rise, { a, b });
+        seed_box(a.e_pos[0], a.e_pos[1], a.e_pos[2], a.radius, a.radius, a.radius);
+        seed_box(b.e_pos[0], b.e_pos[1], b.e_pos[2], b.radius, b.radius, b.radius);
     } else if (scene == 2) {
         // the plume of DESIGN.md section 16 with an analytic box in place of the level set: active on every frame,
         // blowing upwards with a slow spin about the vertical axis
@@ -73,16 +89,20 @@ int main(int argc, char **argv)
         src.emit_frames = total_frame; src.flags = BQ_SOURCE_VELOCITY;
         mysolver.setSmoke(smoke_drop, smoke_rise, {});
         if (!mysolver.setSources(&src, nullptr, 1)) { std::fprintf(stderr, "%s\n", fl_last_error_string()); return 1; }
+        seed_box(src.shape.cx, src.shape.cy, src.shape.cz, src.shape.rx, src.shape.ry, src.shape.rz);
     } else {
         Emitter src;                                                 // one warm sphere, applied at frame 0 only
         src.emitFrame = 1; src.emit_density = 1.f; src.emit_temperature = 1.f; src.emiter = 0.f;
         src.e_pos[0] = 0.5f; src.e_pos[1] = 0.2f; src.e_pos[2] = 0.5f; src.radius = 0.1f;
         mysolver.setSmoke(smoke_drop, smoke_rise, { src });
+        seed_box(src.e_pos[0], src.e_pos[1], src.e_pos[2], src.radius, src.radius, src.radius);
     }
     if (projection == 1) { mysolver.projection_kind = BQ_PROJECTION_MGCG; mysolver.mg_iters = 50; }
     else                 { mysolver.jacobi_iters = 200; }
     if (!mysolver.setWalls(walls)) { std::fprintf(stderr, "%s\n", fl_last_error_string()); return 1; }   // (not with projection 1)
     if (diag_every > 0 && !mysolver.setDiagnosticsEvery(diag_every)) { std::fprintf(stderr, "%s\n", fl_last_error_string()); return 1; }
+    if (fl_last_error() != FL_OK) { std::fprintf(stderr, "%s\n", fl_last_error_string()); return 1; }
+    if (tracers_per_cell > 0) std::printf("[ Tracers: %ld ]\n", mysolver.tracer_count);
     mysolver.verbose = true;                                         // "[Bimocq GPU Time: ...ms ]" like the reference
 
     const auto t0 = std::chrono::steady_clock::now();
@@ -95,6 +115,8 @@ int main(int argc, char **argv)
             std::printf("[ Vorticity voxel: %ld ]\n", mysolver.outputVorticity((unsigned)i, filepath, 0.1f));
         if (preview_every > 0 && (i + 1) % preview_every == 0)         // eye looking along +z, light falling along -y
             std::printf("[ Preview bytes: %ld ]\n", mysolver.outputPreview((unsigned)i, filepath, /*view +z*/4, /*light -y*/3, 12.f, 1.f, 0.1f, 0.f));
+        if (tracers_per_cell > 0)
+            std::printf("[ Tracer bytes: %ld ]\n", mysolver.outputTracers((unsigned)i, filepath, BQ_F_RHO));
         if (fl_last_error() != FL_OK) { std::fprintf(stderr, "%s\n", fl_last_error_string()); return 1; }
     }
     if (diag_every > 0) {                                            // the samples waited in device memory: one download for all of them

@@ -173,6 +173,11 @@ HIP_SIGS = {
     # shadowed density preview: rho, shadow (may be NULL without a light), h, dims, view, light, a HOST
     # pointer to three floats (sigma, albedo, ambient), d_image in DEVICE memory
     "gpu_render_density": (c_i, [VP, VP] + _G + [c_i, c_i, VP, VP]),
+    # passive tracer particles: positions are three device arrays of n floats
+    "gpu_trace_particles": (c_i, [VP] * 6 + [C.c_long] + _G + [c_f, c_f]),
+    "gpu_sample_particles": (c_i, [VP, c_i, c_i, c_i, c_f, c_f, c_f, c_f, VP, VP, VP, VP, C.c_long]),
+    "gpu_seed_particles": (c_i, [VP] * 3 + [c_i] * 7 + [C.c_uint] + _G),
+    "gpu_sort_particles": (c_i, [VP] * 8 + [C.c_long] + _G),
 }
 
 FL_OK, FL_ERR_NO_DEVICE, FL_ERR_HIP, FL_ERR_BAD_ARGUMENT, FL_ERR_UNSUPPORTED, FL_ERR_COMM = range(6)

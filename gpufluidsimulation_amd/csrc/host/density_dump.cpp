@@ -131,6 +131,30 @@ long write_preview_pgm(unsigned frame, const std::string &filepath, const float 
     return (long)head + (long)w * h;
 }
 
+long write_tracer_dump(unsigned frame, const std::string &filepath, const float *xyz, const float *attribute, long count,
+                       int nx, int ny, int nz, float h, int which)
+{
+    if (!make_dirs(filepath)) return -1;
+    char name[512];
+    snprintf(name, sizeof name, "%s/tracers_%04u.bqp", filepath.c_str(), frame);
+    FILE *f = fopen(name, "wb");
+    if (!f) return -1;
+#pragma pack(push, 1)
+    struct { char magic[8]; uint32_t version, frame; uint64_t count; int32_t nx, ny, nz; float h; int32_t attribute; } hd;
+#pragma pack(pop)
+    memset(&hd, 0, sizeof hd);
+    memcpy(hd.magic, "BQPART01", 8);
+    hd.version = 1; hd.frame = frame; hd.count = (uint64_t)count; hd.nx = nx; hd.ny = ny; hd.nz = nz; hd.h = h;
+    hd.attribute = attribute ? which : -1;
+    const size_t n = (size_t)count;
+    bool ok = fwrite(&hd, sizeof hd, 1, f) == 1;
+    ok = ok && (n == 0 || fwrite(xyz, 3 * sizeof(float), n, f) == n);
+    ok = ok && (!attribute || n == 0 || fwrite(attribute, sizeof(float), n, f) == n);
+    fclose(f);
+    if (!ok) return -1;
+    return (long)(sizeof hd + n * 3 * sizeof(float) + (attribute ? n * sizeof(float) : 0));
+}
+
 #ifdef HAVE_OPENVDB
 // The real thing, for boxes that have OpenVDB: <path>/density_render_%04d.vdb (slab ranks:
 // .k%05d.vdb) holding one float grid "density" -- fog volume, linear transform of the voxel size, active

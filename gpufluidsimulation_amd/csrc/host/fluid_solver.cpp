@@ -197,6 +197,7 @@ void BimocqGPUSolver::advance(int framenum, float dt)
     // FL_OPT_COMM_CHECK (debugging aid for the first runs on real links): every rank has issued this step's communicator
     // calls; compare the ledgers (include/bimocq_gpu.h: fl_comm_check)
     if (diagnostics_every > 0 && steps_taken % diagnostics_every == 0) sampleDiagnostics();     // BQ_OPT_DIAGNOSTICS_EVERY
+    if (tracer_sort_every > 0 && tracer_count > 0 && steps_taken % tracer_sort_every == 0) sortTracers();   // BQ_OPT_TRACER_SORT_EVERY
     if (fl_comm_size() > 1 && fl_get_option(FL_OPT_COMM_CHECK) > 0) (void)fl_comm_check(0);
     last_ms = GpuSolver->endEventRecord();
     if (verbose) printf("[Bimocq GPU Time: %gms ]\n", last_ms);
@@ -362,6 +363,7 @@ bool BimocqGPUSolver::beginSchemeStep()
 void BimocqGPUSolver::advanceMacCormack(int framenum, float dt)
 {
     if (!beginSchemeStep()) return;
+    moveTracers(step_cfldt_, dt);                         // through the step's old velocity, before anything writes it
     macCormack({ 1, { &Density }, { &Density } }, dt, dt);
     macCormack({ 1, { &Temperature }, { &Temperature } }, dt, dt);
     macCormack({ 3, { &VelocityU, &VelocityV, &VelocityW }, { &VelocityU, &VelocityV, &VelocityW } }, dt, dt);
@@ -379,6 +381,7 @@ void BimocqGPUSolver::advanceReflection(int framenum, float dt)
     gpuMapper &gs = *GpuSolver;
     const bool slabs = gs.slab.on && gs.slab.nranks > 1;
     if (!beginSchemeStep()) return;                      // :234
+    moveTracers(step_cfldt_, dt);                         // through the step's old velocity, before anything writes it
     const size_t nu = g.nu(), nv = g.nv(), nw = g.nw();
 
     macCormack({ 1, { &Density }, { &Density } }, dt, dt);                  // :237-263
@@ -1231,6 +1234,7 @@ void BimocqGPUSolver::advanceBimocq(int framenum, float dt)
     // :138-139.  One update serves both advectors (shared map set).
     VelocityAdvector.updateMapping(VelocityU, VelocityV, VelocityW, cfldt, dt, dcells);
     if (!ScalarAdvector.sharesMaps()) ScalarAdvector.updateMapping(VelocityU, VelocityV, VelocityW, cfldt, dt, dcells);
+    moveTracers(cfldt, dt);                               // the forward map's own trace, per particle (tracers.cpp)
     trace_stage(*this, "maps", framenum);
     phaseMark(PH_ADVECT);
 

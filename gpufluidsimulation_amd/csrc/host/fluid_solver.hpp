@@ -222,6 +222,34 @@ public:
     std::vector<double> host_image;
     std::vector<float> host_radiance, host_transmittance;
 
+    // Passive tracer particles: positions live on the device as three arrays; advance() moves them
+    // over the whole dt through the velocity the step starts with (gpu_trace_particles, the forward map's own trace), on
+    // the compute stream, no host sync.  One GPU.  With no tracers a step issues exactly the launches it issues without
+    // this feature and nothing is allocated.  Everything public is in id order: id = position in the set as it was given
+    // (setTracers) or appended (seedTracers), whatever sorting has happened in between.
+    static bool tracerOperators();                  // the operator library has the tracer operators
+    long tracer_count = 0;
+    int  tracer_sort_every = 0;                     // BQ_OPT_TRACER_SORT_EVERY
+    long long tracer_sorts = 0;                     // sorts issued so far
+    bool setTracerSortEvery(int n);
+    bool tracersAllowed(const char *who);           // latches the refusal
+    bool setTracers(const float *xyz, long n);      // replaces the set; any failure leaves none
+    long seedTracers(const int lo[3], const int hi[3], int per_cell, unsigned seed);    // appends; the number added or -1
+    long tracers(float *xyz, long capacity);        // blocking; the count, min(count, capacity) triples copied
+    long tracerSample(int which, float *out, long capacity);    // blocking; the count or -1
+    long outputTracers(unsigned frame, const std::string &filepath, int which);        // which < 0: no attribute
+    void dropTracers();
+    bool growTracers(long total);                   // room for `total` particles, the first tracer_count kept
+    void moveTracers(float cfldt, float dt);
+    void sortTracers();
+    bool downloadTracerIds();                       // host_tracer_ids: the id of every stored slot (empty: identity)
+    DeviceField TracerX, TracerY, TracerZ;
+    DeviceField TracerX2, TracerY2, TracerZ2, TracerAttr;   // the sort's second buffers; scratch of tracerSample
+    DeviceBytes tracer_id, tracer_id2;              // unsigned per stored slot, allocated by the first sort
+    bool tracer_ids = false;
+    std::vector<float> host_tracers, host_tracer_xyz, host_tracer_attr;
+    std::vector<unsigned> host_tracer_ids;
+
     gpuMapper *GpuSolver;
     MapperBaseGPU VelocityAdvector, ScalarAdvector;
     int vel_lastReinit = -11, scalar_lastReinit = -31;          // BimocqGPUSolver.h:109-110
@@ -254,6 +282,11 @@ long write_field_dump(unsigned frame, const std::string &filepath, float voxel_s
 // double: one rounding) times 255 rounded to nearest; image rows are written highest index first.  Returns the bytes written or -1.
 long write_preview_pgm(unsigned frame, const std::string &filepath, const float *radiance, const float *transmittance, int w, int h,
                        float background);
+// <path>/tracers_%04u.bqp, little endian, packed: char magic[8] = "BQPART01", uint32 version = 1, uint32 frame, uint64 count,
+// int32 nx, ny, nz, float h, int32 attribute (-1: none, else the BQ_F_* id sampled); then count x (x, y, z) float32 in id
+// order; then, with an attribute, count float32.  Returns the bytes written or -1.
+long write_tracer_dump(unsigned frame, const std::string &filepath, const float *xyz, const float *attribute, long count,
+                       int nx, int ny, int nz, float h, int which);
 // exp_portable of the operators (the oracle's orc_expf), operation for operation, on the host; att() of gpu_render_density
 float portable_expf(float x);
 float render_attenuation(double afix);

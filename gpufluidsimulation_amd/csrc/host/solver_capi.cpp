@@ -153,6 +153,8 @@ void bq_solver_set_option(bq_solver *s, int option, int value)
         s->solver->fused_maccormack = value;
     } else if (option == BQ_OPT_DIAGNOSTICS_EVERY) {
         s->solver->setDiagnosticsEvery(value);
+    } else if (option == BQ_OPT_TRACER_SORT_EVERY) {
+        s->solver->setTracerSortEvery(value);
     } else if (option == BQ_OPT_REINIT_POLICY) {
         s->solver->setReinitPolicy(value);
         s->solver->ScalarAdvector.keepDmcBorder = s->solver->VelocityAdvector.keepDmcBorder;
@@ -179,6 +181,7 @@ int bq_solver_get_option(const bq_solver *s, int option)
     case BQ_OPT_REINIT_MAX_TRAVEL:   return s->solver->travel_limit;
     case BQ_OPT_FUSED_MACCORMACK:    return s->solver->fused_maccormack;
     case BQ_OPT_DIAGNOSTICS_EVERY:   return s->solver->diagnostics_every;
+    case BQ_OPT_TRACER_SORT_EVERY:   return s->solver->tracer_sort_every;
     default:                         return -1;
     }
 }
@@ -413,6 +416,59 @@ long bq_solver_output_preview(bq_solver *s, unsigned frame, const char *path, in
     BQ_ENTER(s);
     if (!s || !path) return -1;
     return s->solver->outputPreview(frame, std::string(path), view, light, sigma, albedo, ambient, background);
+}
+
+int bq_solver_set_tracers(bq_solver *s, const float *xyz, long n)
+{
+    BQ_ENTER(s);
+    if (!s) return FL_ERR_BAD_ARGUMENT;
+    if (s->solver->setTracers(xyz, n)) return FL_OK;
+    const int err = fl_last_error();
+    return err != FL_OK ? err : (int)FL_ERR_HIP;
+}
+
+long bq_solver_seed_tracers(bq_solver *s, const int lo[3], const int hi[3], int per_cell, unsigned seed)
+{
+    BQ_ENTER(s);
+    return s ? s->solver->seedTracers(lo, hi, per_cell, seed) : -1;
+}
+
+long bq_solver_tracer_count(const bq_solver *s) { return s ? s->solver->tracer_count : 0; }
+
+long bq_solver_tracers(bq_solver *s, float *xyz, long capacity)
+{
+    BQ_ENTER(s);
+    return s ? s->solver->tracers(xyz, capacity) : -1;
+}
+
+long bq_solver_tracer_sample(bq_solver *s, int which, float *out, long capacity)
+{
+    BQ_ENTER(s);
+    return s ? s->solver->tracerSample(which, out, capacity) : -1;
+}
+
+long bq_solver_output_tracers(bq_solver *s, unsigned frame, const char *path, int which)
+{
+    BQ_ENTER(s);
+    if (!s || !path) return -1;
+    return s->solver->outputTracers(frame, std::string(path), which);
+}
+
+long bq_solver_tracer_stored(bq_solver *s, float *xyz, unsigned *ids, long capacity)
+{
+    BQ_ENTER(s);
+    if (!s) return -1;
+    BimocqGPUSolver &b = *s->solver;
+    const long n = std::min(b.tracer_count, std::max(capacity, 0L));
+    if (n > 0 && xyz) {
+        const DeviceField *f[3] = { &b.TracerX, &b.TracerY, &b.TracerZ };
+        for (int c = 0; c < 3; c++) fl_memcpy_d2h(xyz + (size_t)c * n, f[c]->get(), (size_t)n * sizeof(float));
+    }
+    if (n > 0 && ids) {
+        if (b.tracer_ids) fl_memcpy_d2h(ids, b.tracer_id.u8(), (size_t)n * sizeof(unsigned));
+        else for (long a = 0; a < n; a++) ids[a] = (unsigned)a;
+    }
+    return b.tracer_count;
 }
 
 float bq_solver_last_cfldt(const bq_solver *s) { return s ? s->solver->last_cfldt : 0.f; }

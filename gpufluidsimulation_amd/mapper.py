@@ -212,3 +212,19 @@ class GpuMapper:
         self.lib.gpu_projection_jacobi(u.ptr, v.ptr, w.ptr, div.ptr, p.ptr, p_temp.ptr,
                                        debug.ptr if debug is not None else None,
                                        self.ni, self.nj, self.nk, iters, halfrdx, alpha, beta)
+
+    # passive tracer particles: px, py, pz DeviceBuffers of n floats; each returns the status
+    def traceParticles(self, u, v, w, px, py, pz, n, cfldt, dt):
+        return self.lib.gpu_trace_particles(u.ptr, v.ptr, w.ptr, px.ptr, py.ptr, pz.ptr, n, *self._g(), cfldt, dt)
+
+    def sampleParticles(self, field, dims, offset, px, py, pz, out, n):
+        return self.lib.gpu_sample_particles(field.ptr, *dims, self.h, *offset, px.ptr, py.ptr, pz.ptr, out.ptr, n)
+
+    def seedParticles(self, px, py, pz, lo, hi, per_cell=1, seed=0):
+        return self.lib.gpu_seed_particles(px.ptr, py.ptr, pz.ptr, lo[0], hi[0], lo[1], hi[1], lo[2], hi[2], per_cell, seed,
+                                           *self._g())
+
+    def sortParticles(self, px, py, pz, ids, qx, qy, qz, qids, n):
+        """ids / qids: DeviceBuffers of n 32-bit words (ids may be None: the identity)"""
+        return self.lib.gpu_sort_particles(px.ptr, py.ptr, pz.ptr, ids.ptr if ids is not None else None,
+                                           qx.ptr, qy.ptr, qz.ptr, qids.ptr, n, *self._g())

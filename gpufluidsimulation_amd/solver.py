@@ -223,6 +223,13 @@ HOST_SIGS = {
     "bq_solver_render": (C.c_long, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_long]),
     "bq_solver_output_preview": (C.c_long, [C.c_void_p, C.c_uint, C.c_char_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
                                             C.c_float]),
+    "bq_solver_set_tracers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long]),
+    "bq_solver_seed_tracers": (C.c_long, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_uint]),
+    "bq_solver_tracer_count": (C.c_long, [C.c_void_p]),
+    "bq_solver_tracers": (C.c_long, [C.c_void_p, C.c_void_p, C.c_long]),
+    "bq_solver_tracer_sample": (C.c_long, [C.c_void_p, C.c_int, C.c_void_p, C.c_long]),
+    "bq_solver_output_tracers": (C.c_long, [C.c_void_p, C.c_uint, C.c_char_p, C.c_int]),
+    "bq_solver_tracer_stored": (C.c_long, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long]),
 }
 PROJECTION_JACOBI, PROJECTION_MGCG, PROJECTION_PCG = 0, 1, 2
 # enum Scheme of the reference (BimocqSolver.h:29) as far as it is built: SEMILAG (1) is refused
@@ -231,6 +238,9 @@ SCHEME_BIMOCQ, SCHEME_MACCORMACK, SCHEME_MAC_REFLECTION = 0, 2, 3
 OPT_FUSED_MACCORMACK = 15
 # setOption(OPT_DIAGNOSTICS_EVERY, N): after every N-th advance() the flow diagnostics go into a device ring (diagnosticsHistory)
 OPT_DIAGNOSTICS_EVERY = 16
+# setOption(OPT_TRACER_SORT_EVERY, N): the tracers are re-sorted by brick after every N-th advance() (0, the default: never)
+OPT_TRACER_SORT_EVERY = 17
+MAX_TRACERS = 1 << 26
 # the entries of a diagnostics row (BQ_DIAG_* of include/bimocq_solver.h), in order
 DIAG_NAMES = ("kinetic", "enstrophy", "div_l2", "div_max", "rho_sum", "centroid_x", "centroid_y", "centroid_z", "T_sum",
               "vort_max", "step")
@@ -343,7 +353,7 @@ class BimocqGPUSolver:
         """option 1 = BQ_OPT_KEEP_DMC_BORDER, 2 = BQ_OPT_REINIT_POLICY (0 every frame, 1 distortion-driven),
         3 = BQ_OPT_FULL_STATE, 4 = BQ_OPT_FUSED_HOUSEKEEPING, 5 = BQ_OPT_OVERLAP_EXCHANGES, 6 = BQ_OPT_SHALLOW_BLOCKING_EXCHANGE,
         7 = BQ_OPT_JACOBI_ENDS_FIRST, 8 = BQ_OPT_PROFILE_PHASES, 9 = BQ_OPT_REINIT_MAX_TRAVEL, 10 = BQ_OPT_JACOBI_TRIPLES, 14 = BQ_OPT_NODE_LOOKUPS,
-        15 = BQ_OPT_FUSED_MACCORMACK, 16 = BQ_OPT_DIAGNOSTICS_EVERY (include/bimocq_solver.h)"""
+        15 = BQ_OPT_FUSED_MACCORMACK, 16 = BQ_OPT_DIAGNOSTICS_EVERY, 17 = BQ_OPT_TRACER_SORT_EVERY (include/bimocq_solver.h)"""
         self.lib.bq_solver_set_option(self.s, option, value)
         self._check()
 
@@ -524,6 +534,71 @@ class BimocqGPUSolver:
             raise _lib.BimocqError("bq_solver_output_preview failed")
         return n
 
+    # ---- passive tracer particles ----
+    def setTracers(self, positions):
+        """replaces the tracer set with `positions` ((n, 3) float32 world coordinates; an empty array releases everything).
+        Finite positions are clamped into [h, (n - 1) h] per axis; a NaN or an Inf is refused and leaves no tracers.  While
+        there are tracers every advance() moves them through the velocity the step starts with -- the forward map's own
+        trace, so a tracer on a grid node stays bit for bit on that node's forward-map entry until a re-initialisation.
+        One GPU; tracers are passive and ignore obstacles."""
+        a = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+        rc = self.lib.bq_solver_set_tracers(self.s, a.ctypes.data if a.size else None, a.shape[0])
+        self._check()
+        if rc != 0:
+            raise _lib.BimocqError(f"bq_solver_set_tracers failed ({rc})")
+
+    def seedTracers(self, cell_lo, cell_hi, per_cell=1, seed=0):
+        """appends per_cell jittered tracers in every cell of the half-open cell box [cell_lo, cell_hi) (cut to the cells
+        1 .. n - 2); ids continue from the current count.  Returns the number added."""
+        lo, hi = (C.c_int * 3)(*[int(x) for x in cell_lo]), (C.c_int * 3)(*[int(x) for x in cell_hi])
+        n = self.lib.bq_solver_seed_tracers(self.s, lo, hi, int(per_cell), int(seed) & 0xFFFFFFFF)
+        self._check()
+        if n < 0:
+            raise _lib.BimocqError("bq_solver_seed_tracers failed")
+        return n
+
+    def tracerCount(self):
+        return self.lib.bq_solver_tracer_count(self.s)
+
+    def tracers(self):
+        """the tracer positions as an (n, 3) float32 array in id order, whatever sorting has happened.  Blocking."""
+        n = self.tracerCount()
+        out = np.empty((n, 3), dtype=np.float32)
+        rc = self.lib.bq_solver_tracers(self.s, out.ctypes.data if n else None, n)
+        self._check()
+        if rc < 0:
+            raise _lib.BimocqError("bq_solver_tracers failed")
+        return out
+
+    def tracerSample(self, which):
+        """the current field `which` ("rho", "T", "u", "v", "w" or its id) at every tracer, in id order.  Blocking."""
+        which = FIELD_IDS[which] if isinstance(which, str) else int(which)
+        n = self.tracerCount()
+        out = np.empty(n, dtype=np.float32)
+        rc = self.lib.bq_solver_tracer_sample(self.s, which, out.ctypes.data if n else None, n)
+        self._check()
+        if rc < 0:
+            raise _lib.BimocqError("bq_solver_tracer_sample failed")
+        return out
+
+    def outputTracers(self, frame, path, which=None):
+        """writes <path>/tracers_%04u.bqp for frame + 1 (read_tracer_dump reads it): the positions in id order and, with
+        `which`, that field sampled at them; returns the bytes written"""
+        w = -1 if which is None else (FIELD_IDS[which] if isinstance(which, str) else int(which))
+        n = self.lib.bq_solver_output_tracers(self.s, frame, path.encode(), w)
+        self._check()
+        if n < 0:
+            raise _lib.BimocqError("bq_solver_output_tracers failed")
+        return n
+
+    def tracersStored(self):
+        """(positions (n, 3), ids (n,)) in the STORED order -- what the trace kernel walks; for tests and tools"""
+        n = self.tracerCount()
+        soa, ids = np.empty((3, n), dtype=np.float32), np.empty(n, dtype=np.uint32)
+        self.lib.bq_solver_tracer_stored(self.s, soa.ctypes.data if n else None, ids.ctypes.data if n else None, n)
+        self._check()
+        return np.ascontiguousarray(soa.T), ids
+
     def outputResultAsync(self, frame, path=None):
         """start the dump of the current density without stalling the simulation; waitOutput() joins it"""
         ok = self.lib.bq_solver_output_result_async(self.s, frame, path.encode() if path else None)
@@ -588,3 +663,17 @@ def read_density_dump(path):
         r = np.frombuffer(f.read(), dtype=rec)
     assert len(r) == h["count"]
     return h, r
+
+
+def read_tracer_dump(path):
+    """Reader of the BQPART01 container written by outputTracers: (header, positions (n, 3) float32, attribute (n,) or None)"""
+    hdr = np.dtype([("magic", "S8"), ("version", "<u4"), ("frame", "<u4"), ("count", "<u8"), ("nx", "<i4"), ("ny", "<i4"),
+                    ("nz", "<i4"), ("h", "<f4"), ("attribute", "<i4")])
+    with open(path, "rb") as f:
+        h = np.frombuffer(f.read(hdr.itemsize), dtype=hdr)[0]
+        assert h["magic"] == b"BQPART01" and h["version"] == 1, (h["magic"], h["version"])
+        n = int(h["count"])
+        xyz = np.frombuffer(f.read(12 * n), dtype="<f4").reshape(n, 3)
+        attr = np.frombuffer(f.read(4 * n), dtype="<f4") if h["attribute"] >= 0 else None
+        assert f.read() == b"" and xyz.shape[0] == n and (attr is None or attr.size == n)
+    return h, xyz, attr

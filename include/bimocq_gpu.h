@@ -981,6 +981,52 @@ typedef struct { float sigma, albedo, ambient; } fl_render_params;
 int gpu_render_density(const float *rho, float *shadow, float h, int ni, int nj, int nk, int view, int light,
                        const fl_render_params *p, double *d_image);
 
+/* ---- passive tracer particles ---------------------------------------------------------------------
+ * Particles are three device arrays of n floats each (px, py, pz): world positions, cell centre i at i h like everything
+ * else here.  All four operators are asynchronous on the compute stream, return FL_OK or the error they latched, launch
+ * nothing when they refuse, and treat n = 0 (an empty box) as a no-op.  One GPU: FL_ERR_UNSUPPORTED under a z-slab context
+ * (fl_set_slab) -- particles would have to migrate between ranks, which is not built.
+ *
+ * gpu_trace_particles: the reference's trace() (GPU_kernel.cu:92-125) per particle, in place: RK3 sub-steps of cfldt
+ * (the last one shorter) until |dt| is used up, backwards for dt < 0, every sub-step clamped to [h, (n_a - 1) h] (the upper
+ * bound evaluated as (float)n_a * h - h).  Same bits as gpu_solve_forward for a map entry that holds the same position,
+ * with FL_OPT_FAST_LERP on or off.  The caller promises cfldt * max|u| <= h and positions inside the clamp box, as for the
+ * forward map.  FL_ERR_BAD_ARGUMENT: a NULL pointer, n < 0, a dimension below 5 or beyond the operators' size limits,
+ * cfldt <= 0 with dt != 0, a non-finite h, cfldt or dt, a position array overlapping a velocity array or another one. */
+int gpu_trace_particles(const float *u, const float *v, const float *w, float *px, float *py, float *pz, long n,
+                        float h, int ni, int nj, int nk, float cfldt, float dt);
+/* gpu_sample_particles: out[a] = sample_buffer (GPU_kernel.cu:43-62) of `field` (nx x ny x nz floats, x fastest, value index
+ * (i, j, k) at position (ox + i h, oy + j h, oz + k h)) at particle a: trilinear, a cell whose base corner has a negative
+ * flat index reads zeros, a corner outside the allocation is 0.  Positions must be finite with |(p - o) / h| < 2^22.
+ * A cell-centred field has o = 0, the u faces ox = (float)(-0.5 * (double)h) (v: oy, w: oz).  FL_ERR_BAD_ARGUMENT: a NULL
+ * pointer, n < 0, a non-positive dimension or one beyond the size limits, `out` overlapping an input. */
+int gpu_sample_particles(const float *field, int nx, int ny, int nz, float h, float ox, float oy, float oz,
+                         const float *px, const float *py, const float *pz, float *out, long n);
+/* gpu_seed_particles: per_cell jittered positions in every cell of the half-open cell box [i0, i1) x [j0, j1) x [k0, k1),
+ * which is first intersected with the cells 1 .. n_a - 2 of every axis; bx, by, bz the extents left.  Returns nothing but the
+ * status: the count bx * by * bz * per_cell is closed-form (the caller sizes the arrays with it; at most 2^31 - 1).
+ * Particle p = s + per_cell * (x + bx * (y + by * z)) sits in cell C = (i0' + x, j0' + y, k0' + z): k outermost, then j, then
+ * i, then the sample s.  With G = C_x + ni * (C_y + nj * C_z), the 64-bit counter c = G * per_cell + s and, all in unsigned
+ * 32-bit arithmetic (wrapping),
+ *     mix(x):  x ^= x >> 16;  x *= 0x7feb352d;  x ^= x >> 15;  x *= 0x846ca68b;  x ^= x >> 16;  return x
+ *     r_a    = mix(mix(mix((uint32)c ^ seed) + (uint32)(c >> 32)) + a * 0x9e3779b9) >> 8        (a = 0, 1, 2: a 24-bit value)
+ * component a of the particle is  fminf(fmaxf(((float)C_a + (float)r_a * 2^-24f) * h, h), (float)n_a * h - h)  -- a float sum,
+ * a float product (the sum can round up to C_a + 1: a particle may sit ON the upper face of its cell), then the trace's clamp,
+ * which can move the last bit on the outermost cells only.  The same cell and sample get the same jitter whatever the box.
+ * No state, no library generator.  FL_ERR_BAD_ARGUMENT: a NULL pointer with a non-empty box, per_cell < 1, a count
+ * above 2^31 - 1, a dimension below 5. */
+int gpu_seed_particles(float *px, float *py, float *pz, int i0, int i1, int j0, int j1, int k0, int k1, int per_cell,
+                       unsigned seed, float h, int ni, int nj, int nk);
+/* gpu_sort_particles: counting sort of the particles (px, py, pz, id) into (qx, qy, qz, qid) by brick key: bricks of 4 x 4 x 4
+ * cells, key = bx + nbx * (by + nby * bz) with b_a = clamp(floor(p_a / h), 0, n_a - 1) >> 2 (IEEE division) and
+ * nb_a = (n_a + 3) / 4.  Histogram (integer atomics), exclusive scan, scatter (slots handed out by integer atomics): the
+ * order INSIDE a brick is whatever the atomics made it and may differ from run to run; positions and ids travel together.
+ * id == NULL stands for the identity (particle a has id a).  The key table (nbx nby nbz + 1 unsigned) lives in the library's
+ * scratch.  FL_ERR_BAD_ARGUMENT: a NULL pointer other than id, n < 0 or n >= 2^31, an output overlapping an input or another
+ * output, a dimension below 1 or beyond the size limits. */
+int gpu_sort_particles(const float *px, const float *py, const float *pz, const unsigned *id,
+                       float *qx, float *qy, float *qz, unsigned *qid, long n, float h, int ni, int nj, int nk);
+
 #ifdef __cplusplus
 }
 #endif

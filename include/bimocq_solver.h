@@ -151,7 +151,13 @@ enum {
      * left are enqueued into the next row of a device ring of 1024 rows -- in stream order, no host sync; read them with
      * bq_solver_diagnostics_history.  0 (default): nothing is launched or allocated and a step is exactly what it was.
      * Refused with FL_ERR_UNSUPPORTED on an operator library without gpu_flow_stats, FL_ERR_BAD_ARGUMENT for N < 0. */
-    BQ_OPT_DIAGNOSTICS_EVERY = 16
+    BQ_OPT_DIAGNOSTICS_EVERY = 16,
+    /* N > 0: after every N-th advance() the tracers are re-sorted by 4 x 4 x 4-cell brick (gpu_sort_particles) so that
+     * neighbouring lanes of the trace read neighbouring cells again once the flow has mixed the set; an id array and a second
+     * set of position arrays then exist.  0 (default, by measurement: DESIGN.md section 22): never, and neither exists.
+     * Everything public is in id order and the same bits either way.  FL_ERR_BAD_ARGUMENT for N < 0, FL_ERR_UNSUPPORTED for
+     * N > 0 where tracers are (z-slab ranks, an operator library without the tracer operators). */
+    BQ_OPT_TRACER_SORT_EVERY = 17
 };
 /* BQ_OPT_PROFILE_PHASES: milliseconds per phase summed over the steps since the last reset -- map update (DMC + RK3,
  * BimocqGPUSolver.cpp:136-139), advection with error compensation (:143-145), sources and forces (:157-177), projection
@@ -274,6 +280,38 @@ long  bq_solver_render(bq_solver *s, int view, int light, float sigma, float alb
  * first, so +y or +z points up.  On z-slab ranks only rank 0 writes (the others return 0).  Returns the bytes written or -1. */
 long  bq_solver_output_preview(bq_solver *s, unsigned frame, const char *path, int view, int light, float sigma, float albedo,
                                float ambient, float background);
+/* Passive tracer particles (the operators' contracts are in include/bimocq_gpu.h).  The solver owns
+ * the positions on the device.  In every scheme, while the count is non-zero, advance() moves each tracer over the whole dt
+ * through the velocity the step STARTS with, in sub-steps of that step's getCFL() value, clamped to [h, (n - 1) h]: the
+ * trace the forward map's nodes take (gpu_trace_particles / gpu_solve_forward), on the compute stream with no host sync,
+ * before anything writes the velocity.  A tracer placed on a grid node therefore equals, bit for bit, the forward map's entry
+ * of that node for as long as the map is not re-initialised.  Tracers are passive: they follow the velocity as it is, inside
+ * obstacles and walls too.  With no tracers advance() launches and allocates nothing for this.  A tracer's id is its index in
+ * the set as given (set_tracers) or appended (seed_tracers); everything below is in id order, whatever
+ * BQ_OPT_TRACER_SORT_EVERY has done to the stored order.  FL_ERR_UNSUPPORTED: z-slab ranks (migration of particles between
+ * ranks is deliberately not built) and an operator library without gpu_trace_particles.
+ * set_tracers: replaces the set with n positions (x, y, z interleaved, float32); n = 0 releases everything.  A non-finite
+ * component is refused with FL_ERR_BAD_ARGUMENT before anything is uploaded; finite positions are clamped componentwise into
+ * the trace's box; at most BQ_MAX_TRACERS.  Any failure leaves no tracers.  Returns FL_OK or the error. */
+#define BQ_MAX_TRACERS (1L << 26)
+int   bq_solver_set_tracers(bq_solver *s, const float *xyz, long n);
+/* appends per_cell jittered tracers in every cell of the half-open cell box [lo, hi) intersected with the cells 1 .. n - 2
+ * (gpu_seed_particles: k outermost, then j, i, the sample; the same cell and sample get the same jitter whatever the box).
+ * Ids continue from the current count.  Returns the number added -- (hi' - lo') products times per_cell -- or -1. */
+long  bq_solver_seed_tracers(bq_solver *s, const int lo[3], const int hi[3], int per_cell, unsigned seed);
+long  bq_solver_tracer_count(const bq_solver *s);
+/* positions in id order: copies min(count, capacity) triples when xyz != NULL; returns the count or -1.  Blocking. */
+long  bq_solver_tracers(bq_solver *s, float *xyz, long capacity);
+/* the CURRENT field `which` (BQ_F_RHO, BQ_F_T, BQ_F_U, BQ_F_V, BQ_F_W; each with its own stagger) sampled at every tracer
+ * (gpu_sample_particles), in id order: copies min(count, capacity) values when out != NULL; returns the count or -1. Blocking. */
+long  bq_solver_tracer_sample(bq_solver *s, int which, float *out, long capacity);
+/* <path>/tracers_%04u.bqp for frame + 1, little endian, packed: char magic[8] = "BQPART01", uint32 version = 1, uint32 frame,
+ * uint64 count, int32 nx, ny, nz, float h, int32 attribute (-1: none, else the BQ_F_* id); then count x (x, y, z) float32 in
+ * id order; then, when which >= 0, count float32 of bq_solver_tracer_sample(which).  Returns the bytes written or -1. */
+long  bq_solver_output_tracers(bq_solver *s, unsigned frame, const char *path, int which);
+/* the STORED order, for tests and tools: xyz receives three runs of min(count, capacity) floats (all x, all y, all z), ids
+ * the id of every stored slot (either may be NULL).  Returns the count.  Blocking. */
+long  bq_solver_tracer_stored(bq_solver *s, float *xyz, unsigned *ids, long capacity);
 float bq_solver_last_cfldt(const bq_solver *s);
 float bq_solver_last_ms(const bq_solver *s);          /* event time of the last advance()        */
 int   bq_solver_reinit_count(const bq_solver *s);
