@@ -45,7 +45,7 @@ FAST_OBJS := $(OBJDIR)/bq_advect_fast.o $(OBJDIR)/bq_tracers_fast.o
 $(PKG)/libbimocq_hip.so: $(KERNEL_OBJS) $(FAST_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(KERNEL_OBJS) $(FAST_OBJS) $(RCCL_LIB)
 
-$(OBJDIR)/host_%.o: $(CSRC)/host/%.cpp $(wildcard $(CSRC)/host/*.hpp) $(CSRC)/bq_levelset.h include/bimocq_gpu.h include/bimocq_solver.h
+$(OBJDIR)/host_%.o: $(CSRC)/host/%.cpp $(wildcard $(CSRC)/host/*.hpp) $(CSRC)/bq_levelset.h $(CSRC)/bq_pose.h include/bimocq_gpu.h include/bimocq_solver.h
 	@mkdir -p $(OBJDIR)
 	g++ -O2 -std=c++17 -fPIC -pthread -Wall -Wextra -Iinclude $(VDB_FLAGS) -c $< -o $@
 

@@ -166,6 +166,11 @@ HIP_SIGS = {
     "gpu_obstacle_flags_ls": (None, [VP, VP, VP, c_i, VP] + _G),
     "gpu_semilag_band_ls": (None, [VP] * 5 + [c_i, c_i, c_i] + _G + [c_f, c_f, VP, c_i, VP]),
     "gpu_obstacle_blend_ls": (None, [VP] * 11 + [VP, c_i, VP] + _G),
+    # rigid poses (the bq_pose array travels as a HOST pointer: solver.PoseDesc)
+    "gpu_obstacle_flags_pose": (None, [VP, VP, VP, c_i, VP, VP] + _G),
+    "gpu_semilag_band_pose": (None, [VP] * 5 + [c_i, c_i, c_i] + _G + [c_f, c_f, VP, c_i, VP, VP]),
+    "gpu_obstacle_blend_pose": (None, [VP] * 11 + [VP, c_i, VP, VP] + _G),
+    "gpu_obstacle_faces_pose": (None, [VP] * 7 + [VP, VP, c_i] + _G),
     # shaped sources (bq_source and bq_levelset arrays travel as HOST pointers: solver.SourceDesc / LevelSetDesc)
     "gpu_emit_sources": (None, [VP] * 5 + [VP, VP, c_i] + _G),
     # flow diagnostics: rho, T and vort_mag may be NULL, d_out is DEVICE memory

@@ -1624,20 +1624,26 @@ BQ_ENTRY(gpu_semilag, (float *field, float *field_src, float *u, float *v, float
     BQ_DISPATCH1(semilag_kernel, sp.pow2, grid_for(ni + dim_x, nj + dim_y, nk + dim_z), field, field_src, u, v, w, sp, g, dim_x, dim_y, dim_z, cfldt, dt);
 }
 
-// gpu_semilag_band and gpu_semilag_band_ls: one set of checks, the analytic kernel whenever there are no descriptors
+// gpu_semilag_band, gpu_semilag_band_ls and gpu_semilag_band_pose: one set of checks, the analytic kernel whenever there
+// are no descriptors
 static void semilag_band(float *field, float *field_src, float *u, float *v, float *w, int dim_x, int dim_y, int dim_z,
                          float h, int ni, int nj, int nk, float cfldt, float dt, const bq_boundary *b, int n,
-                         const bq_levelset *ls, const char *op)
+                         const bq_levelset *ls, const bq_pose *pose, const char *op)
 {
     BQ_ENTER(op, field, field_src, u, v, w)
     BQ_REQUIRE(cfldt > 0.f || dt == 0.f, op);
     BQ_REQUIRE((dim_x | dim_y | dim_z) == 0 || (dim_x + dim_y + dim_z) == 1, op);
     BQ_REQUIRE(n >= 0 && n <= BQ_MAX_BOUNDARIES && (b || n == 0), op);
     if (const char *why = ls_check(b, ls, n)) { latch(FL_ERR_BAD_ARGUMENT, op, why); return; }
+    if (const char *why = pose_check(pose, n)) { latch(FL_ERR_BAD_ARGUMENT, op, why); return; }
     if (n == 0) return;
     Spacing sp = make_spacing(h); Grid g = mk_grid(ni, nj, nk);
     const dim3 grid = grid_for(ni + dim_x, nj + dim_y, nk + dim_z);
-    if (ls)
+    if (pose && ls)
+        BQ_DISPATCH1(semilag_band_kernel, sp.pow2, grid, field, field_src, u, v, w, sp, g, dim_x, dim_y, dim_z, cfldt, dt, make_obs(b, n, h), make_ls(b, ls, n), make_pose(b, pose, n));
+    else if (pose)
+        BQ_DISPATCH1(semilag_band_kernel, sp.pow2, grid, field, field_src, u, v, w, sp, g, dim_x, dim_y, dim_z, cfldt, dt, make_obs(b, n, h), make_pose(b, pose, n));
+    else if (ls)
         BQ_DISPATCH1(semilag_band_kernel, sp.pow2, grid, field, field_src, u, v, w, sp, g, dim_x, dim_y, dim_z, cfldt, dt, make_obs(b, n, h), make_ls(b, ls, n));
     else
         BQ_DISPATCH1(semilag_band_kernel, sp.pow2, grid, field, field_src, u, v, w, sp, g, dim_x, dim_y, dim_z, cfldt, dt, make_obs(b, n, h));
@@ -1647,14 +1653,23 @@ BQ_ENTRY(gpu_semilag_band, (float *field, float *field_src, float *u, float *v, 
                       float h, int ni, int nj, int nk, float cfldt, float dt, const bq_boundary *b, int n),
          (field, field_src, u, v, w, dim_x, dim_y, dim_z, h, ni, nj, nk, cfldt, dt, b, n))
 {
-    semilag_band(field, field_src, u, v, w, dim_x, dim_y, dim_z, h, ni, nj, nk, cfldt, dt, b, n, nullptr, "gpu_semilag_band");
+    semilag_band(field, field_src, u, v, w, dim_x, dim_y, dim_z, h, ni, nj, nk, cfldt, dt, b, n, nullptr, nullptr, "gpu_semilag_band");
 }
 
 BQ_ENTRY(gpu_semilag_band_ls, (float *field, float *field_src, float *u, float *v, float *w, int dim_x, int dim_y, int dim_z,
                          float h, int ni, int nj, int nk, float cfldt, float dt, const bq_boundary *b, int n, const bq_levelset *ls),
          (field, field_src, u, v, w, dim_x, dim_y, dim_z, h, ni, nj, nk, cfldt, dt, b, n, ls))
 {
-    semilag_band(field, field_src, u, v, w, dim_x, dim_y, dim_z, h, ni, nj, nk, cfldt, dt, b, n, ls, "gpu_semilag_band_ls");
+    semilag_band(field, field_src, u, v, w, dim_x, dim_y, dim_z, h, ni, nj, nk, cfldt, dt, b, n, ls, nullptr, "gpu_semilag_band_ls");
+}
+
+BQ_ENTRY(gpu_semilag_band_pose, (float *field, float *field_src, float *u, float *v, float *w, int dim_x, int dim_y, int dim_z,
+                           float h, int ni, int nj, int nk, float cfldt, float dt, const bq_boundary *b, int n, const bq_levelset *ls,
+                           const bq_pose *pose),
+         (field, field_src, u, v, w, dim_x, dim_y, dim_z, h, ni, nj, nk, cfldt, dt, b, n, ls, pose))
+{
+    semilag_band(field, field_src, u, v, w, dim_x, dim_y, dim_z, h, ni, nj, nk, cfldt, dt, b, n, ls, pose,
+                 pose ? "gpu_semilag_band_pose" : "gpu_semilag_band_ls");
 }
 
 BQ_ENTRY(gpu_clamp_extrema, (float *field, float *fieldTemp, float *u, float *v, float *w,

@@ -66,6 +66,62 @@ __global__ __launch_bounds__(256) void obstacle_faces_kernel(float *__restrict__
     }
 }
 
+// obstacle_faces_kernel for lists with spinning entries: a face owned by entry o with bit o of
+// `spin` set takes the rigid velocity v + omega x (p - c) at its own sample position p, in gpu_emit_sources' operation order
+struct ObsSpin {
+    unsigned spin;
+    float cx[BQ_MAX_BOUNDARIES], cy[BQ_MAX_BOUNDARIES], cz[BQ_MAX_BOUNDARIES];
+    float ox[BQ_MAX_BOUNDARIES], oy[BQ_MAX_BOUNDARIES], oz[BQ_MAX_BOUNDARIES];
+};
+__global__ __launch_bounds__(256) void obstacle_faces_pose_kernel(float *__restrict__ u, float *__restrict__ v, float *__restrict__ w,
+                                                                  float *__restrict__ du, float *__restrict__ dv, float *__restrict__ dw,
+                                                                  const unsigned char *__restrict__ solid, ObsVel ov, ObsSpin os,
+                                                                  float h, int ni, int nj, int nk)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x, j = blockIdx.y * 4 + threadIdx.y, k = blockIdx.z;
+    if (i > ni || j > nj || k > nk) return;
+    const float x0 = obs_pos(i, 0, h), y0 = obs_pos(j, 0, h), z0 = obs_pos(k, 0, h);
+    if (j < nj && k < nk) {                                         // u face between cells i-1 and i
+        const int o = max(flag_at(solid, i - 1, j, k, ni, nj, nk), flag_at(solid, i, j, k, ni, nj, nk));
+        if (o) {
+            const size_t id = (size_t)i + (size_t)(ni + 1) * ((size_t)j + (size_t)nj * k);
+            float vo = ov.vx[o - 1];
+            if ((os.spin >> (o - 1)) & 1u) {
+                const float dy = y0 - os.cy[o - 1], dz = z0 - os.cz[o - 1];
+                vo = vo + (os.oy[o - 1] * dz - os.oz[o - 1] * dy);
+            }
+            if (du) du[id] = vo - u[id];
+            u[id] = vo;
+        }
+    }
+    if (i < ni && k < nk) {                                         // v face between cells j-1 and j
+        const int o = max(flag_at(solid, i, j - 1, k, ni, nj, nk), flag_at(solid, i, j, k, ni, nj, nk));
+        if (o) {
+            const size_t id = (size_t)i + (size_t)ni * ((size_t)j + (size_t)(nj + 1) * k);
+            float vo = ov.vy[o - 1];
+            if ((os.spin >> (o - 1)) & 1u) {
+                const float dx = x0 - os.cx[o - 1], dz = z0 - os.cz[o - 1];
+                vo = vo + (os.oz[o - 1] * dx - os.ox[o - 1] * dz);
+            }
+            if (dv) dv[id] = vo - v[id];
+            v[id] = vo;
+        }
+    }
+    if (i < ni && j < nj) {                                         // w face between cells k-1 and k
+        const int o = max(flag_at(solid, i, j, k - 1, ni, nj, nk), flag_at(solid, i, j, k, ni, nj, nk));
+        if (o) {
+            const size_t id = (size_t)i + (size_t)ni * ((size_t)j + (size_t)nj * k);
+            float vo = ov.vz[o - 1];
+            if ((os.spin >> (o - 1)) & 1u) {
+                const float dx = x0 - os.cx[o - 1], dy = y0 - os.cy[o - 1];
+                vo = vo + (os.ox[o - 1] * dy - os.oy[o - 1] * dx);
+            }
+            if (dw) dw[id] = vo - w[id];
+            w[id] = vo;
+        }
+    }
+}
+
 // ---- masked Jacobi sweep, one per launch ------------------------------------------------------------------------------
 // Odd sweep counts and the test baseline of the fused masked sweeps (jacobi_lds_kernel<8, 1, 3, true>, bq_project.hip).  A
 // cell whose rows summary is clean (no solid cell in its row or the neighbouring rows and planes) evaluates
@@ -277,16 +333,21 @@ static bool obs_args_ok(const bq_boundary *b, int n, int ni, int nj, int nk, con
     return true;
 }
 
-// gpu_obstacle_flags and gpu_obstacle_blend with (ls non-NULL) and without level sets: one set of checks, and the
-// analytic kernels whenever there are no descriptors
+// gpu_obstacle_flags and gpu_obstacle_blend with (ls non-NULL) and without level sets, with (pose non-NULL) and without
+// poses: one set of checks, and the analytic kernels whenever there are no descriptors
 static void obstacle_flags(unsigned char *solid, unsigned char *rows, const bq_boundary *b, int n, const bq_levelset *ls,
-                           float h, int ni, int nj, int nk, const char *op)
+                           const bq_pose *pose, float h, int ni, int nj, int nk, const char *op)
 {
     if (!obs_args_ok(b, n, ni, nj, nk, op)) return;
     if (const char *why = ls_check(b, ls, n)) { latch(FL_ERR_BAD_ARGUMENT, op, why); return; }
+    if (const char *why = pose_check(pose, n)) { latch(FL_ERR_BAD_ARGUMENT, op, why); return; }
     if (!solid || !rows) { latch(FL_ERR_BAD_ARGUMENT, op, "null device pointer"); return; }
     if (!BQ_HIP(hipMemsetAsync(rows, 0, (size_t)nj * (size_t)nk, rt().compute))) return;
-    if (ls)
+    if (pose && ls)
+        obstacle_flags_kernel<LsSet, PoseSet><<<grid_for(ni, nj, nk), kBlock, 0, rt().compute>>>(solid, rows, make_obs(b, n, h), make_ls(b, ls, n), make_pose(b, pose, n), h, ni, nj, nk);
+    else if (pose)
+        obstacle_flags_kernel<PoseSet><<<grid_for(ni, nj, nk), kBlock, 0, rt().compute>>>(solid, rows, make_obs(b, n, h), make_pose(b, pose, n), h, ni, nj, nk);
+    else if (ls)
         obstacle_flags_kernel<LsSet><<<grid_for(ni, nj, nk), kBlock, 0, rt().compute>>>(solid, rows, make_obs(b, n, h), make_ls(b, ls, n), h, ni, nj, nk);
     else
         obstacle_flags_kernel<><<<grid_for(ni, nj, nk), kBlock, 0, rt().compute>>>(solid, rows, make_obs(b, n, h), h, ni, nj, nk);
@@ -295,13 +356,19 @@ static void obstacle_flags(unsigned char *solid, unsigned char *rows, const bq_b
 
 static void obstacle_blend(float *u, float *v, float *w, float *rho, float *T, const float *us, const float *vs,
                            const float *ws, const float *rhos, const float *Ts, const unsigned char *solid,
-                           const bq_boundary *b, int n, const bq_levelset *ls, float h, int ni, int nj, int nk, const char *op)
+                           const bq_boundary *b, int n, const bq_levelset *ls, const bq_pose *pose, float h, int ni, int nj, int nk,
+                           const char *op)
 {
     if (!obs_args_ok(b, n, ni, nj, nk, op)) return;
     if (const char *why = ls_check(b, ls, n)) { latch(FL_ERR_BAD_ARGUMENT, op, why); return; }
+    if (const char *why = pose_check(pose, n)) { latch(FL_ERR_BAD_ARGUMENT, op, why); return; }
     if (!rho || !solid || (us && (!u || !v || !w || !T || !vs || !ws || !rhos || !Ts))) { latch(FL_ERR_BAD_ARGUMENT, op, "null device pointer"); return; }
     const dim3 grid = grid_for(ni + 1, nj + 1, nk + 1);
-    if (ls)
+    if (pose && ls)
+        obstacle_blend_kernel<LsSet, PoseSet><<<grid, kBlock, 0, rt().compute>>>(u, v, w, rho, T, us, vs, ws, rhos, Ts, solid, make_obs(b, n, h), make_ls(b, ls, n), make_pose(b, pose, n), h, ni, nj, nk);
+    else if (pose)
+        obstacle_blend_kernel<PoseSet><<<grid, kBlock, 0, rt().compute>>>(u, v, w, rho, T, us, vs, ws, rhos, Ts, solid, make_obs(b, n, h), make_pose(b, pose, n), h, ni, nj, nk);
+    else if (ls)
         obstacle_blend_kernel<LsSet><<<grid, kBlock, 0, rt().compute>>>(u, v, w, rho, T, us, vs, ws, rhos, Ts, solid, make_obs(b, n, h), make_ls(b, ls, n), h, ni, nj, nk);
     else
         obstacle_blend_kernel<><<<grid, kBlock, 0, rt().compute>>>(u, v, w, rho, T, us, vs, ws, rhos, Ts, solid, make_obs(b, n, h), h, ni, nj, nk);
@@ -319,7 +386,7 @@ extern "C" {
 
 void gpu_obstacle_flags(unsigned char *solid, unsigned char *rows, const bq_boundary *b, int n, float h, int ni, int nj, int nk)
 {
-    obstacle_flags(solid, rows, b, n, nullptr, h, ni, nj, nk, "gpu_obstacle_flags");
+    obstacle_flags(solid, rows, b, n, nullptr, nullptr, h, ni, nj, nk, "gpu_obstacle_flags");
 }
 
 void gpu_obstacle_faces(float *u, float *v, float *w, float *du, float *dv, float *dw, const unsigned char *solid,
@@ -466,20 +533,55 @@ void gpu_obstacle_blend(float *u, float *v, float *w, float *rho, float *T, cons
                         const float *ws, const float *rhos, const float *Ts, const unsigned char *solid,
                         const bq_boundary *b, int n, float h, int ni, int nj, int nk)
 {
-    obstacle_blend(u, v, w, rho, T, us, vs, ws, rhos, Ts, solid, b, n, nullptr, h, ni, nj, nk, "gpu_obstacle_blend");
+    obstacle_blend(u, v, w, rho, T, us, vs, ws, rhos, Ts, solid, b, n, nullptr, nullptr, h, ni, nj, nk, "gpu_obstacle_blend");
 }
 
 void gpu_obstacle_flags_ls(unsigned char *solid, unsigned char *rows, const bq_boundary *b, int n, const bq_levelset *ls,
                            float h, int ni, int nj, int nk)
 {
-    obstacle_flags(solid, rows, b, n, ls, h, ni, nj, nk, "gpu_obstacle_flags_ls");
+    obstacle_flags(solid, rows, b, n, ls, nullptr, h, ni, nj, nk, "gpu_obstacle_flags_ls");
 }
 
 void gpu_obstacle_blend_ls(float *u, float *v, float *w, float *rho, float *T, const float *us, const float *vs,
                            const float *ws, const float *rhos, const float *Ts, const unsigned char *solid,
                            const bq_boundary *b, int n, const bq_levelset *ls, float h, int ni, int nj, int nk)
 {
-    obstacle_blend(u, v, w, rho, T, us, vs, ws, rhos, Ts, solid, b, n, ls, h, ni, nj, nk, "gpu_obstacle_blend_ls");
+    obstacle_blend(u, v, w, rho, T, us, vs, ws, rhos, Ts, solid, b, n, ls, nullptr, h, ni, nj, nk, "gpu_obstacle_blend_ls");
+}
+
+void gpu_obstacle_flags_pose(unsigned char *solid, unsigned char *rows, const bq_boundary *b, int n, const bq_levelset *ls,
+                             const bq_pose *pose, float h, int ni, int nj, int nk)
+{
+    obstacle_flags(solid, rows, b, n, ls, pose, h, ni, nj, nk, pose ? "gpu_obstacle_flags_pose" : "gpu_obstacle_flags_ls");
+}
+
+void gpu_obstacle_blend_pose(float *u, float *v, float *w, float *rho, float *T, const float *us, const float *vs,
+                             const float *ws, const float *rhos, const float *Ts, const unsigned char *solid,
+                             const bq_boundary *b, int n, const bq_levelset *ls, const bq_pose *pose, float h, int ni, int nj, int nk)
+{
+    obstacle_blend(u, v, w, rho, T, us, vs, ws, rhos, Ts, solid, b, n, ls, pose, h, ni, nj, nk,
+                   pose ? "gpu_obstacle_blend_pose" : "gpu_obstacle_blend_ls");
+}
+
+void gpu_obstacle_faces_pose(float *u, float *v, float *w, float *du, float *dv, float *dw, const unsigned char *solid,
+                             const bq_boundary *b, const bq_pose *pose, int n, float h, int ni, int nj, int nk)
+{
+    const char *op = "gpu_obstacle_faces_pose";
+    if (!obs_args_ok(b, n, ni, nj, nk, op)) return;
+    if (const char *why = pose_check(pose, n)) { latch(FL_ERR_BAD_ARGUMENT, op, why); return; }
+    ObsSpin os{};
+    for (int o = 0; pose && o < n; o++) {
+        if (!pose_spins(pose[o])) continue;
+        os.spin |= 1u << o;
+        os.cx[o] = b[o].cx; os.cy[o] = b[o].cy; os.cz[o] = b[o].cz;
+        os.ox[o] = pose[o].ox; os.oy[o] = pose[o].oy; os.oz[o] = pose[o].oz;
+    }
+    if (!os.spin) { gpu_obstacle_faces(u, v, w, du, dv, dw, solid, b, n, ni, nj, nk); return; }
+    if (!u || !v || !w || !solid || (!du) != (!dv) || (!du) != (!dw)) { latch(FL_ERR_BAD_ARGUMENT, op, "null device pointer"); return; }
+    ObsVel ov{};
+    for (int o = 0; o < n; o++) { ov.vx[o] = b[o].vx; ov.vy[o] = b[o].vy; ov.vz[o] = b[o].vz; }
+    obstacle_faces_pose_kernel<<<grid_for(ni + 1, nj + 1, nk + 1), kBlock, 0, rt().compute>>>(u, v, w, du, dv, dw, solid, ov, os, h, ni, nj, nk);
+    BQ_LAUNCH_CHECK("obstacle_faces_pose_kernel");
 }
 
 } // extern "C"

@@ -4,8 +4,10 @@
 #include <hip/hip_runtime.h>
 #include "bimocq_gpu.h"
 #include "bq_levelset.h"
+#include "bq_pose.h"
 
 #include <cmath>
+#include <type_traits>
 
 namespace bq {
 
@@ -59,14 +61,11 @@ static inline LsSet make_ls(const bq_boundary *b, const bq_levelset *ls, int n)
 // p + (q - p) t with the difference and the sum in float and the product in double (BoxSampler's lerp)
 __device__ __forceinline__ float ls_lerp(float p, float q, double t) { return p + (float)((double)(q - p) * t); }
 
-// trilinear sample of level set o at (x, y, z), its index origin at (cx, cy, cz) ("Level sets").
+// trilinear sample of level set o at the position (gx, gy, gz) of its own index space ("Level sets").
 // false when all eight corners lie outside the stored nodes (the sample is exactly the background there): the exact
 // early-out, taken before any load.  Otherwise corners outside the stored nodes read the background.
-__device__ __forceinline__ bool ls_sample(const LsSet &l, int o, float x, float y, float z, float cx, float cy, float cz,
-                                          float &sdf)
+__device__ __forceinline__ bool ls_sample_index(const LsSet &l, int o, double gx, double gy, double gz, float &sdf)
 {
-    const double vox = (double)l.voxel[o];
-    const double gx = ((double)x - (double)cx) / vox, gy = ((double)y - (double)cy) / vox, gz = ((double)z - (double)cz) / vox;
     const int nx = l.nx[o], ny = l.ny[o], nz = l.nz[o], i0 = l.i0[o], j0 = l.j0[o], k0 = l.k0[o];
     if (gx < (double)(i0 - 1) || gx >= (double)(i0 + nx) || gy < (double)(j0 - 1) || gy >= (double)(j0 + ny) ||
         gz < (double)(k0 - 1) || gz >= (double)(k0 + nz))
@@ -88,20 +87,90 @@ __device__ __forceinline__ bool ls_sample(const LsSet &l, int o, float x, float 
     sdf = ls_lerp(a0, a1, tx);
     return true;
 }
+// ... at the world point (x, y, z), the index origin at (cx, cy, cz): index = (point - origin) / voxel in double
+__device__ __forceinline__ bool ls_sample(const LsSet &l, int o, float x, float y, float z, float cx, float cy, float cz,
+                                          float &sdf)
+{
+    const double vox = (double)l.voxel[o];
+    const double gx = ((double)x - (double)cx) / vox, gy = ((double)y - (double)cy) / vox, gz = ((double)z - (double)cz) / vox;
+    return ls_sample_index(l, o, gx, gy, gz, sdf);
+}
+
+// the rotations of a list with poses, one more optional element of the pack after LsSet: bit o of
+// `oriented` marks the entries classified in body coordinates, r[3 a + c][o] is R_ac (body -> world) of entry o.
+struct PoseSet {
+    unsigned oriented;
+    float r[9][BQ_MAX_BOUNDARIES];
+};
+
+static inline PoseSet make_pose(const bq_boundary *b, const bq_pose *pose, int n)
+{
+    PoseSet s{};
+    for (int o = 0; o < n; o++) {
+        if (!pose_oriented(b[o], pose[o])) continue;
+        float R[9];
+        pose_matrix(pose[o], R);
+        s.oriented |= 1u << o;
+        for (int m = 0; m < 9; m++) s.r[m][o] = R[m];
+    }
+    return s;
+}
+
+// the pack of a kernel: <>, <LsSet>, <PoseSet> or <LsSet, PoseSet>
+template <typename T, typename... A> inline constexpr bool pack_has = (std::is_same_v<T, A> || ...);
+template <typename... A> inline constexpr bool pack_ok = (sizeof...(A) == 0) || (sizeof...(A) == 1 && (pack_has<LsSet, A...> || pack_has<PoseSet, A...>)) ||
+                                                         (sizeof...(A) == 2 && pack_has<LsSet, A...> && pack_has<PoseSet, A...>);
+template <typename T, typename A0, typename... A>
+__device__ __forceinline__ const T &pack_get(const A0 &a0, const A &...a)
+{
+    if constexpr (std::is_same_v<T, A0>) return a0;
+    else return pack_get<T>(a...);
+}
 
 // o + 1 when obstacle o is the last one covering (x, y, z); -1 when the point lies in the band of some obstacle and
-// inside none; 0 otherwise.  Without ls: analytic entries only; with ls (one LsSet): level-set entries are sampled, solid
-// when the sample is <= 0, band when 0 < sample < background.
+// inside none; 0 otherwise.  Without ls: analytic entries only; with an LsSet in ls: level-set entries are sampled, solid
+// when the sample is <= 0, band when 0 < sample < background; with a PoseSet in ls: its oriented entries are classified
+// in body coordinates.
 template <typename... Ls>
 __device__ __forceinline__ int obs_classify(float x, float y, float z, const ObsSet &s, const Ls &...ls)
 {
-    static_assert(sizeof...(Ls) <= 1, "one LsSet at most");
+    static_assert(pack_ok<Ls...>, "one LsSet and one PoseSet at most");
     int solid = 0;
     bool band = false;
     for (int o = 0; o < s.n; o++) {
-        if constexpr (sizeof...(Ls) == 1) {
+        if constexpr (pack_has<PoseSet, Ls...>) {
+            const PoseSet &ps = pack_get<PoseSet>(ls...);
+            if ((ps.oriented >> o) & 1u) {                  // body coordinates R^T d, each product and sum one float operation
+                const float dx = x - s.cx[o], dy = y - s.cy[o], dz = z - s.cz[o];
+                const float bx = ps.r[0][o] * dx + ps.r[3][o] * dy + ps.r[6][o] * dz;
+                const float by = ps.r[1][o] * dx + ps.r[4][o] * dy + ps.r[7][o] * dz;
+                const float bz = ps.r[2][o] * dx + ps.r[5][o] * dy + ps.r[8][o] * dz;
+                if (s.shape[o] == BQ_SHAPE_LEVELSET) {
+                    if constexpr (pack_has<LsSet, Ls...>) {
+                        const LsSet &l = pack_get<LsSet>(ls...);
+                        const double vox = (double)l.voxel[o];
+                        float sdf;
+                        if (ls_sample_index(l, o, (double)bx / vox, (double)by / vox, (double)bz / vox, sdf)) {
+                            if (sdf <= 0.f) solid = o + 1;
+                            else if (sdf < l.bg[o]) band = true;
+                        }
+                    }
+                } else {
+                    const float ax = fabsf(bx) - s.rx[o], ay = fabsf(by) - s.ry[o], az = fabsf(bz) - s.rz[o];
+                    if (ax <= 0.f && ay <= 0.f && az <= 0.f) {
+                        solid = o + 1;
+                    } else {
+                        const float qx = fmaxf(ax, 0.f), qy = fmaxf(ay, 0.f), qz = fmaxf(az, 0.f);
+                        const float d2 = qx * qx + qy * qy + qz * qz;
+                        if (d2 > 0.f && d2 < s.h3 * s.h3) band = true;
+                    }
+                }
+                continue;
+            }
+        }
+        if constexpr (pack_has<LsSet, Ls...>) {
             if (s.shape[o] == BQ_SHAPE_LEVELSET) {
-                const LsSet &l = (ls, ...);
+                const LsSet &l = pack_get<LsSet>(ls...);
                 float sdf;
                 if (ls_sample(l, o, x, y, z, s.cx[o], s.cy[o], s.cz[o], sdf)) {
                     if (sdf <= 0.f) solid = o + 1;

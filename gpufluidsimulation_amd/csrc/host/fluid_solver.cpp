@@ -12,6 +12,7 @@
 // reaches further than that (no-ops on a single GPU).
 #include "fluid_solver.hpp"
 #include "../bq_levelset.h"
+#include "../bq_pose.h"
 
 #include <algorithm>
 #include <cmath>
@@ -31,6 +32,10 @@
 #pragma weak gpu_obstacle_flags_ls
 #pragma weak gpu_semilag_band_ls
 #pragma weak gpu_obstacle_blend_ls
+#pragma weak gpu_obstacle_flags_pose
+#pragma weak gpu_semilag_band_pose
+#pragma weak gpu_obstacle_blend_pose
+#pragma weak gpu_obstacle_faces_pose
 #pragma weak gpu_divergence_double
 #pragma weak gpu_pcg_solve
 #pragma weak gpu_pcg_gradient
@@ -48,27 +53,40 @@ namespace bqhost {
 
 // The obstacle operators for a list with level-set descriptors ls (non-NULL only when it holds a level set, and then
 // setBoundary has found the _ls operators), else the analytic ones: runs without level sets issue the launches they did
-// before level sets existed, and the stand-ins without the _ls operators still run analytic lists.
-static void obstacle_flags(unsigned char *solid, unsigned char *rows, const bq_boundary *b, int n, const bq_levelset *ls, float h,
-                           int ni, int nj, int nk)
+// before level sets existed, and the stand-ins without the _ls operators still run analytic lists.  Likewise `pose`
+// (DESIGN.md section 23): non-NULL only when the list holds an oriented or spinning entry, and then setBoundary has found the
+// _pose operators.
+static void obstacle_flags(unsigned char *solid, unsigned char *rows, const bq_boundary *b, int n, const bq_levelset *ls,
+                           const bq_pose *pose, float h, int ni, int nj, int nk)
 {
-    if (ls) gpu_obstacle_flags_ls(solid, rows, b, n, ls, h, ni, nj, nk);
+    if (pose) gpu_obstacle_flags_pose(solid, rows, b, n, ls, pose, h, ni, nj, nk);
+    else if (ls) gpu_obstacle_flags_ls(solid, rows, b, n, ls, h, ni, nj, nk);
     else    gpu_obstacle_flags(solid, rows, b, n, h, ni, nj, nk);
 }
 
 static void semilag_band(float *field, float *field_src, float *u, float *v, float *w, int dim_x, int dim_y, int dim_z, float h,
-                         int ni, int nj, int nk, float cfldt, float dt, const bq_boundary *b, int n, const bq_levelset *ls)
+                         int ni, int nj, int nk, float cfldt, float dt, const bq_boundary *b, int n, const bq_levelset *ls,
+                         const bq_pose *pose)
 {
-    if (ls) gpu_semilag_band_ls(field, field_src, u, v, w, dim_x, dim_y, dim_z, h, ni, nj, nk, cfldt, dt, b, n, ls);
+    if (pose) gpu_semilag_band_pose(field, field_src, u, v, w, dim_x, dim_y, dim_z, h, ni, nj, nk, cfldt, dt, b, n, ls, pose);
+    else if (ls) gpu_semilag_band_ls(field, field_src, u, v, w, dim_x, dim_y, dim_z, h, ni, nj, nk, cfldt, dt, b, n, ls);
     else    gpu_semilag_band(field, field_src, u, v, w, dim_x, dim_y, dim_z, h, ni, nj, nk, cfldt, dt, b, n);
 }
 
 static void obstacle_blend(float *u, float *v, float *w, float *rho, float *T, const float *us, const float *vs, const float *ws,
                            const float *rhos, const float *Ts, const unsigned char *solid, const bq_boundary *b, int n,
-                           const bq_levelset *ls, float h, int ni, int nj, int nk)
+                           const bq_levelset *ls, const bq_pose *pose, float h, int ni, int nj, int nk)
 {
-    if (ls) gpu_obstacle_blend_ls(u, v, w, rho, T, us, vs, ws, rhos, Ts, solid, b, n, ls, h, ni, nj, nk);
+    if (pose) gpu_obstacle_blend_pose(u, v, w, rho, T, us, vs, ws, rhos, Ts, solid, b, n, ls, pose, h, ni, nj, nk);
+    else if (ls) gpu_obstacle_blend_ls(u, v, w, rho, T, us, vs, ws, rhos, Ts, solid, b, n, ls, h, ni, nj, nk);
     else    gpu_obstacle_blend(u, v, w, rho, T, us, vs, ws, rhos, Ts, solid, b, n, h, ni, nj, nk);
+}
+
+static void obstacle_faces(float *u, float *v, float *w, float *du, float *dv, float *dw, const unsigned char *solid,
+                           const bq_boundary *b, const bq_pose *pose, int n, float h, int ni, int nj, int nk)
+{
+    if (pose) gpu_obstacle_faces_pose(u, v, w, du, dv, dw, solid, b, pose, n, h, ni, nj, nk);
+    else      gpu_obstacle_faces(u, v, w, du, dv, dw, solid, b, n, ni, nj, nk);
 }
 
 // Every level-set grid of a list (entry o is one when is_ls[o]; ls[o].phi a HOST array) copied into ONE device allocation,
@@ -704,8 +722,10 @@ std::vector<double> BimocqGPUSolver::mgHistory() const
 // setBoundary (BimocqSolver.cpp:936-1064 without the domain walls): the list replaces the previous one, the flags are built
 // at the given centres.  n = 0 removes every obstacle and the step is exactly the one without this feature.  ls[o] is read
 // for the entries of shape BQ_SHAPE_LEVELSET ("Level sets"), its phi a HOST array that is copied into
-// one device allocation with every other grid of the list.  A refused list leaves the previous one in place.
-bool BimocqGPUSolver::setBoundary(const bq_boundary *b, const bq_levelset *ls, int n)
+// one device allocation with every other grid of the list.  pose (NULL: none): one orientation and
+// angular velocity per entry; the quaternions become the double master copies that updateBoundary integrates.  A refused
+// list leaves the previous one in place.
+bool BimocqGPUSolver::setBoundary(const bq_boundary *b, const bq_levelset *ls, int n, const bq_pose *pose)
 {
     if (n < 0 || n > BQ_MAX_BOUNDARIES || (n > 0 && !b)) {
         fl_report_error(FL_ERR_BAD_ARGUMENT, "setBoundary: 0 .. 16 obstacles");
@@ -752,6 +772,15 @@ bool BimocqGPUSolver::setBoundary(const bq_boundary *b, const bq_levelset *ls, i
         fl_report_error(FL_ERR_BAD_ARGUMENT, (std::string("setBoundary: ") + why).c_str());
         return false;
     }
+    if (const char *why = bq::pose_check(pose, n)) {
+        fl_report_error(FL_ERR_BAD_ARGUMENT, (std::string("setBoundary: ") + why).c_str());
+        return false;
+    }
+    const bool posed = bq::pose_any(b, pose, n);
+    if (posed && (!gpu_obstacle_flags_pose || !gpu_semilag_band_pose || !gpu_obstacle_blend_pose || !gpu_obstacle_faces_pose)) {
+        fl_report_error(FL_ERR_UNSUPPORTED, "setBoundary: the operator library has no pose operators (rotating obstacles)");
+        return false;
+    }
     // every grid into one allocation, the descriptors pointing into it
     DeviceBytes grids;
     std::vector<bq_levelset> descs;
@@ -764,9 +793,15 @@ bool BimocqGPUSolver::setBoundary(const bq_boundary *b, const bq_levelset *ls, i
     if (solid.bytes() != g.n() && !solid.alloc(g.n())) return false;
     if (rows.bytes() != nrows && !rows.alloc(nrows)) return false;
     std::vector<bq_boundary> list(b, b + n);
-    if (!buildFlags(list, any_ls ? descs.data() : nullptr)) return false;
+    std::vector<bq_pose> pl((size_t)n, bq_pose{ 1.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f });
+    if (pose) pl.assign(pose, pose + n);
+    if (!buildFlags(list, any_ls ? descs.data() : nullptr, posed ? pl.data() : nullptr)) return false;
     boundaries.swap(list);
     levelsets.swap(descs);
+    orientations.resize((size_t)n);
+    for (int o = 0; o < n; o++) orientations[(size_t)o] = { (double)pl[o].qw, (double)pl[o].qx, (double)pl[o].qy, (double)pl[o].qz };
+    poses.swap(pl);
+    posed_list = posed;
     lsgrids = std::move(grids);
     return buildWallFlags();
 }
@@ -776,6 +811,9 @@ void BimocqGPUSolver::dropBoundaries()
 {
     boundaries.clear();
     levelsets.clear();
+    poses.clear();
+    orientations.clear();
+    posed_list = false;
     solid.release();
     rows.release();
     lsgrids.release();
@@ -783,9 +821,9 @@ void BimocqGPUSolver::dropBoundaries()
 
 // the flags of `list` (ls: its level-set descriptors, or NULL when it holds none); on failure the obstacles are dropped (no
 // step may run on flags that were never built)
-bool BimocqGPUSolver::buildFlags(const std::vector<bq_boundary> &list, const bq_levelset *ls)
+bool BimocqGPUSolver::buildFlags(const std::vector<bq_boundary> &list, const bq_levelset *ls, const bq_pose *pose)
 {
-    obstacle_flags(solid.u8(), rows.u8(), list.data(), (int)list.size(), ls, CellSize, g.ni, g.nj, g.nk);
+    obstacle_flags(solid.u8(), rows.u8(), list.data(), (int)list.size(), ls, pose, CellSize, g.ni, g.nj, g.nk);
     if (fl_last_error() == FL_OK) return true;
     dropBoundaries();
     dropWalls();                                    // (solidw held the flags of the list that is gone)
@@ -793,7 +831,9 @@ bool BimocqGPUSolver::buildFlags(const std::vector<bq_boundary> &list, const bq_
 }
 
 // updateBoundary: Boundary::update (BimocqSolver.h:71-73, b_pos += vel_func(framenum) * dt) with the velocity of the list,
-// then the flags at the new centres
+// then the flags at the new centres.  A spinning entry turns by theta = |omega| dt about omega:
+// q <- dq (x) q with dq = (cos(theta/2), sin(theta/2) omega/|omega|), renormalised, all in double on the master copy; the
+// four floats the operators see are rounded from it, so nothing drifts.  Zero omega leaves q's bits alone.
 bool BimocqGPUSolver::updateBoundary(int /*framenum*/, float dt)
 {
     if (boundaries.empty()) return true;
@@ -803,8 +843,31 @@ bool BimocqGPUSolver::updateBoundary(int /*framenum*/, float dt)
         b.cy += b.vy * dt;
         b.cz += b.vz * dt;
     }
-    if (!buildFlags(list, levelsetList())) return false;
+    if (!posed_list) {
+        if (!buildFlags(list, levelsetList(), nullptr)) return false;
+        boundaries.swap(list);
+        return buildWallFlags();
+    }
+    std::vector<bq_pose> pl = poses;
+    std::vector<std::array<double, 4>> ql = orientations;
+    for (size_t o = 0; o < pl.size(); o++) {
+        if (!bq::pose_spins(pl[o])) continue;
+        const double ox = pl[o].ox, oy = pl[o].oy, oz = pl[o].oz, len = std::sqrt(ox * ox + oy * oy + oz * oz);
+        const double half = 0.5 * len * (double)dt, sn = std::sin(half) / len;
+        const double a = std::cos(half), bx = sn * ox, by = sn * oy, bz = sn * oz;       // dq
+        const std::array<double, 4> q = ql[o];
+        double w = a * q[0] - bx * q[1] - by * q[2] - bz * q[3];
+        double x = a * q[1] + bx * q[0] + by * q[3] - bz * q[2];
+        double y = a * q[2] - bx * q[3] + by * q[0] + bz * q[1];
+        double z = a * q[3] + bx * q[2] - by * q[1] + bz * q[0];
+        const double norm = std::sqrt(w * w + x * x + y * y + z * z);
+        ql[o] = { w / norm, x / norm, y / norm, z / norm };
+        pl[o].qw = (float)ql[o][0]; pl[o].qx = (float)ql[o][1]; pl[o].qy = (float)ql[o][2]; pl[o].qz = (float)ql[o][3];
+    }
+    if (!buildFlags(list, levelsetList(), pl.data())) return false;
     boundaries.swap(list);
+    poses.swap(pl);
+    orientations.swap(ql);
     return buildWallFlags();
 }
 
@@ -891,12 +954,13 @@ void BimocqGPUSolver::semilagBand(float cfldt, float dt)
     const bq_boundary *b = boundaries.data();
     const int n = (int)boundaries.size(), ni = g.ni, nj = g.nj, nk = g.nk;
     const bq_levelset *ls = levelsetList();
+    const bq_pose *pose = poseList();
     const float h = CellSize;
-    semilag_band(TempSrcU, VelocityU, VelocityU, VelocityV, VelocityW, 1, 0, 0, h, ni, nj, nk, cfldt, -dt, b, n, ls);
-    semilag_band(TempSrcV, VelocityV, VelocityU, VelocityV, VelocityW, 0, 1, 0, h, ni, nj, nk, cfldt, -dt, b, n, ls);
-    semilag_band(TempSrcW, VelocityW, VelocityU, VelocityV, VelocityW, 0, 0, 1, h, ni, nj, nk, cfldt, -dt, b, n, ls);
-    semilag_band(DensityTemp, Density, VelocityU, VelocityV, VelocityW, 0, 0, 0, h, ni, nj, nk, cfldt, -dt, b, n, ls);
-    semilag_band(TemperatureTemp, Temperature, VelocityU, VelocityV, VelocityW, 0, 0, 0, h, ni, nj, nk, cfldt, -dt, b, n, ls);
+    semilag_band(TempSrcU, VelocityU, VelocityU, VelocityV, VelocityW, 1, 0, 0, h, ni, nj, nk, cfldt, -dt, b, n, ls, pose);
+    semilag_band(TempSrcV, VelocityV, VelocityU, VelocityV, VelocityW, 0, 1, 0, h, ni, nj, nk, cfldt, -dt, b, n, ls, pose);
+    semilag_band(TempSrcW, VelocityW, VelocityU, VelocityV, VelocityW, 0, 0, 1, h, ni, nj, nk, cfldt, -dt, b, n, ls, pose);
+    semilag_band(DensityTemp, Density, VelocityU, VelocityV, VelocityW, 0, 0, 0, h, ni, nj, nk, cfldt, -dt, b, n, ls, pose);
+    semilag_band(TemperatureTemp, Temperature, VelocityU, VelocityV, VelocityW, 0, 0, 0, h, ni, nj, nk, cfldt, -dt, b, n, ls, pose);
 }
 
 // blendBoundary (:879-912) of all five fields from semilagBand's values + clearBoundary (:914-934) of rho; band = false:
@@ -907,10 +971,10 @@ void BimocqGPUSolver::blendBoundary(bool band)
     const int n = (int)boundaries.size();
     if (band)
         obstacle_blend(VelocityU, VelocityV, VelocityW, Density, Temperature, TempSrcU, TempSrcV, TempSrcW, DensityTemp,
-                       TemperatureTemp, solid.u8(), b, n, levelsetList(), CellSize, g.ni, g.nj, g.nk);
+                       TemperatureTemp, solid.u8(), b, n, levelsetList(), poseList(), CellSize, g.ni, g.nj, g.nk);
     else
         obstacle_blend(nullptr, nullptr, nullptr, Density, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                       solid.u8(), b, n, levelsetList(), CellSize, g.ni, g.nj, g.nk);
+                       solid.u8(), b, n, levelsetList(), poseList(), CellSize, g.ni, g.nj, g.nk);
 }
 
 // the Jacobi projection with obstacles (:1120-1413): solid faces take the obstacle velocity (with_delta: its share of
@@ -921,7 +985,8 @@ bool BimocqGPUSolver::projectionObstacles(bool with_delta)
     float *du = with_delta ? duProj.get() : nullptr, *dv = with_delta ? dvProj.get() : nullptr, *dw = with_delta ? dwProj.get() : nullptr;
     div.zero(); p.zero(); p_temp.zero();
     if (!boundaries.empty())
-        gpu_obstacle_faces(VelocityU, VelocityV, VelocityW, du, dv, dw, solid.u8(), boundaries.data(), (int)boundaries.size(), g.ni, g.nj, g.nk);
+        obstacle_faces(VelocityU, VelocityV, VelocityW, du, dv, dw, solid.u8(), boundaries.data(), poseList(), (int)boundaries.size(),
+                       CellSize, g.ni, g.nj, g.nk);
     if (walls) gpu_wall_faces(VelocityU, VelocityV, VelocityW, du, dv, dw, solidw.u8(), g.ni, g.nj, g.nk);   // (disjoint faces: the order is free)
     gpu_divergence(VelocityU, VelocityV, VelocityW, div, g.ni, g.nj, g.nk, halfrdx);
     // p and p_temp carry the same (zero) boundary layer and +0 in every solid cell: three masked sweeps per launch
@@ -948,8 +1013,8 @@ bool BimocqGPUSolver::projectionPcg()
     const bool obst = !boundaries.empty();
     const unsigned char *sol = projectionFlags();       // (walls on: solid + walls)
     if (obst)
-        gpu_obstacle_faces(VelocityU, VelocityV, VelocityW, nullptr, nullptr, nullptr, solid.u8(), boundaries.data(),
-                           (int)boundaries.size(), g.ni, g.nj, g.nk);
+        obstacle_faces(VelocityU, VelocityV, VelocityW, nullptr, nullptr, nullptr, solid.u8(), boundaries.data(), poseList(),
+                       (int)boundaries.size(), CellSize, g.ni, g.nj, g.nk);
     if (walls) gpu_wall_faces(VelocityU, VelocityV, VelocityW, nullptr, nullptr, nullptr, solidw.u8(), g.ni, g.nj, g.nk);
     gpu_divergence_double(VelocityU, VelocityV, VelocityW, mg.div.f64(), g.ni, g.nj, g.nk, (double)halfrdx);
     SCoarseLevelInfo &L0 = mg.levels[0];

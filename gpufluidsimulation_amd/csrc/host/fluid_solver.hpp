@@ -8,6 +8,7 @@
 #pragma once
 #include <string>
 #include <thread>
+#include <array>
 #include <vector>
 #include "bimocq_solver.h"
 #include "mapping.hpp"
@@ -150,7 +151,7 @@ public:
     // one GPU only.  With an empty list a step issues exactly the launches it issues without this feature.
     std::vector<bq_boundary> boundaries;
     DeviceBytes solid, rows;                        // cell flags (0 fluid, o + 1 solid by obstacle o), rows summary (include/bimocq_gpu.h)
-    bool setBoundary(const bq_boundary *b, const bq_levelset *ls, int n);      // ls: NULL when no entry is a level set
+    bool setBoundary(const bq_boundary *b, const bq_levelset *ls, int n, const bq_pose *pose = nullptr);   // ls: NULL when no entry is a level set
     bool updateBoundary(int framenum, float dt);
     // Level sets (shape BQ_SHAPE_LEVELSET): `levelsets` holds one descriptor per entry of `boundaries` (phi into lsgrids)
     // when the list holds a level set, and is empty otherwise -- then every obstacle operator call is the analytic one.
@@ -158,8 +159,15 @@ public:
     std::vector<bq_levelset> levelsets;
     DeviceBytes lsgrids;                            // every level-set grid of the list, one allocation
     const bq_levelset *levelsetList() const { return levelsets.empty() ? nullptr : levelsets.data(); }
+    // Rigid poses: one pose per entry of `boundaries`, `orientations` the double master copies of the
+    // quaternions that updateBoundary integrates (the floats of `poses` are rounded from them).  posed_list: the list holds an
+    // oriented or spinning entry -- only then do the obstacle operator calls become the _pose ones.
+    std::vector<bq_pose> poses;
+    std::vector<std::array<double, 4>> orientations;
+    bool posed_list = false;
+    const bq_pose *poseList() const { return posed_list ? poses.data() : nullptr; }
     void dropBoundaries();
-    bool buildFlags(const std::vector<bq_boundary> &list, const bq_levelset *ls);
+    bool buildFlags(const std::vector<bq_boundary> &list, const bq_levelset *ls, const bq_pose *pose);
     bool projectionObstacles(bool with_delta);
     // Closed domain walls (the reference's container, BimocqSolver.cpp:938-948): `walls` the closed sides
     // (BQ_WALL_* bits), `solidw` = solid + BQ_FLAG_WALL in the wall cells, allocated only while walls are on and rebuilt when the

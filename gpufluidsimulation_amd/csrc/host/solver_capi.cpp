@@ -258,6 +258,27 @@ int bq_solver_set_boundary_levelsets(bq_solver *s, const bq_boundary *b, const b
     return -1;
 }
 
+int bq_solver_set_boundary_poses(bq_solver *s, const bq_boundary *b, const bq_levelset *ls, const bq_pose *pose, int n)
+{
+    BQ_ENTER(s);
+    if (!s) return -1;
+    if (s->solver->setBoundary(b, ls, n, pose)) return 0;
+    s->solver->dropBoundaries();                    // after any failure no obstacles are left
+    return -1;
+}
+
+int bq_solver_boundary_pose(const bq_solver *s, int i, double out[10])
+{
+    if (!s || !out || i < 0 || i >= (int)s->solver->boundaries.size()) return -1;
+    const bq_boundary &b = s->solver->boundaries[(size_t)i];
+    const bq_pose &p = s->solver->poses[(size_t)i];
+    const std::array<double, 4> &q = s->solver->orientations[(size_t)i];
+    out[0] = b.cx; out[1] = b.cy; out[2] = b.cz;
+    out[3] = q[0]; out[4] = q[1]; out[5] = q[2]; out[6] = q[3];
+    out[7] = p.ox; out[8] = p.oy; out[9] = p.oz;
+    return 0;
+}
+
 int bq_solver_set_sources(bq_solver *s, const bq_source *src, const bq_levelset *ls, int n)
 {
     BQ_ENTER(s);

@@ -59,3 +59,13 @@ def plume(nz_global, h):
     box = levelset_from_sdf(sdf, (-hx, -hy, -hz), (hx, hy, hz), h)
     return [Source(box, (SMOKE[0], SMOKE[1], 0.5 * nz_global * h), 1.0, 1.0, 1 << 30, velocity=(0.0, 0.5, 0.0),
                    spin=(0.0, 0.5, 0.0))]
+
+
+def paddle(n, L, spin=2.0):
+    """a spinning paddle (solver.Rotating list for BimocqGPUSolver.setBoundary): a box of half
+    extents (0.3 L, 2 h, 0.15 L) with h = L / n at the centre of an n^3 grid of side L, turning about the z axis at `spin`
+    rad per time unit -- call updateBoundary every frame"""
+    from .solver import SHAPE_BOX, Rotating
+    h = L / n
+    c = 0.5 * L
+    return [Rotating((SHAPE_BOX, c, c, c, 0.3 * L, 2.0 * h, 0.15 * L, 0.0, 0.0, 0.0), spin=(0.0, 0.0, float(spin)))]

@@ -122,6 +122,42 @@ def levelset_arrays(boundaries):
     return arr, ls, len(boundaries)
 
 
+class PoseDesc(C.Structure):
+    """bq_pose: orientation quaternion (w, x, y, z; body -> world, any non-zero scale), angular velocity about the centre"""
+    _fields_ = [("qw", C.c_float), ("qx", C.c_float), ("qy", C.c_float), ("qz", C.c_float),
+                ("ox", C.c_float), ("oy", C.c_float), ("oz", C.c_float)]
+
+
+class Rotating:
+    """An obstacle with a rigid pose: `obstacle` is an analytic tuple, a Boundary or a
+    LevelSetObstacle; `orientation` a quaternion (w, x, y, z), body -> world, of any non-zero scale; `spin` the angular
+    velocity about the obstacle's centre in the world frame, rad per time unit.  A sphere ignores its orientation."""
+
+    def __init__(self, obstacle, spin=(0.0, 0.0, 0.0), orientation=(1.0, 0.0, 0.0, 0.0)):
+        if isinstance(obstacle, Rotating):
+            raise ValueError("a Rotating wraps a plain obstacle")
+        self.obstacle = obstacle
+        self.spin = tuple(float(x) for x in spin)
+        self.orientation = tuple(float(x) for x in orientation)
+        if len(self.spin) != 3 or len(self.orientation) != 4:
+            raise ValueError("spin has 3 components, orientation 4 (w, x, y, z)")
+
+    def pose(self):
+        return PoseDesc(*self.orientation, *self.spin)
+
+
+def pose_arrays(boundaries):
+    """(Boundary array, LevelSetDesc array or None, PoseDesc array, count) for a list that may mix Rotating objects with
+    everything levelset_arrays takes; entries without a pose get the identity and no spin"""
+    boundaries = list(boundaries)
+    plain = [b.obstacle if isinstance(b, Rotating) else b for b in boundaries]
+    arr, ls, n = levelset_arrays(plain)
+    poses = (PoseDesc * max(1, n))()
+    for i, b in enumerate(boundaries):
+        poses[i] = b.pose() if isinstance(b, Rotating) else PoseDesc(1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0)
+    return arr, (ls if any(isinstance(b, LevelSetObstacle) for b in plain) else None), poses, n
+
+
 SOURCE_VELOCITY = 1
 MAX_SOURCES = 16
 
@@ -207,6 +243,8 @@ HOST_SIGS = {
     "bq_solver_set_boundary": (C.c_int, [C.c_void_p, C.POINTER(Boundary), C.c_int]),
     "bq_solver_set_boundary_levelsets": (C.c_int, [C.c_void_p, C.POINTER(Boundary), C.POINTER(LevelSetDesc), C.c_int]),
     "bq_solver_update_boundary": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
+    "bq_solver_set_boundary_poses": (C.c_int, [C.c_void_p, C.POINTER(Boundary), C.POINTER(LevelSetDesc), C.POINTER(PoseDesc), C.c_int]),
+    "bq_solver_boundary_pose": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double)]),
     "bq_solver_download_solid": (C.c_long, [C.c_void_p, C.c_void_p, C.c_long]),
     "bq_solver_set_walls": (C.c_int, [C.c_void_p, C.c_int]),
     "bq_solver_get_walls": (C.c_int, [C.c_void_p]),
@@ -381,9 +419,14 @@ class BimocqGPUSolver:
         """setBoundary: replaces the obstacle list (Boundary objects or (shape, cx, cy, cz, rx, ry, rz, vx, vy, vz)
         tuples, or LevelSetObstacles; [] removes every obstacle) and builds the cell flags at the given centres.  One GPU,
         Jacobi or PCG (kind 2) projection.  A list with a level set goes through bq_solver_set_boundary_levelsets, which copies the grids to
-        the device; after a failed call with a level set there are no obstacles."""
+        the device; after a failed call with a level set there are no obstacles.  Entries wrapped in Rotating (in any mix with
+        the others) carry an orientation and a spin: such a list goes through
+        bq_solver_set_boundary_poses, after whose failure there are no obstacles either."""
         boundaries = list(boundaries)
-        if any(isinstance(b, LevelSetObstacle) for b in boundaries):
+        if any(isinstance(b, Rotating) for b in boundaries):
+            arr, ls, poses, n = pose_arrays(boundaries)
+            rc = self.lib.bq_solver_set_boundary_poses(self.s, arr, ls, poses, n)
+        elif any(isinstance(b, LevelSetObstacle) for b in boundaries):
             arr, ls, n = levelset_arrays(boundaries)
             rc = self.lib.bq_solver_set_boundary_levelsets(self.s, arr, ls, n)
         else:
@@ -393,8 +436,21 @@ class BimocqGPUSolver:
         if rc != 0:
             raise _lib.BimocqError("bq_solver_set_boundary failed")
 
+    def boundaryPoses(self):
+        """one (centre, orientation quaternion (w, x, y, z), angular velocity) triple of tuples per obstacle: the solver's
+        current poses, the quaternion being its double master copy"""
+        out = []
+        buf = (C.c_double * 10)()
+        i = 0
+        while self.lib.bq_solver_boundary_pose(self.s, i, buf) == 0:
+            v = list(buf)
+            out.append((tuple(v[0:3]), tuple(v[3:7]), tuple(v[7:10])))
+            i += 1
+        return out
+
     def updateBoundary(self, framenum, dt):
-        """updateBoundary: every centre moves by v * dt, then the flags are rebuilt"""
+        """updateBoundary: every centre moves by v * dt and every spinning entry turns by |spin| dt about its spin, then the
+        flags are rebuilt"""
         rc = self.lib.bq_solver_update_boundary(self.s, framenum, dt)
         self._check()
         if rc != 0:

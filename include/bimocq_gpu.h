@@ -819,6 +819,38 @@ void gpu_semilag_band_ls(float *field, float *field_src, float *u, float *v, flo
 void gpu_obstacle_blend_ls(float *u, float *v, float *w, float *rho, float *T, const float *us, const float *vs,
                            const float *ws, const float *rhos, const float *Ts, const unsigned char *solid,
                            const bq_boundary *b, int n, const bq_levelset *ls, float h, int ni, int nj, int nk);
+/* Rigid poses (an extension, the reference's obstacles only translate): entry o of a list may carry
+ * an orientation and an angular velocity about its centre.  The nine entries of the body -> world rotation R are formed
+ * on the host in double from the four floats by the scale-free formula (s = w^2 + x^2 + y^2 + z^2, R00 = 1 - 2 (y^2 +
+ * z^2) / s, R01 = 2 (x y - w z) / s, ...) and rounded to float; the kernels see R only.  An entry is ORIENTED when it is
+ * not a sphere and (qx, qy, qz) != (0, 0, 0): it is classified at the body coordinates R^T (x - c), a box by the
+ * analytic test, a level set sampled at index (double)b / (double)voxel.  Every other entry is classified as above, bit
+ * for bit.  An entry SPINS when (ox, oy, oz) != (0, 0, 0): its faces take v + omega x (p - c) at the face's own sample
+ * position p. */
+#ifndef BQ_POSE_DEFINED
+#define BQ_POSE_DEFINED
+typedef struct bq_pose {
+    float qw, qx, qy, qz;    /* orientation, body -> world; any non-zero quaternion, need not be unit */
+    float ox, oy, oz;        /* angular velocity about the centre (cx, cy, cz), world frame, rad / time unit */
+} bq_pose;
+#endif
+/* gpu_obstacle_flags_ls, gpu_semilag_band_ls and gpu_obstacle_blend_ls for lists with poses: `pose` is a host array of n
+ * entries; NULL: the _ls operator itself.  The _ls refusals apply; a non-finite component of a pose, or a quaternion whose
+ * s is 0 or not finite, latches FL_ERR_BAD_ARGUMENT and launches nothing. */
+void gpu_obstacle_flags_pose(unsigned char *solid, unsigned char *rows, const bq_boundary *b, int n,
+                             const bq_levelset *ls, const bq_pose *pose, float h, int ni, int nj, int nk);
+void gpu_semilag_band_pose(float *field, float *field_src, float *u, float *v, float *w, int dim_x, int dim_y, int dim_z,
+                           float h, int ni, int nj, int nk, float cfldt, float dt, const bq_boundary *b, int n,
+                           const bq_levelset *ls, const bq_pose *pose);
+void gpu_obstacle_blend_pose(float *u, float *v, float *w, float *rho, float *T, const float *us, const float *vs,
+                             const float *ws, const float *rhos, const float *Ts, const unsigned char *solid,
+                             const bq_boundary *b, int n, const bq_levelset *ls, const bq_pose *pose, float h,
+                             int ni, int nj, int nk);
+/* gpu_obstacle_faces where a face owned by a spinning entry takes the rigid velocity at its own sample position
+ * (u = vx + (oy dz - oz dy), v = vy + (oz dx - ox dz), w = vz + (ox dy - oy dx), d = p - c in float); pose == NULL or no
+ * spinning entry: the values of gpu_obstacle_faces.  The same pose refusals. */
+void gpu_obstacle_faces_pose(float *u, float *v, float *w, float *du, float *dv, float *dw, const unsigned char *solid,
+                             const bq_boundary *b, const bq_pose *pose, int n, float h, int ni, int nj, int nk);
 
 /* ---- closed domain walls (reference: updateBoundary's flag-2 border, BimocqSolver.cpp:938-948, which the
  * projection treats as obstacle cells with velocity 0, :1157-1164, :1184-1256, :1288-1356) -------------------------------

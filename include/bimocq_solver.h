@@ -214,6 +214,21 @@ int   bq_solver_set_boundary(bq_solver *s, const bq_boundary *b, int n);
  * obstacles.  Returns 0 on success. */
 int   bq_solver_set_boundary_levelsets(bq_solver *s, const bq_boundary *b, const bq_levelset *ls, int n);
 int   bq_solver_update_boundary(bq_solver *s, int framenum, float dt);
+/* set_boundary_levelsets for lists whose entries may carry a rigid pose (an extension, the reference's
+ * obstacles only translate): pose is an array of n bq_pose (orientation quaternion, any non-zero scale, and angular velocity
+ * about the entry's centre); ls and pose may each be NULL.  A box or level set with (qx, qy, qz) != 0 is ORIENTED: it is
+ * classified in its body frame.  An entry with a non-zero angular velocity SPINS: its solid faces take v + omega x (p - c),
+ * and update_boundary turns its orientation by |omega| dt about omega (a double quaternion kept by the solver, so nothing
+ * drifts).  A list without an oriented or spinning entry issues exactly the launches of set_boundary_levelsets.
+ * set_boundary and set_boundary_levelsets keep their meaning: no rotation.  The refusals of set_boundary_levelsets apply,
+ * plus: a non-finite component of a pose or a quaternion of squared norm 0 or not finite (FL_ERR_BAD_ARGUMENT), and an
+ * oriented or spinning entry on a library without the pose operators (FL_ERR_UNSUPPORTED).  z-slab ranks and
+ * BQ_PROJECTION_MGCG are refused as for every obstacle; orientation of sources and a time-varying angular velocity are not
+ * supported (callers set the list again, as for v).  Any failure leaves no obstacles.  Returns 0 on success.
+ * boundary_pose: centre (3), orientation quaternion w, x, y, z (4), angular velocity (3) of entry i into out; returns 0,
+ * or -1 for a bad index. */
+int   bq_solver_set_boundary_poses(bq_solver *s, const bq_boundary *b, const bq_levelset *ls, const bq_pose *pose, int n);
+int   bq_solver_boundary_pose(const bq_solver *s, int i, double out[10]);
 /* Closed domain walls (the reference's container, BimocqSolver.cpp:938-948): `walls` is a sum of
  * BQ_WALL_* bits (include/bimocq_gpu.h), BQ_WALLS_NONE (default: every side open, p = 0 in the border cells) or
  * BQ_WALLS_REFERENCE_BOX (every side closed but +y).  Border cells of a closed side are solid cells with velocity 0 for
