@@ -5,6 +5,7 @@
 // Every kernel restates one reference kernel with identical arithmetic (see bq_device.hip.h);
 // the launch geometry, the buffer-descriptor loads and the fusion are ours.
 #include "bq_device.hip.h"
+#include "bq_gather_op.hip.h"
 #include "bq_host.h"
 #include "bq_launch_geom.h"
 #include "bq_obstacle.hip.h"
@@ -231,9 +232,9 @@ __device__ __forceinline__ bool wave_all_ge(const f3 (&mp)[9], float h)
     return __all(m >= h);
 }
 
-// Batches: NF fields that live on the same nodes share one map look-up (density + temperature; the
-// two velocity-change fields accumulated back to back).  Results per field are what NF single
-// launches in the same order produce.
+// Argument layouts of the three one-plane kernels (batches of NF fields: GatherArgs of bq_gather_op.hip.h, from which the
+// launcher fills them).  They are kept apart from GatherArgs on purpose: these kernels sit at their register limit, and the
+// order of the pointers in the kernel-argument segment alone moves the allocator's result.
 template <int NF> struct AdvectArgs { float *field[NF]; const float *init[NF]; };
 template <int NF> struct CumulateArgs { const float *src[NF]; float *dst[NF]; float coeff[NF]; };
 template <int NF> struct CompensateArgs { const float *src[NF]; float *init[NF]; float *err[NF]; };
@@ -249,11 +250,13 @@ __global__ __launch_bounds__(256, NF == 1 ? 7 : 5) void advect_kernel(AdvectArgs
                                                      Spacing sp, Grid g, int dx, int dy, int dz, int fused, MapTabs tabs, Sparse sps)
 {
     static_assert(!SPARSE || (SD == 0 && kStaged<P2, PT, SD>), "the skip exists for unstaggered staged launches only");
+    using Op = GatherOp<kOpAdvect>;
+    constexpr int m = Op::margin;
     const int nbi = g.ni + dx, nbj = g.nj + dy, nbk = g.nk + dz;
     int bX = blockIdx.x, bY = blockIdx.y, bZ = blockIdx.z;
     if constexpr (SPARSE == 1) { if (*sps.word != sps.epoch) return; }         // no empty brick: the second launch is the plain one
     if constexpr (SPARSE == 2) { if (!listed_block(sps, bX, bY, bZ)) return; }
-    BQ_IJK_WINDOW_AT(bX, bY, bZ, 2 + dx, nbi - 3, 2 + dy, nbj - 3, 2 + dz, g.nkg + dz - 3)
+    BQ_IJK_WINDOW_AT(bX, bY, bZ, m + dx, nbi - m - 1, m + dy, nbj - m - 1, m + dz, g.nkg + dz - m - 1)
     // FL_OPT_FUSED_HOUSEKEEPING bit 1: nodes outside the window get the zero the caller's clear would have left
     // (SPARSE == 1: only in the blocks this launch finishes -- a listed block is left to the second launch altogether)
     auto housekeeping = [&] {
@@ -267,13 +270,13 @@ __global__ __launch_bounds__(256, NF == 1 ? 7 : 5) void advect_kernel(AdvectArgs
     const float h = sp.h;
     Map3 back{make_field(bx, g.ni, g.nj, g.nk, g.koff), make_field(by, g.ni, g.nj, g.nk, g.koff), make_field(bz, g.ni, g.nj, g.nk, g.koff)};
     Nine n = nine_setup(h, dx, dy, dz);
-    f3 lo = mk3(h, h, h), hi = mk3(h * (float)g.ni - h, h * (float)g.nj - h, h * (float)g.nkg - h);
+    f3 lo = Op::lo(h), hi = Op::hi(h, g.ni, g.nj, g.nkg);
     if constexpr (SPARSE == 1) {
         // (a block that gets here has an active thread -- block_out is exact for boxes -- hence ni, nj, nkg >= 7 and lo <= hi)
         __shared__ float part[32];
         const Field mf[3] = {back.x, back.y, back.z};
         float mn[3], mx[3]; bool bad;
-        tile_range(mf, i0, j0, k, part, 2, nbi - 3, 2, nbj - 3, mn, mx, bad);
+        tile_range(mf, i0, j0, k, part, m, nbi - m - 1, m, nbj - m - 1, mn, mx, bad);
         const bool skip = taps_in_empty_bricks<P2>(sps, mn, mx, bad, lo, hi, sp, nbi, nbj, nbk);
         count_block(sps, skip);
         if (!skip) { list_block(sps, bX + gridDim.x * (bY + gridDim.y * bZ)); return; }
@@ -284,7 +287,7 @@ __global__ __launch_bounds__(256, NF == 1 ? 7 : 5) void advect_kernel(AdvectArgs
         const float sum = 0.f, value = 0.f;
 #pragma unroll
         for (int f = 0; f < NF; f++)
-            a.field[f][(size_t)i + (size_t)nbi * j + (size_t)nbi * nbj * k] = 0.5f * sum + 0.5f * value;
+            a.field[f][(size_t)i + (size_t)nbi * j + (size_t)nbi * nbj * k] = Op::result(sum, value, 1.f, 0.f);
     } else {
     f3 c = nine_centre(n, i, j, kg);
     f3 mp[9];
@@ -310,7 +313,7 @@ __global__ __launch_bounds__(256, NF == 1 ? 7 : 5) void advect_kernel(AdvectArgs
     blend9_gather<P2, PT, NF, true>(src, sp, n.org, mp, sum, value);       // positions clamped to >= h
 #pragma unroll
     for (int f = 0; f < NF; f++)
-        a.field[f][(size_t)i + (size_t)nbi * j + (size_t)nbi * nbj * k] = 0.5f * sum[f] + 0.5f * value[f];
+        a.field[f][(size_t)i + (size_t)nbi * j + (size_t)nbi * nbj * k] = Op::result(sum[f], value[f], 1.f, 0.f);
     }
 }
 
@@ -371,28 +374,30 @@ __global__ __launch_bounds__(256, NF == 1 ? 7 : 6) void cumulate_kernel(Cumulate
                                                        Spacing sp, Grid g, int dx, int dy, int dz, MapTabs tabs, Sparse sps)
 {
     static_assert(!SPARSE || (SD == 0 && !ID && kStaged<P2, PT, SD>), "the skip exists for unstaggered staged launches only");
+    using Op = GatherOp<kOpCumulate>;
+    constexpr int m = Op::margin;
     const int nbi = g.ni + dx, nbj = g.nj + dy, nbk = g.nk + dz;
     int bX = blockIdx.x, bY = blockIdx.y, bZ = blockIdx.z;
     if constexpr (SPARSE == 1) { if (*sps.word != sps.epoch) return; }
     if constexpr (SPARSE == 2) { if (!listed_block(sps, bX, bY, bZ)) return; }
-    BQ_IJK_WINDOW_AT(bX, bY, bZ, 1 + dx, nbi - 2, 1 + dy, nbj - 2, 1 + dz, g.nkg + dz - 2)
+    BQ_IJK_WINDOW_AT(bX, bY, bZ, m + dx, nbi - m - 1, m + dy, nbj - m - 1, m + dz, g.nkg + dz - m - 1)
     if (block_out) return;
     const float h = sp.h;
-    Map3 m{make_field(mx, g.ni, g.nj, g.nk, g.koff), make_field(my, g.ni, g.nj, g.nk, g.koff), make_field(mz, g.ni, g.nj, g.nk, g.koff)};
+    Map3 map{make_field(mx, g.ni, g.nj, g.nk, g.koff), make_field(my, g.ni, g.nj, g.nk, g.koff), make_field(mz, g.ni, g.nj, g.nk, g.koff)};
     Nine n = nine_setup(h, dx, dy, dz);
-    f3 lo = mk3(0.f, 0.f, 0.f), hi = mk3(h * (float)g.ni, h * (float)g.nj, h * (float)g.nkg);
+    f3 lo = Op::lo(h), hi = Op::hi(h, g.ni, g.nj, g.nkg);
     f3 c = nine_centre(n, i, j, kg);
     const size_t id = (size_t)i + (size_t)nbi * j + (size_t)nbi * nbj * k;
     __shared__ float tile[kStaged<P2, PT, SD> && !ID && SPARSE != 1 ? 3 * kTile : 32];
     (void)tabs; (void)sps;
     if constexpr (SPARSE == 1) {
-        const Field mf[3] = {m.x, m.y, m.z};
+        const Field mf[3] = {map.x, map.y, map.z};
         float mn[3], mxv[3]; bool bad;
         // (dst is read ahead of the classification, next to the tile: one wait for memory instead of two)
         float dst_own[NF];
 #pragma unroll
         for (int f = 0; f < NF; f++) dst_own[f] = active ? a.dst[f][id] : 0.f;
-        tile_range(mf, i0, j0, k, tile, 1, nbi - 2, 1, nbj - 2, mn, mxv, bad);
+        tile_range(mf, i0, j0, k, tile, m, nbi - m - 1, m, nbj - m - 1, mn, mxv, bad);
         const bool skip = taps_in_empty_bricks<P2>(sps, mn, mxv, bad, lo, hi, sp, nbi, nbj, nbk);
         count_block(sps, skip);
         if (!skip) { list_block(sps, bX + gridDim.x * (bY + gridDim.y * bZ)); return; }
@@ -402,14 +407,13 @@ __global__ __launch_bounds__(256, NF == 1 ? 7 : 6) void cumulate_kernel(Cumulate
         // path), and dst += ... turns a -0 in dst into +0 as before
 #pragma unroll
         for (int f = 0; f < NF; f++) {
-            const float w = (PT ? 1.0f : 0.125f) * a.coeff[f];
+            const float w = Op::weight(PT, a.coeff[f]);
             float sum = 0.f;
 #pragma unroll
             for (int ii = 0; ii < (PT ? 1 : 8); ii++) sum += w * 0.f;
-            const float v = a.coeff[f] * 0.f;
             // (dst[0] == dst[1] is allowed and applied in order: the second field then starts from what the first stored)
             const float before = (f > 0 && a.dst[f] == a.dst[0]) ? a.dst[f][id] : dst_own[f];
-            a.dst[f][id] = before + (float)(0.5 * (double)sum + 0.5 * (double)v);
+            a.dst[f][id] = before + Op::result(sum, 0.f, a.coeff[f], 0.f);
         }
         return;
     }
@@ -431,23 +435,21 @@ __global__ __launch_bounds__(256, NF == 1 ? 7 : 6) void cumulate_kernel(Cumulate
             map9_component<0, 0, 0>(src, i, j, k, s9);
             float sum = 0.f;
 #pragma unroll
-            for (int ii = 0; ii < 8; ii++) sum += 0.125f * coeff * s9[ii];
-            float value = coeff * s9[8];
-            sum = (float)(0.5 * (double)sum + 0.5 * (double)value);
-            a.dst[f][id] += sum;
+            for (int ii = 0; ii < 8; ii++) sum += Op::weight(false, coeff) * s9[ii];
+            a.dst[f][id] += Op::result(sum, s9[8], coeff, 0.f);
         }
         return;
     }
     f3 mp[9];
     if constexpr (kStaged<P2, PT, SD>) {
-        const Field mf[3] = {m.x, m.y, m.z};
+        const Field mf[3] = {map.x, map.y, map.z};
         stage_tiles<3>(mf, i0, j0, k, tile);
         if (!active) return;
         if constexpr (P2) map9_lds<SD == 1, SD == 2, SD == 3, Q4>(tile, mp);
         else map9_lds_tab<SD == 1, SD == 2, SD == 3>(tile, tabs, i, j, kg, mp);
     } else {
         if (!active) return;
-        mapped9<P2, PT, SD>(m, sp, n, c, i, j, k, mp);
+        mapped9<P2, PT, SD>(map, sp, n, c, i, j, k, mp);
     }
     const bool ge1 = NF == 1 && wave_all_ge<PT>(mp, h);   // (two fields: both code paths together need too many registers)
 #pragma unroll
@@ -458,18 +460,17 @@ __global__ __launch_bounds__(256, NF == 1 ? 7 : 6) void cumulate_kernel(Cumulate
     for (int f = 0; f < NF; f++) {
         src[f] = make_field(a.src[f], nbi, nbj, nbk, g.koff);
         sum[f] = 0.f;
-        w[f] = (PT ? 1.0f : 0.125f) * a.coeff[f];   // (0.125f * coeff) * sample: the reference's left-to-right product
+        w[f] = Op::weight(PT, a.coeff[f]);
     }
     if (NF == 1 && ge1) blend9_gather_w<P2, PT, NF, true>(src, sp, n.org, mp, w, sum, value);
     else                blend9_gather_w<P2, PT, NF, false>(src, sp, n.org, mp, w, sum, value);
 #pragma unroll
     for (int f = 0; f < NF; f++) {
-        const float v = a.coeff[f] * value[f];
-        a.dst[f][id] += (float)(0.5 * (double)sum[f] + 0.5 * (double)v);     // dst[0] == dst[1] is allowed: applied in order
+        a.dst[f][id] += Op::result(sum[f], value[f], a.coeff[f], 0.f);     // dst[0] == dst[1] is allowed: applied in order
     }
 }
 
-// ---- z-slab ranks: cumulate_kernel's expression on ONE wall layer of its index window, source in a wall-sheet copy --
+// ---- z-slab ranks: the accumulate (GatherOp<kOpCumulate>) on ONE wall layer of its index window, source in a wall-sheet copy --
 // (include/bimocq_gpu.h: gpu_accumulate_wall_fixup.)  face_axis 0/1/2: the layer i == face_index, j == face_index or
 // GLOBAL plane kg == face_index; threads cover the other two axes.  The map look-up is mapped9 (direct loads: the same
 // lerps as the LDS-staged form), the gather is blend9_gather_w in its general form (bit-identical to the one-fma form
@@ -489,22 +490,23 @@ __global__ __launch_bounds__(256) void wall_fixup_kernel(const float *src, int s
     else                     { i = a; j = b; k = face_index - g.koff; }
     if (i >= nbi || j >= nbj || k < g.kw0 || k >= kw1 || k >= nbk) return;
     const int kg = k + g.koff;
-    if (!(1 + dx < i && i < nbi - 2 && 1 + dy < j && j < nbj - 2 && 1 + dz < kg && kg < g.nkg + dz - 2)) return;
+    using Op = GatherOp<kOpCumulate>;
+    constexpr int om = Op::margin;
+    if (!(om + dx < i && i < nbi - om - 1 && om + dy < j && j < nbj - om - 1 && om + dz < kg && kg < g.nkg + dz - om - 1)) return;
     const float h = sp.h;
     Map3 m{make_field(mx, g.ni, g.nj, g.nk, g.koff), make_field(my, g.ni, g.nj, g.nk, g.koff), make_field(mz, g.ni, g.nj, g.nk, g.koff)};
     Nine n = nine_setup(h, dx, dy, dz);
-    f3 lo = mk3(0.f, 0.f, 0.f), hi = mk3(h * (float)g.ni, h * (float)g.nj, h * (float)g.nkg);
+    const f3 lo = Op::lo(h), hi = Op::hi(h, g.ni, g.nj, g.nkg);
     f3 c = nine_centre(n, i, j, kg);
     f3 mp[9];
     mapped9<P2, false, SD>(m, sp, n, c, i, j, k, mp);
 #pragma unroll
     for (int a9 = 0; a9 < 9; a9++) mp[a9] = clamp3_ordered(mp[a9], lo, hi);
     const Field s1[1] = { make_field(src, nbi, nbj, src_nk, src_koff) };
-    float sum[1] = { 0.f }, value[1], w[1] = { 0.125f * coeff };
+    float sum[1] = { 0.f }, value[1], w[1] = { Op::weight(false, coeff) };
     blend9_gather_w<P2, false, 1, false>(s1, sp, n.org, mp, w, sum, value);
-    const float v = coeff * value[0];
     const size_t id = (size_t)i + (size_t)nbi * j + (size_t)nbi * nbj * k;
-    dst[id] = before[id] + (float)(0.5 * (double)sum[0] + 0.5 * (double)v);
+    dst[id] = before[id] + Op::result(sum[0], value[0], coeff, 0.f);
 }
 
 // ---- A6: compensate_kernel (GPU_kernel.cu:438-499): err = blend9(src(map(x))) - init(x) ----
@@ -514,11 +516,13 @@ __global__ __launch_bounds__(256, NF == 1 ? 7 : 6) void compensate_kernel(Compen
                                                          Spacing sp, Grid g, int dx, int dy, int dz, int fused, MapTabs tabs, Sparse sps)
 {
     static_assert(!SPARSE || (SD == 0 && kStaged<P2, PT, SD>), "the skip exists for unstaggered staged launches only");
+    using Op = GatherOp<kOpCompensate>;
+    constexpr int m = Op::margin;
     const int nbi = g.ni + dx, nbj = g.nj + dy, nbk = g.nk + dz;
     int bX = blockIdx.x, bY = blockIdx.y, bZ = blockIdx.z;
     if constexpr (SPARSE == 1) { if (*sps.word != sps.epoch) return; }
     if constexpr (SPARSE == 2) { if (!listed_block(sps, bX, bY, bZ)) return; }
-    BQ_IJK_WINDOW_AT(bX, bY, bZ, 1 + dx, nbi - 2, 1 + dy, nbj - 2, 1 + dz, g.nkg + dz - 2)
+    BQ_IJK_WINDOW_AT(bX, bY, bZ, m + dx, nbi - m - 1, m + dy, nbj - m - 1, m + dz, g.nkg + dz - m - 1)
     const size_t id = (size_t)i + (size_t)nbi * j + (size_t)nbi * nbj * k;
     // FL_OPT_FUSED_HOUSEKEEPING.  Bit 2: init <- the uncompensated field, on EVERY node of the buffer (stage 2 of
     // gpu_compensate_*, GPU_kernel.cu:656-658).  A thread reads init only at its own node, before it stores there,
@@ -540,14 +544,14 @@ __global__ __launch_bounds__(256, NF == 1 ? 7 : 6) void compensate_kernel(Compen
     if constexpr (SPARSE != 1) housekeeping();
     if (block_out) { if constexpr (SPARSE == 1) housekeeping(); return; }
     const float h = sp.h;
-    Map3 m{make_field(mx, g.ni, g.nj, g.nk, g.koff), make_field(my, g.ni, g.nj, g.nk, g.koff), make_field(mz, g.ni, g.nj, g.nk, g.koff)};
+    Map3 map{make_field(mx, g.ni, g.nj, g.nk, g.koff), make_field(my, g.ni, g.nj, g.nk, g.koff), make_field(mz, g.ni, g.nj, g.nk, g.koff)};
     Nine n = nine_setup(h, dx, dy, dz);
-    f3 lo = mk3(0.f, 0.f, 0.f), hi = mk3(h * (float)g.ni, h * (float)g.nj, h * (float)g.nkg);
+    f3 lo = Op::lo(h), hi = Op::hi(h, g.ni, g.nj, g.nkg);
     if constexpr (SPARSE == 1) {
         __shared__ float part[32];
-        const Field mf[3] = {m.x, m.y, m.z};
+        const Field mf[3] = {map.x, map.y, map.z};
         float mn[3], mxv[3]; bool bad;
-        tile_range(mf, i0, j0, k, part, 1, nbi - 2, 1, nbj - 2, mn, mxv, bad);
+        tile_range(mf, i0, j0, k, part, m, nbi - m - 1, m, nbj - m - 1, mn, mxv, bad);
         const bool skip = taps_in_empty_bricks<P2>(sps, mn, mxv, bad, lo, hi, sp, nbi, nbj, nbk);
         count_block(sps, skip);
         if (!skip) { list_block(sps, bX + gridDim.x * (bY + gridDim.y * bZ)); return; }
@@ -558,21 +562,21 @@ __global__ __launch_bounds__(256, NF == 1 ? 7 : 6) void compensate_kernel(Compen
         const float sum = 0.f, value = 0.f;
 #pragma unroll
         for (int f = 0; f < NF; f++)
-            a.err[f][id] = (float)(0.5 * (double)sum + 0.5 * (double)value) - init_own[f];
+            a.err[f][id] = Op::result(sum, value, 1.f, init_own[f]);
         return;
     }
     f3 c = nine_centre(n, i, j, kg);
     f3 mp[9];
     if constexpr (kStaged<P2, PT, SD>) {
         __shared__ float tile[SPARSE == 1 ? 1 : 3 * kTile];
-        const Field mf[3] = {m.x, m.y, m.z};
+        const Field mf[3] = {map.x, map.y, map.z};
         stage_tiles<3>(mf, i0, j0, k, tile);
         if (!active) return;
         if constexpr (P2) map9_lds<SD == 1, SD == 2, SD == 3, Q4>(tile, mp);
         else map9_lds_tab<SD == 1, SD == 2, SD == 3>(tile, tabs, i, j, kg, mp);
     } else {
         if (!active) return;
-        mapped9<P2, PT, SD>(m, sp, n, c, i, j, k, mp);
+        mapped9<P2, PT, SD>(map, sp, n, c, i, j, k, mp);
     }
     const bool ge1 = NF == 1 && wave_all_ge<PT>(mp, h);   // (two fields: both code paths together need too many registers)
 #pragma unroll
@@ -585,7 +589,7 @@ __global__ __launch_bounds__(256, NF == 1 ? 7 : 6) void compensate_kernel(Compen
     else                blend9_gather<P2, PT, NF, false>(src, sp, n.org, mp, sum, value);
 #pragma unroll
     for (int f = 0; f < NF; f++)
-        a.err[f][id] = (float)(0.5 * (double)sum[f] + 0.5 * (double)value[f]) - init_own[f];
+        a.err[f][id] = Op::result(sum[f], value[f], 1.f, init_own[f]);
 }
 
 // ---- A6: clampExtrema_kernel (GPU_kernel.cu:146-167) --------------------------------------
@@ -816,26 +820,6 @@ static bool dims_ok(int ni, int nj, int nk, const char *op)
     return true;
 }
 
-// SDV: staggered axis + 1 (0 = none) -> structured power-of-two map look-up when the spacing allows it
-// (FL_OPT_STRUCTURED_MAPS, default on); every other case takes the generic path (SD = -1).
-#define BQ_DISPATCH2(KERNEL, P2V, PTV, SDV, GRID, ...)                                                      \
-    do {                                                                                                    \
-        hipStream_t st_ = rt().compute;                                                                     \
-        if ((P2V) && !(PTV) && rt().opt_structured_maps) {                                                  \
-            switch (SDV) {                                                                                  \
-            case 0:  KERNEL<true, false, 0><<<GRID, kBlock, 0, st_>>>(__VA_ARGS__); break;                  \
-            case 1:  KERNEL<true, false, 1><<<GRID, kBlock, 0, st_>>>(__VA_ARGS__); break;                  \
-            case 2:  KERNEL<true, false, 2><<<GRID, kBlock, 0, st_>>>(__VA_ARGS__); break;                  \
-            default: KERNEL<true, false, 3><<<GRID, kBlock, 0, st_>>>(__VA_ARGS__); break;                  \
-            }                                                                                               \
-        }                                                                                                   \
-        else if (P2V) { if (PTV) KERNEL<true, true, -1><<<GRID, kBlock, 0, st_>>>(__VA_ARGS__);             \
-                        else     KERNEL<true, false, -1><<<GRID, kBlock, 0, st_>>>(__VA_ARGS__); }          \
-        else          { if (PTV) KERNEL<false, true, -1><<<GRID, kBlock, 0, st_>>>(__VA_ARGS__);            \
-                        else     KERNEL<false, false, -1><<<GRID, kBlock, 0, st_>>>(__VA_ARGS__); }         \
-        BQ_LAUNCH_CHECK(#KERNEL);                                                                           \
-    } while (0)
-
 #define BQ_DISPATCH1(KERNEL, P2V, GRID, ...)                                                                \
     do {                                                                                                    \
         hipStream_t st_ = rt().compute;                                                                     \
@@ -943,7 +927,7 @@ static inline int stag_axis(int dx, int dy, int dz) { return dx ? 1 : dy ? 2 : d
 // g carries the plane window (kw0); `planes` = how many planes from there.  Returns false when the option is off or the
 // case is not the structured one (the caller then launches the one-plane kernel).
 template <int KIND, int NF>
-static bool march_launch(const MarchArgs<NF> &a, const float *mx, const float *my, const float *mz,
+static bool march_launch(const GatherArgs<NF> &a, const float *mx, const float *my, const float *mz,
                          Spacing sp, Grid g, int planes, int dx, int dy, int dz, bool pt, bool q4, int fused)
 {
     // -1 (default): on in the one-fma build, whose kernels the window moves from the texture-addresser path onto the VALU
@@ -969,10 +953,10 @@ static bool march_launch(const MarchArgs<NF> &a, const float *mx, const float *m
     const int kw1 = g.kw0 + planes;
     // two fields per launch: the scalar pair (unstaggered) in all three operators, staggered components only in the
     // accumulation (gpu_accumulate_velocity2) -- nothing else is instantiated
-    if (NF == 2 && KIND != kMarchCumulate && sd != 0) return false;
+    if (NF == 2 && KIND != kOpCumulate && sd != 0) return false;
 #define BQ_MARCH(SDV, Q4V) gather_march_kernel<KIND, SDV, NF, Q4V><<<grid, kBlock, 0, st>>>(a, mx, my, mz, sp, g, dx, dy, dz, fused, kchunk, kw1)
 #define BQ_MARCH_SD(Q4V)                                                                     \
-    if constexpr (NF == 2 && KIND != kMarchCumulate) { BQ_MARCH(0, Q4V); }                    \
+    if constexpr (NF == 2 && KIND != kOpCumulate) { BQ_MARCH(0, Q4V); }                    \
     else switch (sd) { case 0: BQ_MARCH(0, Q4V); break; case 1: BQ_MARCH(1, Q4V); break; case 2: BQ_MARCH(2, Q4V); break; default: BQ_MARCH(3, Q4V); break; }
 #ifdef BQ_FAST_LERP
     (void)q4;                                       // (the one-fma lerps do not know the quarter-weight distinction)
@@ -1033,142 +1017,91 @@ static inline bool sparse_eligible(const Grid &g, int planes, int dx, int dy, in
     return staged && !dx && !dy && !dz && !rt().slab_on && g.koff == 0 && g.kw0 == 0 && planes == g.nk;
 }
 
-template <int NF>
-static void advect_multi(AdvectArgs<NF> a, const float *bx, const float *by, const float *bz,
-                         Spacing sp, Grid g, int dx, int dy, int dz, bool pt)
+// The one-plane kernels' own argument layouts from the one the launcher and the marching kernel use (see the note at the structs)
+template <int KIND, int NF>
+static auto plane_args(const GatherArgs<NF> &a)
 {
+    std::conditional_t<KIND == kOpAdvect, AdvectArgs<NF>, std::conditional_t<KIND == kOpCumulate, CumulateArgs<NF>, CompensateArgs<NF>>> k;
+    for (int f = 0; f < NF; f++) {
+        if constexpr (KIND == kOpAdvect) { k.field[f] = a.out[f]; k.init[f] = a.src[f]; }
+        else if constexpr (KIND == kOpCumulate) { k.src[f] = a.src[f]; k.dst[f] = a.out[f]; k.coeff[f] = a.coeff[f]; }
+        else { k.src[f] = a.src[f]; k.init[f] = a.aux[f]; k.err[f] = a.out[f]; }
+    }
+    return k;
+}
+
+// One launch of a nine-point operator (GatherOp<KIND>) on NF co-located fields: the marching kernel where it applies, else
+// the one-plane kernel -- with the skip's two launches where the brick flags are there.
+// identity (accumulate only): the caller vouches that mx/my/mz hold the identity map of gpu_init_maps; the shortcut is
+// taken on the structured power-of-two path (its nodes are read directly: no marching launch, no staged map, no skip),
+// otherwise the map is read like any other.
+template <int KIND, int NF>
+static void gather_launch(const GatherArgs<NF> &a, const float *mx, const float *my, const float *mz,
+                          Spacing sp, Grid g, int dx, int dy, int dz, bool pt, bool identity = false)
+{
+    using Op = GatherOp<KIND>;
     int planes;
     g = mk_grid_win(g.ni, g.nj, g.nk, dz, &planes);      // plane window (fl_set_plane_window)
     if (planes <= 0) return;
     const dim3 grid = grid_for(g.ni + dx, g.nj + dy, planes);
     hipStream_t st = rt().compute;
     const bool q4 = rt().opt_map_quarter_fp32 != 0;
-    {
-        MarchArgs<NF> ma;
-        for (int f = 0; f < NF; f++) { ma.src[f] = a.init[f]; ma.out[f] = a.field[f]; ma.aux[f] = nullptr; ma.coeff[f] = 1.f; }
-        if (march_launch<kMarchAdvect, NF>(ma, bx, by, bz, sp, g, planes, dx, dy, dz, pt, q4, rt().opt_fused_housekeeping)) return;
-    }
+    const int fused = Op::has_housekeeping ? rt().opt_fused_housekeeping : 0;
+    const int sda = stag_axis(dx, dy, dz);
+    if (!identity && march_launch<KIND, NF>(a, mx, my, mz, sp, g, planes, dx, dy, dz, pt, q4, fused)) return;
     int tab_ok = 0;
     const MapTabs tabs = (!sp.pow2 && !pt && rt().opt_structured_maps) ? map_tabs(sp, g, &tab_ok) : MapTabs{ nullptr, nullptr, 0 };
-    const bool tabled = tabs.frac && tabs_cover(tab_ok, stag_axis(dx, dy, dz));
-    const Sparse sps = brick_flags<NF>(sparse_eligible(g, planes, dx, dy, dz, !pt && rt().opt_structured_maps && (sp.pow2 || tabled)), 0,
-                                       a.init, g.ni, g.nj, g.nk, (size_t)grid.x * grid.y * grid.z);
-    dispatch_sd(sp.pow2, pt, stag_axis(dx, dy, dz), [&](auto P2, auto PT, auto SD) {
+    const bool tabled = tabs.frac && tabs_cover(tab_ok, sda);
+    // The accumulate takes part at option values 3 / 4 only: it usually samples through a BACKWARD map, whose zeroed border
+    //  its window reaches; at 256^3 half of its blocks then cannot be skipped and the two launches cost more
+    // than the one (EXPERIMENTS section 14), so the default leaves this operator alone.
+    const bool staged = !pt && rt().opt_structured_maps && (tabled || (sp.pow2 && !identity));
+    const Sparse sps = brick_flags<NF>((KIND != kOpCumulate || rt().opt_skip_empty_bricks >= 3) && sparse_eligible(g, planes, dx, dy, dz, staged),
+                                       Op::counter_slot, a.src, g.ni, g.nj, g.nk, (size_t)grid.x * grid.y * grid.z);
+    const auto ka = plane_args<KIND>(a);
+    dispatch_sd(sp.pow2, pt, sda, [&](auto P2, auto PT, auto SD) {
         constexpr bool p2 = decltype(P2)::value, ptc = decltype(PT)::value;
         constexpr int sd = decltype(SD)::value;
+        auto launch = [&](auto ID, auto Q4, auto SPARSE) {
+            constexpr bool idc = decltype(ID)::value, q4c = decltype(Q4)::value;
+            constexpr int sparse = decltype(SPARSE)::value;
+            if constexpr (KIND == kOpAdvect) advect_kernel<p2, ptc, sd, NF, q4c, sparse><<<grid, kBlock, 0, st>>>(ka, mx, my, mz, sp, g, dx, dy, dz, fused, tabs, sps);
+            else if constexpr (KIND == kOpCumulate) cumulate_kernel<p2, ptc, sd, NF, idc, q4c, sparse><<<grid, kBlock, 0, st>>>(ka, mx, my, mz, sp, g, dx, dy, dz, tabs, sps);
+            else compensate_kernel<p2, ptc, sd, NF, q4c, sparse><<<grid, kBlock, 0, st>>>(ka, mx, my, mz, sp, g, dx, dy, dz, fused, tabs, sps);
+        };
+        using T = std::true_type; using F = std::false_type;
+        using Plain = std::integral_constant<int, 0>; using Classify = std::integral_constant<int, 1>; using Listed = std::integral_constant<int, 2>;
         if constexpr (sd == 0 && kStaged<p2, ptc, sd>) {
             if (sps.flags) {            // classify (and finish the blocks that can be skipped), then the listed blocks
-                advect_kernel<p2, ptc, sd, NF, false, 1><<<grid, kBlock, 0, st>>>(a, bx, by, bz, sp, g, dx, dy, dz, rt().opt_fused_housekeeping, tabs, sps);
-                if (p2 && q4) advect_kernel<p2, ptc, sd, NF, p2, 2><<<grid, kBlock, 0, st>>>(a, bx, by, bz, sp, g, dx, dy, dz, rt().opt_fused_housekeeping, tabs, sps);
-                else advect_kernel<p2, ptc, sd, NF, false, 2><<<grid, kBlock, 0, st>>>(a, bx, by, bz, sp, g, dx, dy, dz, rt().opt_fused_housekeeping, tabs, sps);
+                launch(F{}, F{}, Classify{});
+                if (p2 && q4) launch(F{}, std::bool_constant<p2>{}, Listed{});
+                else launch(F{}, F{}, Listed{});
                 return;
             }
         }
         if constexpr (p2 && kStaged<p2, ptc, sd>) {
-            if (q4) { advect_kernel<p2, ptc, sd, NF, true><<<grid, kBlock, 0, st>>>(a, bx, by, bz, sp, g, dx, dy, dz, rt().opt_fused_housekeeping, tabs, sps); return; }
+            if constexpr (KIND == kOpCumulate) { if (identity) { launch(T{}, F{}, Plain{}); return; } }
+            if (q4) { launch(F{}, T{}, Plain{}); return; }
         }
-        advect_kernel<p2, ptc, sd, NF, false><<<grid, kBlock, 0, st>>>(a, bx, by, bz, sp, g, dx, dy, dz, rt().opt_fused_housekeeping, tabs, sps);
+        launch(F{}, F{}, Plain{});
     }, tabled);
-    BQ_LAUNCH_CHECK("advect_kernel");
-}
-// identity: the caller vouches that mx/my/mz hold the identity map of gpu_init_maps; the shortcut is
-// taken on the structured power-of-two path, otherwise the map is read like any other
-template <int NF>
-static void cumulate_multi(CumulateArgs<NF> a, const float *mx, const float *my, const float *mz,
-                           Spacing sp, Grid g, int dx, int dy, int dz, bool pt, bool identity)
-{
-    int planes;
-    g = mk_grid_win(g.ni, g.nj, g.nk, dz, &planes);
-    if (planes <= 0) return;
-    const dim3 grid = grid_for(g.ni + dx, g.nj + dy, planes);
-    hipStream_t st = rt().compute;
-    if (!identity) {
-        MarchArgs<NF> ma;
-        for (int f = 0; f < NF; f++) { ma.src[f] = a.src[f]; ma.out[f] = a.dst[f]; ma.aux[f] = nullptr; ma.coeff[f] = a.coeff[f]; }
-        if (march_launch<kMarchCumulate, NF>(ma, mx, my, mz, sp, g, planes, dx, dy, dz, pt, rt().opt_map_quarter_fp32 != 0, 0)) return;
-    }
-    int tab_ok = 0;
-    const MapTabs tabs = (!sp.pow2 && !pt && rt().opt_structured_maps) ? map_tabs(sp, g, &tab_ok) : MapTabs{ nullptr, nullptr, 0 };
-    const bool tabled = tabs.frac && tabs_cover(tab_ok, stag_axis(dx, dy, dz));
-    // (the identity accumulate reads its nodes directly on the power-of-two path: no staged map, no skip)
-    // Option values 3 / 4 only: the accumulation usually samples through a BACKWARD map, whose zeroed border its
-    // window reaches; at 256^3 half of its blocks then cannot be skipped and the two launches cost more than the one
-    // (EXPERIMENTS section 14), so the default leaves this operator alone.
-    const Sparse sps = brick_flags<NF>(rt().opt_skip_empty_bricks >= 3 &&
-                                       sparse_eligible(g, planes, dx, dy, dz, !pt && rt().opt_structured_maps && (tabled || (sp.pow2 && !identity))), 2,
-                                       a.src, g.ni, g.nj, g.nk, (size_t)grid.x * grid.y * grid.z);
-    dispatch_sd(sp.pow2, pt, stag_axis(dx, dy, dz), [&](auto P2, auto PT, auto SD) {
-        constexpr bool p2 = decltype(P2)::value, ptc = decltype(PT)::value;
-        constexpr int sd = decltype(SD)::value;
-        if constexpr (sd == 0 && kStaged<p2, ptc, sd>) {
-            if (sps.flags) {
-                cumulate_kernel<p2, ptc, sd, NF, false, false, 1><<<grid, kBlock, 0, st>>>(a, mx, my, mz, sp, g, dx, dy, dz, tabs, sps);
-                if (p2 && rt().opt_map_quarter_fp32) cumulate_kernel<p2, ptc, sd, NF, false, p2, 2><<<grid, kBlock, 0, st>>>(a, mx, my, mz, sp, g, dx, dy, dz, tabs, sps);
-                else cumulate_kernel<p2, ptc, sd, NF, false, false, 2><<<grid, kBlock, 0, st>>>(a, mx, my, mz, sp, g, dx, dy, dz, tabs, sps);
-                return;
-            }
-        }
-        if constexpr (p2 && !ptc && sd >= 0) {
-            if (identity) { cumulate_kernel<p2, ptc, sd, NF, true><<<grid, kBlock, 0, st>>>(a, mx, my, mz, sp, g, dx, dy, dz, tabs, sps); return; }
-            if (rt().opt_map_quarter_fp32) { cumulate_kernel<p2, ptc, sd, NF, false, true><<<grid, kBlock, 0, st>>>(a, mx, my, mz, sp, g, dx, dy, dz, tabs, sps); return; }
-        }
-        cumulate_kernel<p2, ptc, sd, NF, false><<<grid, kBlock, 0, st>>>(a, mx, my, mz, sp, g, dx, dy, dz, tabs, sps);
-    }, tabled);
-    BQ_LAUNCH_CHECK("cumulate_kernel");
-}
-template <int NF>
-static void compensate_multi(CompensateArgs<NF> a, const float *mx, const float *my, const float *mz,
-                             Spacing sp, Grid g, int dx, int dy, int dz, bool pt)
-{
-    int planes;
-    g = mk_grid_win(g.ni, g.nj, g.nk, dz, &planes);
-    if (planes <= 0) return;
-    const dim3 grid = grid_for(g.ni + dx, g.nj + dy, planes);
-    hipStream_t st = rt().compute;
-    const bool q4 = rt().opt_map_quarter_fp32 != 0;
-    {
-        MarchArgs<NF> ma;
-        for (int f = 0; f < NF; f++) { ma.src[f] = a.src[f]; ma.out[f] = a.err[f]; ma.aux[f] = a.init[f]; ma.coeff[f] = 1.f; }
-        if (march_launch<kMarchCompensate, NF>(ma, mx, my, mz, sp, g, planes, dx, dy, dz, pt, q4, rt().opt_fused_housekeeping)) return;
-    }
-    int tab_ok = 0;
-    const MapTabs tabs = (!sp.pow2 && !pt && rt().opt_structured_maps) ? map_tabs(sp, g, &tab_ok) : MapTabs{ nullptr, nullptr, 0 };
-    const bool tabled = tabs.frac && tabs_cover(tab_ok, stag_axis(dx, dy, dz));
-    const Sparse sps = brick_flags<NF>(sparse_eligible(g, planes, dx, dy, dz, !pt && rt().opt_structured_maps && (sp.pow2 || tabled)), 1,
-                                       a.src, g.ni, g.nj, g.nk, (size_t)grid.x * grid.y * grid.z);
-    dispatch_sd(sp.pow2, pt, stag_axis(dx, dy, dz), [&](auto P2, auto PT, auto SD) {
-        constexpr bool p2 = decltype(P2)::value, ptc = decltype(PT)::value;
-        constexpr int sd = decltype(SD)::value;
-        if constexpr (sd == 0 && kStaged<p2, ptc, sd>) {
-            if (sps.flags) {
-                compensate_kernel<p2, ptc, sd, NF, false, 1><<<grid, kBlock, 0, st>>>(a, mx, my, mz, sp, g, dx, dy, dz, rt().opt_fused_housekeeping, tabs, sps);
-                if (p2 && q4) compensate_kernel<p2, ptc, sd, NF, p2, 2><<<grid, kBlock, 0, st>>>(a, mx, my, mz, sp, g, dx, dy, dz, rt().opt_fused_housekeeping, tabs, sps);
-                else compensate_kernel<p2, ptc, sd, NF, false, 2><<<grid, kBlock, 0, st>>>(a, mx, my, mz, sp, g, dx, dy, dz, rt().opt_fused_housekeeping, tabs, sps);
-                return;
-            }
-        }
-        if constexpr (p2 && kStaged<p2, ptc, sd>) {
-            if (q4) { compensate_kernel<p2, ptc, sd, NF, true><<<grid, kBlock, 0, st>>>(a, mx, my, mz, sp, g, dx, dy, dz, rt().opt_fused_housekeeping, tabs, sps); return; }
-        }
-        compensate_kernel<p2, ptc, sd, NF, false><<<grid, kBlock, 0, st>>>(a, mx, my, mz, sp, g, dx, dy, dz, rt().opt_fused_housekeeping, tabs, sps);
-    }, tabled);
-    BQ_LAUNCH_CHECK("compensate_kernel");
+    BQ_LAUNCH_CHECK(Op::kernel_name);
 }
 
 static void advect_comp(float *f, const float *init, const float *bx, const float *by, const float *bz,
                         Spacing sp, Grid g, int dx, int dy, int dz, bool pt)
 {
-    advect_multi<1>(AdvectArgs<1>{{f}, {init}}, bx, by, bz, sp, g, dx, dy, dz, pt);
+    gather_launch<kOpAdvect, 1>(GatherArgs<1>{{init}, {f}, {nullptr}, {1.f}}, bx, by, bz, sp, g, dx, dy, dz, pt);
 }
 static void cumulate_comp(const float *src, float *dst, const float *mx, const float *my, const float *mz,
                           Spacing sp, Grid g, int dx, int dy, int dz, bool pt, float coeff, bool identity = false)
 {
-    cumulate_multi<1>(CumulateArgs<1>{{src}, {dst}, {coeff}}, mx, my, mz, sp, g, dx, dy, dz, pt, identity);
+    gather_launch<kOpCumulate, 1>(GatherArgs<1>{{src}, {dst}, {nullptr}, {coeff}}, mx, my, mz, sp, g, dx, dy, dz, pt, identity);
 }
 static void compensate_comp(const float *src, float *init, float *err, const float *mx, const float *my, const float *mz,
                             Spacing sp, Grid g, int dx, int dy, int dz, bool pt)
 {
-    compensate_multi<1>(CompensateArgs<1>{{src}, {init}, {err}}, mx, my, mz, sp, g, dx, dy, dz, pt);
+    gather_launch<kOpCompensate, 1>(GatherArgs<1>{{src}, {err}, {init}, {1.f}}, mx, my, mz, sp, g, dx, dy, dz, pt);
 }
 static void double_comp(float *f, const float *prev, const float *bx, const float *by, const float *bz,
                         const float *px, const float *py, const float *pz,
@@ -1183,7 +1116,14 @@ static void double_comp(float *f, const float *prev, const float *bx, const floa
         BQ_LAUNCH_CHECK("unit_blend_kernel");
         return;
     }
-    BQ_DISPATCH2(double_advect_kernel, sp.pow2, pt, (dx ? 1 : dy ? 2 : dz ? 3 : 0), grid_for(g.ni + dx, g.nj + dy, g.nk + dz), f, prev, bx, by, bz, px, py, pz, sp, g, dx, dy, dz, blend, prev_global);
+    const dim3 grid = grid_for(g.ni + dx, g.nj + dy, g.nk + dz);
+    dispatch_sd(sp.pow2, pt, stag_axis(dx, dy, dz), [&](auto P2, auto PT, auto SD) {
+        constexpr bool p2 = decltype(P2)::value, ptc = decltype(PT)::value;
+        constexpr int sd = decltype(SD)::value;
+        if constexpr (p2 || ptc || sd < 0)          // (not `tabled`: this operator has no instance of the tabled form)
+            double_advect_kernel<p2, ptc, sd><<<grid, kBlock, 0, rt().compute>>>(f, prev, bx, by, bz, px, py, pz, sp, g, dx, dy, dz, blend, prev_global);
+    });
+    BQ_LAUNCH_CHECK("double_advect_kernel");
 }
 // The same limiter, separable and k-marching: a thread owns one float4 column of row j, reduces min/max over the
 // 3x3 (x, y) neighbourhood of each plane once (rows j-1, j, j+1 as float4 loads, x-neighbours from the neighbouring
@@ -1493,7 +1433,7 @@ BQ_ENTRY(gpu_advect_field2, (float *field1, float *field1_init, float *field2, f
 {
     BQ_ENTER("gpu_advect_field2", field1, field1_init, field2, field2_init, backward_x, backward_y, backward_z)
     Spacing sp = make_spacing(h); Grid g = mk_grid(ni, nj, nk);
-    advect_multi<2>(AdvectArgs<2>{{field1, field2}, {field1_init, field2_init}}, backward_x, backward_y, backward_z, sp, g, 0, 0, 0, is_point);
+    gather_launch<kOpAdvect, 2>(GatherArgs<2>{{field1_init, field2_init}, {field1, field2}, {nullptr, nullptr}, {1.f, 1.f}}, backward_x, backward_y, backward_z, sp, g, 0, 0, 0, is_point);
 }
 
 BQ_ENTRY(gpu_compensate_error_field2, (float *u1, float *du1, float *u1_src, float *u2, float *du2, float *u2_src,
@@ -1502,7 +1442,7 @@ BQ_ENTRY(gpu_compensate_error_field2, (float *u1, float *du1, float *u1_src, flo
 {
     BQ_ENTER("gpu_compensate_error_field2", u1, du1, u1_src, u2, du2, u2_src, forward_x, forward_y, forward_z)
     Spacing sp = make_spacing(h); Grid g = mk_grid(ni, nj, nk);
-    compensate_multi<2>(CompensateArgs<2>{{u1, u2}, {du1, du2}, {u1_src, u2_src}}, forward_x, forward_y, forward_z, sp, g, 0, 0, 0, is_point);
+    gather_launch<kOpCompensate, 2>(GatherArgs<2>{{u1, u2}, {u1_src, u2_src}, {du1, du2}, {1.f, 1.f}}, forward_x, forward_y, forward_z, sp, g, 0, 0, 0, is_point);
 }
 
 BQ_ENTRY(gpu_accumulate_field2, (float *change1, float *dinit1, float coeff1, float *change2, float *dinit2, float coeff2,
@@ -1511,7 +1451,7 @@ BQ_ENTRY(gpu_accumulate_field2, (float *change1, float *dinit1, float coeff1, fl
 {
     BQ_ENTER("gpu_accumulate_field2", change1, dinit1, change2, dinit2, forward_x, forward_y, forward_z)
     Spacing sp = make_spacing(h); Grid g = mk_grid(ni, nj, nk);
-    cumulate_multi<2>(CumulateArgs<2>{{change1, change2}, {dinit1, dinit2}, {coeff1, coeff2}}, forward_x, forward_y, forward_z, sp, g, 0, 0, 0, is_point, false);
+    gather_launch<kOpCumulate, 2>(GatherArgs<2>{{change1, change2}, {dinit1, dinit2}, {nullptr, nullptr}, {coeff1, coeff2}}, forward_x, forward_y, forward_z, sp, g, 0, 0, 0, is_point);
 }
 
 // du_init += blend9(coeff1 * change1(psi(x))), then += blend9(coeff2 * change2(psi(x))): two
@@ -1525,9 +1465,9 @@ BQ_ENTRY(gpu_accumulate_velocity2, (float *u_change1, float *v_change1, float *w
     BQ_ENTER("gpu_accumulate_velocity2", u_change1, v_change1, w_change1, u_change2, v_change2, w_change2,
              du_init, dv_init, dw_init, forward_x, forward_y, forward_z)
     Spacing sp = make_spacing(h); Grid g = mk_grid(ni, nj, nk);
-    cumulate_multi<2>(CumulateArgs<2>{{u_change1, u_change2}, {du_init, du_init}, {coeff1, coeff2}}, forward_x, forward_y, forward_z, sp, g, 1, 0, 0, is_point, false);
-    cumulate_multi<2>(CumulateArgs<2>{{v_change1, v_change2}, {dv_init, dv_init}, {coeff1, coeff2}}, forward_x, forward_y, forward_z, sp, g, 0, 1, 0, is_point, false);
-    cumulate_multi<2>(CumulateArgs<2>{{w_change1, w_change2}, {dw_init, dw_init}, {coeff1, coeff2}}, forward_x, forward_y, forward_z, sp, g, 0, 0, 1, is_point, false);
+    gather_launch<kOpCumulate, 2>(GatherArgs<2>{{u_change1, u_change2}, {du_init, du_init}, {nullptr, nullptr}, {coeff1, coeff2}}, forward_x, forward_y, forward_z, sp, g, 1, 0, 0, is_point);
+    gather_launch<kOpCumulate, 2>(GatherArgs<2>{{v_change1, v_change2}, {dv_init, dv_init}, {nullptr, nullptr}, {coeff1, coeff2}}, forward_x, forward_y, forward_z, sp, g, 0, 1, 0, is_point);
+    gather_launch<kOpCumulate, 2>(GatherArgs<2>{{w_change1, w_change2}, {dw_init, dw_init}, {nullptr, nullptr}, {coeff1, coeff2}}, forward_x, forward_y, forward_z, sp, g, 0, 0, 1, is_point);
 }
 
 // One velocity component of gpu_accumulate_velocity (axis 0/1/2 = u/v/w) with one or two sources:
@@ -1542,8 +1482,8 @@ BQ_ENTRY(gpu_accumulate_component, (float *change1, float coeff1, float *change2
     Spacing sp = make_spacing(h); Grid g = mk_grid(ni, nj, nk);
     const int dx = axis == 0, dy = axis == 1, dz = axis == 2;
     if (change2)
-        cumulate_multi<2>(CumulateArgs<2>{{change1, change2}, {d_init, d_init}, {coeff1, coeff2}}, forward_x, forward_y, forward_z,
-                          sp, g, dx, dy, dz, is_point, false);
+        gather_launch<kOpCumulate, 2>(GatherArgs<2>{{change1, change2}, {d_init, d_init}, {nullptr, nullptr}, {coeff1, coeff2}}, forward_x, forward_y, forward_z,
+                                       sp, g, dx, dy, dz, is_point);
     else
         cumulate_comp(change1, d_init, forward_x, forward_y, forward_z, sp, g, dx, dy, dz, is_point, coeff1);
 }

@@ -1,5 +1,7 @@
 // bq_gather_march.hip.h -- the nine-point gather kernels (advect / cumulate / compensate, GPU_kernel.cu:312-499) as
-// z-MARCHING blocks that read the sampled field out of a rolling LDS window (round 4, FL_OPT_FIELD_WINDOW).
+// z-MARCHING blocks that read the sampled field out of a rolling LDS window (round 4, FL_OPT_FIELD_WINDOW).  What an operator
+// is -- index window, clamp box, weights, fused housekeeping, the value a node gets -- is GatherOp<KIND> of bq_gather_op.hip.h;
+// this file is how a marching block evaluates it.
 //
 // Why.  The one-plane kernels of bq_advect.hip fetch the eight corners of each of a node's nine taps straight from
 // memory: 36 two-dword gathers per sampled field and node-wave.  Round 3's counters put the texture-addresser path at
@@ -25,6 +27,7 @@
 // bq_device.hip.h in both builds (exact / BQ_FAST_LERP).
 #pragma once
 #include "bq_device.hip.h"
+#include "bq_gather_op.hip.h"
 
 namespace bq {
 inline namespace BQ_VARIANT {
@@ -39,11 +42,6 @@ constexpr int kWField = kWSlots * kWPS;         // floats per field window
 constexpr int kMR = 4;                          // map ring slots
 constexpr int kMPS = 3 * kTileX * kTileY;       // floats per map plane slot (three components)
 static_assert(2 * kWD + 4 <= kWR, "ring too short for the window");
-
-enum { kMarchAdvect = 0, kMarchCumulate = 1, kMarchCompensate = 2 };
-
-// src: sampled field; out: advect -> field, cumulate -> dst, compensate -> err; aux: compensate -> init
-template <int NF> struct MarchArgs { const float *src[NF]; float *out[NF]; float *aux[NF]; float coeff[NF]; };
 
 struct CellW { int i, j, kl; float fx, fy, fz; };
 
@@ -283,9 +281,10 @@ struct StageSlots {
 };
 
 template <int KIND, int SD, int NF, bool Q4>
-__global__ __launch_bounds__(256, NF == 1 ? 3 : 2) void gather_march_kernel(MarchArgs<NF> a, const float *mx, const float *my, const float *mz,
+__global__ __launch_bounds__(256, NF == 1 ? 3 : 2) void gather_march_kernel(GatherArgs<NF> a, const float *mx, const float *my, const float *mz,
                                                               Spacing sp, Grid g, int dx, int dy, int dz, int fused, int kchunk, int kw1)
 {
+    using Op = GatherOp<KIND>;
     __shared__ float fwin[NF * kWField];
     __shared__ float mring[kMR * kMPS];
     const int nbi = g.ni + dx, nbj = g.nj + dy, nbk = g.nk + dz;
@@ -293,8 +292,7 @@ __global__ __launch_bounds__(256, NF == 1 ? 3 : 2) void gather_march_kernel(Marc
     const int tid = threadIdx.y * 64 + threadIdx.x;
     const int i = i0 + threadIdx.x, j = j0 + threadIdx.y;
     const int kb = g.kw0 + blockIdx.z * kchunk, ke = min(kb + kchunk, kw1);
-    // index window of the operator (GPU_kernel.cu:353, :414, :476)
-    const int m = KIND == kMarchAdvect ? 2 : 1;
+    constexpr int m = Op::margin;                           // index window of the operator
     const int ilo = m + dx, ihi = nbi - m - 1, jlo = m + dy, jhi = nbj - m - 1, klo = m + dz, khi = g.nkg + dz - m - 1;
     const bool ij_in = ilo < i && i < ihi && jlo < j && j < jhi;
     const bool block_ij_out = i0 + 63 <= ilo || i0 >= ihi || j0 + 3 <= jlo || j0 >= jhi;
@@ -305,20 +303,7 @@ __global__ __launch_bounds__(256, NF == 1 ? 3 : 2) void gather_march_kernel(Marc
     // ---- housekeeping the one-plane kernels do on the side (FL_OPT_FUSED_HOUSEKEEPING), per node and plane --------------------
     auto housekeeping = [&](int k, bool active, float (&init_own)[NF]) {
         if (!node) return;
-        const size_t id = id0 + plane * k;
-        if (KIND == kMarchAdvect) {
-            if ((fused & 1) && !active) {
-#pragma unroll
-                for (int f = 0; f < NF; f++) a.out[f][id] = 0.f;
-            }
-        } else if (KIND == kMarchCompensate) {
-#pragma unroll
-            for (int f = 0; f < NF; f++) {
-                init_own[f] = a.aux[f][id];
-                if (fused & 2) a.aux[f][id] = a.src[f][id];
-                if ((fused & 1) && !active) a.out[f][id] = 0.f;
-            }
-        }
+        Op::housekeeping(a, id0, plane * k, fused, active, init_own);
     };
     if (block_ij_out) {                                     // no node of this block is ever inside the window: no staging
         for (int k = kb; k < ke; k++) { float io[NF]; housekeeping(k, false, io); }
@@ -397,16 +382,14 @@ __global__ __launch_bounds__(256, NF == 1 ? 3 : 2) void gather_march_kernel(Marc
 
     const float h = sp.h;
     const Nine n = nine_setup(h, dx, dy, dz);
-    const f3 lo = KIND == kMarchAdvect ? mk3(h, h, h) : mk3(0.f, 0.f, 0.f);
-    const f3 hi = KIND == kMarchAdvect ? mk3(h * (float)g.ni - h, h * (float)g.nj - h, h * (float)g.nkg - h)
-                                       : mk3(h * (float)g.ni, h * (float)g.nj, h * (float)g.nkg);
+    const f3 lo = Op::lo(h), hi = Op::hi(h, g.ni, g.nj, g.nkg);
     // plane stages of the map look-up carried from node to node (map_plane_stage): P[c][z] belongs to map plane k - 1 + z
     constexpr int SXc = SD == 1, SYc = SD == 2, SZc = SD == 3;
     constexpr int NZ = SZc ? 2 : 3;
     // ZR: carry them (45 more live registers).  Measured at 256^3 (profiles/r04_e_*): the two-field kernels, which LDS holds at
     // two waves per SIMD anyway, run 4-10 % faster with it; the single-field kernels need their third wave more than the 12 %
     // fewer instructions (332 -> 395 us at two waves) and re-evaluate all NZ planes per node instead, as map9_nodes does.
-    constexpr bool ZR = NF == 2 && !(KIND == kMarchCompensate && SD == 0);
+    constexpr bool ZR = NF == 2 && !(KIND == kOpCompensate && SD == 0);
     float P[3][NZ][5];
     const float *mt = mring + threadIdx.y * kTileX + threadIdx.x;
     if (ZR && ij_in) {
@@ -457,47 +440,33 @@ __global__ __launch_bounds__(256, NF == 1 ? 3 : 2) void gather_march_kernel(Marc
 #pragma unroll
                 for (int t = 0; t < 9; t++) mp[t] = mk3(x9[t], y9[t], z9[t]);
             }
-            // exact build, single field: the one-fma lerps where every position of the wave is >= h (bq_advect.hip: wave_all_ge);
-            // advect clamps to >= h.  The fast build's lerps do not depend on it.
+            // exact build, single field: the one-fma lerps where every position of the wave is >= h, unless the operator
+            // clamps to >= h anyway.  The fast build's lerps do not depend on it.
 #ifdef BQ_FAST_LERP
             constexpr bool kTestGe = false;
 #else
-            constexpr bool kTestGe = KIND != kMarchAdvect && NF == 1;
+            constexpr bool kTestGe = !Op::always_ge1 && NF == 1;
 #endif
-            bool ge1 = KIND == kMarchAdvect;
-            if (kTestGe) {
-                float mn = fminf(mp[8].x, fminf(mp[8].y, mp[8].z));
-#pragma unroll
-                for (int t = 0; t < 8; t++) mn = fminf(mn, fminf(mp[t].x, fminf(mp[t].y, mp[t].z)));
-                ge1 = __all(mn >= h);
-            }
+            bool ge1 = Op::always_ge1;
+            if (kTestGe) ge1 = wave_all_ge<false>(mp, h);
 #pragma unroll
             for (int t = 0; t < 9; t++) mp[t] = clamp3_ordered(mp[t], lo, hi);
             float sum[NF], value[NF], w[NF];
 #pragma unroll
-            for (int f = 0; f < NF; f++) { sum[f] = 0.f; w[f] = KIND == kMarchCumulate ? 0.125f * a.coeff[f] : 0.125f; }
+            for (int f = 0; f < NF; f++) { sum[f] = 0.f; w[f] = Op::weight(false, a.coeff[f]); }
             // 0: tap by tap; 3 / 5: batches (see blend9_window).  The two-field advection (unstaggered, forward-free map
             // border: every tap in the window) is the one launch the batched form serves better: 487 against 531 / 619 us
-            constexpr int TB = (KIND == kMarchAdvect && NF == 2) ? 3 : 0;
+            constexpr int TB = (KIND == kOpAdvect && NF == 2) ? 3 : 0;
             if constexpr (TB == 0) {
-                if (KIND == kMarchAdvect) blend9_window_pertap<NF, true>(src, wv, sp, n.org, mp, w, sum, value);
-                else if (kTestGe && ge1)  blend9_window_pertap<NF, true>(src, wv, sp, n.org, mp, w, sum, value);
-                else                      blend9_window_pertap<NF, false>(src, wv, sp, n.org, mp, w, sum, value);
+                if (ge1) blend9_window_pertap<NF, true>(src, wv, sp, n.org, mp, w, sum, value);
+                else     blend9_window_pertap<NF, false>(src, wv, sp, n.org, mp, w, sum, value);
             } else {
-                constexpr int TBB = TB > 0 ? TB : 3;
-                if (KIND == kMarchAdvect) blend9_window<NF, true, TBB>(src, wv, sp, n.org, mp, w, sum, value);
-                else if (kTestGe && ge1)  blend9_window<NF, true, TBB>(src, wv, sp, n.org, mp, w, sum, value);
-                else                      blend9_window<NF, false, TBB>(src, wv, sp, n.org, mp, w, sum, value);
+                if (ge1) blend9_window<NF, true, TB>(src, wv, sp, n.org, mp, w, sum, value);
+                else     blend9_window<NF, false, TB>(src, wv, sp, n.org, mp, w, sum, value);
             }
             const size_t id = id0 + plane * k;
 #pragma unroll
-            for (int f = 0; f < NF; f++) {
-                if (KIND == kMarchAdvect) a.out[f][id] = 0.5f * sum[f] + 0.5f * value[f];
-                else if (KIND == kMarchCumulate) {
-                    const float v = a.coeff[f] * value[f];
-                    a.out[f][id] += (float)(0.5 * (double)sum[f] + 0.5 * (double)v);
-                } else a.out[f][id] = (float)(0.5 * (double)sum[f] + 0.5 * (double)value[f]) - init_own[f];
-            }
+            for (int f = 0; f < NF; f++) Op::store(a, f, id, Op::result(sum[f], value[f], a.coeff[f], init_own[f]));
         }
         if (ZR && ij_in) {                                  // the planes move down by one for the next node
 #pragma unroll

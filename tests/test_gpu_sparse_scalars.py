@@ -49,8 +49,15 @@ def stats(hip, reset=1):
 COEFF = (-0.5, 2.0)
 
 
-def gpu_ops(hip, ni, nj, nk, h, a, b, d1, d2, dback, dfwd):
-    """every operator of the issue, two fields and one; returns the output arrays by name"""
+def kind_stats(hip, kind):
+    out = (C.c_longlong * 2)()
+    hip.fl_sparse_stats_kind(kind, out, 0)
+    return int(out[0]), int(out[1])
+
+
+def gpu_ops(hip, ni, nj, nk, h, a, b, d1, d2, dback, dfwd, counts=None):
+    """every operator of the issue, two fields and one; returns the output arrays by name.  counts (a dict): gets the blocks
+    (tested, skipped) that the accumulation of two fields into ONE buffer added to the accumulation's counters"""
     n = ni * nj * nk
     out = {}
     da, db = dev(a, b)
@@ -72,6 +79,12 @@ def gpu_ops(hip, ni, nj, nk, h, a, b, d1, d2, dback, dfwd):
     (t3,) = dev(d1)
     hip.gpu_accumulate_field(db.ptr, t3.ptr, *ptrs(dback), h, ni, nj, nk, False, COEFF[1])
     out["accumulate1"] = (t3.numpy(),)
+    (t,) = dev(d1)                                  # both fields into one buffer: the second starts from what the first stored
+    before = kind_stats(hip, 2)
+    hip.gpu_accumulate_field2(da.ptr, t.ptr, COEFF[0], db.ptr, t.ptr, COEFF[1], *ptrs(dback), h, ni, nj, nk, False)
+    if counts is not None:
+        counts["accumulate2_shared"] = tuple(x - y for x, y in zip(kind_stats(hip, 2), before))
+    out["accumulate2_shared"] = (t.numpy(),)
     return out
 
 
@@ -92,6 +105,10 @@ def oracle_ops(ni, nj, nk, h, a, b, d1, d2, back, fwd):
     o.orc_accumulate_field(fp(b), fp(t2), *map(fp, back), h, ni, nj, nk, 0, COEFF[1])
     o.orc_accumulate_field(fp(b), fp(t3), *map(fp, back), h, ni, nj, nk, 0, COEFF[1])
     out["accumulate2"], out["accumulate1"] = (t1, t2), (t3,)
+    t4 = d1.copy()
+    o.orc_accumulate_field(fp(a), fp(t4), *map(fp, back), h, ni, nj, nk, 0, COEFF[0])
+    o.orc_accumulate_field(fp(b), fp(t4), *map(fp, back), h, ni, nj, nk, 0, COEFF[1])
+    out["accumulate2_shared"] = (t4,)
     return out
 
 
@@ -117,15 +134,19 @@ def test_skip_changes_no_bit_and_matches_the_oracle(hip, ni, nj, nk, kind):
         default = gpu_ops(hip, ni, nj, nk, h, a, b, d1, d2, dback, dfwd)
         stats(hip)
         set_skip(hip, 4)
-        skip = gpu_ops(hip, ni, nj, nk, h, a, b, d1, d2, dback, dfwd)
+        counts = {}
+        skip = gpu_ops(hip, ni, nj, nk, h, a, b, d1, d2, dback, dfwd, counts)
         tested, skipped = stats(hip)
         set_skip(hip, 1)
+        if case == "zero" and kind == "smooth":     # every brick empty, every map tile finite: the shared-buffer stores are the skip's
+            assert counts["accumulate2_shared"][1] > 0, counts
         for name in plain:
             for x, y, z in zip(plain[name], default[name], skip[name]):
                 assert np.array_equal(x.view(np.uint32), y.view(np.uint32)), (case, name, 1)
                 assert np.array_equal(x.view(np.uint32), z.view(np.uint32)), (case, name, 4)
         ref = oracle_ops(ni, nj, nk, h, a, b, d1, d2, back, fwd)
-        for name, win in (("advect2", 2), ("advect1", 2), ("error2", 1), ("error1", 1), ("accumulate2", 1), ("accumulate1", 1)):
+        for name, win in (("advect2", 2), ("advect1", 2), ("error2", 1), ("error1", 1), ("accumulate2", 1), ("accumulate1", 1),
+                          ("accumulate2_shared", 1)):
             inside = window_mask(ni, nj, nk, win)
             for r, g in zip(ref[name], skip[name]):
                 if name.startswith("accumulate"):
