@@ -8,7 +8,7 @@
 // rings blown along x by the reference's emitter velocity formula (main.cpp:52-73, emiter = +1 for both: the rear
 // ring catches up and threads the front one -- leapfrogging), no buoyancy, density dumped every frame.
 //
-//   make example && build/bimocq3d [N=128] [frames=20] [outdir=out] [scheme=0|2|3] [projection=0|1] [async=1] [scene=0|1] [walls=0] [diag_every=0] [preview_every=0] [tracers_per_cell=0] [paddle_spin=0]
+//   make example && build/bimocq3d [N=128] [frames=20] [outdir=out] [scheme=0|2|3] [projection=0|1] [async=1] [scene=0|1] [walls=0] [diag_every=0] [preview_every=0] [tracers_per_cell=0] [paddle_spin=0] [confinement=0]
 // diag_every = N > 0: the flow diagnostics of every N-th frame (bq_solver_diagnostics' row: kinetic energy, enstrophy, ...) are
 // sampled on the device while the run goes on, printed one line per sampled frame at the end, and the vorticity magnitude of
 // those frames is dumped next to the density (vorticity_render_%04u.bqd)
@@ -18,6 +18,7 @@
 // device and dumped with every frame (tracers_%04u.bqp: positions and the density sampled at them)
 // paddle_spin = S != 0: a box paddle of half extents (0.3 L, 2 h, 0.15 L) at the centre of the domain (scenes.paddle of the Python
 // package) turns about the z axis at S rad per time unit in the rising smoke; updateBoundary every frame
+// confinement = E > 0: vorticity confinement with the dimensionless coefficient E
 // walls: the closed sides (BQ_WALL_* bits of include/bimocq_gpu.h; 55 = the reference CPU solver's container, open at the top)
 #include <chrono>
 #include <cmath>
@@ -44,8 +45,9 @@ int main(int argc, char **argv)
     const int preview_every = argc > 10 ? std::atoi(argv[10]) : 0;   // a shadowed preview image every N-th frame (0: none)
     const int tracers_per_cell = argc > 11 ? std::atoi(argv[11]) : 0; // passive tracers per cell of the emitters' bounding cells (0: none)
     const float paddle_spin = argc > 12 ? (float)std::atof(argv[12]) : 0.f; // angular velocity of the paddle about z (0: no paddle)
-    if (n < 8 || total_frame < 1 || diag_every < 0 || preview_every < 0 || tracers_per_cell < 0 || !std::isfinite(paddle_spin) || (scene == 1 && n % 2) || (scheme != 0 && scheme != 2 && scheme != 3)) {
-        std::fprintf(stderr, "usage: %s [N>=8] [frames] [outdir] [scheme: 0 BiMocq, 2 MacCormack, 3 reflection] [projection] [async] [scene] [walls] [diag_every] [preview_every] [tracers_per_cell] [paddle_spin]\n", argv[0]); return 2;
+    const float confinement = argc > 13 ? (float)std::atof(argv[13]) : 0.f; // vorticity confinement coefficient (0: none)
+    if (n < 8 || total_frame < 1 || !(confinement >= 0.f) || !std::isfinite(confinement) || diag_every < 0 || preview_every < 0 || tracers_per_cell < 0 || !std::isfinite(paddle_spin) || (scene == 1 && n % 2) || (scheme != 0 && scheme != 2 && scheme != 3)) {
+        std::fprintf(stderr, "usage: %s [N>=8] [frames] [outdir] [scheme: 0 BiMocq, 2 MacCormack, 3 reflection] [projection] [async] [scene] [walls] [diag_every] [preview_every] [tracers_per_cell] [paddle_spin] [confinement]\n", argv[0]); return 2;
     }
 
     const int ni = n, nj = n, nk = scene == 1 ? n / 2 : n;
@@ -111,6 +113,7 @@ int main(int argc, char **argv)
         const bq_pose pose{ 1.f, 0.f, 0.f, 0.f, 0.f, 0.f, paddle_spin };
         if (!mysolver.setBoundary(&box, nullptr, 1, &pose)) { std::fprintf(stderr, "%s\n", fl_last_error_string()); return 1; }
     }
+    if (!mysolver.setVorticityConfinement(confinement)) { std::fprintf(stderr, "%s\n", fl_last_error_string()); return 1; }
     if (diag_every > 0 && !mysolver.setDiagnosticsEvery(diag_every)) { std::fprintf(stderr, "%s\n", fl_last_error_string()); return 1; }
     if (fl_last_error() != FL_OK) { std::fprintf(stderr, "%s\n", fl_last_error_string()); return 1; }
     if (tracers_per_cell > 0) std::printf("[ Tracers: %ld ]\n", mysolver.tracer_count);

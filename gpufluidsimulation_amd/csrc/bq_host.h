@@ -48,6 +48,7 @@ struct Runtime {
     int         num_cus = 256;              // CUs the compute stream may use (device CUs - opt_reserve_cus)
     int         opt_diag_kchunk = 0;        // FL_OPT_DIAG_KCHUNK: planes per block of gpu_flow_stats' march (0 = its rule, -1 = one thread per cell)
     int         opt_render_kchunk = 0;      // FL_OPT_RENDER_KCHUNK: cells per chunk of gpu_render_density's marches along y and z (0 = its rule, -1 = one march per ray)
+    int         opt_confine_kchunk = 0;     // FL_OPT_CONFINE_KCHUNK: planes per block of gpu_vorticity_confinement's march (0 = its rule, -1 = one thread per output node)
     int         opt_jacobi_rows = 0;        // FL_OPT_JACOBI_ROWS: one code per kernel choice (option table in include/bimocq_gpu.h)
     // z-slab context (fl_set_slab): local plane k is global plane k + slab_koff of slab_nkg planes;
     // this rank owns global planes [slab_own0, slab_own1) (reductions count only those)

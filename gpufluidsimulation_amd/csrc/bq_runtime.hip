@@ -476,6 +476,7 @@ void fl_set_option(int option, int value)
     case FL_OPT_SKIP_EMPTY_BRICKS: g_rt.opt_skip_empty_bricks = (value >= 1 && value <= 4) ? value : 0; break;
     case FL_OPT_DIAG_KCHUNK:     g_rt.opt_diag_kchunk = value < 0 ? -1 : value; break;
     case FL_OPT_RENDER_KCHUNK:   g_rt.opt_render_kchunk = value < 0 ? -1 : value; break;
+    case FL_OPT_CONFINE_KCHUNK:  g_rt.opt_confine_kchunk = value < 0 ? -1 : value; break;
     case FL_OPT_RESERVE_CUS: {
         const int k = value < 0 ? 0 : value;
         if (k == g_rt.opt_reserve_cus) break;
@@ -519,6 +520,7 @@ int fl_get_option(int option)
     case FL_OPT_SKIP_EMPTY_BRICKS: return g_rt.opt_skip_empty_bricks;
     case FL_OPT_DIAG_KCHUNK:     return g_rt.opt_diag_kchunk;
     case FL_OPT_RENDER_KCHUNK:   return g_rt.opt_render_kchunk;
+    case FL_OPT_CONFINE_KCHUNK:  return g_rt.opt_confine_kchunk;
     case FL_OPT_RESERVE_CUS:     return g_rt.opt_reserve_cus;
     default: return -1;
     }

@@ -48,6 +48,7 @@
 #pragma weak gpu_pcg_gradient_walls
 #pragma weak gpu_flow_stats
 #pragma weak gpu_render_density
+#pragma weak gpu_vorticity_confinement
 
 namespace bqhost {
 
@@ -286,6 +287,7 @@ void BimocqGPUSolver::applySources(bool emit, int framenum, float dt_emit, float
     const int ni = g.ni, nj = g.nj, nk = g.nk;
     if (emit) emitSmoke(framenum, dt_emit);
     addBuoyancy(dt_forces);
+    confine(dt_forces);
     if (Viscosity) {
         if (gs.slab.on && gs.slab.nranks > 1) {
             diffuseFieldSlab(VelocityU, VelocityUTemp, TempSrcU, ni + 1, nj, nk, 20, Viscosity, dt_forces);
@@ -530,6 +532,39 @@ void BimocqGPUSolver::addBuoyancy(float dt)
 {
     GpuSolver->add_buoyancy(VelocityV, Density, Temperature, _alpha, _beta, dt);
     GpuSolver->produced(VelocityV, gpuMapper::minValid({ &VelocityV, &Density, &Temperature }));
+}
+
+bool BimocqGPUSolver::confinementOperator() { return gpu_vorticity_confinement != nullptr; }
+
+// A refused coefficient leaves the previous one in place; 0 is accepted everywhere (the step is then exactly the one without
+// this feature).
+bool BimocqGPUSolver::setVorticityConfinement(float eps)
+{
+    if (!(eps >= 0.f) || !std::isfinite(eps)) {
+        fl_report_error(FL_ERR_BAD_ARGUMENT, "setVorticityConfinement: the coefficient must be finite and not negative");
+        return false;
+    }
+    if (eps != 0.f && GpuSolver->slab.on) {
+        fl_report_error(FL_ERR_UNSUPPORTED, "setVorticityConfinement: vorticity confinement is not supported on z-slab ranks");
+        return false;
+    }
+    if (eps != 0.f && !confinementOperator()) {
+        fl_report_error(FL_ERR_UNSUPPORTED, "setVorticityConfinement: the operator library has no gpu_vorticity_confinement");
+        return false;
+    }
+    confinement = eps;
+    return true;
+}
+
+// Vorticity confinement over dt, right after the buoyancy: the operator is out of place, its outputs
+// are TempSrcU/V/W, which then become the velocity by a swap, as in the fused MacCormack.  Nothing holds a value in
+// TempSrc* here: advanceBimocq used them last in blendBoundary(true), which precedes the forces; macCormack() leaves them
+// as scratch (both bodies), and the viscous diffusion that follows only uses them as work arrays.
+void BimocqGPUSolver::confine(float dt)
+{
+    if (confinement == 0.f) return;
+    gpu_vorticity_confinement(TempSrcU, TempSrcV, TempSrcW, VelocityU, VelocityV, VelocityW, CellSize, g.ni, g.nj, g.nk, confinement, dt);
+    VelocityU.swap(TempSrcU); VelocityV.swap(TempSrcV); VelocityW.swap(TempSrcW);
 }
 
 // :399-404
@@ -1322,7 +1357,7 @@ void BimocqGPUSolver::advanceBimocq(int framenum, float dt)
     const bool prev_dead = !keep_full_state && reinit_policy == 0 && VelocityAdvector.BlendCoeff == 1.f;
     // Buoyancy acts on v only: unless a source imposes its velocity ring this frame or viscosity smooths all three
     // components, u and w stay what they are until the projection.
-    bool forces_touch_uw = Viscosity != 0.f;
+    bool forces_touch_uw = Viscosity != 0.f || confinement != 0.f;     // (the confinement force has all three components)
     for (const Emitter &e : sim_emitter) forces_touch_uw = forces_touch_uw || framenum < e.emitFrame;
     forces_touch_uw = forces_touch_uw || velocitySourceActive(framenum);
     // :157-159 snapshots for the force delta (:175-177).  The u and w snapshots are only ever read by that delta
@@ -1337,6 +1372,7 @@ void BimocqGPUSolver::advanceBimocq(int framenum, float dt)
 
     emitSmoke(framenum, dt);                             // :164
     addBuoyancy(dt);                                     // :165
+    confine(dt);                                         // (no counterpart in the reference: DESIGN.md section 25)
 
     if (Viscosity) {                                     // :167-172, with the reference's buffer aliasing
         if (gs.slab.on && gs.slab.nranks > 1) {

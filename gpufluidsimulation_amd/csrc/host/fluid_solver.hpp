@@ -57,6 +57,13 @@ public:
     float getCFL();
     void emitSmoke(int framenum, float dt);
     void addBuoyancy(float dt);
+    // Vorticity confinement (an extension, the reference has no such force): u += dt eps h (N x omega) by one
+    // gpu_vorticity_confinement call right after the buoyancy, over the same dt, in every scheme.  One GPU.  With the
+    // coefficient at 0 (default) a step issues exactly the launches it issues without this feature and nothing is allocated.
+    float confinement = 0.f;
+    static bool confinementOperator();              // the operator library has gpu_vorticity_confinement
+    bool setVorticityConfinement(float eps);
+    void confine(float dt);
     void diffuseField(float *field, float *t0, float *t1, int ni, int nj, int nk, int iter, float nu, float dt);
     void diffuseFieldSlab(DeviceField &field, DeviceField &t0, DeviceField &t1, int bi, int bj, int bk, int iter, float nu, float dt);
     bool projection(bool with_delta = false);

@@ -313,6 +313,18 @@ int bq_solver_get_walls(bq_solver *s)
     return s ? s->solver->walls : 0;
 }
 
+int bq_solver_set_vorticity_confinement(bq_solver *s, float eps)
+{
+    BQ_ENTER(s);
+    if (!s) return -1;
+    return s->solver->setVorticityConfinement(eps) ? FL_OK : fl_last_error();
+}
+
+float bq_solver_get_vorticity_confinement(const bq_solver *s)
+{
+    return s ? s->solver->confinement : 0.f;
+}
+
 long bq_solver_download_solid(bq_solver *s, unsigned char *host, long capacity)
 {
     BQ_ENTER(s);

@@ -248,6 +248,8 @@ HOST_SIGS = {
     "bq_solver_download_solid": (C.c_long, [C.c_void_p, C.c_void_p, C.c_long]),
     "bq_solver_set_walls": (C.c_int, [C.c_void_p, C.c_int]),
     "bq_solver_get_walls": (C.c_int, [C.c_void_p]),
+    "bq_solver_set_vorticity_confinement": (C.c_int, [C.c_void_p, C.c_float]),
+    "bq_solver_get_vorticity_confinement": (C.c_float, [C.c_void_p]),
     "bq_solver_set_sources": (C.c_int, [C.c_void_p, C.POINTER(SourceDesc), C.POINTER(LevelSetDesc), C.c_int]),
     "bq_solver_source_position": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
     "bq_solver_set_pcg_tolerance": (C.c_int, [C.c_void_p, C.c_double]),
@@ -468,6 +470,19 @@ class BimocqGPUSolver:
     def walls(self):
         """the closed sides in force (WALL_* bits)"""
         return self.lib.bq_solver_get_walls(self.s)
+
+    def setVorticityConfinement(self, eps):
+        """vorticity confinement with the dimensionless coefficient `eps` (0, the default, turns it off): every step adds
+        dt eps h (N x omega) to the velocity right after the buoyancy.  One GPU, every scheme and
+        projection kind.  The force does not see obstacles or walls.  A refused value leaves the previous one."""
+        rc = self.lib.bq_solver_set_vorticity_confinement(self.s, float(eps))
+        self._check()
+        if rc != 0:
+            raise _lib.BimocqError("bq_solver_set_vorticity_confinement failed")
+
+    def vorticityConfinement(self):
+        """the confinement coefficient in force"""
+        return float(self.lib.bq_solver_get_vorticity_confinement(self.s))
 
     def setSources(self, sources):
         """replaces the list of shaped sources (Source objects; [] removes them and releases their grids).  Level-set

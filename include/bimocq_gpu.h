@@ -425,6 +425,10 @@ enum {
                                  * chunks of about 32 cells in whole rounds of blocks, one chunk where that covers the ray);
                                  * k > 0 = chunks of k cells along the march (tests and tuning); negative = one sequential march
                                  * per ray.  Marches along x are a wave-level scan and take no chunks.  Same bits whatever the value. */
+    FL_OPT_CONFINE_KCHUNK = 24,/* gpu_vorticity_confinement: 0 (default) = the marching kernel with its own chunk rule (the chunk
+                                 * count that costs the fewest rounds of blocks, about 32 planes per block, bq_launch_geom.h);
+                                 * k > 0 = chunks of k planes (tests and tuning); negative = the one-thread-per-output-node
+                                 * kernel (the A/B partner).  Same bits in every output whatever the value.           */
     FL_OPT_MAP_QUARTER_FP32 = 13 /* 0 (default): every lerp of the structured map look-up follows the double-rounding
                                  * contract.  1: the caller vouches that every value of the map arrays it passes to the
                                  * 9-point operators is 0 or lies in [h/256, 1024 h] (gpu_maps_quarter_safe checks a map
@@ -969,6 +973,36 @@ enum { BQ_STAT_E2 = 0, BQ_STAT_M2, BQ_STAT_D2, BQ_STAT_DIV_MAX, BQ_STAT_RHO, BQ_
        BQ_STAT_T, BQ_STAT_VORT_MAX, BQ_STAT_COUNT };
 int gpu_flow_stats(const float *u, const float *v, const float *w, const float *rho, const float *T, float *vort_mag,
                    float h, int ni, int nj, int nk, double *d_out);
+
+/* ---- vorticity confinement ----------------------------------------------------------------------
+ * uo, vo, wo = u, v, w + dt f on the faces, f = eps h (N x omega) on the cells: the confinement force of Fedkiw, Stam and Jensen
+ * (Visual Simulation of Smoke, 2001) as ONE fused operator.  An extension: the reference has no such force.  Arrays as
+ * everywhere: u (ni+1, nj, nk), v (ni, nj+1, nk), w (ni, nj, nk+1), x fastest.  Out of place: EVERY element of uo, vo, wo is
+ * written.  Every line is one IEEE fp32 operation unless it says double (no contraction):
+ *   cells 1 <= i <= ni-2, 1 <= j <= nj-2, 1 <= k <= nk-2:  uc, vc, wc and (wx, wy, wz) exactly as in gpu_flow_stats above;
+ *     border cells: wx = wy = wz = 0.  m = (float)sqrt(m2) with that operator's double m2: the bits of its vort_mag.
+ *   confined cells 2 <= i <= ni-3, 2 <= j <= nj-3, 2 <= k <= nk-3 (all six neighbours carry a computed omega); every other
+ *   cell has f = 0:
+ *     gx = (m(i+1) - m(i-1)) / (2.0f * h);  gy, gz likewise along y and z
+ *     g2 = (double)gx*gx + (double)gy*gy + (double)gz*gz          (double, left to right)
+ *     len = (float)sqrt(g2);   !(len > 0.f): f = 0 for this cell, else
+ *     nx = gx / len;  ny = gy / len;  nz = gz / len
+ *     eh = eps * h
+ *     fx = eh * (ny * wz - nz * wy);  fy = eh * (nz * wx - nx * wz);  fz = eh * (nx * wy - ny * wx)
+ *                                                                  (two products, one subtraction, one product each)
+ *   faces:  1 <= i <= ni-1:  uo(i,j,k) = u(i,j,k) + dt * (0.5f * (fx(i-1,j,k) + fx(i,j,k)));  i = 0 and i = ni: copied.
+ *           vo along j and wo along k likewise.
+ * The operator does not see the obstacle mask or the walls, like gpu_flow_stats: solid cells count as fluid, and the shear at
+ * a solid surface or at the domain border counts as vorticity.  (Both projections rewrite solid and wall faces before they
+ * take the divergence, so the force on those faces is overwritten.)  A dimension below 5 has no confined cell: the outputs
+ * equal the inputs in value.  Non-finite inputs propagate through the arithmetic as written; no special cases.
+ * Asynchronous on the compute stream, one launch, nothing allocated, no floating-point atomics: same bits on every call
+ * and for every FL_OPT_CONFINE_KCHUNK.  FL_ERR_BAD_ARGUMENT, nothing launched: a NULL pointer, a dimension below 3, the size
+ * limits above, a negative or non-finite eps, an output overlapping an input or another output.  FL_ERR_UNSUPPORTED, nothing
+ * launched: a z-slab context (fl_set_slab) -- the stencil needs three valid ghost planes and a global-plane border rule, which
+ * are not built.  Returns FL_OK or the error it latched. */
+int gpu_vorticity_confinement(float *uo, float *vo, float *wo, const float *u, const float *v, const float *w,
+                              float h, int ni, int nj, int nk, float eps, float dt);
 
 /* ---- shadowed density preview --------------------------------------------------------------------
  * An emission-absorption image of the density with single-scattering self-shadowing from one directional light; the view is

@@ -240,6 +240,18 @@ int   bq_solver_boundary_pose(const bq_solver *s, int i, double out[10]);
  * Returns 0 on success; get_walls returns the setting in force. */
 int   bq_solver_set_walls(bq_solver *s, int walls);
 int   bq_solver_get_walls(bq_solver *s);
+/* Vorticity confinement (an extension: the reference's only forces are buoyancy and viscosity): with a
+ * coefficient eps > 0 every step adds dt eps h (N x omega) to the velocity by one gpu_vorticity_confinement call
+ * (include/bimocq_gpu.h has the contract) right after the buoyancy, over the same dt and before the viscous diffusion: once
+ * per step in BiMocq and MacCormack, in both half steps of the reflection scheme over dt / 2 each.  eps is dimensionless
+ * (the force scales with h); useful values lie between 0.05 and 1.  The operator sees neither obstacles nor walls: the shear
+ * at a solid surface and at the domain border counts as vorticity, so the force near a solid is not physically filtered (the
+ * projections overwrite the solid and wall faces themselves).  Default 0: a step then issues exactly the launches it issues
+ * without this feature.  Refused through fl_last_error, the previous coefficient staying in place: a negative or
+ * non-finite eps with FL_ERR_BAD_ARGUMENT; eps > 0 on z-slab ranks or on an operator library without
+ * gpu_vorticity_confinement with FL_ERR_UNSUPPORTED.  set returns FL_OK or that error; get the coefficient in force. */
+int   bq_solver_set_vorticity_confinement(bq_solver *s, float eps);
+float bq_solver_get_vorticity_confinement(const bq_solver *s);
 /* Shaped, moving smoke sources (Emitter / emitSmoke of the CPU solver, BimocqSolver.h:31-59, BimocqSolver.cpp:696-813;
  * DESIGN.md section 16): a second list next to the emitters of set_smoke, which keep their launches and their bits.
  * set_sources replaces the list (n = 0 releases list and grids; at most BQ_MAX_SOURCES).  ls is an array of n
