@@ -13,6 +13,7 @@
 #include "fluid_solver.hpp"
 #include "../bq_levelset.h"
 #include "../bq_pose.h"
+#include "slab_jacobi_plan.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -51,6 +52,19 @@
 #pragma weak gpu_vorticity_confinement
 
 namespace bqhost {
+namespace slab = bq::slab;
+
+// While one lives, the caller vouches that the two pressure buffers it hands to the sweep entry points carry the same boundary
+// layer (and the same values in every solid cell): FL_OPT_JACOBI_FUSE 1 (fuse after checking the shells) becomes 2 (fuse on the
+// caller's word); every other setting is the user's and stays.
+class JacobiFuseVouched {
+    const int was_ = fl_get_option(FL_OPT_JACOBI_FUSE);
+public:
+    JacobiFuseVouched() { if (was_ == 1) fl_set_option(FL_OPT_JACOBI_FUSE, 2); }
+    ~JacobiFuseVouched() { fl_set_option(FL_OPT_JACOBI_FUSE, was_); }
+    JacobiFuseVouched(const JacobiFuseVouched &) = delete;
+    JacobiFuseVouched &operator=(const JacobiFuseVouched &) = delete;
+};
 
 // The obstacle operators for a list with level-set descriptors ls (non-NULL only when it holds a level set, and then
 // setBoundary has found the _ls operators), else the analytic ones: runs without level sets issue the launches they did
@@ -283,22 +297,10 @@ void BimocqGPUSolver::axpy(DeviceField &f1, DeviceField &f2, float coeff, size_t
 // emission over dt_emit (legacy emitters and the source list), buoyancy and viscous diffusion over dt_forces
 void BimocqGPUSolver::applySources(bool emit, int framenum, float dt_emit, float dt_forces)
 {
-    const gpuMapper &gs = *GpuSolver;
-    const int ni = g.ni, nj = g.nj, nk = g.nk;
     if (emit) emitSmoke(framenum, dt_emit);
     addBuoyancy(dt_forces);
     confine(dt_forces);
-    if (Viscosity) {
-        if (gs.slab.on && gs.slab.nranks > 1) {
-            diffuseFieldSlab(VelocityU, VelocityUTemp, TempSrcU, ni + 1, nj, nk, 20, Viscosity, dt_forces);
-            diffuseFieldSlab(VelocityV, VelocityVTemp, TempSrcV, ni, nj + 1, nk, 20, Viscosity, dt_forces);
-            diffuseFieldSlab(VelocityW, VelocityWTemp, TempSrcW, ni, nj, nk + 1, 20, Viscosity, dt_forces);
-        } else {
-            diffuseField(VelocityU, VelocityUTemp, TempSrcU, ni + 1, nj, nk, 20, Viscosity, dt_forces);
-            diffuseField(VelocityV, VelocityVTemp, TempSrcV, ni, nj + 1, nk, 20, Viscosity, dt_forces);
-            diffuseField(VelocityW, VelocityWTemp, TempSrcW, ni, nj, nk + 1, 20, Viscosity, dt_forces);
-        }
-    }
+    if (Viscosity) diffuseVelocity(dt_forces);
 }
 
 bool BimocqGPUSolver::fusedMacCormack() const
@@ -572,6 +574,21 @@ void BimocqGPUSolver::diffuseField(float *field, float *t0, float *t1, int ni, i
 {
     float coef = nu * (dt / (CellSize * CellSize));
     GpuSolver->diffuseField(field, t0, t1, ni, nj, nk, iter, coef);
+}
+
+// :167-172: 20 diffusion sweeps per velocity component, with the reference's buffer aliasing
+void BimocqGPUSolver::diffuseVelocity(float dt)
+{
+    const int ni = g.ni, nj = g.nj, nk = g.nk;
+    if (GpuSolver->slab.on && GpuSolver->slab.nranks > 1) {
+        diffuseFieldSlab(VelocityU, VelocityUTemp, TempSrcU, ni + 1, nj, nk, 20, Viscosity, dt);
+        diffuseFieldSlab(VelocityV, VelocityVTemp, TempSrcV, ni, nj + 1, nk, 20, Viscosity, dt);
+        diffuseFieldSlab(VelocityW, VelocityWTemp, TempSrcW, ni, nj, nk + 1, 20, Viscosity, dt);
+    } else {
+        diffuseField(VelocityU, VelocityUTemp, TempSrcU, ni + 1, nj, nk, 20, Viscosity, dt);
+        diffuseField(VelocityV, VelocityVTemp, TempSrcV, ni, nj + 1, nk, 20, Viscosity, dt);
+        diffuseField(VelocityW, VelocityWTemp, TempSrcW, ni, nj, nk + 1, 20, Viscosity, dt);
+    }
 }
 
 // gpu_diffuse_field (GPU_kernel.cu:855-876) on a z-slab rank: t0 <- field, `iter` sweeps in chunks of at most G
@@ -1024,14 +1041,12 @@ bool BimocqGPUSolver::projectionObstacles(bool with_delta)
                        CellSize, g.ni, g.nj, g.nk);
     if (walls) gpu_wall_faces(VelocityU, VelocityV, VelocityW, du, dv, dw, solidw.u8(), g.ni, g.nj, g.nk);   // (disjoint faces: the order is free)
     gpu_divergence(VelocityU, VelocityV, VelocityW, div, g.ni, g.nj, g.nk, halfrdx);
-    // p and p_temp carry the same (zero) boundary layer and +0 in every solid cell: three masked sweeps per launch
-    const int fuse_was = fl_get_option(FL_OPT_JACOBI_FUSE);
-    if (fuse_was == 1) fl_set_option(FL_OPT_JACOBI_FUSE, 2);
-    const int where = jacobi_iters <= 1 ? 0
-                    : walls ? gpu_jacobi_sweeps_masked_walls(p, div, p_temp, solidw.u8(), rows.u8(), walls, g.ni, g.nj, g.nk,
-                                                             jacobi_iters - 1, alpha, beta)
-                            : gpu_jacobi_sweeps_masked(p, div, p_temp, solid.u8(), rows.u8(), g.ni, g.nj, g.nk, jacobi_iters - 1, alpha, beta);
-    fl_set_option(FL_OPT_JACOBI_FUSE, fuse_was);
+    int where = 0;
+    if (jacobi_iters > 1) {
+        JacobiFuseVouched same_shell;       // p and p_temp carry the same (zero) boundary layer and +0 in every solid cell: three masked sweeps per launch
+        where = walls ? gpu_jacobi_sweeps_masked_walls(p, div, p_temp, solidw.u8(), rows.u8(), walls, g.ni, g.nj, g.nk, jacobi_iters - 1, alpha, beta)
+                      : gpu_jacobi_sweeps_masked(p, div, p_temp, solid.u8(), rows.u8(), g.ni, g.nj, g.nk, jacobi_iters - 1, alpha, beta);
+    }
     if (where) p.swap(p_temp);
     if (walls) gpu_gradient_masked_walls(VelocityU, VelocityV, VelocityW, p, du, dv, dw, solidw.u8(), walls, g.ni, g.nj, g.nk, halfrdx);
     else       gpu_gradient_masked(VelocityU, VelocityV, VelocityW, p, du, dv, dw, solid.u8(), g.ni, g.nj, g.nk, halfrdx);
@@ -1068,44 +1083,51 @@ bool BimocqGPUSolver::projectionPcg()
 // whether it did).
 bool BimocqGPUSolver::projection(bool with_delta)
 {
-    gpuMapper &gs = *GpuSolver;
-    const float alpha = -1.f, beta = (float)(1.0 / 6.0);
+    const gpuMapper &gs = *GpuSolver;
+    const bool slabs = gs.slab.on && gs.slab.nranks > 1;
     if (projection_kind == BQ_PROJECTION_PCG) return projectionPcg();   // (refused on slabs by bq_solver_set_projection)
     if (projection_kind == BQ_PROJECTION_MGCG) {            // :443-446
-        if (gs.slab.on && gs.slab.nranks > 1) {
-            if (projectionMgcgShared()) return false;
-            if (!allocMgcg()) return false;
-            projectionMgcgSlabs();
-            return false;
-        }
+        if (slabs && projectionMgcgShared()) return false;
         if (!allocMgcg()) return false;
-        gpu_multi_grid_conjugate_gradient(VelocityU, VelocityV, VelocityW, mg.div.f64(), mg.p.f64(), mg.dir.f64(),
-                                          mg.residual.f64(), mg.temp0.f64(), mg.temp1.f64(), mg.result.f64(),
-                                          mg.levels.data(), (int)mg.levels.size(), mg_iters, (double)halfrdx);
+        if (slabs) projectionMgcgSlabs();
+        else gpu_multi_grid_conjugate_gradient(VelocityU, VelocityV, VelocityW, mg.div.f64(), mg.p.f64(), mg.dir.f64(),
+                                               mg.residual.f64(), mg.temp0.f64(), mg.temp1.f64(), mg.result.f64(),
+                                               mg.levels.data(), (int)mg.levels.size(), mg_iters, (double)halfrdx);
         return false;
     }
     if (!boundaries.empty() || walls) return projectionObstacles(with_delta);   // (setBoundary / setWalls admit one GPU + Jacobi or PCG only)
-    if (!gs.slab.on || gs.slab.nranks <= 1) {
-        if (!with_delta) {
-            gs.projectionJacobi(VelocityU, VelocityV, VelocityW, div, p, p_temp, debugParam, jacobi_iters, halfrdx, alpha, beta);
-            return false;
-        }
-        // gpu_projection_jacobi (GPU_kernel.cu:1839-1895) in its pieces: divergence, iter-1 sweeps, the
-        // newest iterate made `p` by a buffer swap instead of the copy-back, gradient with the change handed out
-        div.zero(); p.zero(); p_temp.zero();                             // GPU_Advection.h:604-606
-        gpu_divergence(VelocityU, VelocityV, VelocityW, div, g.ni, g.nj, g.nk, halfrdx);
-        const int fuse_was = fl_get_option(FL_OPT_JACOBI_FUSE);
-        if (fuse_was == 1) fl_set_option(FL_OPT_JACOBI_FUSE, 2);        // p and p_temp carry the same (zero) boundary layer
-        const int where = jacobi_iters > 1 ? gpu_jacobi_sweeps(p, div, p_temp, g.ni, g.nj, g.nk, jacobi_iters - 1, alpha, beta) : 0;
-        fl_set_option(FL_OPT_JACOBI_FUSE, fuse_was);
-        if (where) p.swap(p_temp);
-        gpu_gradient_delta(VelocityU, VelocityV, VelocityW, p, duProj, dvProj, dwProj, g.ni, g.nj, g.nk, halfrdx);
-        return true;
+    return slabs ? projectionJacobiSlabs(with_delta) : projectionJacobi(with_delta);
+}
+
+bool BimocqGPUSolver::projectionJacobi(bool with_delta)
+{
+    const float alpha = -1.f, beta = (float)(1.0 / 6.0);
+    if (!with_delta) {
+        GpuSolver->projectionJacobi(VelocityU, VelocityV, VelocityW, div, p, p_temp, debugParam, jacobi_iters, halfrdx, alpha, beta);
+        return false;
     }
-    // z-slab form of gpu_projection_jacobi (GPU_kernel.cu:1839-1895): same three kernels, with the
-    // sweeps issued in chunks of G: one exchange of G ghost planes of p buys G sweeps, because each
-    // sweep shrinks the correct ghost depth by one plane (the ghost planes are swept redundantly,
-    // which yields the very values the neighbour computes).
+    // gpu_projection_jacobi (GPU_kernel.cu:1839-1895) in its pieces: divergence, iter-1 sweeps, the
+    // newest iterate made `p` by a buffer swap instead of the copy-back, gradient with the change handed out
+    div.zero(); p.zero(); p_temp.zero();                                 // GPU_Advection.h:604-606
+    gpu_divergence(VelocityU, VelocityV, VelocityW, div, g.ni, g.nj, g.nk, halfrdx);
+    int where = 0;
+    if (jacobi_iters > 1) {
+        JacobiFuseVouched same_shell;                                    // p and p_temp carry the same (zero) boundary layer
+        where = gpu_jacobi_sweeps(p, div, p_temp, g.ni, g.nj, g.nk, jacobi_iters - 1, alpha, beta);
+    }
+    if (where) p.swap(p_temp);
+    gpu_gradient_delta(VelocityU, VelocityV, VelocityW, p, duProj, dvProj, dwProj, g.ni, g.nj, g.nk, halfrdx);
+    return true;
+}
+
+// z-slab form of gpu_projection_jacobi (GPU_kernel.cu:1839-1895): same three kernels, with the sweeps issued in chunks of G:
+// one exchange of G ghost planes of p buys G sweeps, because each sweep shrinks the correct ghost depth by one plane (the ghost
+// planes are swept redundantly, which yields the very values the neighbour computes).  What a chunk consists of is stated in
+// slab_jacobi_plan.hpp; this function issues it and keeps the plan's two permissions up to date when the library refuses a launch.
+bool BimocqGPUSolver::projectionJacobiSlabs(bool with_delta)
+{
+    gpuMapper &gs = *GpuSolver;
+    const float alpha = -1.f, beta = (float)(1.0 / 6.0);
     const int G = gs.slab.G;
     // The redundant ghost sweeps need div on all G ghost planes.  Rather than refreshing three velocity components to
     // depth G and evaluating div there, div is evaluated where the velocities are valid (the owned planes need one ghost
@@ -1118,121 +1140,99 @@ bool BimocqGPUSolver::projection(bool with_delta)
     gs.require({ &div }, G);
     DeviceField *cur = &p, *oth = &p_temp;
     gs.produced(*cur, G);                                                // zeros everywhere
-    // p and p_temp carry the same (zero) boundary layer: gpu_jacobi_sweeps may fuse sweeps pairwise
-    const int fuse_was = fl_get_option(FL_OPT_JACOBI_FUSE);
-    if (fuse_was == 1) fl_set_option(FL_OPT_JACOBI_FUSE, 2);
-    int left = jacobi_iters - 1;                                         // iterate iter-1 is applied
     const int own0 = G, own1 = g.nk - G;                                 // local owned planes [own0, own1)
-    bool pair_split = G >= 2 && own1 - own0 >= 5;                        // until the operator library says it cannot
-    bool triples_ok = gs.jacobi_triples && G == 8;                       // likewise
-    // The exchange a chunk starts with is hidden by the interior part of its first pair only -- one launch (40 us at
-    // 512 x 512 x 80) against 8 planes per direction (130 us at 64 GB/s).  So the last two pairs of a chunk that another
-    // chunk follows run ENDS FIRST: the G + 2 and then the G owned planes at either end (which need nothing beyond what
-    // the pair before produced), the exchange of the now final boundary planes starts, and the two interiors plus the
-    // interior of the next chunk's first pair run while it travels (three launches instead of one).
-    const bool ends_first_ok = gs.overlap_exchanges && gs.jacobi_ends_first && G >= 6 && G % 2 == 0 && own1 - own0 >= 2 * G + 8;
+    // S = 2 or 3 sweeps in one launch on up to two plane ranges; false: the library refuses (nothing was launched)
+    auto fused = [&](int S, DeviceField &in, DeviceField &out, slab::Planes a, slab::Planes b = slab::Planes{0, 0}) {
+        return (S == 3 ? gpu_jacobi_sweep_triple_ranges : gpu_jacobi_sweep_pair_ranges)(in, div, out, g.ni, g.nj, g.nk, a.k0, a.k1, b.k0, b.k1,
+                                                                                         alpha, beta) != 0;
+    };
+    auto single = [&](DeviceField &in, DeviceField &out, slab::Planes a) { gpu_jacobi_sweep_range(in, div, out, g.ni, g.nj, g.nk, a.k0, a.k1, alpha, beta); };
+    // the G ghost planes of `f` start travelling on the halo stream; fl_halo_wait (or the next blocking exchange) joins them
+    auto startExchange = [&](DeviceField &f) {
+        float *ptr = f.get(); size_t pe = f.plane; int ex = 0;
+        fl_halo_exchange(1, &ptr, &pe, &ex, g.nk, G, G, /*wait=*/0);
+    };
+    // The exchange a chunk starts with is hidden by the interior part of its first pass only -- one launch (40 us at 512 x 512 x 80)
+    // against 8 planes per direction (130 us at 64 GB/s).  ENDS FIRST, for the last two passes A and B of a chunk that another
+    // chunk follows: both on the planes next to the slab ends (which need nothing beyond what the pass before produced; B's are
+    // the planes the neighbours receive), the exchange of those now final planes starts, and the two interiors plus the interior
+    // of the next chunk's first pass run while it travels (three launches instead of one).  A's interior reads `in` from plane
+    // own0 + G on, which is where B's end stopped writing it.  d: ghost planes correct after A.  The newest iterate is back in `in`.
+    // All four launches apply or none: the same kernel on the same rows either takes every one of these ranges or refuses the
+    // first; a later refusal would leave `in` half-updated, so it is an error, not a fall-back.
+    auto endsFirst = [&](int S, DeviceField &in, DeviceField &out, int d) {
+        const slab::Ends ea = slab::ends(own0, own1, G, d), eb = slab::ends(own0, own1, G, d - S);
+        if (!fused(S, in, out, ea.a, ea.b)) return false;
+        bool later = fused(S, out, in, eb.a, eb.b);
+        startExchange(in);
+        later &= fused(S, in, out, slab::interior(own0, own1, G, d));
+        later &= fused(S, out, in, slab::interior(own0, own1, G, d - S));
+        if (!later) fl_report_error(FL_ERR_UNSUPPORTED, "projection on slabs: a follow-up launch of an ends-first group was refused after the first one ran");
+        return true;
+    };
+    JacobiFuseVouched same_shell;                                        // p and p_temp carry the same (zero) boundary layer: gpu_jacobi_sweeps may fuse
+    slab::ChunkIn plan{};
+    plan.left = jacobi_iters - 1;                                        // iterate iter-1 is applied
+    plan.G = G; plan.owned = own1 - own0;
+    plan.pairs_ok = G >= 2 && own1 - own0 >= 5;                          // until the operator library says it cannot
+    plan.triples_ok = true;                                              // likewise
+    plan.overlap_exchanges = gs.overlap_exchanges; plan.ends_first = gs.jacobi_ends_first; plan.triples = gs.jacobi_triples;
     bool in_flight = false;                                              // the exchange of `cur`'s ghost planes has been started
-    while (left > 0) {
-        int where;
-        int chunk;
-        if (!in_flight && cur->valid >= std::min(left, G)) {
-            chunk = std::min(left, G);
+    while (plan.left > 0) {
+        int where, chunk;
+        if (!in_flight && cur->valid >= std::min(plan.left, G)) {
+            chunk = std::min(plan.left, G);
             where = gpu_jacobi_sweeps(*cur, div, *oth, g.ni, g.nj, g.nk, chunk, alpha, beta);
         } else {
             // The ghost planes of `cur` travel on the halo stream while the compute stream sweeps what does not
             // depend on them; the planes next to them follow the exchange.
-            if (!in_flight) {
-                float *ptr = cur->get(); size_t pe = cur->plane; int ex = 0;
-                fl_halo_exchange(1, &ptr, &pe, &ex, g.nk, G, G, /*wait=*/0);
-            }
+            if (!in_flight) startExchange(*cur);
             in_flight = false;
-            int done = 0;
-            chunk = std::min(left, G);
-            if (pair_split && chunk >= 2) {
-                // first TWO sweeps of the chunk as one fused launch per piece: output planes whose two-sweep stencil
-                // stays inside the owned planes now, the two ends after the exchange (one launch for both)
-                if (gpu_jacobi_sweep_pair_ranges(*cur, div, *oth, g.ni, g.nj, g.nk, own0 + 2, own1 - 2, 0, 0, alpha, beta)) {
-                    fl_halo_wait();
-                    gs.produced(*cur, G);
-                    gpu_jacobi_sweep_pair_ranges(*cur, div, *oth, g.ni, g.nj, g.nk, 0, own0 + 2, own1 - 2, g.nk, alpha, beta);
-                    done = 2;
-                } else {
-                    pair_split = false;                                  // fused kernel does not apply to this grid
-                }
+            slab::Chunk c = slab::plan_chunk(plan);
+            if (c.first == 2 && !fused(2, *cur, *oth, slab::first_interior(own0, own1, 2))) {
+                plan.pairs_ok = false;                                   // the fused kernel does not apply to this grid
+                c = slab::plan_chunk(plan);
             }
-            if (!done) {
-                // one sweep in three plane ranges; an odd chunk so that everything after it runs as fused pairs
-                chunk = std::min(left, (G % 2 == 0 && G > 1) ? G - 1 : G);
-                gpu_jacobi_sweep_range(*cur, div, *oth, g.ni, g.nj, g.nk, own0 + 1, own1 - 1, alpha, beta);
-                fl_halo_wait();
-                gs.produced(*cur, G);
-                gpu_jacobi_sweep_range(*cur, div, *oth, g.ni, g.nj, g.nk, 0, own0 + 1, alpha, beta);
-                gpu_jacobi_sweep_range(*cur, div, *oth, g.ni, g.nj, g.nk, own1 - 1, g.nk, alpha, beta);
-                done = 1;
-            }
-            // The remaining sweeps of the chunk start from `oth`.  A sweep leaves one ghost plane less correct on each
-            // side, and nothing reads the planes beyond: every further fused pair is restricted to the planes that will
-            // still be correct after it (done = 2 of G = 8: 264, 260, 256 of 272 planes).
-            int rest = chunk - done;
+            const slab::Ends fe = slab::first_ends(own0, own1, g.nk, c.first);
+            if (c.first == 1) single(*cur, *oth, slab::first_interior(own0, own1, 1));
+            fl_halo_wait();
+            gs.produced(*cur, G);
+            if (c.first == 2) fused(2, *cur, *oth, fe.a, fe.b);          // (one launch for both ends)
+            else { single(*cur, *oth, fe.a); single(*cur, *oth, fe.b); }
+            // The remaining sweeps of the chunk start from `oth`.  Nothing reads the planes beyond the depth that stays correct:
+            // every fused pass is restricted to the planes that will still be correct after it (G = 8 in pairs: 264, 260, 256 of
+            // 272 planes).
             DeviceField *in = oth, *out = cur;
-            int depth = G - done;                                        // correct ghost planes of `in`
-            const bool ends_first = ends_first_ok && pair_split && done == 2 && chunk == G && left > chunk;
-            // The six sweeps after the overlapped pair of a full chunk as TWO triples (BQ_OPT_JACOBI_TRIPLES, G = 8): triple A
-            // produces [own0 - 3, own1 + 3) from the pair's result (correct to depth 6), triple B the owned planes.  Ends
-            // first: A and B on the planes next to the slab ends (A: G + 6 planes per end, B: the G planes the neighbours
-            // need), the exchange starts, then the two interiors -- A's interior reads `in` from plane own0 + G on, which is
-            // where B's end stopped writing it.
-            if (triples_ok && pair_split && done == 2 && rest == 6 && depth == 6) {
-                bool ran;
-                if (ends_first) {
-                    ran = gpu_jacobi_sweep_triple_ranges(*in, div, *out, g.ni, g.nj, g.nk, own0 - 3, own0 + G + 3, own1 - G - 3, own1 + 3, alpha, beta) != 0;
-                    // (all four launches must apply or none: the same kernel on the same rows either takes every one of these
-                    // ranges or refused the first; a later refusal would leave `in` half-updated, so it is an error, not a fall-back)
-                    int later = 1;
-                    if (ran) {
-                        later &= gpu_jacobi_sweep_triple_ranges(*out, div, *in, g.ni, g.nj, g.nk, own0, own0 + G, own1 - G, own1, alpha, beta) != 0;
-                        { float *ptr = in->get(); size_t pe = in->plane; int ex = 0; fl_halo_exchange(1, &ptr, &pe, &ex, g.nk, G, G, /*wait=*/0); }
-                        in_flight = true;
-                        later &= gpu_jacobi_sweep_triple_ranges(*in, div, *out, g.ni, g.nj, g.nk, own0 + G + 3, own1 - G - 3, 0, 0, alpha, beta) != 0;
-                        later &= gpu_jacobi_sweep_triple_ranges(*out, div, *in, g.ni, g.nj, g.nk, own0 + G, own1 - G, 0, 0, alpha, beta) != 0;
-                    }
-                    if (!later) fl_report_error(FL_ERR_UNSUPPORTED, "projection on slabs: a follow-up three-sweep launch was refused after the first one ran");
-                } else {
-                    ran = gpu_jacobi_sweep_triple_ranges(*in, div, *out, g.ni, g.nj, g.nk, own0 - 3, own1 + 3, 0, 0, alpha, beta) != 0;
-                    if (ran && !gpu_jacobi_sweep_triple_ranges(*out, div, *in, g.ni, g.nj, g.nk, own0, own1, 0, 0, alpha, beta))
-                        fl_report_error(FL_ERR_UNSUPPORTED, "projection on slabs: the second three-sweep launch was refused after the first one ran");
+            int d = G - c.first;                                         // correct ghost planes of `in`
+            for (int i = 0; i < c.fused;) {
+                const bool group = c.ends_first && i == c.fused - 2;     // this pass and the next, ends first
+                const bool ran = group ? endsFirst(c.S, *in, *out, d - c.S) : fused(c.S, *in, *out, slab::whole(own0, own1, d - c.S));
+                if (!ran && c.S == 3 && i == 0) {                        // the kernels do not apply to this grid: pairs from now on
+                    plan.triples_ok = false;
+                    c = slab::plan_chunk(plan);
+                    continue;
                 }
-                if (ran) { rest = 0; depth = 0; }                        // (two launches per piece: the newest iterate is back in `in`)
-                else triples_ok = false;                                 // the kernels do not apply to this grid: pairs from now on
+                if (!ran && c.S == 3)
+                    fl_report_error(FL_ERR_UNSUPPORTED, "projection on slabs: the second three-sweep launch was refused after the first one ran");
+                if (!ran) break;                                         // what is left of the chunk goes to gpu_jacobi_sweeps
+                if (group) in_flight = true;                             // (two launches per piece: the newest iterate is back in `in`)
+                else std::swap(in, out);
+                const int passes = group ? 2 : 1;
+                i += passes; d -= passes * c.S;
             }
-            while (pair_split && rest >= 2) {
-                if (ends_first && rest == 4) {
-                    // the last two pairs, ends first (depth is 4 here: this pair covers [own0 - 2, own1 + 2), the last [own0, own1))
-                    if (!gpu_jacobi_sweep_pair_ranges(*in, div, *out, g.ni, g.nj, g.nk, own0 - 2, own0 + G + 2, own1 - G - 2, own1 + 2, alpha, beta)) break;
-                    gpu_jacobi_sweep_pair_ranges(*out, div, *in, g.ni, g.nj, g.nk, own0, own0 + G, own1 - G, own1, alpha, beta);
-                    // `in` now holds the chunk's result on the planes the neighbours need: send them, receive theirs
-                    { float *ptr = in->get(); size_t pe = in->plane; int ex = 0; fl_halo_exchange(1, &ptr, &pe, &ex, g.nk, G, G, /*wait=*/0); }
-                    in_flight = true;
-                    gpu_jacobi_sweep_pair_ranges(*in, div, *out, g.ni, g.nj, g.nk, own0 + G + 2, own1 - G - 2, 0, 0, alpha, beta);
-                    gpu_jacobi_sweep_pair_ranges(*out, div, *in, g.ni, g.nj, g.nk, own0 + G, own1 - G, 0, 0, alpha, beta);
-                    rest -= 4; depth -= 4;                               // (two pairs: the newest iterate is back in `in`)
-                    break;
-                }
-                if (!gpu_jacobi_sweep_pair_ranges(*in, div, *out, g.ni, g.nj, g.nk, own0 - (depth - 2), own1 + (depth - 2), 0, 0, alpha, beta)) break;
-                std::swap(in, out); rest -= 2; depth -= 2;
-            }
+            const int rest = c.sweeps - (G - d);
             const int w2 = rest > 0 ? gpu_jacobi_sweeps(*in, div, *out, g.ni, g.nj, g.nk, rest, alpha, beta) : 0;
             DeviceField *newest = w2 ? out : in;
             where = newest == cur ? 0 : 1;
+            chunk = c.sweeps;
         }
         int v = cur->valid;
         for (int s = 0; s < chunk; s++) v = std::min(v - 1, div.valid);     // each sweep reaches one plane
         if (where) std::swap(cur, oth);
         gs.produced(*cur, v);
         gs.produced(*oth, 0);
-        left -= chunk;
+        plan.left -= chunk;
     }
-    fl_set_option(FL_OPT_JACOBI_FUSE, fuse_was);
     if (cur != &p) p.swap(p_temp);                                       // the newest iterate becomes `p` (no copy-back)
     gs.require({ &p }, 1);
     const int vu = std::min(VelocityU.valid, p.valid), vv = std::min(VelocityV.valid, p.valid), vw = std::min(VelocityW.valid, p.valid - 1);
@@ -1374,17 +1374,7 @@ void BimocqGPUSolver::advanceBimocq(int framenum, float dt)
     addBuoyancy(dt);                                     // :165
     confine(dt);                                         // (no counterpart in the reference: DESIGN.md section 25)
 
-    if (Viscosity) {                                     // :167-172, with the reference's buffer aliasing
-        if (gs.slab.on && gs.slab.nranks > 1) {
-            diffuseFieldSlab(VelocityU, VelocityUTemp, TempSrcU, g.ni + 1, g.nj, g.nk, 20, Viscosity, dt);
-            diffuseFieldSlab(VelocityV, VelocityVTemp, TempSrcV, g.ni, g.nj + 1, g.nk, 20, Viscosity, dt);
-            diffuseFieldSlab(VelocityW, VelocityWTemp, TempSrcW, g.ni, g.nj, g.nk + 1, 20, Viscosity, dt);
-        } else {
-            diffuseField(VelocityU, VelocityUTemp, TempSrcU, g.ni + 1, g.nj, g.nk, 20, Viscosity, dt);
-            diffuseField(VelocityV, VelocityVTemp, TempSrcV, g.ni, g.nj + 1, g.nk, 20, Viscosity, dt);
-            diffuseField(VelocityW, VelocityWTemp, TempSrcW, g.ni, g.nj, g.nk + 1, 20, Viscosity, dt);
-        }
-    }
+    if (Viscosity) diffuseVelocity(dt);                  // :167-172
 
     // :175-177 velocity change due to external forces.  When nothing touched u and w they still equal their
     // snapshots, U - UTemp is identically +0, and accumulating blend9 of a zero field (:213) changes no value --

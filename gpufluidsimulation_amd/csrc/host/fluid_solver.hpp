@@ -66,7 +66,10 @@ public:
     void confine(float dt);
     void diffuseField(float *field, float *t0, float *t1, int ni, int nj, int nk, int iter, float nu, float dt);
     void diffuseFieldSlab(DeviceField &field, DeviceField &t0, DeviceField &t1, int bi, int bj, int bk, int iter, float nu, float dt);
+    void diffuseVelocity(float dt);
     bool projection(bool with_delta = false);
+    bool projectionJacobi(bool with_delta);         // one GPU
+    bool projectionJacobiSlabs(bool with_delta);    // z-slab ranks: chunks of G sweeps per exchange (slab_jacobi_plan.hpp)
     void velocityReinitialize();
     void scalarReinitialize();
     bool whole_grid_prev = true;            // BQ_OPT_WHOLE_GRID_PREV

@@ -7,6 +7,7 @@ GPU tests as references.  Test infrastructure.
   build_launch_geom() tests/_build/liblaunch_geom.so: csrc/bq_launch_geom.h behind tests/cpu_abi/launch_geom_shim.cpp
   build_jacobi_plan() tests/_build/libjacobi_plan.so: csrc/bq_jacobi_plan.h behind tests/cpu_abi/jacobi_plan_shim.cpp
   build_box_chunk()  tests/_build/libbox_chunk.so: csrc/bq_box_chunk.h behind tests/cpu_abi/box_chunk_shim.cpp
+  build_slab_jacobi_plan() tests/_build/libslab_jacobi_plan.so: csrc/host/slab_jacobi_plan.hpp behind tests/cpu_abi/slab_jacobi_plan_shim.cpp
 A stand-in without some operators leaves the host solver's weak references to them null: set_boundary refuses there."""
 import glob
 import os
@@ -86,5 +87,10 @@ def build_box_chunk():
     return _build_header_shim("libbox_chunk.so", "box_chunk_shim.cpp", ["bq_box_chunk.h"])
 
 
+def build_slab_jacobi_plan():
+    """a chunk of the z-slab Jacobi projection as a list of passes, and their plane ranges"""
+    return _build_header_shim("libslab_jacobi_plan.so", "slab_jacobi_plan_shim.cpp", ["host/slab_jacobi_plan.hpp"])
+
+
 if __name__ == "__main__":
-    print(build(), build_obstacles(), build_levelsets(), build_launch_geom(), build_jacobi_plan(), build_box_chunk())
+    print(build(), build_obstacles(), build_levelsets(), build_launch_geom(), build_jacobi_plan(), build_box_chunk(), build_slab_jacobi_plan())

@@ -17,7 +17,8 @@
 
 static int g_err = FL_OK;
 static char g_text[256];
-static int g_opt[8];
+static int g_opt[9] = { [FL_OPT_JACOBI_FUSE] = 1 };     /* (the library's default: include/bimocq_gpu.h) */
+#define N_OPT ((int)(sizeof g_opt / sizeof g_opt[0]))
 
 static void latch(int code, const char *what)
 {
@@ -48,18 +49,18 @@ int fl_last_error(void) { return g_err; }
 const char *fl_last_error_string(void) { return g_err == FL_OK ? "" : g_text; }
 void fl_clear_error(void) { g_err = FL_OK; g_text[0] = 0; }
 void *fl_compute_stream(void) { return NULL; }
-/* options 0..7 are stored; FL_OPT_FUSED_HOUSEKEEPING (12) is implemented below; everything else is unknown (-1) */
+/* options 0..8 are stored; FL_OPT_FUSED_HOUSEKEEPING (12) is implemented below; everything else is unknown (-1) */
 static int g_fused = 0;
 static int g_nk_local = 0;          /* local cell planes, from fl_set_slab */
 void fl_set_option(int option, int value)
 {
-    if (option >= 0 && option < 8) g_opt[option] = value;
+    if (option >= 0 && option < N_OPT) g_opt[option] = value;
     if (option == FL_OPT_FUSED_HOUSEKEEPING) g_fused = value & 15;
 }
 int fl_get_option(int option)
 {
     if (option == FL_OPT_FUSED_HOUSEKEEPING) return g_fused;
-    return (option >= 0 && option < 8) ? g_opt[option] : -1;
+    return (option >= 0 && option < N_OPT) ? g_opt[option] : -1;
 }
 /* plane window of the map operators (fl_set_plane_window): handed to the oracle's loops; the clears and copies of the
  * fused housekeeping below are restricted to the same planes */
@@ -189,15 +190,44 @@ int fl_comm_rank(void) { return c_rank; }
 int fl_comm_size(void) { return c_nranks; }
 void fl_comm_set_custom(int rank, int nranks, fl_exchange_cb ex, fl_allreduce_cb ar)
 { c_rank = rank; c_nranks = nranks; c_exchange = ex; c_allreduce = ar; }
+/* ---- optional log of a z-slab Jacobi projection's schedule (tests/test_slab_jacobi_trace_cpu.py): every sweep launch,
+ * exchange of a pressure buffer and wait between the projection's gpu_divergence and its gradient, one line per call.  The two
+ * pressure buffers are called A and B in the order a projection first names them. */
+static FILE *j_log;
+static int j_open;                  /* between a slab projection's divergence and its gradient */
+static const void *j_div, *j_buf[2];
+void abi_jacobi_log(const char *path)
+{
+    if (j_log) fclose(j_log);
+    j_log = path ? fopen(path, "w") : NULL;
+    j_open = 0;
+}
+static void j_begin(const void *div)
+{
+    if (!j_log || !s_on) return;
+    j_open = 1; j_div = div; j_buf[0] = j_buf[1] = NULL;
+    fprintf(j_log, "projection\n");
+}
+static void j_end(void) { if (j_open) { j_open = 0; fflush(j_log); } }
+static char j_name(const void *b)
+{
+    for (int a = 0; a < 2; a++) {
+        if (!j_buf[a]) j_buf[a] = b;
+        if (j_buf[a] == b) return (char)('A' + a);
+    }
+    return '?';
+}
 void fl_halo_exchange(int n, float *const *fields, const size_t *plane_elems, const int *extra,
                       int nk_local, int G, int depth, int wait)
 {
-    (void)wait;
+    if (j_open)
+        for (int a = 0; a < n; a++)
+            if (fields[a] != j_div) fprintf(j_log, "exchange %c depth %d wait %d\n", j_name(fields[a]), depth, wait);
     if (c_nranks <= 1) return;
     if (!c_exchange) { latch(FL_ERR_COMM, "fl_halo_exchange: no transport"); return; }
     c_exchange(n, fields, plane_elems, extra, nk_local, G, depth);
 }
-void fl_halo_wait(void) {}
+void fl_halo_wait(void) { if (j_open) fprintf(j_log, "wait\n"); }
 void fl_comm_stats(long long out[4], int reset) { (void)reset; if (out) for (int a = 0; a < 4; a++) out[a] = 0; }
 
 /* ---- wall sheets (include/bimocq_gpu.h, section 4) on host memory ---- */
@@ -389,10 +419,11 @@ void gpu_map_travel_z(const float *bz, const float *fz, float h, int ni, int nj,
 void gpu_clamp_extrema_box_w(const float *before, float *after, int ni, int nj, int nk)
 { orc_clamp_extrema_box_w(before, after, ni, nj, nk); }
 void gpu_divergence(const float *u, const float *v, const float *w, float *div, int ni, int nj, int nk, float hr)
-{ orc_divergence(u, v, w, div, ni, nj, nk, hr); }
+{ orc_divergence(u, v, w, div, ni, nj, nk, hr); j_begin(div); }
 int gpu_jacobi_sweeps(float *p, const float *div, float *pt, int ni, int nj, int nk, int sweeps, float alpha, float beta)
 {
     float *in = p, *out = pt;
+    if (j_open) { const char a = j_name(p); fprintf(j_log, "sweeps %c->%c %d\n", a, j_name(pt), sweeps); }
     for (int s = 0; s < sweeps; s++) { orc_jacobi_sweep(in, div, out, ni, nj, nk, alpha, beta); float *t = in; in = out; out = t; }
     return in == p ? 0 : 1;
 }
@@ -401,6 +432,7 @@ void gpu_gradient_delta(float *u, float *v, float *w, const float *p, float *du,
 {
     size_t nu = (size_t)(ni + 1) * nj * nk, nv = (size_t)ni * (nj + 1) * nk, nw = (size_t)ni * nj * (nk + 1);
     memcpy(du, u, nu * sizeof(float)); memcpy(dv, v, nv * sizeof(float)); memcpy(dw, w, nw * sizeof(float));
+    j_end();
     gpu_gradient(u, v, w, p, ni, nj, nk, hr);
     for (size_t q = 0; q < nu; q++) du[q] = u[q] - du[q];
     for (size_t q = 0; q < nv; q++) dv[q] = v[q] - dv[q];
@@ -408,13 +440,23 @@ void gpu_gradient_delta(float *u, float *v, float *w, const float *p, float *du,
 }
 void gpu_jacobi_sweep_range(const float *in, const float *div, float *out, int ni, int nj, int nk,
                             int k_begin, int k_end, float alpha, float beta)
-{ orc_jacobi_sweep_range(in, div, out, ni, nj, nk, k_begin, k_end, alpha, beta); }
+{
+    if (j_open) { const char a = j_name(in); fprintf(j_log, "range %c->%c %d %d\n", a, j_name(out), k_begin, k_end); }
+    orc_jacobi_sweep_range(in, div, out, ni, nj, nk, k_begin, k_end, alpha, beta);
+}
+/* what a fused launch on plane ranges answers goes into the log with the call */
+static int j_ranges(const char *what, const float *in, float *out, int k0a, int k1a, int k0b, int k1b, int ran)
+{
+    if (j_open) { const char a = j_name(in); fprintf(j_log, "%s %c->%c %d %d %d %d = %d\n", what, a, j_name(out), k0a, k1a, k0b, k1b, ran); }
+    return ran;
+}
 /* two sweeps, output on two plane ranges: L1 on the planes those outputs read (into a scratch copy of `in`, which
  * also gives it the same boundary layer), then L2 on the ranges themselves */
 int gpu_jacobi_sweep_pair_ranges(const float *in, const float *div, float *out, int ni, int nj, int nk,
                                  int k0a, int k1a, int k0b, int k1b, float alpha, float beta)
 {
     size_t n = (size_t)ni * nj * nk;
+    if (g_opt[FL_OPT_JACOBI_FUSE] == 0) return j_ranges("pair", in, out, k0a, k1a, k0b, k1b, 0);
     float *l1 = (float *)malloc(n * sizeof(float));
     if (!l1) return 0;
     memcpy(l1, in, n * sizeof(float));
@@ -430,13 +472,14 @@ int gpu_jacobi_sweep_pair_ranges(const float *in, const float *div, float *out, 
         orc_jacobi_sweep_range(l1, div, out, ni, nj, nk, k0, k1, alpha, beta);
     }
     free(l1);
-    return 1;
+    return j_ranges("pair", in, out, k0a, k1a, k0b, k1b, 1);
 }
 /* three sweeps, output on two plane ranges: L1 on the planes two beyond, L2 one beyond, L3 on the ranges themselves */
 int gpu_jacobi_sweep_triple_ranges(const float *in, const float *div, float *out, int ni, int nj, int nk,
                                    int k0a, int k1a, int k0b, int k1b, float alpha, float beta)
 {
     size_t n = (size_t)ni * nj * nk;
+    if (g_opt[FL_OPT_JACOBI_FUSE] == 0 || g_opt[FL_OPT_JACOBI_FUSE] == 4) return j_ranges("triple", in, out, k0a, k1a, k0b, k1b, 0);
     float *l1 = (float *)malloc(n * sizeof(float)), *l2 = (float *)malloc(n * sizeof(float));
     if (!l1 || !l2) { free(l1); free(l2); return 0; }
     memcpy(l1, in, n * sizeof(float));
@@ -453,10 +496,11 @@ int gpu_jacobi_sweep_triple_ranges(const float *in, const float *div, float *out
             else orc_jacobi_sweep_range(l2, div, out, ni, nj, nk, e0, e1, alpha, beta);
         }
     free(l1); free(l2);
-    return 1;
+    return j_ranges("triple", in, out, k0a, k1a, k0b, k1b, 1);
 }
 void gpu_gradient(float *u, float *v, float *w, const float *p, int ni, int nj, int nk, float hr)
 {
+    j_end();
     orc_gradient(u, p, ni + 1, nj, nk, 1, 0, 0, hr);
     orc_gradient(v, p, ni, nj + 1, nk, 0, 1, 0, hr);
     orc_gradient(w, p, ni, nj, nk + 1, 0, 0, 1, hr);

@@ -41,6 +41,9 @@ def main():
     ap.add_argument("--shallow", type=int, default=0, help="BQ_OPT_SHALLOW_BLOCKING_EXCHANGE")
     ap.add_argument("--ends-first", type=int, default=1, help="BQ_OPT_JACOBI_ENDS_FIRST")
     ap.add_argument("--triples", type=int, default=1, help="BQ_OPT_JACOBI_TRIPLES")
+    ap.add_argument("--jacobi-fuse", type=int, default=None, help="FL_OPT_JACOBI_FUSE (the library's default when not given)")
+    ap.add_argument("--jacobi-log", default=None, help="cpu backend: file for the stand-in's log of the Jacobi projections' launches, "
+                    "exchanges and waits (tests/cpu_abi/oracle_abi.c); {rank} in the name becomes the rank")
     ap.add_argument("--reserve-cus", type=int, default=0, help="FL_OPT_RESERVE_CUS (gpu backend): CU-masked compute stream")
     ap.add_argument("--policy", type=int, default=0, help="BQ_OPT_REINIT_POLICY: 1 = distortion-driven re-initialisation (maps live for several steps)")
     ap.add_argument("--travel-limit", type=int, default=0, help="BQ_OPT_REINIT_MAX_TRAVEL / oracle option 4 (policy 1): 0 = the rank's ghost depth")
@@ -88,6 +91,13 @@ def main():
             abilib.fl_set_option(bq._lib.FL_OPT_RESERVE_CUS, a.reserve_cus)
             assert abilib.fl_get_option(bq._lib.FL_OPT_RESERVE_CUS) == a.reserve_cus and abilib.fl_last_error() == 0
         abilib.fl_set_option(bq._lib.FL_OPT_PROFILE_COMM, 1)
+    if a.jacobi_fuse is not None:
+        abilib.fl_set_option(8, a.jacobi_fuse)
+        assert abilib.fl_get_option(8) == a.jacobi_fuse
+    if a.jacobi_log:
+        assert a.backend == "cpu"
+        abilib.abi_jacobi_log.argtypes = [C.c_char_p]
+        abilib.abi_jacobi_log(a.jacobi_log.format(rank=rank).encode())
     if a.transport == "rccl":
         assert a.backend == "gpu"
         assert abilib.fl_comm_selftest() == 0, abilib.fl_last_error_string()
@@ -216,6 +226,8 @@ def main():
           f"p2p={tr.p2p_messages}msgs/{tr.p2p_floats}floats max|v|={moved:.4f} mismatches={bad}", flush=True)
     if tr.trace is not None and rank == 0:
         print(f"[rank 0] exchange trace (fields, depth, bytes per neighbour): {[t for t in tr.trace if not (t[0] == 1 and t[1] == a.ghost)]}", flush=True)
+    if a.jacobi_log:
+        abilib.abi_jacobi_log(None)
     ok = torch.tensor([bad])
     dist.all_reduce(ok)
     s.close()

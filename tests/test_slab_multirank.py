@@ -162,7 +162,7 @@ def test_wall_sheets_are_what_makes_the_default_exact_cpu():
 
 def test_tall_slabs_run_the_ends_first_chunks_cpu():
     """slabs of at least 2 G + 8 owned planes: the last two fused pairs of every pressure chunk run ends first and the
-    exchange for the next chunk starts before their interiors (fluid_solver.cpp: projection); G = 6 (three pairs per
+    exchange for the next chunk starts before their interiors (fluid_solver.cpp: projectionJacobiSlabs); G = 6 (three pairs per
     chunk) on two ranks, G = 8 (four pairs) on three"""
     rc, out = launch(2, "--backend", "cpu", "--dims", 24, 20, 64, "--ghost", 6, "--steps", 3, "--iters", 40)
     assert rc == 0, out
@@ -254,6 +254,24 @@ def test_tall_slabs_run_the_ends_first_chunks_gpu():
     rc, out = launch(3, "--backend", "gpu", "--dims", 24, 20, 96, "--ghost", 6, "--steps", 2, "--iters", 40, "--dt-cells", 1.0, threads=4)
     assert rc == 0, out
     assert out.count("mismatches=0") == 3
+
+
+@pytest.mark.gpu
+def test_ends_first_edge_gpu():
+    """24 owned planes = 2 G + 8, the shortest slab that runs ends first: the interiors of the two triples are 2 and 8 planes
+    (tests/test_slab_jacobi_trace_cpu.py pins the calls; here the real kernels take those ranges)"""
+    rc, out = launch(2, "--backend", "gpu", "--dims", 32, 32, 48, "--L", 1.0, "--ghost", 8, "--steps", 2, "--iters", 36, threads=4)
+    assert rc == 0, out
+    assert out.count("mismatches=0") == 2
+
+
+@pytest.mark.gpu
+def test_rows_wider_than_512_floats_fall_back_to_pairs_gpu():
+    """rows of 516 floats: the library refuses the chunk's first three-sweep launch and takes the pairs, so the host re-plans
+    the six sweeps as three pairs (ends first) and asks for no triple again in that projection; h = 1/32 as in the 32-cell cases"""
+    rc, out = launch(2, "--backend", "gpu", "--dims", 516, 12, 96, "--L", 16.125, "--ghost", 8, "--steps", 2, "--iters", 36, threads=4)
+    assert rc == 0, out
+    assert out.count("mismatches=0") == 2
 
 
 @pytest.mark.gpu
