@@ -8,7 +8,7 @@
 // rings blown along x by the reference's emitter velocity formula (main.cpp:52-73, emiter = +1 for both: the rear
 // ring catches up and threads the front one -- leapfrogging), no buoyancy, density dumped every frame.
 //
-//   make example && build/bimocq3d [N=128] [frames=20] [outdir=out] [scheme=0|2|3] [projection=0|1] [async=1] [scene=0|1] [walls=0] [diag_every=0] [preview_every=0] [tracers_per_cell=0] [paddle_spin=0] [confinement=0]
+//   make example && build/bimocq3d [N=128] [frames=20] [outdir=out] [scheme=0|2|3] [projection=0|1] [async=1] [scene=0|1] [walls=0] [diag_every=0] [preview_every=0] [tracers_per_cell=0] [paddle_spin=0] [confinement=0] [loads_every=0]
 // diag_every = N > 0: the flow diagnostics of every N-th frame (bq_solver_diagnostics' row: kinetic energy, enstrophy, ...) are
 // sampled on the device while the run goes on, printed one line per sampled frame at the end, and the vorticity magnitude of
 // those frames is dumped next to the density (vorticity_render_%04u.bqd)
@@ -19,6 +19,8 @@
 // paddle_spin = S != 0: a box paddle of half extents (0.3 L, 2 h, 0.15 L) at the centre of the domain (scenes.paddle of the Python
 // package) turns about the z axis at S rad per time unit in the rising smoke; updateBoundary every frame
 // confinement = E > 0: vorticity confinement with the dimensionless coefficient E
+// loads_every = N > 0 (with obstacles, i.e. a paddle): the pressure force and torque on every obstacle are
+// sampled on the device with every N-th frame and printed, one line per obstacle
 // walls: the closed sides (BQ_WALL_* bits of include/bimocq_gpu.h; 55 = the reference CPU solver's container, open at the top)
 #include <chrono>
 #include <cmath>
@@ -46,8 +48,9 @@ int main(int argc, char **argv)
     const int tracers_per_cell = argc > 11 ? std::atoi(argv[11]) : 0; // passive tracers per cell of the emitters' bounding cells (0: none)
     const float paddle_spin = argc > 12 ? (float)std::atof(argv[12]) : 0.f; // angular velocity of the paddle about z (0: no paddle)
     const float confinement = argc > 13 ? (float)std::atof(argv[13]) : 0.f; // vorticity confinement coefficient (0: none)
-    if (n < 8 || total_frame < 1 || !(confinement >= 0.f) || !std::isfinite(confinement) || diag_every < 0 || preview_every < 0 || tracers_per_cell < 0 || !std::isfinite(paddle_spin) || (scene == 1 && n % 2) || (scheme != 0 && scheme != 2 && scheme != 3)) {
-        std::fprintf(stderr, "usage: %s [N>=8] [frames] [outdir] [scheme: 0 BiMocq, 2 MacCormack, 3 reflection] [projection] [async] [scene] [walls] [diag_every] [preview_every] [tracers_per_cell] [paddle_spin] [confinement]\n", argv[0]); return 2;
+    const int loads_every = argc > 14 ? std::atoi(argv[14]) : 0;     // pressure loads on the obstacles every N-th frame (0: none)
+    if (n < 8 || total_frame < 1 || loads_every < 0 || !(confinement >= 0.f) || !std::isfinite(confinement) || diag_every < 0 || preview_every < 0 || tracers_per_cell < 0 || !std::isfinite(paddle_spin) || (scene == 1 && n % 2) || (scheme != 0 && scheme != 2 && scheme != 3)) {
+        std::fprintf(stderr, "usage: %s [N>=8] [frames] [outdir] [scheme: 0 BiMocq, 2 MacCormack, 3 reflection] [projection] [async] [scene] [walls] [diag_every] [preview_every] [tracers_per_cell] [paddle_spin] [confinement] [loads_every]\n", argv[0]); return 2;
     }
 
     const int ni = n, nj = n, nk = scene == 1 ? n / 2 : n;
@@ -115,6 +118,7 @@ int main(int argc, char **argv)
     }
     if (!mysolver.setVorticityConfinement(confinement)) { std::fprintf(stderr, "%s\n", fl_last_error_string()); return 1; }
     if (diag_every > 0 && !mysolver.setDiagnosticsEvery(diag_every)) { std::fprintf(stderr, "%s\n", fl_last_error_string()); return 1; }
+    if (loads_every > 0 && !mysolver.setObstacleLoads(loads_every)) { std::fprintf(stderr, "%s\n", fl_last_error_string()); return 1; }
     if (fl_last_error() != FL_OK) { std::fprintf(stderr, "%s\n", fl_last_error_string()); return 1; }
     if (tracers_per_cell > 0) std::printf("[ Tracers: %ld ]\n", mysolver.tracer_count);
     mysolver.verbose = true;                                         // "[Bimocq GPU Time: ...ms ]" like the reference
@@ -130,6 +134,15 @@ int main(int argc, char **argv)
             std::printf("[ Vorticity voxel: %ld ]\n", mysolver.outputVorticity((unsigned)i, filepath, 0.1f));
         if (preview_every > 0 && (i + 1) % preview_every == 0)         // eye looking along +z, light falling along -y
             std::printf("[ Preview bytes: %ld ]\n", mysolver.outputPreview((unsigned)i, filepath, /*view +z*/4, /*light -y*/3, 12.f, 1.f, 0.1f, 0.f));
+        if (loads_every > 0 && !mysolver.boundaries.empty() && (i + 1) % loads_every == 0) {
+            double row[BQ_OLOAD_ROW];
+            if (mysolver.obstacleLoads(row) == 1)
+                for (int o = 0; o < (int)row[BQ_OLOAD_N]; o++) {
+                    const double *q = row + BQ_OLOAD_HEADER + o * BQ_OLOAD_COUNT;
+                    std::printf("loads frame %d obstacle %d force %.9e %.9e %.9e torque %.9e %.9e %.9e area %.9e\n", i, o, q[BQ_OLOAD_FX],
+                                q[BQ_OLOAD_FY], q[BQ_OLOAD_FZ], q[BQ_OLOAD_TX], q[BQ_OLOAD_TY], q[BQ_OLOAD_TZ], q[BQ_OLOAD_AREA]);
+                }
+        }
         if (tracers_per_cell > 0)
             std::printf("[ Tracer bytes: %ld ]\n", mysolver.outputTracers((unsigned)i, filepath, BQ_F_RHO));
         if (fl_last_error() != FL_OK) { std::fprintf(stderr, "%s\n", fl_last_error_string()); return 1; }

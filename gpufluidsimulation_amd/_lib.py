@@ -176,6 +176,9 @@ HIP_SIGS = {
     # flow diagnostics: rho, T and vort_mag may be NULL, d_out is DEVICE memory
     "gpu_flow_stats": (c_i, [VP] * 6 + _G + [VP]),
     "gpu_vorticity_confinement": (c_i, [VP] * 6 + _G + [c_f, c_f]),
+    # per-obstacle pressure loads: p, p64 (exactly one non-NULL), solid, rows (may be NULL), the HOST
+    # bq_boundary list, n, h, dims, d_out in DEVICE memory (16 x 8 doubles)
+    "gpu_obstacle_loads": (c_i, [VP] * 5 + [c_i] + _G + [VP]),
     # shadowed density preview: rho, shadow (may be NULL without a light), h, dims, view, light, a HOST
     # pointer to three floats (sigma, albedo, ambient), d_image in DEVICE memory
     "gpu_render_density": (c_i, [VP, VP] + _G + [c_i, c_i, VP, VP]),
@@ -207,6 +210,10 @@ FL_OPT_CONFINE_KCHUNK = 24
 # rows of gpu_flow_stats' d_out (BQ_STAT_*)
 STAT_NAMES = ("e2", "m2", "d2", "div_max", "rho", "rho_i", "rho_j", "rho_k", "T", "vort_max")
 STAT_COUNT = len(STAT_NAMES)
+# columns of a row of gpu_obstacle_loads' d_out (BQ_LOAD_*); BQ_MAX_BOUNDARIES rows
+LOAD_NAMES = ("px", "py", "pz", "mx", "my", "mz", "faces", "psum")
+LOAD_COUNT = len(LOAD_NAMES)
+MAX_BOUNDARIES = 16
 
 
 class BimocqLibraryMissing(RuntimeError):

@@ -50,6 +50,7 @@
 #pragma weak gpu_flow_stats
 #pragma weak gpu_render_density
 #pragma weak gpu_vorticity_confinement
+#pragma weak gpu_obstacle_loads
 
 namespace bqhost {
 namespace slab = bq::slab;
@@ -221,12 +222,14 @@ void BimocqGPUSolver::setSmoke(float drop, float raise, const std::vector<Emitte
 void BimocqGPUSolver::advance(int framenum, float dt)
 {
     GpuSolver->startEventRecord();
+    if (loads_every > 0 && (steps_taken + 1) % loads_every == 0) beginLoadRow(dt);      // BQ_OPT_OBSTACLE_LOADS
     switch (myscheme) {
     case BIMOCQ: advanceBimocq(framenum, dt); break;
     case MAC_REFLECTION: advanceReflection(framenum, dt); break;
     case MACCORMACK: advanceMacCormack(framenum, dt); break;      // (the CPU solver's scheme, BimocqSolver.cpp:282-364)
     default: break;                                      // SEMILAG: refused by bq_solver_create
     }
+    if (load_open) endLoadRow();
     // FL_OPT_COMM_CHECK (debugging aid for the first runs on real links): every rank has issued this step's communicator
     // calls; compare the ledgers (include/bimocq_gpu.h: fl_comm_check)
     if (diagnostics_every > 0 && steps_taken % diagnostics_every == 0) sampleDiagnostics();     // BQ_OPT_DIAGNOSTICS_EVERY
@@ -1050,6 +1053,7 @@ bool BimocqGPUSolver::projectionObstacles(bool with_delta)
     if (where) p.swap(p_temp);
     if (walls) gpu_gradient_masked_walls(VelocityU, VelocityV, VelocityW, p, du, dv, dw, solidw.u8(), walls, g.ni, g.nj, g.nk, halfrdx);
     else       gpu_gradient_masked(VelocityU, VelocityV, VelocityW, p, du, dv, dw, solid.u8(), g.ni, g.nj, g.nk, halfrdx);
+    if (load_open && !boundaries.empty()) sampleLoads(p, nullptr);
     return with_delta;
 }
 
@@ -1075,6 +1079,7 @@ bool BimocqGPUSolver::projectionPcg()
     if (pcg_stats[3] != BQ_PCG_CONVERGED) pcg_unconverged++;
     if (walls) gpu_pcg_gradient_walls(VelocityU, VelocityV, VelocityW, mg.p.f64(), sol, walls, g.ni, g.nj, g.nk, (double)halfrdx);
     else       gpu_pcg_gradient(VelocityU, VelocityV, VelocityW, mg.p.f64(), sol, g.ni, g.nj, g.nk, (double)halfrdx);
+    if (load_open && obst) sampleLoads(nullptr, mg.p.f64());
     return false;
 }
 
@@ -1533,6 +1538,128 @@ long BimocqGPUSolver::outputResult(unsigned frame, const std::string &filepath)
     const size_t plane = (size_t)g.ni * g.nj;
     return write_density_dump(frame + 1, filepath, CellSize, host_density.data() + plane * sl.G, g.ni, g.nj,
                               sl.own1 - sl.own0, sl.own0, sl.nkg);
+}
+
+// ---- per-obstacle pressure loads ----------------------------------------------------------------
+bool BimocqGPUSolver::loadsOperator() { return gpu_obstacle_loads != nullptr; }
+
+// A refused value leaves the previous one in place; 0 is accepted everywhere.
+bool BimocqGPUSolver::setObstacleLoads(int n)
+{
+    if (n < 0) { fl_report_error(FL_ERR_BAD_ARGUMENT, "BQ_OPT_OBSTACLE_LOADS: a step count >= 0"); return false; }
+    if (n > 0) {
+        if (GpuSolver->slab.on) { fl_report_error(FL_ERR_UNSUPPORTED, "BQ_OPT_OBSTACLE_LOADS: obstacle loads are not supported on z-slab ranks"); return false; }
+        if (!loadsOperator()) { fl_report_error(FL_ERR_UNSUPPORTED, "BQ_OPT_OBSTACLE_LOADS: the operator library has no gpu_obstacle_loads"); return false; }
+        if (!load_ring.f64() && !load_ring.alloc((size_t)kLoadRing * 2 * kLoadSlot * sizeof(double))) return false;
+        load_ring_rows.resize(kLoadRing);
+    }
+    loads_every = n;
+    return true;
+}
+
+// the row of the step that is about to run: what the projections of this step share.  The reflection scheme's reflected
+// velocity 2 u_projected - u_unprojected applies the first projection's pressure gradient twice, so the fluid's net pressure
+// momentum change over the step is 2 J1 + J2; the other schemes project once.
+void BimocqGPUSolver::beginLoadRow(float dt)
+{
+    LoadRow r;
+    r.dt = (double)dt;
+    r.halfrdx = (double)halfrdx;
+    r.n = (int)boundaries.size();
+    if (myscheme == MAC_REFLECTION) { r.w[0] = 2.0; r.w[1] = 1.0; }
+    load_ring_rows[(size_t)(load_rows % kLoadRing)] = r;
+    load_open = true;
+    load_slot = 0;
+}
+
+// gpu_obstacle_loads on the pressure a projection has just produced (p after the ping-pong swap, or mg.p), the flags it used
+// and the list at its current centres, in stream order behind it
+void BimocqGPUSolver::sampleLoads(const float *pf, const double *pd)
+{
+    if (load_slot > 1) return;
+    const size_t row = (size_t)(load_rows % kLoadRing);
+    double *d_out = load_ring.f64() + (row * 2 + (size_t)load_slot) * kLoadSlot;
+    if (gpu_obstacle_loads(pf, pd, projectionFlags(), rows.u8(), boundaries.data(), (int)boundaries.size(), CellSize, g.ni, g.nj, g.nk,
+                           d_out) == FL_OK)
+        load_ring_rows[row].filled |= 1 << load_slot;
+    load_slot++;
+}
+
+void BimocqGPUSolver::endLoadRow()
+{
+    load_ring_rows[(size_t)(load_rows % kLoadRing)].step = steps_taken;
+    load_rows++;
+    load_open = false;
+}
+
+// the two raw slots of a row (unfilled ones already zeroed) -> the row a caller sees (include/bimocq_solver.h: BQ_OLOAD_*)
+void BimocqGPUSolver::loadRow(const LoadRow &r, const double *slots, double out[BQ_OLOAD_ROW]) const
+{
+    std::fill(out, out + BQ_OLOAD_ROW, 0.0);
+    out[BQ_OLOAD_STEP] = (double)r.step;
+    out[BQ_OLOAD_DT] = r.dt;
+    out[BQ_OLOAD_N] = (double)r.n;
+    const double h = (double)CellSize;
+    const double kf = r.dt != 0.0 ? r.halfrdx * (h * h * h) / r.dt : 0.0, kp = r.dt != 0.0 ? r.halfrdx * h / r.dt : 0.0;
+    // the step's last projection: slot 1 of a scheme that projects twice (w[1] != 0), whatever was filled -- a sample that was
+    // refused latched its error and reads 0 here like it does in the force
+    const double *last = slots + (r.w[1] != 0.0 ? kLoadSlot : 0);
+    for (int o = 0; o < r.n; o++) {
+        const double *s0 = slots + o * BQ_LOAD_COUNT, *s1 = slots + kLoadSlot + o * BQ_LOAD_COUNT, *sl = last + o * BQ_LOAD_COUNT;
+        double *q = out + BQ_OLOAD_HEADER + o * BQ_OLOAD_COUNT;
+        for (int a = 0; a < 6; a++) q[BQ_OLOAD_FX + a] = r.dt != 0.0 ? kf * (r.w[0] * s0[BQ_LOAD_PX + a] + r.w[1] * s1[BQ_LOAD_PX + a]) : 0.0;
+        q[BQ_OLOAD_AREA] = (h * h) * sl[BQ_LOAD_FACES];
+        q[BQ_OLOAD_P_MEAN] = (r.dt != 0.0 && sl[BQ_LOAD_FACES] != 0.0) ? kp * sl[BQ_LOAD_PSUM] / sl[BQ_LOAD_FACES] : 0.0;
+    }
+}
+
+// ring row `row` downloaded into slots (2 kLoadSlot doubles), the slots no projection filled zeroed
+static void download_load_row(const DeviceBytes &ring, size_t row, int filled, double *slots)
+{
+    fl_memcpy_d2h(slots, ring.f64() + row * 2 * BimocqGPUSolver::kLoadSlot, 2 * BimocqGPUSolver::kLoadSlot * sizeof(double));    // blocking, after the queued work
+    for (int s = 0; s < 2; s++)
+        if (!(filled & (1 << s))) std::fill(slots + s * BimocqGPUSolver::kLoadSlot, slots + (s + 1) * BimocqGPUSolver::kLoadSlot, 0.0);
+}
+
+long BimocqGPUSolver::obstacleLoadsRaw(long back, double *slots, double weights[2])
+{
+    const long kept = (long)std::min<long long>(load_rows, kLoadRing);
+    if (back < 0 || back >= kept) return -1;
+    const size_t row = (size_t)((load_rows - 1 - back) % kLoadRing);
+    const LoadRow &r = load_ring_rows[row];
+    download_load_row(load_ring, row, r.filled, slots);
+    if (fl_last_error() != FL_OK) return -1;
+    weights[0] = r.w[0]; weights[1] = r.w[1];
+    return r.step;
+}
+
+int BimocqGPUSolver::obstacleLoads(double out[BQ_OLOAD_ROW])
+{
+    if (load_rows == 0) return 0;
+    double slots[2 * kLoadSlot];
+    const size_t row = (size_t)((load_rows - 1) % kLoadRing);
+    download_load_row(load_ring, row, load_ring_rows[row].filled, slots);
+    if (fl_last_error() != FL_OK) return -1;
+    loadRow(load_ring_rows[row], slots, out);
+    return 1;
+}
+
+long BimocqGPUSolver::obstacleLoadsHistory(double *host, long capacity_rows)
+{
+    const long kept = (long)std::min<long long>(load_rows, kLoadRing);
+    if (!host || capacity_rows <= 0 || kept == 0) return kept;
+    const long long first = load_rows - kept;                       // oldest retained row
+    std::vector<double> raw((size_t)kLoadRing * 2 * kLoadSlot);
+    fl_memcpy_d2h(raw.data(), load_ring.f64(), raw.size() * sizeof(double));        // blocking, after the queued work
+    if (fl_last_error() != FL_OK) return -1;
+    for (long a = 0; a < std::min(kept, capacity_rows); a++) {
+        const size_t row = (size_t)((first + a) % kLoadRing);
+        double *slots = raw.data() + row * 2 * kLoadSlot;
+        for (int s = 0; s < 2; s++)
+            if (!(load_ring_rows[row].filled & (1 << s))) std::fill(slots + s * kLoadSlot, slots + (s + 1) * kLoadSlot, 0.0);
+        loadRow(load_ring_rows[row], slots, host + (size_t)a * BQ_OLOAD_ROW);
+    }
+    return kept;
 }
 
 // ---- flow diagnostics ---------------------------------------------------------------------------

@@ -226,6 +226,32 @@ public:
     DeviceField Vorticity;                          // scratch of vorticity(), allocated on first use
     std::vector<float> host_vorticity;
 
+    // Per-obstacle pressure loads: on a sampled step every projection that ran with obstacles is followed
+    // by one gpu_obstacle_loads call into a slot of a device ring (row = step, slot = which projection of the step); the host
+    // keeps what it needs to scale a row at read time.  With loads_every == 0 (default) nothing is allocated and a step
+    // issues exactly the launches it issues without this.
+    static constexpr int kLoadRing = 1024;          // rows of the device ring of BQ_OPT_OBSTACLE_LOADS
+    static constexpr int kLoadSlot = BQ_MAX_BOUNDARIES * BQ_LOAD_COUNT;    // doubles per slot; two slots per row
+    struct LoadRow {
+        int    step = 0, n = 0, filled = 0;         // filled: slots a projection of the step wrote (the others read 0)
+        double dt = 0.0, halfrdx = 0.0, w[2] = { 1.0, 0.0 };       // w[1] != 0: the scheme projects twice, slot 1 is its last
+    };
+    static bool loadsOperator();                    // the operator library has gpu_obstacle_loads
+    int  loads_every = 0;                           // BQ_OPT_OBSTACLE_LOADS
+    bool setObstacleLoads(int n);
+    int  obstacleLoads(double row[BQ_OLOAD_ROW]);   // the newest row; blocking; 1, 0 when there is none, -1 on error
+    long obstacleLoadsHistory(double *host, long capacity_rows);   // the retained rows, oldest first; blocking
+    long obstacleLoadsRaw(long back, double *slots, double weights[2]);    // STEP of that row or -1; blocking
+    void beginLoadRow(float dt);                    // advance(): opens the row of a sampled step
+    void sampleLoads(const float *p, const double *p64);           // after a projection with obstacles: the next slot
+    void endLoadRow();
+    void loadRow(const LoadRow &r, const double *slots, double out[BQ_OLOAD_ROW]) const;
+    DeviceBytes load_ring;                          // kLoadRing rows of 2 kLoadSlot doubles
+    std::vector<LoadRow> load_ring_rows;            // what the host keeps per ring row
+    long long load_rows = 0;                        // rows sampled so far
+    bool load_open = false;                         // a sampled step is running
+    int  load_slot = 0;                             // the slot its next projection fills
+
     // Shadowed density preview: gpu_render_density on the current density.  The shadow field and the
     // image buffer are allocated on the first call; advance() never touches any of this.
     static bool renderOperator();                   // the operator library has gpu_render_density

@@ -155,6 +155,8 @@ void bq_solver_set_option(bq_solver *s, int option, int value)
         s->solver->setDiagnosticsEvery(value);
     } else if (option == BQ_OPT_TRACER_SORT_EVERY) {
         s->solver->setTracerSortEvery(value);
+    } else if (option == BQ_OPT_OBSTACLE_LOADS) {
+        s->solver->setObstacleLoads(value);
     } else if (option == BQ_OPT_REINIT_POLICY) {
         s->solver->setReinitPolicy(value);
         s->solver->ScalarAdvector.keepDmcBorder = s->solver->VelocityAdvector.keepDmcBorder;
@@ -182,6 +184,7 @@ int bq_solver_get_option(const bq_solver *s, int option)
     case BQ_OPT_FUSED_MACCORMACK:    return s->solver->fused_maccormack;
     case BQ_OPT_DIAGNOSTICS_EVERY:   return s->solver->diagnostics_every;
     case BQ_OPT_TRACER_SORT_EVERY:   return s->solver->tracer_sort_every;
+    case BQ_OPT_OBSTACLE_LOADS:      return s->solver->loads_every;
     default:                         return -1;
     }
 }
@@ -414,6 +417,26 @@ long bq_solver_diagnostics_history(bq_solver *s, double *host, long capacity_row
 {
     BQ_ENTER(s);
     return s ? s->solver->diagnosticsHistory(host, capacity_rows) : 0;
+}
+
+int bq_solver_obstacle_loads(bq_solver *s, double row[BQ_OLOAD_ROW])
+{
+    BQ_ENTER(s);
+    if (!s || !row) return -1;
+    return s->solver->obstacleLoads(row);
+}
+
+long bq_solver_obstacle_loads_history(bq_solver *s, double *host, long capacity_rows)
+{
+    BQ_ENTER(s);
+    return s ? s->solver->obstacleLoadsHistory(host, capacity_rows) : 0;
+}
+
+long bq_solver_obstacle_loads_raw(bq_solver *s, long back, double slots[2 * 128], double weights[2])
+{
+    BQ_ENTER(s);
+    if (!s || !slots || !weights) return -1;
+    return s->solver->obstacleLoadsRaw(back, slots, weights);
 }
 
 long bq_solver_vorticity(bq_solver *s, float *host, long capacity)

@@ -257,6 +257,9 @@ HOST_SIGS = {
     "bq_solver_pcg_pressure": (C.c_long, [C.c_void_p, C.POINTER(C.c_double), C.c_long]),
     "bq_solver_diagnostics": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "bq_solver_diagnostics_history": (C.c_long, [C.c_void_p, C.POINTER(C.c_double), C.c_long]),
+    "bq_solver_obstacle_loads": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "bq_solver_obstacle_loads_history": (C.c_long, [C.c_void_p, C.POINTER(C.c_double), C.c_long]),
+    "bq_solver_obstacle_loads_raw": (C.c_long, [C.c_void_p, C.c_long, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "bq_solver_vorticity": (C.c_long, [C.c_void_p, C.c_void_p, C.c_long]),
     "bq_solver_output_vorticity": (C.c_long, [C.c_void_p, C.c_uint, C.c_char_p, C.c_float]),
     "bq_solver_render_size": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -280,6 +283,11 @@ OPT_FUSED_MACCORMACK = 15
 OPT_DIAGNOSTICS_EVERY = 16
 # setOption(OPT_TRACER_SORT_EVERY, N): the tracers are re-sorted by brick after every N-th advance() (0, the default: never)
 OPT_TRACER_SORT_EVERY = 17
+# setOption(OPT_OBSTACLE_LOADS, N): on every N-th advance() the pressure loads of every obstacle go into a device ring (obstacleLoads)
+OPT_OBSTACLE_LOADS = 18
+# a row of obstacleLoads (BQ_OLOAD_* of include/bimocq_solver.h): step, dt, n, then OLOAD_COUNT values per obstacle
+OLOAD_COUNT = 8
+OLOAD_ROW = 3 + _lib.MAX_BOUNDARIES * OLOAD_COUNT
 MAX_TRACERS = 1 << 26
 # the entries of a diagnostics row (BQ_DIAG_* of include/bimocq_solver.h), in order
 DIAG_NAMES = ("kinetic", "enstrophy", "div_l2", "div_max", "rho_sum", "centroid_x", "centroid_y", "centroid_z", "T_sum",
@@ -393,7 +401,8 @@ class BimocqGPUSolver:
         """option 1 = BQ_OPT_KEEP_DMC_BORDER, 2 = BQ_OPT_REINIT_POLICY (0 every frame, 1 distortion-driven),
         3 = BQ_OPT_FULL_STATE, 4 = BQ_OPT_FUSED_HOUSEKEEPING, 5 = BQ_OPT_OVERLAP_EXCHANGES, 6 = BQ_OPT_SHALLOW_BLOCKING_EXCHANGE,
         7 = BQ_OPT_JACOBI_ENDS_FIRST, 8 = BQ_OPT_PROFILE_PHASES, 9 = BQ_OPT_REINIT_MAX_TRAVEL, 10 = BQ_OPT_JACOBI_TRIPLES, 14 = BQ_OPT_NODE_LOOKUPS,
-        15 = BQ_OPT_FUSED_MACCORMACK, 16 = BQ_OPT_DIAGNOSTICS_EVERY, 17 = BQ_OPT_TRACER_SORT_EVERY (include/bimocq_solver.h)"""
+        15 = BQ_OPT_FUSED_MACCORMACK, 16 = BQ_OPT_DIAGNOSTICS_EVERY, 17 = BQ_OPT_TRACER_SORT_EVERY, 18 = BQ_OPT_OBSTACLE_LOADS
+        (include/bimocq_solver.h)"""
         self.lib.bq_solver_set_option(self.s, option, value)
         self._check()
 
@@ -541,6 +550,47 @@ class BimocqGPUSolver:
             self.lib.bq_solver_diagnostics_history(self.s, out.ctypes.data_as(C.POINTER(C.c_double)), n)
         self._check()
         return out
+
+    @staticmethod
+    def _loadsDict(row):
+        n = int(row[2])
+        per = np.array(row[3:3 + n * OLOAD_COUNT], dtype=np.float64).reshape(n, OLOAD_COUNT)
+        return {"step": int(row[0]), "dt": float(row[1]), "force": per[:, 0:3].copy(), "torque": per[:, 3:6].copy(),
+                "area": per[:, 6].copy(), "p_mean": per[:, 7].copy()}
+
+    def obstacleLoads(self):
+        """the newest row OPT_OBSTACLE_LOADS sampled, or None before the first one: a dict with `step`,
+        `dt`, and per obstacle `force` (n, 3) and `torque` (n, 3) about its centre -- what the pressure of the step's
+        projection(s) puts on the body, fluid density 1 --, `area` (n,) of its wetted faces and `p_mean` (n,) over them.
+        Pressure loads only (no viscous traction); with halfrdx = 1 the projection has its physical strength, the default 0.5
+        reports what that projection applied; the Jacobi pressure is as converged as its sweeps make it.  Blocking."""
+        row = (C.c_double * OLOAD_ROW)()
+        rc = self.lib.bq_solver_obstacle_loads(self.s, row)
+        self._check()
+        if rc < 0:
+            raise _lib.BimocqError("bq_solver_obstacle_loads failed")
+        return self._loadsDict(list(row)) if rc else None
+
+    def obstacleLoadsHistory(self):
+        """the rows OPT_OBSTACLE_LOADS retained (at most the last 1024), oldest first, as a list of obstacleLoads() dicts"""
+        n = self.lib.bq_solver_obstacle_loads_history(self.s, None, 0)
+        out = np.zeros((max(n, 0), OLOAD_ROW), dtype=np.float64)
+        if n > 0:
+            n = self.lib.bq_solver_obstacle_loads_history(self.s, out.ctypes.data_as(C.POINTER(C.c_double)), n)
+        self._check()
+        if n < 0:
+            raise _lib.BimocqError("bq_solver_obstacle_loads_history failed")
+        return [self._loadsDict(r) for r in out]
+
+    def obstacleLoadsRaw(self, back=0):
+        """for tests and tools: the raw sums of the row `back` rows before the newest as {"step", "slots": (2, 16, 8) float64
+        (gpu_obstacle_loads' d_out of the step's first and second projection; a slot the step did not fill is 0), "weights":
+        (w0, w1)}, or None when there is no such row"""
+        slots = np.zeros((2, _lib.MAX_BOUNDARIES, _lib.LOAD_COUNT), dtype=np.float64)
+        w = (C.c_double * 2)()
+        step = self.lib.bq_solver_obstacle_loads_raw(self.s, int(back), slots.ctypes.data_as(C.POINTER(C.c_double)), w)
+        self._check()
+        return None if step < 0 else {"step": int(step), "slots": slots, "weights": (w[0], w[1])}
 
     def vorticity(self):
         """the cell-centred vorticity magnitude of the local planes as a (nk_local, ny, nx) float32 array"""

@@ -1004,6 +1004,48 @@ int gpu_flow_stats(const float *u, const float *v, const float *w, const float *
 int gpu_vorticity_confinement(float *uo, float *vo, float *wo, const float *u, const float *v, const float *w,
                               float h, int ni, int nj, int nk, float eps, float dt);
 
+/* ---- per-obstacle pressure loads --------------------------------------------------------------------
+ * One pass over the owner-tagged cell flags that returns, per obstacle, the sums of the pressure over its wetted faces: what a
+ * caller scales into the force and the torque the fluid's pressure puts on the body.  Exactly one of p (float, the Jacobi
+ * pressure) and p64 (double, the PCG pressure) is non-NULL; each holds ni nj nk values, x fastest.  `solid`: the flags as
+ * gpu_obstacle_flags* / gpu_wall_flags write them.  `b`: the HOST list of n obstacles (only the centres are read).
+ *   own(c) = solid[c] & 0x7f.  Cell c is an OBSTACLE CELL of o when 1 <= own(c) <= n and o = own(c) - 1, with or without
+ *   BQ_FLAG_WALL (an obstacle in the border layer keeps its flag); a FLUID CELL when solid[c] == 0.  A cell with only
+ *   BQ_FLAG_WALL is neither, and so is a cell with own(c) > n (the list is shorter than the flags say: the cell is ignored and
+ *   never used as an index).
+ *   A WETTED FACE of o is a pair of face-adjacent cells (S, F), both inside the array, S an obstacle cell of o and F a fluid
+ *   cell.  Each is counted once.  Obstacle-obstacle pairs, obstacle-wall pairs and faces on the outside of the array are not
+ *   wetted; a border-layer fluid cell counts like any other (on an open side its p is 0).
+ * Per wetted face along axis a, with s = +1 when S has the higher index along a and -1 otherwise (+a s points from the fluid
+ * into the solid), every line one IEEE double operation (no contraction):
+ *   pf = (double)p[F];   f = s * pf
+ *   face centre x: along a ((double)(idx_a(S) + idx_a(F)) * 0.5) * (double)h, on the other two axes (double)idx * (double)h
+ *   r = x - ((double)b[o].cx, (double)b[o].cy, (double)b[o].cz)
+ *   P[a] += f
+ *   M += r x (f e_a):   a = x: My += rz*f, Mz -= ry*f;   a = y: Mz += rx*f, Mx -= rz*f;   a = z: Mx += ry*f, My -= rx*f
+ *   FACES += 1;   PSUM += pf
+ * d_out (DEVICE, BQ_MAX_BOUNDARIES x BQ_LOAD_COUNT doubles, row o = obstacle o in the order of BQ_LOAD_*): all 128 are written by
+ * every successful call, rows o >= n are 0.  Non-finite pressures propagate.  The result depends only on p at the F cells of
+ * wetted faces: p in solid cells, wall cells and fluid cells away from every obstacle never enters the arithmetic (a NaN there
+ * leaves no trace; no such value is multiplied by 0).
+ * `rows` (may be NULL): the rows summary of the obstacle flags as gpu_obstacle_flags writes it; rows with a zero byte are skipped
+ * without being read.  It changes what is read, not which terms are added or their order: the 128 doubles are the same bits
+ * with and without it.  No floating-point atomics: two calls on the same data return the same bits; the summation order is
+ * otherwise the kernel's own.
+ * What the sums mean: the masked gradient applies du = -halfrdx (p_c - p_left) on fluid-fluid faces only, so summing by parts
+ * over the fluid, halfrdx h^3 P is the momentum the obstacle's surface takes from the fluid (density 1) in that projection and
+ * halfrdx h^3 M the angular momentum about its centre.  The scaling is the caller's, in double.
+ * Asynchronous on the compute stream: two launches, nothing allocated beyond the library's scratch (the blocks' partials,
+ * blocks x n x 8 doubles), nothing synchronises once that scratch is large enough: like every operator that uses it, the
+ * first call that needs more than the scratch holds waits for the compute stream and reallocates it.
+ * Single GPU.  Nothing is launched and d_out is untouched on a refusal.  FL_ERR_BAD_ARGUMENT: both or neither of p / p64, NULL
+ * solid or d_out, n < 0 or n > BQ_MAX_BOUNDARIES, n > 0 with NULL b, a non-finite centre, h not finite or <= 0, a dimension
+ * below 3, the size limits above, d_out overlapping an input.  FL_ERR_UNSUPPORTED: a z-slab context (fl_set_slab).  n == 0 is
+ * allowed and writes 128 zeros.  Returns FL_OK or the error it latched. */
+enum { BQ_LOAD_PX = 0, BQ_LOAD_PY, BQ_LOAD_PZ, BQ_LOAD_MX, BQ_LOAD_MY, BQ_LOAD_MZ, BQ_LOAD_FACES, BQ_LOAD_PSUM, BQ_LOAD_COUNT };
+int gpu_obstacle_loads(const float *p, const double *p64, const unsigned char *solid, const unsigned char *rows,
+                       const bq_boundary *b, int n, float h, int ni, int nj, int nk, double *d_out);
+
 /* ---- shadowed density preview --------------------------------------------------------------------
  * An emission-absorption image of the density with single-scattering self-shadowing from one directional light; the view is
  * orthographic along a grid axis.  Directions are codes 0..5 = +x, -x, +y, -y, +z, -z: the direction a ray TRAVELS.  `view` is

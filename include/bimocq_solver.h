@@ -157,7 +157,16 @@ enum {
      * set of position arrays then exist.  0 (default, by measurement: DESIGN.md section 22): never, and neither exists.
      * Everything public is in id order and the same bits either way.  FL_ERR_BAD_ARGUMENT for N < 0, FL_ERR_UNSUPPORTED for
      * N > 0 where tracers are (z-slab ranks, an operator library without the tracer operators). */
-    BQ_OPT_TRACER_SORT_EVERY = 17
+    BQ_OPT_TRACER_SORT_EVERY = 17,
+    /* N > 0: on every N-th advance() (advance() calls so far % N == 0, as for BQ_OPT_DIAGNOSTICS_EVERY) each projection of the
+     * step that ran with a non-empty obstacle list is followed, in stream order and with no host sync, by one
+     * gpu_obstacle_loads call (include/bimocq_gpu.h) on the pressure that projection produced, the flags it used and the list
+     * at its current centres, into a slot of a device ring of 1024 rows of two slots; read them with
+     * bq_solver_obstacle_loads / _history.  A sampled step with an empty list records a row with N = 0 and launches nothing.
+     * 0 (default): nothing is launched or allocated and a step is exactly what it was.  Refused, the previous value staying
+     * in place: N < 0 with FL_ERR_BAD_ARGUMENT; N > 0 on z-slab ranks or on an operator library without gpu_obstacle_loads
+     * with FL_ERR_UNSUPPORTED. */
+    BQ_OPT_OBSTACLE_LOADS = 18
 };
 /* BQ_OPT_PROFILE_PHASES: milliseconds per phase summed over the steps since the last reset -- map update (DMC + RK3,
  * BimocqGPUSolver.cpp:136-139), advection with error compensation (:143-145), sources and forces (:157-177), projection
@@ -281,6 +290,33 @@ int   bq_solver_diagnostics(bq_solver *s, double out[BQ_DIAG_COUNT]);
  * bq_solver_diagnostics' layout with STEP = the step the sample followed.  Blocking.  Returns the number of retained rows
  * and copies min(rows, capacity_rows) of them when host != NULL. */
 long  bq_solver_diagnostics_history(bq_solver *s, double *host, long capacity_rows);
+/* Per-obstacle pressure loads (BQ_OPT_OBSTACLE_LOADS): the force and the torque about its centre that
+ * the pressure of a step's projection(s) puts on every obstacle, from the raw sums P, M, FACES, PSUM of gpu_obstacle_loads.
+ * BiMocq and MacCormack project once per step and fill slot 0 of a row; the reflection scheme projects twice and fills slot 0
+ * at its first projection and slot 1 at its second.  The slot weights (w0, w1) are (1, 0) for the one-projection schemes and
+ * (2, 1) for the reflection scheme: its reflected velocity 2 u_projected - u_unprojected applies the first projection's
+ * pressure gradient twice, so the fluid's net pressure momentum change over the step is 2 J1 + J2.
+ * A row is BQ_OLOAD_ROW doubles, computed on the host in double at read time: STEP (advance() calls so far when it was
+ * sampled), DT, N (obstacles), then per obstacle o < N the BQ_OLOAD_COUNT values
+ *   FX, FY, FZ = halfrdx h^3 / dt (w0 P0 + w1 P1)        TX, TY, TZ likewise from M (about the centre the projection used)
+ *   AREA = h^2 FACES of the step's last projection        P_MEAN = halfrdx h / dt PSUM / FACES of it (0 without faces)
+ * (the six loads and P_MEAN are 0 when dt == 0); the entries of obstacles o >= N are 0.  The values survive a later
+ * set_boundary: a row keeps the N, halfrdx and weights it was sampled with.  "Last projection": slot 1 when w1 != 0.
+ * Limits: pressure loads only, no viscous traction; halfrdx = 1 is the physical projection strength, the default 0.5
+ * reports what that projection actually applied; the Jacobi pressure is as converged as its sweeps make it, BQ_PROJECTION_PCG
+ * is the converged one; one GPU.
+ * obstacle_loads: the newest sampled row; blocking; 1, 0 when none has been sampled yet, -1 on error.
+ * obstacle_loads_history: the retained rows (at most the last 1024), oldest first; blocking; returns their number and copies
+ * min(rows, capacity_rows) of them when host != NULL.
+ * obstacle_loads_raw (for tests and tools): the two raw slots (BQ_MAX_BOUNDARIES x BQ_LOAD_COUNT doubles each; a slot the
+ * step did not fill reads 0) and the weights of the row `back` rows before the newest; returns its STEP, or -1 when there
+ * is no such row or on error.  Blocking. */
+enum { BQ_OLOAD_STEP = 0, BQ_OLOAD_DT, BQ_OLOAD_N, BQ_OLOAD_HEADER };
+enum { BQ_OLOAD_FX = 0, BQ_OLOAD_FY, BQ_OLOAD_FZ, BQ_OLOAD_TX, BQ_OLOAD_TY, BQ_OLOAD_TZ, BQ_OLOAD_AREA, BQ_OLOAD_P_MEAN, BQ_OLOAD_COUNT };
+enum { BQ_OLOAD_ROW = 3 + BQ_MAX_BOUNDARIES * BQ_OLOAD_COUNT };
+int   bq_solver_obstacle_loads(bq_solver *s, double row[BQ_OLOAD_ROW]);
+long  bq_solver_obstacle_loads_history(bq_solver *s, double *host, long capacity_rows);
+long  bq_solver_obstacle_loads_raw(bq_solver *s, long back, double slots[2 * 128], double weights[2]);
 /* the cell-centred vorticity magnitude |omega| of the LOCAL planes (nk_local * ny * nx, x fastest; border cells 0) through a
  * scratch field that is allocated on the first call.  Returns the element count (host == NULL: only that) and copies
  * min(count, capacity); -1 on error.  Blocking. */
