@@ -25,6 +25,7 @@
 #include <type_traits>
 #include "bq_host.h"
 #include "bq_jacobi_plan.h"
+#include "bq_mgcg_slab_plan.h"
 
 #include <cstdint>
 
@@ -1907,15 +1908,13 @@ void gpu_multi_grid_conjugate_gradient(float *u, float *v, float *w, double *div
     BQ_LAUNCH_CHECK("mg_gradient_kernel");
 }
 
-// 1 when gpu_multi_grid_conjugate_gradient_slab can run this decomposition (bq_mgcg_slab.hip.inc: requirements), else 0
+// 1 when gpu_multi_grid_conjugate_gradient_slab can run this decomposition, else 0: the plan's answer (bq_mgcg_slab_plan.h), which
+// depends on the grid, the ghost depth and the NUMBER of ranks only -- the callers choose between two collectives by it, so every
+// rank must get the same.  rank, own0, own1 only have to describe the equal slabs the plan assumes; pass the communicator's
+// rank and size (fl_comm_rank, fl_comm_size), which is what the operator itself consults.
 int gpu_mgcg_slab_supported(int ni, int nj, int nkg, int own0, int own1, int ghost, int rank, int nranks)
 {
-    if (nranks < 2 || ni < 8 || nj < 8 || nkg < 8 || rank < 0 || rank >= nranks) return 0;
-    if (((long long)ni * nj) % 256 != 0) return 0;                  // block dot products: slab boundaries must be block boundaries
-    if (nkg % nranks != 0 || own0 != rank * (nkg / nranks) || own1 != own0 + nkg / nranks) return 0;
-    if (own0 % 8 != 0 || own1 - own0 < 17 || ghost < 8) return 0;   // even ranges on three levels, G = 8 on level 0 inside the velocity's ghosts
-    if ((double)ni * nj * (own1 - own0 + 16) * 8.0 >= 2147483648.0) return 0;
-    return 1;
+    return mgslab::supported(ni, nj, nkg, own0, own1, ghost, rank, nranks) ? 1 : 0;
 }
 
 // gpu_multi_grid_conjugate_gradient (GPU_kernel.cu:1764-1815) on a z-slab rank, the grid's levels shared between the ranks.
@@ -1931,9 +1930,10 @@ void gpu_multi_grid_conjugate_gradient_slab(float *u, float *v, float *w, double
     BQ_REQUIRE(u && v && w && tempResult && iter >= 0, op);
     BQ_REQUIRE(2 * iter + 2 < 2000 && 2001 + iter <= 4096, op);
     const int rank = fl_comm_rank(), nranks = fl_comm_size();
-    if (!gpu_mgcg_slab_supported(ni, nj, nkg, own0, own1, ghost, rank, nranks)) { latch(FL_ERR_UNSUPPORTED, op, "geometry not supported (gpu_mgcg_slab_supported)"); return; }
+    const mgslab::Plan plan = mgslab::make_plan(ni, nj, nkg, ghost, rank, nranks);
+    if (!plan.supported || !mgslab::rank_args_match(nkg, own0, own1, rank, nranks)) { latch(FL_ERR_UNSUPPORTED, op, "geometry not supported (gpu_mgcg_slab_supported)"); return; }
     SlabMg &m = ms().slab;
-    if (!slab_mg_setup(m, ni, nj, nkg, own0, own1, rank, nranks)) { if (rt().err == FL_OK) latch(FL_ERR_UNSUPPORTED, op, "levels too thin to share"); return; }
+    if (!slab_mg_setup(m, plan)) { if (rt().err == FL_OK) latch(FL_ERR_HIP, op, "allocation of the slab levels failed"); return; }
     const SlabLevel &L0 = m.lv[0];
     const int nkl = L0.nkl(), ulo = own0 - ghost;
     const size_t pd = L0.plane(), n0 = pd * (size_t)nkl;
@@ -1974,7 +1974,7 @@ void gpu_multi_grid_conjugate_gradient_slab(float *u, float *v, float *w, double
         BQ_LAUNCH_CHECK("mg_update_dir_kernel");
     }
     // p is correct on every stored plane (the cycle's last exchange + elementwise updates); the gradient needs p(k - 1)
-    const int k_first = std::max(L0.lo + 1, 2), k_end = std::min(L0.hi, nkg);
+    const int k_first = plan.k_first, k_end = plan.k_end;
     if (k_end > k_first) {
         mg_gradient_slab_kernel<<<grid_for(ni + 1, nj + 1, k_end - k_first), kBlock, 0, st>>>(u, v, w, m.p, ni, nj, nkg, L0.lo, k_end, ulo, k_first, halfrdx);
         BQ_LAUNCH_CHECK("mg_gradient_slab_kernel");

@@ -26,13 +26,11 @@
 //   * the transfer operators index the coarse array by flat index with the reference's wrap at row and plane ends (M4): a range
 //     that starts at an even fine plane f0 pairs with the coarse range that starts at f0 / 2, and whatever a wrap reaches beyond a
 //     range's last plane only ever feeds the outermost ghost planes.
-// Requirements (else the caller keeps the replicated path): planes of a multiple of 256 cells, own0 a multiple of 8, at least
-// 17 owned planes on level 0.
-struct SlabLevel {
-    int ni = 0, nj = 0, nk = 0;             // global dims of the level
-    int own0 = 0, own1 = 0;                 // planes this rank owns
-    int lo = 0, hi = 0;                     // planes it stores
-    int G = 0;                              // ghost depth both neighbours exchange at
+// Requirements (else the caller keeps the replicated path): planes of a multiple of 256 cells, equal slabs of a multiple of 8
+// planes, at least 17 of them -- the same answer on every rank.  The predicate, the pyramid, every plane range and every count
+// or offset derived from them are stated once in bq_mgcg_slab_plan.h (host-only, swept on the CPU by
+// tests/test_mgcg_slab_plan_cpu.py); this file allocates and launches by that plan and computes no geometry of its own.
+struct SlabLevel : mgslab::Level {          // dims, owned / stored planes, ghost depth, transfer and exchange numbers: the plan's
     double alpha = -1.0, beta = 1.0 / 6.0;
     double *x = nullptr, *b = nullptr, *r = nullptr;
     size_t plane() const { return (size_t)ni * nj; }
@@ -41,7 +39,8 @@ struct SlabLevel {
 
 struct SlabMg {
     bool ready = false;
-    int ni = 0, nj = 0, nkg = 0, own0 = 0, own1 = 0, rank = 0, nranks = 1;
+    mgslab::Plan plan;                      // what everything below was allocated by
+    int nranks = 1;
     int LS = 0;                             // levels [0, LS) are shared, [LS, levels) replicated
     int nlevels = 0;
     SlabLevel lv[LEVEL_COUNT];
@@ -51,7 +50,6 @@ struct SlabMg {
     double *temp_full = nullptr;            // ping-pong buffer of the replicated levels' smoothing
     double *partials = nullptr;             // one per 256-cell block of the GLOBAL level-0 array
     std::vector<void *> owned;              // everything allocated here
-    std::vector<int> own0_of, own1_of;      // level-0 ownership of every rank (for the gathers)
 };
 
 static void slab_mg_release(SlabMg &m)
@@ -69,13 +67,6 @@ static double *slab_alloc(SlabMg &m, size_t doubles)
     return (double *)p;
 }
 
-// planes of level l + 1 owned by the owner of the fine planes [a, b): K with 2 K + 1 in [a, b), inside [0, nkc)
-static inline void coarse_own(int a, int b, int nkc, int *c0, int *c1)
-{
-    *c0 = std::min(nkc, std::max(0, a / 2));        // 2 K + 1 >= a  <=>  K >= (a - 1) / 2, rounded up: a / 2 for either parity
-    *c1 = std::min(nkc, std::max(0, b / 2));        // 2 K + 1 <  b  <=>  K <  (b - 1) / 2 rounded up = b / 2
-}
-
 // refresh `depth` ghost planes of a level's array on both sides (blocking for the compute stream)
 static void slab_exchange(const SlabLevel &L, double *arr, int depth)
 {
@@ -85,11 +76,11 @@ static void slab_exchange(const SlabLevel &L, double *arr, int depth)
     // at the grid's end starts later, so the base is moved back by the planes that do not exist (never touched: the rank
     // there has no neighbour on that side)
     const size_t pd = L.plane();
-    float *base = (float *)(arr - (ptrdiff_t)pd * (ptrdiff_t)(L.G - (L.own0 - L.lo)));
+    float *base = (float *)(arr - (ptrdiff_t)pd * (ptrdiff_t)L.xch_shift);
     float *fields[1] = { base };
     const size_t pe[1] = { pd * 2 };
     const int extra[1] = { 0 };
-    fl_halo_exchange(1, fields, pe, extra, (L.own1 - L.own0) + 2 * L.G, L.G, depth, 1);
+    fl_halo_exchange(1, fields, pe, extra, L.xch_nk_local, L.G, depth, 1);
 }
 
 // `iter` (even) smoothing sweeps of level L on its stored range, ghost planes refreshed every G sweeps.  x_zero: x counts as
@@ -118,14 +109,13 @@ static void slab_gather_planes(const SlabMg &m, int l, const double *local, doub
     if (m.nranks <= 1) return;
     std::vector<int> peers; std::vector<float *> send, recv; std::vector<size_t> sc, rc;
     for (int r = 0; r < m.nranks; r++) {
-        if (r == m.rank) continue;
-        int a = m.own0_of[(size_t)r], b = m.own1_of[(size_t)r];
-        for (int q = 0; q < l; q++) { int c0, c1; coarse_own(a, b, m.lv[q + 1].nk, &c0, &c1); a = c0; b = c1; }
+        if (r == m.plan.rank) continue;
+        const mgslab::Range o = m.plan.own(r, l);
         peers.push_back(r);
         send.push_back((float *)(local + pd * (size_t)(L.own0 - L.lo)));
         sc.push_back(pd * 2 * (size_t)(L.own1 - L.own0));
-        recv.push_back((float *)(full + pd * (size_t)a));
-        rc.push_back(pd * 2 * (size_t)std::max(0, b - a));
+        recv.push_back((float *)(full + pd * (size_t)o.a));
+        rc.push_back(pd * 2 * (size_t)std::max(0, o.b - o.a));
     }
     fl_p2p_exchange((int)peers.size(), peers.data(), send.data(), sc.data(), recv.data(), rc.data());
 }
@@ -135,17 +125,16 @@ static void slab_dot(const SlabMg &m, const double *v0, const double *v1, double
 {
     const SlabLevel &L = m.lv[0];
     const size_t pd = L.plane(), off = pd * (size_t)(L.own0 - L.lo), own_cells = pd * (size_t)(L.own1 - L.own0);
-    const size_t total = pd * (size_t)L.nk;
-    const unsigned nb_own = blocks1d(own_cells), nb = blocks1d(total);
-    const size_t first = pd * (size_t)L.own0 / 256;                     // (planes are multiples of 256 cells)
+    const unsigned nb_own = (unsigned)m.plan.dot_nb_own, nb = (unsigned)m.plan.dot_nb;
+    const size_t first = (size_t)m.plan.dot_first;                      // (planes are multiples of 256 cells)
     hipStream_t st = rt().compute;
     mg_dot_kernel<<<nb_own, 256, 0, st>>>(v0 + off, v1 + off, m.partials + first, own_cells);
     BQ_LAUNCH_CHECK("mg_dot_kernel");
     if (m.nranks > 1) {
         std::vector<int> peers; std::vector<float *> send, recv; std::vector<size_t> sc, rc;
         for (int r = 0; r < m.nranks; r++) {
-            if (r == m.rank) continue;
-            const size_t f = pd * (size_t)m.own0_of[(size_t)r] / 256, n = pd * (size_t)(m.own1_of[(size_t)r] - m.own0_of[(size_t)r]) / 256;
+            if (r == m.plan.rank) continue;
+            const size_t f = (size_t)m.plan.dot_first_of(r), n = (size_t)m.plan.dot_nb_of(r);
             peers.push_back(r);
             send.push_back((float *)(m.partials + first)); sc.push_back((size_t)nb_own * 2);
             recv.push_back((float *)(m.partials + f));     rc.push_back(n * 2);
@@ -182,48 +171,24 @@ __global__ __launch_bounds__(256) void mg_gradient_slab_kernel(float *__restrict
     }
 }
 
-static bool slab_mg_setup(SlabMg &m, int ni, int nj, int nkg, int own0, int own1, int rank, int nranks)
+static bool same_plan(const mgslab::Plan &a, const mgslab::Plan &b)
 {
-    if (m.ready && m.ni == ni && m.nj == nj && m.nkg == nkg && m.own0 == own0 && m.own1 == own1 && m.rank == rank && m.nranks == nranks) return true;
+    return a.ni == b.ni && a.nj == b.nj && a.nkg == b.nkg && a.ghost == b.ghost && a.rank == b.rank && a.nranks == b.nranks;
+}
+
+// the arrays of a supported plan (the caller has checked plan.supported: nothing here depends on the geometry any more, what can
+// still fail is an allocation)
+static bool slab_mg_setup(SlabMg &m, const mgslab::Plan &plan)
+{
+    if (m.ready && same_plan(m.plan, plan)) return true;
     (void)hipStreamSynchronize(rt().compute);
     slab_mg_release(m);
-    m.ni = ni; m.nj = nj; m.nkg = nkg; m.own0 = own0; m.own1 = own1; m.rank = rank; m.nranks = nranks;
-    m.own0_of.resize((size_t)nranks); m.own1_of.resize((size_t)nranks);
-    for (int r = 0; r < nranks; r++) { m.own0_of[(size_t)r] = (int)((long long)r * nkg / nranks); m.own1_of[(size_t)r] = (int)((long long)(r + 1) * nkg / nranks); }
-    // the pyramid and how deep it can be shared: every rank needs G_l + 1 owned planes on a shared level (fl_halo_exchange)
-    int di = ni, dj = nj, dk = nkg, nl = 0;
-    for (int l = 0; l < LEVEL_COUNT; l++) {
-        if (l) { di = (di - 1) / 2; dj = (dj - 1) / 2; dk = (dk - 1) / 2; }
-        if (di < 1 || dj < 1 || dk < 1) break;
-        m.lv[l].ni = di; m.lv[l].nj = dj; m.lv[l].nk = dk;
-        nl++;
-    }
-    m.nlevels = nl;
-    int LS = 0;
-    {
-        std::vector<int> a(m.own0_of), b(m.own1_of);
-        for (int l = 0; l < nl && l < 3; l++) {
-            if (l) for (int r = 0; r < nranks; r++) { int c0, c1; coarse_own(a[(size_t)r], b[(size_t)r], m.lv[l].nk, &c0, &c1); a[(size_t)r] = c0; b[(size_t)r] = c1; }
-            int fewest = 1 << 30;
-            for (int r = 0; r < nranks; r++) fewest = std::min(fewest, b[(size_t)r] - a[(size_t)r]);
-            int G = std::min(8, fewest - 1);
-            G -= G % 2;
-            if (G < 4 || l + 1 >= nl) break;            // too thin to share (and the coarsest level is never shared)
-            m.lv[l].G = G;
-            LS = l + 1;
-        }
-    }
-    if (LS < 1) return false;
-    m.LS = LS;
-    // ranges: ownership nests; a shared level stores own +- G clipped to the grid, with lo even on every level but the last
-    // shared one (transfer operators pair a fine range that starts at an even plane with the coarse range that starts at half of it)
-    int a = own0, b = own1;
+    m.plan = plan;
+    m.nranks = plan.nranks; m.nlevels = plan.nlevels; m.LS = plan.LS;
+    const int LS = plan.LS, nl = plan.nlevels;
+    for (int l = 0; l < nl; l++) static_cast<mgslab::Level &>(m.lv[l]) = plan.lv[l];
     for (int l = 0; l < LS; l++) {
         SlabLevel &L = m.lv[l];
-        if (l) { int c0, c1; coarse_own(a, b, L.nk, &c0, &c1); a = c0; b = c1; }
-        L.own0 = a; L.own1 = b;
-        L.lo = std::max(0, a - L.G); L.hi = std::min(L.nk, b + L.G);
-        if (L.lo % 2) L.lo -= 1;                        // (a - G is even whenever a is; a clipped range starts at 0)
         const size_t cells = L.plane() * (size_t)L.nkl();
         L.x = slab_alloc(m, cells); L.b = slab_alloc(m, cells); L.r = slab_alloc(m, cells);
         if (!L.x || !L.b || !L.r) return false;
@@ -239,15 +204,8 @@ static bool slab_mg_setup(SlabMg &m, int ni, int nj, int nkg, int own0, int own1
     }
     m.temp_full = slab_alloc(m, biggest);
     if (!m.temp_full) return false;
-    {   // the first replicated level as the gather sees it: this rank's planes of it (nesting), stored in full
-        SlabLevel &C = m.lv[LS];
-        int c0, c1;
-        coarse_own(a, b, C.nk, &c0, &c1);
-        C.own0 = c0; C.own1 = c1; C.lo = 0; C.hi = C.nk; C.G = 0;
-    }
-    // a fine range [lo, hi) samples the coarse range that starts at lo / 2: it must be stored
-    for (int l = 0; l + 1 < LS; l++)
-        if (m.lv[l + 1].lo > m.lv[l].lo / 2) { latch(FL_ERR_UNSUPPORTED, "slab multigrid", "coarse ghost range too shallow for the fine one"); return false; }
+    // (level LS, the first replicated one, carries this rank's planes of it as the gather sees them, stored in full; that a fine
+    // range [lo, hi) finds the coarse range from lo / 2 on stored is part of plan.supported, for every rank alike)
     const SlabLevel &L0 = m.lv[0];
     const size_t c0 = L0.plane() * (size_t)L0.nkl();
     m.div = slab_alloc(m, c0); m.p = slab_alloc(m, c0); m.dir = slab_alloc(m, c0); m.residual = slab_alloc(m, c0);
@@ -278,11 +236,9 @@ static void slab_v_cycle(SlabMg &m, bool last_iteration)
         slab_exchange(L, L.x, L.G);
         mg_residual(L.r, rhs(l), L.x, L.ni, L.nj, L.nkl());
         // restriction onto the next level's OWNED planes; the fine range starts at twice the first coarse plane
-        int c0, c1;
-        coarse_own(L.own0, L.own1, m.lv[l + 1].nk, &c0, &c1);
-        const int ci = m.lv[l + 1].ni, cj = m.lv[l + 1].nj, ck = c1 - c0;
-        const double *fine = L.r + L.plane() * (size_t)(2 * c0 - L.lo);
-        const int fine_planes = L.hi - 2 * c0;
+        const int c0 = L.rest_c0, ck = L.rest_ck, fine_planes = L.rest_fine_planes;
+        const int ci = m.lv[l + 1].ni, cj = m.lv[l + 1].nj;
+        const double *fine = L.r + L.plane() * (size_t)(L.rest_fine0 - L.lo);
         if (l + 1 < LS) {
             SlabLevel &C = m.lv[l + 1];
             if (ck > 0)
@@ -337,12 +293,11 @@ static void slab_v_cycle(SlabMg &m, bool last_iteration)
         if (l + 1 < LS) {
             SlabLevel &C = m.lv[l + 1];
             slab_exchange(C, C.x, C.G);
-            coarse = C.x + C.plane() * (size_t)(L.lo / 2 - C.lo);
-            ck = C.hi - L.lo / 2;
+            coarse = C.x + C.plane() * (size_t)(L.prol_c0 - C.lo);
         } else {
-            coarse = m.full[l + 1].x + (size_t)ci * cj * (size_t)(L.lo / 2);
-            ck = m.lv[l + 1].nk - L.lo / 2;
+            coarse = m.full[l + 1].x + (size_t)ci * cj * (size_t)L.prol_c0;
         }
+        ck = L.prol_ck;
         mg_prolong_kernel<<<grid_for(L.ni, L.nj, L.nkl()), kBlock, 0, st>>>(L.x, coarse, L.ni, L.nj, L.nkl(), ci, cj, ck);
         BQ_LAUNCH_CHECK("mg_prolong_kernel");
         slab_exchange(L, L.x, L.G);

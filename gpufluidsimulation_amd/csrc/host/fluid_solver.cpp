@@ -748,18 +748,28 @@ bool BimocqGPUSolver::projectionMgcgSlabs()
 // The multigrid-CG projection on z-slab ranks with the fine levels SHARED (round 4: include/bimocq_gpu.h,
 // gpu_multi_grid_conjugate_gradient_slab; csrc/bq_mgcg_slab.hip.inc): nothing global is allocated here -- the operator owns its
 // per-level slab arrays -- and the velocity needs its ghost planes only as deep as level 0's (8).  false when the decomposition
-// is not covered (planes that are not a multiple of 256 cells, thin or unaligned slabs, the CPU stand-in): the caller falls
-// back to the replicated solve, which is bit-identical.
+// is not covered (planes that are not a multiple of 256 cells, thin slabs or slabs of no multiple of 8 planes, the CPU
+// stand-in): the caller falls back to the replicated solve, which is bit-identical.  Both are collectives, so the choice must
+// be the same on every rank: the predicate is asked with the communicator's rank and size -- exactly what the operator will
+// consult (csrc/bq_mgcg_slab_plan.h: an answer that depends on the grid and the number of ranks alone) -- and an operator that
+// refuses all the same (FL_ERR_UNSUPPORTED: the predicate or the plan, computed alike on every rank) is not a projection: the
+// error is cleared and the replicated solve runs.  Any other error stays latched, and nothing counts as projected.
 bool BimocqGPUSolver::projectionMgcgShared()
 {
     gpuMapper &gs = *GpuSolver;
     const SlabCtx &sl = gs.slab;
     mgcg_shared_ran = false;
-    if (!mgcg_shared || !gpu_mgcg_slab_supported(g.ni, g.nj, sl.nkg, sl.own0, sl.own1, sl.G, sl.rank, sl.nranks)) return false;
+    if (!mgcg_shared || !gpu_mgcg_slab_supported(g.ni, g.nj, sl.nkg, sl.own0, sl.own1, sl.G, fl_comm_rank(), fl_comm_size())) return false;
     if (mg.result.bytes() < 4096 * sizeof(double) && !mg.result.alloc(4096 * sizeof(double))) return false;
     gs.require({ &VelocityU, &VelocityV, &VelocityW }, sl.G);
+    const int before = fl_last_error();                     // (an earlier failure stays what it is: the refusal below cannot be told from it)
     gpu_multi_grid_conjugate_gradient_slab(VelocityU, VelocityV, VelocityW, mg.result.f64(), g.ni, g.nj, sl.nkg, sl.own0, sl.own1, sl.G,
                                            mg_iters, (double)halfrdx);
+    if (const int err = before == FL_OK ? fl_last_error() : FL_OK) {
+        if (err != FL_ERR_UNSUPPORTED) return true;         // local to this rank (an allocation): latched, nothing projected
+        fl_clear_error();
+        return false;
+    }
     // projected on the owned planes and on the 7 ghost planes next to them (the gradient needs p one plane below)
     const int depth = std::min(sl.G, 8) - 1;
     gs.produced(VelocityU, depth); gs.produced(VelocityV, depth); gs.produced(VelocityW, depth);

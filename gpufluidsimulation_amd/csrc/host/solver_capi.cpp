@@ -357,7 +357,8 @@ void bq_solver_slab_info(const bq_solver *s, int out[8])
 long bq_solver_mg_history(const bq_solver *s, double *host, long capacity)
 {
     BQ_ENTER(s);
-    if (!s || !s->solver->mg.ready) return 0;
+    // (the shared solve on slab ranks owns its vectors: only tempResult is allocated here, mg.ready stays false)
+    if (!s || (!s->solver->mg.ready && s->solver->mg.result.bytes() < 4096 * sizeof(double))) return 0;
     const std::vector<double> h = s->solver->mgHistory();
     if (host)
         for (long a = 0; a < capacity && a < (long)h.size(); a++) host[a] = h[(size_t)a];

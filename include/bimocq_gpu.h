@@ -599,9 +599,11 @@ int gpu_diffuse_sweeps(const float *field, float *in, float *out, int ni, int nj
  *   u, v, w      the rank's LOCAL velocity buffers, planes [own0 - ghost, own1 + ghost) (w one more), ghost planes correct
  *   tempResult   device, 4096 doubles: the reference's residual history (identical on every rank)
  * Collective (every rank of the communicator calls it with its own planes).  gpu_mgcg_slab_supported says whether a
- * decomposition can run this way: planes of a multiple of 256 cells, equal slabs that start at a multiple of 8 and hold at least
- * 17 planes, ghost >= 8; the host solver keeps the replicated solve otherwise.  On return the velocity is projected on the owned
- * planes and on 7 ghost planes of either side. */
+ * decomposition can run this way: planes of a multiple of 256 cells, equal slabs of a multiple of 8 planes that hold at least
+ * 17, ghost >= 8 (csrc/bq_mgcg_slab_plan.h); the host solver keeps the replicated solve otherwise.  The answer depends on the
+ * grid, the ghost depth and the number of ranks only, so every rank of a communicator gets the same one -- callers choose
+ * between two collectives by it; rank, own0 and own1 must describe those equal slabs (pass fl_comm_rank / fl_comm_size).  On
+ * return the velocity is projected on the owned planes and on 7 ghost planes of either side. */
 int  gpu_mgcg_slab_supported(int ni, int nj, int nkg, int own0, int own1, int ghost, int rank, int nranks);
 void gpu_multi_grid_conjugate_gradient_slab(float *u, float *v, float *w, double *tempResult,
                                             int ni, int nj, int nkg, int own0, int own1, int ghost, int iter, double halfrdx);

@@ -8,6 +8,7 @@ GPU tests as references.  Test infrastructure.
   build_jacobi_plan() tests/_build/libjacobi_plan.so: csrc/bq_jacobi_plan.h behind tests/cpu_abi/jacobi_plan_shim.cpp
   build_box_chunk()  tests/_build/libbox_chunk.so: csrc/bq_box_chunk.h behind tests/cpu_abi/box_chunk_shim.cpp
   build_slab_jacobi_plan() tests/_build/libslab_jacobi_plan.so: csrc/host/slab_jacobi_plan.hpp behind tests/cpu_abi/slab_jacobi_plan_shim.cpp
+  build_mgcg_slab_plan() tests/_build/libmgcg_slab_plan.so: csrc/bq_mgcg_slab_plan.h behind tests/cpu_abi/mgcg_slab_plan_shim.cpp
 A stand-in without some operators leaves the host solver's weak references to them null: set_boundary refuses there."""
 import glob
 import os
@@ -92,5 +93,11 @@ def build_slab_jacobi_plan():
     return _build_header_shim("libslab_jacobi_plan.so", "slab_jacobi_plan_shim.cpp", ["host/slab_jacobi_plan.hpp"])
 
 
+def build_mgcg_slab_plan():
+    """the decomposition of the slab-shared multigrid-CG projection: predicate, pyramid, plane ranges, derived counts"""
+    return _build_header_shim("libmgcg_slab_plan.so", "mgcg_slab_plan_shim.cpp", ["bq_mgcg_slab_plan.h"])
+
+
 if __name__ == "__main__":
-    print(build(), build_obstacles(), build_levelsets(), build_launch_geom(), build_jacobi_plan(), build_box_chunk(), build_slab_jacobi_plan())
+    print(build(), build_obstacles(), build_levelsets(), build_launch_geom(), build_jacobi_plan(), build_box_chunk(), build_slab_jacobi_plan(),
+          build_mgcg_slab_plan())

@@ -189,6 +189,22 @@ def main():
                 planes = sorted(set((np.nonzero(d)[0] // pe + s.own0).tolist()))
                 print(f"[rank {rank}] step {f}: {name} differs, max|diff| {d.max():.3e} in global planes {planes[:12]}{'...' if len(planes) > 12 else ''}", flush=True)
                 bad += 1
+        if a.projection_kind == 1:
+            # the residual history of the step's last multigrid-CG projection (tempResult: the CG coefficients [0, 2 iters + 3) and
+            # the residual maxima [2000, 2001 + iters)): the oracle's, value for value, and the same on every rank
+            pick = np.r_[0:2 * a.iters + 3, 2000:2001 + a.iters]
+            ho, hs = o.mg_history(), s.mgHistory()
+            if ho is None or hs is None or not np.array_equal(ho[pick], hs[pick]):
+                where = "none recorded" if ho is None or hs is None else np.nonzero(ho[pick] != hs[pick])[0][:8].tolist()
+                print(f"[rank {rank}] step {f}: multigrid history differs from the oracle's at entries {where}", flush=True)
+                bad += 1
+            mine = torch.from_numpy(np.ascontiguousarray(hs[pick] if hs is not None else np.full(pick.size, np.nan)))
+            every = [torch.empty_like(mine) for _ in range(world)]
+            dist.all_gather(every, mine)
+            for r, other in enumerate(every):
+                if not np.array_equal(other.numpy(), mine.numpy()):
+                    print(f"[rank {rank}] step {f}: multigrid history differs from rank {r}'s", flush=True)
+                    bad += 1
     if a.policy:
         mine = s.reinitCounts() + (s.forcedReinits(),) + s.lastDistortion()
         want = o.reinit_counts() + (o.l.orc_solver_reinit_counts(o.s, 2),) + o.last_distortion()
@@ -211,7 +227,7 @@ def main():
         print(f"[rank {rank}] comm check: communicators={abilib.fl_comm_count()} clean rc={rc_clean} falsified rc={rc_bad} ({text[:60]})", flush=True)
         if rc_clean != 0 or rc_bad != bq._lib.FL_ERR_COMM:
             bad += 1
-    if a.projection_kind and a.backend == "gpu":
+    if a.projection_kind and (a.backend == "gpu" or a.expect_shared >= 0):
         took = s.getOption(11) == 2
         print(f"[rank {rank}] multigrid projection on slabs: {'levels SHARED between the ranks' if took else 'replicated solve'}", flush=True)
         if a.expect_shared >= 0 and took != bool(a.expect_shared):

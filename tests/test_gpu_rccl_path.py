@@ -189,6 +189,32 @@ def test_multigrid_levels_shared_between_the_ranks(fake, nranks, dims):
         assert out.count("mismatches=0") == nranks and out.count("replicated solve") == nranks, out
 
 
+@pytest.mark.parametrize("nranks,dims,shared", [
+    (2, (16, 16, 48), 1),       # ghost depths (8, 8, 4), planes of ONE 256-cell dot block, one replicated level: no fused bottom launch
+    (3, (16, 16, 72), 1),       # (8, 8, 4) with a middle rank
+    (2, (32, 8, 48), 1),        # a three-level pyramid: two shared levels
+    (2, (48, 16, 48), 1),       # planes of three dot blocks, h = 1 / 48
+    (2, (16, 16, 40), 0),       # 20 planes per rank: the ranks used to split between the two collectives
+    (4, (32, 32, 80), 0),       # ... [1, 0, 1, 0]
+], ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else str(v))
+def test_multigrid_shared_levels_at_the_small_geometries(fake, nranks, dims, shared):
+    """The smallest grids that reach what the 48- and 32-plane cases above do not (24 planes per rank; what the plan makes of each
+    is asserted on the CPU: tests/test_mgcg_slab_plan_cpu.py::test_the_gpu_cases_reach_the_classes_they_are_there_for), and two
+    geometries with 20 planes per rank, on which gpu_mgcg_slab_supported used to answer by `own0 % 8` -- per rank -- so that the
+    ranks entered different collectives: every rank now takes the replicated solve.  Every field equals the single-domain oracle's
+    bit for bit, the residual history equals the oracle's and is the same on every rank (tests/slab_worker.py)."""
+    skip_plain_async(fake)
+    common = ["--dims", *dims, "--L", 1.0, "--ghost", 8, "--steps", 2, "--iters", 3, "--dt-cells", 1.0, "--projection-kind", 1]
+    line = "levels SHARED between the ranks" if shared else "replicated solve"
+    rc, out = launch_worker(fake, nranks, *common, "--expect-shared", shared)
+    assert rc == 0, out
+    assert out.count("mismatches=0") == nranks and out.count(line) == nranks, out
+    if dims == (48, 16, 48):
+        rc, out = launch_worker(fake, nranks, *common, "--scheme", 3, "--expect-shared", shared)
+        assert rc == 0, out
+        assert out.count("mismatches=0") == nranks and out.count(line) == nranks, out
+
+
 @pytest.mark.parametrize("nranks", [2, 4])
 def test_slab_ranks_reproduce_the_mgcg_128_hashes(fake, nranks):
     """BASELINE-size evidence for the same: 2 and 4 z-slab ranks of the 128^3 rising-smoke run with the multigrid-CG projection

@@ -127,6 +127,21 @@ def test_multigrid_projection_replicated_on_slabs_cpu():
     assert out.count("mismatches=0") == 3
 
 
+def test_shared_solve_that_the_operator_refuses_falls_back_to_the_replicated_one_cpu():
+    """BQ_STANDIN_MGCG_SLAB_SUPPORTED=1: the stand-in's gpu_mgcg_slab_supported answers 1 while its
+    gpu_multi_grid_conjugate_gradient_slab still refuses (FL_ERR_UNSUPPORTED) -- a refusal every rank computes alike.  The host
+    must not take that for a projection: it clears the error, runs the replicated solve and reports the shared path as not
+    taken; fields and residual history equal the single-domain oracle's"""
+    env = dict(os.environ)
+    os.environ["BQ_STANDIN_MGCG_SLAB_SUPPORTED"] = "1"
+    try:
+        rc, out = launch(2, "--backend", "cpu", "--steps", 3, "--iters", 4, "--projection-kind", 1, "--expect-shared", 0)
+    finally:
+        os.environ.clear(); os.environ.update(env)
+    assert rc == 0, out
+    assert out.count("mismatches=0") == 2 and out.count("replicated solve") == 2, out
+
+
 def test_viscous_diffusion_on_slabs_cpu():
     """nu != 0: the 20 diffusion sweeps per component run in chunks of G with ghost refreshes in between
     (gpu_diffuse_sweeps), including the reference's buffer aliasing; bit-exact on 2 and 3 ranks"""
@@ -291,6 +306,26 @@ def test_reflection_scheme_on_slabs_gpu():
                      "--viscosity", 2e-3, threads=4)
     assert rc == 0, out
     assert out.count("mismatches=0") == 3
+
+
+@pytest.mark.gpu
+def test_multigrid_levels_shared_over_the_host_staged_transport_gpu():
+    """the fp64 multigrid-CG projection with its fine levels shared between the ranks, its exchanges, gathers and all-reduces
+    carried by the host-staged callbacks (fl_comm_set_custom, fl_comm_set_custom_p2p) instead of the RCCL branch: 16 x 16 x 48 on
+    two ranks, ghost depths (8, 8, 4); fields and residual history equal the oracle's"""
+    rc, out = launch(2, "--backend", "gpu", "--dims", 16, 16, 48, "--L", 1.0, "--ghost", 8, "--steps", 2, "--iters", 3, "--dt-cells", 1.0,
+                     "--projection-kind", 1, "--expect-shared", 1, threads=4)
+    assert rc == 0, out
+    assert out.count("mismatches=0") == 2 and out.count("levels SHARED between the ranks") == 2, out
+
+
+@pytest.mark.gpu
+def test_multigrid_projection_replicated_on_slabs_gpu():
+    """planes of 480 cells and 6 ghost planes: the replicated solve with the HIP kernels, on every rank"""
+    rc, out = launch(2, "--backend", "gpu", "--dims", 24, 20, 32, "--L", 1.0, "--ghost", 6, "--steps", 2, "--iters", 3, "--dt-cells", 1.0,
+                     "--projection-kind", 1, "--expect-shared", 0, threads=4)
+    assert rc == 0, out
+    assert out.count("mismatches=0") == 2 and out.count("replicated solve") == 2, out
 
 
 @pytest.mark.gpu
