@@ -11,7 +11,8 @@
 // Each rank dumps the planes it owns: <outdir>/density_render_%04d.k%05d.bqd (the slab files stitch to the global grid).
 //
 //   build/bimocq3d_ranks [NX=512] [NY=512] [NZ=512] [frames=20] [outdir=out] [scene=0 smoke|1 leapfrog] [ghost=8] [jacobi=200]
-//                      [scheme=0 BiMocq|2 MacCormack|3 reflection]
+//                      [scheme=0 BiMocq|2 MacCormack|3 reflection] [walls=0: BQ_WALL_* bits of the closed sides, 55 = the
+//                      reference's container]
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -70,11 +71,12 @@ int main(int argc, char **argv)
     const int ghost = argc > 7 ? std::atoi(argv[7]) : 8;
     const int jacobi = argc > 8 ? std::atoi(argv[8]) : 200;
     const int scheme = argc > 9 ? std::atoi(argv[9]) : 0;
+    const int walls = argc > 10 ? std::atoi(argv[10]) : 0;
     const int rank = env_int("RANK", 0), world = env_int("WORLD_SIZE", 1), local = env_int("LOCAL_RANK", rank);
     if (ni < 8 || nj < 8 || nk < 8 || total_frame < 1 || world < 1 || rank < 0 || rank >= world || nk % world != 0 ||
-        (scheme != 0 && scheme != 2 && scheme != 3)) {
+        (scheme != 0 && scheme != 2 && scheme != 3) || walls < 0 || walls >= 63) {
         std::fprintf(stderr, "usage: RANK=r WORLD_SIZE=n %s [NX] [NY] [NZ divisible by n] [frames] [outdir] [scene] [ghost] [jacobi] "
-                             "[scheme: 0 BiMocq, 2 MacCormack, 3 reflection]\n", argv[0]);
+                             "[scheme: 0 BiMocq, 2 MacCormack, 3 reflection] [walls: BQ_WALL_* bits, one side open]\n", argv[0]);
         return 2;
     }
     ::mkdir(filepath.c_str(), 0777);
@@ -114,6 +116,9 @@ int main(int argc, char **argv)
         mysolver.setSmoke(0.f, 1.f, { src });
     }
     mysolver.jacobi_iters = jacobi;
+    // closed domain walls, on slab ranks too: every rank sets the same mask, the z sides close on the
+    // ranks that hold the first and the last global plane
+    if (walls && !mysolver.setWalls(walls)) { std::fprintf(stderr, "[rank %d] %s\n", rank, fl_last_error_string()); return 1; }
     mysolver.verbose = rank == 0;
 
     const auto t0 = std::chrono::steady_clock::now();

@@ -162,6 +162,9 @@ HIP_SIGS = {
     "gpu_jacobi_sweeps_masked_walls": (c_i, [VP] * 5 + [c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
     "gpu_gradient_masked_walls": (None, [VP] * 8 + [c_i, c_i, c_i, c_i, c_f]),
     "gpu_pcg_gradient_walls": (None, [VP] * 5 + [c_i, c_i, c_i, c_i, c_d]),
+    # ... on plane ranges, for z-slab ranks (in, div, out, solidw, rows, walls, ni, nj, nk, ranges, alpha, beta)
+    "gpu_jacobi_sweep_masked_walls_range": (c_i, [VP] * 5 + [c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
+    "gpu_jacobi_sweep_masked_walls_triple_ranges": (c_i, [VP] * 5 + [c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
     # level-set obstacles (the bq_levelset array travels as a HOST pointer, its phi device pointers: solver.LevelSetDesc)
     "gpu_obstacle_flags_ls": (None, [VP, VP, VP, c_i, VP] + _G),
     "gpu_semilag_band_ls": (None, [VP] * 5 + [c_i, c_i, c_i] + _G + [c_f, c_f, VP, c_i, VP]),

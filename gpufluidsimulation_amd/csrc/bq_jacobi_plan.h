@@ -325,11 +325,21 @@ inline LaunchPlan plan_triple(int ni, int nj, int nk, bool aligned16, const Jaco
 }
 
 // Three MASKED sweeps in one launch (gpu_jacobi_sweeps_masked; walled: gpu_jacobi_sweeps_masked_walls): whole array, never on a
-// z-slab rank.  The walled launch takes the shapes of the masked one, and short chunks too.
+// z-slab rank -- there the walled launch goes through plan_triple_masked_ranges on the plane ranges of the slab schedule, and the
+// masked one (obstacles) does not exist yet.  The walled launch takes the shapes of the masked one, and short chunks too.
 inline LaunchPlan plan_triple_masked(int ni, int nj, int nk, bool aligned16, const JacobiTuning &tun, int num_cus, bool slab_on, bool walled = false)
 {
     if (ni < 3 || nj < 4 || nk < 3 || slab_on) return LaunchPlan{};
     return plan_lds(ni, nj, nk, aligned16, geom::PlaneRanges(0, 1 << 30, 0, 0, nk), tun, num_cus, 3, true, 0, walled);
+}
+
+// Three WALLED sweeps on plane ranges (gpu_jacobi_sweep_masked_walls_triple_ranges), z-slab ranks included: the shapes
+// plan_triple_masked admits on whole arrays, under the switches of plan_triple_ranges; chunks as short as 2 planes, like every
+// launch on plane ranges.
+inline LaunchPlan plan_triple_masked_ranges(int ni, int nj, int nk, bool aligned16, const geom::PlaneRanges &pr, const JacobiTuning &tun, int num_cus)
+{
+    if (!tun.triple_ranges || ni < 3 || nj < 4 || nk < 3) return LaunchPlan{};
+    return plan_lds(ni, nj, nk, aligned16, pr, tun, num_cus, 3, true, 0, true);
 }
 
 // Three sweeps on plane ranges (gpu_jacobi_sweep_triple_ranges): the LDS kernels only.

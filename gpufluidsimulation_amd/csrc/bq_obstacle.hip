@@ -149,6 +149,10 @@ __global__ __launch_bounds__(256) void jacobi_masked_kernel(const float *__restr
 }
 
 // ---- closed domain walls (BimocqSolver.cpp:938-948) --------------------------------------------------
+// On a z-slab rank (fl_set_slab) every position below is GLOBAL: the kernels pass plane k + koff for k and the global plane count
+// nkg for nk, so BQ_WALL_ZLO is global plane 0 and BQ_WALL_ZHI global plane nkg - 1 on whichever rank holds them, and a rank in
+// the middle has x and y walls only.  One domain: koff = 0, nkg = nk -- the same expressions on the same operands.
+struct SlabZ { int koff, nkg; };
 // a border cell of a closed side
 __device__ __forceinline__ bool wall_cell(int walls, int i, int j, int k, int ni, int nj, int nk)
 {
@@ -163,14 +167,17 @@ __device__ __forceinline__ int wall_neighbours(int walls, int i, int j, int k, i
 }
 
 // solidw = solid (or 0) with BQ_FLAG_WALL in the wall cells no obstacle covers: one thread per cell
+// (a slab rank's planes outside the global grid hold no cell: flag 0)
 __global__ __launch_bounds__(256) void wall_flags_kernel(unsigned char *__restrict__ solidw, const unsigned char *__restrict__ solid,
-                                                         int walls, int ni, int nj, int nk)
+                                                         int walls, int ni, int nj, int nk, SlabZ sz)
 {
     const int i = blockIdx.x * 64 + threadIdx.x, j = blockIdx.y * 4 + threadIdx.y, k = blockIdx.z;
     if (i >= ni || j >= nj) return;
+    const int kg = k + sz.koff;
     const size_t id = (size_t)i + (size_t)ni * ((size_t)j + (size_t)nj * k);
     const unsigned char f = solid ? solid[id] : (unsigned char)0;
-    solidw[id] = f ? f : (wall_cell(walls, i, j, k, ni, nj, nk) ? (unsigned char)BQ_FLAG_WALL : (unsigned char)0);
+    const bool wall = kg >= 0 && kg < sz.nkg && wall_cell(walls, i, j, kg, ni, nj, sz.nkg);
+    solidw[id] = f ? f : (wall ? (unsigned char)BQ_FLAG_WALL : (unsigned char)0);
 }
 
 // wall faces: one thread per node of the (ni+1, nj+1, nk+1) super-grid; a face takes 0 when one of its cells is a wall cell
@@ -179,13 +186,21 @@ __device__ __forceinline__ bool wall_face(int a, int b)
 {
     return (a == BQ_FLAG_WALL || b == BQ_FLAG_WALL) && (a == 0 || a == BQ_FLAG_WALL) && (b == 0 || b == BQ_FLAG_WALL);
 }
+// z-slab ranks: the flags are those of the rank's window.  The cell below the window's first plane (above its last one) is not in
+// it; where it lies inside the global grid it is taken to carry the flag of its neighbour inside the window -- exact for the x and
+// y walls, which do not depend on the plane, and wrong only for the w face between the window and a closed z plane just outside it
+// (window from global plane 1, or up to nkg - 2): that face is the outermost ghost face of w, and the host counts w's ghost
+// planes one short after this pass.
 __global__ __launch_bounds__(256) void wall_faces_kernel(float *__restrict__ u, float *__restrict__ v, float *__restrict__ w,
                                                          float *__restrict__ du, float *__restrict__ dv, float *__restrict__ dw,
-                                                         const unsigned char *__restrict__ solidw, int ni, int nj, int nk)
+                                                         const unsigned char *__restrict__ solidw, int ni, int nj, int nk, SlabZ sz)
 {
     const int i = blockIdx.x * 64 + threadIdx.x, j = blockIdx.y * 4 + threadIdx.y, k = blockIdx.z;
     if (i > ni || j > nj || k > nk) return;
-    const int c = flag_at(solidw, i, j, k, ni, nj, nk);
+    const int kg = k + sz.koff;
+    // the flag of cell (i, j, k): beyond the window but inside the grid, that of the nearest plane of the window
+    const int kc = k == nk && kg < sz.nkg ? nk - 1 : k;
+    const int c = flag_at(solidw, i, j, kc, ni, nj, nk);
     if (j < nj && k < nk && wall_face(flag_at(solidw, i - 1, j, k, ni, nj, nk), c)) {
         const size_t id = (size_t)i + (size_t)(ni + 1) * ((size_t)j + (size_t)nj * k);
         if (du) du[id] = 0.f - u[id];
@@ -196,7 +211,7 @@ __global__ __launch_bounds__(256) void wall_faces_kernel(float *__restrict__ u, 
         if (dv) dv[id] = 0.f - v[id];
         v[id] = 0.f;
     }
-    if (i < ni && j < nj && wall_face(flag_at(solidw, i, j, k - 1, ni, nj, nk), c)) {
+    if (i < ni && j < nj && wall_face(flag_at(solidw, i, j, k == 0 && kg > 0 ? 0 : k - 1, ni, nj, nk), c)) {
         const size_t id = (size_t)i + (size_t)ni * ((size_t)j + (size_t)nj * k);
         if (dw) dw[id] = 0.f - w[id];
         w[id] = 0.f;
@@ -204,19 +219,21 @@ __global__ __launch_bounds__(256) void wall_faces_kernel(float *__restrict__ u, 
 }
 
 // jacobi_masked_kernel with walls: a cell whose (obstacle) rows summary is clean counts its solid neighbours by position and
-// reads no flag; the others read the flags of solid + walls
+// reads no flag; the others read the flags of solid + walls.  [klo, khi): the local planes of the launch, one per blockIdx.z
+// (gpu_jacobi_sweep_masked_walls_range; whole arrays: [0, nk)); planes outside the interior of the global grid keep their value, as in the unmasked sweeps
 __global__ __launch_bounds__(256) void jacobi_masked_walls_kernel(const float *__restrict__ p, const float *__restrict__ div,
                                                                   float *__restrict__ out, const unsigned char *__restrict__ solidw,
                                                                   const unsigned char *__restrict__ rows, int walls,
-                                                                  int ni, int nj, int nk, float alpha, BetaTab bt)
+                                                                  int ni, int nj, int nk, float alpha, BetaTab bt, SlabZ sz, int klo, int khi)
 {
-    const int i = blockIdx.x * 64 + threadIdx.x, j = blockIdx.y * 4 + threadIdx.y, k = blockIdx.z;
-    if (!(i > 0 && i < ni - 1 && j > 0 && j < nj - 1 && k > 0 && k < nk - 1)) return;
+    const int i = blockIdx.x * 64 + threadIdx.x, j = blockIdx.y * 4 + threadIdx.y, k = klo + blockIdx.z;
+    const int kg = k + sz.koff;
+    if (!(i > 0 && i < ni - 1 && j > 0 && j < nj - 1 && k > 0 && k < nk - 1 && kg > 0 && kg < sz.nkg - 1 && k < khi)) return;
     const size_t sj = ni, sk = (size_t)ni * nj;
     const size_t id = (size_t)i + sj * j + sk * k;
     int s;
     if (!rows[(size_t)j + (size_t)nj * k]) {
-        s = wall_neighbours(walls, i, j, k, ni, nj, nk);
+        s = wall_neighbours(walls, i, j, kg, ni, nj, sz.nkg);
     } else {
         if (solidw[id]) return;
         s = (solidw[id - 1] != 0) + (solidw[id + 1] != 0) + (solidw[id - sj] != 0) + (solidw[id + sj] != 0)
@@ -228,16 +245,18 @@ __global__ __launch_bounds__(256) void jacobi_masked_walls_kernel(const float *_
 
 // ---- masked gradient (gradient_delta_kernel / gradient_kernel with solid faces left alone) ----------------------------
 // i0, j0, k0: the first cell index of the window on each axis -- 2 (the open-boundary window of gradient_kernel), or 1 behind a
-// closed wall (gradient_masked_walls_kernel), where the faces between the cells of the first interior layer are projected too
+// closed wall (gradient_masked_walls_kernel), where the faces between the cells of the first interior layer are projected too;
+// along z the window is that of the GLOBAL planes (sz)
 __device__ __forceinline__ void gradient_masked_body(float *__restrict__ u, float *__restrict__ v, float *__restrict__ w,
                                                      const float *__restrict__ p,
                                                      float *__restrict__ du, float *__restrict__ dv, float *__restrict__ dw,
                                                      const unsigned char *__restrict__ solid, int ni, int nj, int nk, float halfrdx,
-                                                     int i0, int j0, int k0)
+                                                     int i0, int j0, int k0, SlabZ sz)
 {
     const int i = blockIdx.x * 64 + threadIdx.x, j = blockIdx.y * 4 + threadIdx.y, k = blockIdx.z;
     if (i > ni || j > nj || k > nk) return;
-    const bool win = !(i < i0 || i >= ni || j < j0 || j >= nj || k < k0 || k >= nk);
+    const int kg = k + sz.koff;
+    const bool win = !(i < i0 || i >= ni || j < j0 || j >= nj || kg < k0 || kg >= sz.nkg || k >= nk);
     const size_t iu = (size_t)i + (size_t)(ni + 1) * ((size_t)j + (size_t)nj * k);
     const size_t iv = (size_t)i + (size_t)ni * ((size_t)j + (size_t)(nj + 1) * k);
     const size_t ic = (size_t)i + (size_t)ni * ((size_t)j + (size_t)nj * k);
@@ -257,11 +276,11 @@ __device__ __forceinline__ void gradient_masked_body(float *__restrict__ u, floa
             v[iv] = vn;
             if (dv) dv[iv] = vn - vo;
         }
-        if (!sw) {
+        if (!sw && k >= 1) {
             const float wo = w[ic], wn = wo - halfrdx * (p0 - p[ic - (size_t)ni * nj]);
             w[ic] = wn;
             if (dw) dw[ic] = wn - wo;
-        }
+        } else if (!sw && dw) dw[ic] = 0.f;      // a slab rank's first plane inside the window: w needs the plane below (gradient_kernel)
     } else if (du) {
         if (hu && !su) du[iu] = 0.f;
         if (hv && !sv) dv[iv] = 0.f;
@@ -273,7 +292,7 @@ __global__ __launch_bounds__(256) void gradient_masked_kernel(float *__restrict_
                                                               float *__restrict__ du, float *__restrict__ dv, float *__restrict__ dw,
                                                               const unsigned char *__restrict__ solid, int ni, int nj, int nk, float halfrdx)
 {
-    gradient_masked_body(u, v, w, p, du, dv, dw, solid, ni, nj, nk, halfrdx, 2, 2, 2);
+    gradient_masked_body(u, v, w, p, du, dv, dw, solid, ni, nj, nk, halfrdx, 2, 2, 2, SlabZ{0, nk});
 }
 // closed domain walls: the window starts at cell 1 behind a closed low side (BimocqSolver.cpp:1288-1335
 // updates every face between two fluid cells); the faces of the wall cells themselves are solid faces and stay alone
@@ -281,10 +300,10 @@ __global__ __launch_bounds__(256) void gradient_masked_walls_kernel(float *__res
                                                                     const float *__restrict__ p,
                                                                     float *__restrict__ du, float *__restrict__ dv, float *__restrict__ dw,
                                                                     const unsigned char *__restrict__ solidw, int walls,
-                                                                    int ni, int nj, int nk, float halfrdx)
+                                                                    int ni, int nj, int nk, float halfrdx, SlabZ sz)
 {
     gradient_masked_body(u, v, w, p, du, dv, dw, solidw, ni, nj, nk, halfrdx, (walls & BQ_WALL_XLO) ? 1 : 2, (walls & BQ_WALL_YLO) ? 1 : 2,
-                         (walls & BQ_WALL_ZLO) ? 1 : 2);
+                         (walls & BQ_WALL_ZLO) ? 1 : 2, sz);
 }
 
 // ---- band blend + density clear: one thread per super-grid node -------------------------------------------------------
@@ -321,7 +340,8 @@ __global__ __launch_bounds__(256) void obstacle_blend_kernel(float *__restrict__
     }
 }
 
-static bool obs_args_ok(const bq_boundary *b, int n, int ni, int nj, int nk, const char *op)
+// slab_ok: the operator honours the z-slab context (the wall operators); every other one refuses a slab rank
+static bool obs_args_ok(const bq_boundary *b, int n, int ni, int nj, int nk, const char *op, bool slab_ok = false)
 {
     if (!ensure_ready(op)) return false;
     if (ni < 3 || nj < 3 || nk < 3 || 4.0 * (double)(ni + 1) * (double)(nj + 1) * (double)(nk + 1) >= 4294967296.0 || nk + 1 > 65535) {
@@ -329,7 +349,7 @@ static bool obs_args_ok(const bq_boundary *b, int n, int ni, int nj, int nk, con
         return false;
     }
     if (n < 0 || n > BQ_MAX_BOUNDARIES || (n > 0 && !b)) { latch(FL_ERR_BAD_ARGUMENT, op, "1 .. 16 obstacles"); return false; }
-    if (rt().slab_on) { latch(FL_ERR_UNSUPPORTED, op, "obstacles on z-slab ranks"); return false; }
+    if (rt().slab_on && !slab_ok) { latch(FL_ERR_UNSUPPORTED, op, "obstacles on z-slab ranks"); return false; }
     return true;
 }
 
@@ -377,6 +397,16 @@ static void obstacle_blend(float *u, float *v, float *w, float *rho, float *T, c
 
 bool jacobi_sweep_triple_masked(const plan::JacobiTuning &tun, const float *in, const float *div, float *out, int ni, int nj, int nk, float alpha,
                                 const unsigned char *solid, const unsigned char *rows, const float betas[7], int walls = 0);   // bq_project.hip
+bool jacobi_sweep_triple_masked_ranges(const plan::JacobiTuning &tun, const float *in, const float *div, float *out, int ni, int nj, int nk, float alpha,
+                                       const unsigned char *solid, const unsigned char *rows, const float betas[7], int walls,
+                                       const geom::PlaneRanges &pr);                                                          // bq_project.hip
+
+// the z-slab context of the wall operators: the global plane of local plane 0 and the global plane count
+static inline SlabZ slab_z(int nk)
+{
+    const Runtime &r = rt();
+    return r.slab_on ? SlabZ{r.slab_koff, r.slab_nkg} : SlabZ{0, nk};
+}
 
 } // namespace bq
 
@@ -456,17 +486,17 @@ static bool walls_ok(int walls, const char *op)
 
 void gpu_wall_flags(unsigned char *solidw, const unsigned char *solid, int walls, int ni, int nj, int nk)
 {
-    if (!obs_args_ok(nullptr, 0, ni, nj, nk, "gpu_wall_flags") || !walls_ok(walls, "gpu_wall_flags")) return;
+    if (!obs_args_ok(nullptr, 0, ni, nj, nk, "gpu_wall_flags", true) || !walls_ok(walls, "gpu_wall_flags")) return;
     if (!solidw || solidw == solid) { latch(FL_ERR_BAD_ARGUMENT, "gpu_wall_flags", "null or aliased buffers"); return; }
-    wall_flags_kernel<<<grid_for(ni, nj, nk), kBlock, 0, rt().compute>>>(solidw, solid, walls, ni, nj, nk);
+    wall_flags_kernel<<<grid_for(ni, nj, nk), kBlock, 0, rt().compute>>>(solidw, solid, walls, ni, nj, nk, slab_z(nk));
     BQ_LAUNCH_CHECK("wall_flags_kernel");
 }
 
 void gpu_wall_faces(float *u, float *v, float *w, float *du, float *dv, float *dw, const unsigned char *solidw, int ni, int nj, int nk)
 {
-    if (!obs_args_ok(nullptr, 0, ni, nj, nk, "gpu_wall_faces")) return;
+    if (!obs_args_ok(nullptr, 0, ni, nj, nk, "gpu_wall_faces", true)) return;
     if (!u || !v || !w || !solidw || (!du) != (!dv) || (!du) != (!dw)) { latch(FL_ERR_BAD_ARGUMENT, "gpu_wall_faces", "null device pointer"); return; }
-    wall_faces_kernel<<<grid_for(ni + 1, nj + 1, nk + 1), kBlock, 0, rt().compute>>>(u, v, w, du, dv, dw, solidw, ni, nj, nk);
+    wall_faces_kernel<<<grid_for(ni + 1, nj + 1, nk + 1), kBlock, 0, rt().compute>>>(u, v, w, du, dv, dw, solidw, ni, nj, nk, slab_z(nk));
     BQ_LAUNCH_CHECK("wall_faces_kernel");
 }
 
@@ -474,10 +504,49 @@ void gpu_jacobi_sweep_masked_walls(const float *in, const float *div, float *out
                                    const unsigned char *rows, int walls, int ni, int nj, int nk, float alpha, float beta)
 {
     if (walls == 0) { gpu_jacobi_sweep_masked(in, div, out, solidw, rows, ni, nj, nk, alpha, beta); return; }
-    if (!obs_args_ok(nullptr, 0, ni, nj, nk, "gpu_jacobi_sweep_masked_walls") || !walls_ok(walls, "gpu_jacobi_sweep_masked_walls")) return;
+    if (!obs_args_ok(nullptr, 0, ni, nj, nk, "gpu_jacobi_sweep_masked_walls", true) || !walls_ok(walls, "gpu_jacobi_sweep_masked_walls")) return;
     if (!in || !div || !out || !solidw || !rows || in == out) { latch(FL_ERR_BAD_ARGUMENT, "gpu_jacobi_sweep_masked_walls", "null or aliased buffers"); return; }
-    jacobi_masked_walls_kernel<<<grid_for(ni, nj, nk), kBlock, 0, rt().compute>>>(in, div, out, solidw, rows, walls, ni, nj, nk, alpha, beta_table(beta));
+    jacobi_masked_walls_kernel<<<grid_for(ni, nj, nk), kBlock, 0, rt().compute>>>(in, div, out, solidw, rows, walls, ni, nj, nk, alpha, beta_table(beta),
+                                                                                 slab_z(nk), 0, nk);
     BQ_LAUNCH_CHECK("jacobi_masked_walls_kernel");
+}
+
+// The walled sweeps of a z-slab rank's schedule (one domain: of any caller that wants part of the planes).  walls = 0 is refused:
+// the masked family without walls has no sweep on plane ranges.
+static bool walls_range_args(const float *in, const float *div, float *out, const unsigned char *solidw, const unsigned char *rows,
+                             int walls, int ni, int nj, int nk, const char *op)
+{
+    if (!obs_args_ok(nullptr, 0, ni, nj, nk, op, true)) return false;
+    if (walls <= 0 || walls >= 63) { latch(FL_ERR_BAD_ARGUMENT, op, "walls: BQ_WALL_* bits, at least one side closed and one open"); return false; }
+    if (!in || !div || !out || !solidw || !rows || in == out) { latch(FL_ERR_BAD_ARGUMENT, op, "null or aliased buffers"); return false; }
+    return true;
+}
+
+// one walled sweep in -> out on the local planes [k_begin, k_end), clipped to the interior: returns 1 (0: refused arguments)
+int gpu_jacobi_sweep_masked_walls_range(const float *in, const float *div, float *out, const unsigned char *solidw,
+                                        const unsigned char *rows, int walls, int ni, int nj, int nk, int k_begin, int k_end,
+                                        float alpha, float beta)
+{
+    if (!walls_range_args(in, div, out, solidw, rows, walls, ni, nj, nk, "gpu_jacobi_sweep_masked_walls_range")) return 0;
+    const int k0 = std::max(k_begin, 1), k1 = std::min(k_end, nk - 1);
+    if (k0 >= k1) return 1;
+    jacobi_masked_walls_kernel<<<grid_for(ni, nj, k1 - k0), kBlock, 0, rt().compute>>>(in, div, out, solidw, rows, walls, ni, nj, nk, alpha,
+                                                                                      beta_table(beta), slab_z(nk), k0, k1);
+    BQ_LAUNCH_CHECK("jacobi_masked_walls_kernel");
+    return 1;
+}
+
+// three walled sweeps in one launch, `out` written on the planes [k0a, k1a) and [k0b, k1b) (either may be empty): the input must
+// be valid three planes beyond each range, and both buffers carry the same boundary layer.  Returns 1 when the kernel ran, 0 when
+// it does not apply (nothing launched): the shapes the whole-array walled triple refuses, and FL_OPT_JACOBI_FUSE = 0 or 4.
+int gpu_jacobi_sweep_masked_walls_triple_ranges(const float *in, const float *div, float *out, const unsigned char *solidw,
+                                                const unsigned char *rows, int walls, int ni, int nj, int nk,
+                                                int k0a, int k1a, int k0b, int k1b, float alpha, float beta)
+{
+    if (!walls_range_args(in, div, out, solidw, rows, walls, ni, nj, nk, "gpu_jacobi_sweep_masked_walls_triple_ranges")) return 0;
+    const BetaTab bt = beta_table(beta);
+    return jacobi_sweep_triple_masked_ranges(jacobi_tuning(), in, div, out, ni, nj, nk, alpha, solidw, rows, bt.b, walls,
+                                             geom::PlaneRanges(k0a, k1a, k0b, k1b, nk)) ? 1 : 0;
 }
 
 // gpu_jacobi_sweeps_masked's loop with the walled kernels (FL_OPT_JACOBI_FUSE >= 2: three sweeps per launch where
@@ -486,7 +555,7 @@ int gpu_jacobi_sweeps_masked_walls(float *p, const float *div, float *p_temp, co
                                    int walls, int ni, int nj, int nk, int sweeps, float alpha, float beta)
 {
     if (walls == 0) return gpu_jacobi_sweeps_masked(p, div, p_temp, solidw, rows, ni, nj, nk, sweeps, alpha, beta);
-    if (!obs_args_ok(nullptr, 0, ni, nj, nk, "gpu_jacobi_sweeps_masked_walls") || !walls_ok(walls, "gpu_jacobi_sweeps_masked_walls")) return 0;
+    if (!obs_args_ok(nullptr, 0, ni, nj, nk, "gpu_jacobi_sweeps_masked_walls", true) || !walls_ok(walls, "gpu_jacobi_sweeps_masked_walls")) return 0;
     if (!p || !div || !p_temp || !solidw || !rows || p == p_temp) { latch(FL_ERR_BAD_ARGUMENT, "gpu_jacobi_sweeps_masked_walls", "null or aliased buffers"); return 0; }
     const BetaTab bt = beta_table(beta);
     float *in = p, *out = p_temp;
@@ -501,7 +570,7 @@ int gpu_jacobi_sweeps_masked_walls(float *p, const float *div, float *p_temp, co
         s += 3; launches++;
     }
     for (; s < sweeps; s++) {
-        jacobi_masked_walls_kernel<<<grid_for(ni, nj, nk), kBlock, 0, rt().compute>>>(in, div, out, solidw, rows, walls, ni, nj, nk, alpha, bt);
+        jacobi_masked_walls_kernel<<<grid_for(ni, nj, nk), kBlock, 0, rt().compute>>>(in, div, out, solidw, rows, walls, ni, nj, nk, alpha, bt, slab_z(nk), 0, nk);
         if (!BQ_LAUNCH_CHECK("jacobi_masked_walls_kernel")) break;
         float *t = in; in = out; out = t;
         launches++;
@@ -523,9 +592,9 @@ void gpu_gradient_masked_walls(float *u, float *v, float *w, const float *p, flo
                                const unsigned char *solidw, int walls, int ni, int nj, int nk, float halfrdx)
 {
     if (walls == 0) { gpu_gradient_masked(u, v, w, p, du, dv, dw, solidw, ni, nj, nk, halfrdx); return; }
-    if (!obs_args_ok(nullptr, 0, ni, nj, nk, "gpu_gradient_masked_walls") || !walls_ok(walls, "gpu_gradient_masked_walls")) return;
+    if (!obs_args_ok(nullptr, 0, ni, nj, nk, "gpu_gradient_masked_walls", true) || !walls_ok(walls, "gpu_gradient_masked_walls")) return;
     if (!u || !v || !w || !p || !solidw || (!du) != (!dv) || (!du) != (!dw)) { latch(FL_ERR_BAD_ARGUMENT, "gpu_gradient_masked_walls", "null device pointer"); return; }
-    gradient_masked_walls_kernel<<<grid_for(ni + 1, nj + 1, nk + 1), kBlock, 0, rt().compute>>>(u, v, w, p, du, dv, dw, solidw, walls, ni, nj, nk, halfrdx);
+    gradient_masked_walls_kernel<<<grid_for(ni + 1, nj + 1, nk + 1), kBlock, 0, rt().compute>>>(u, v, w, p, du, dv, dw, solidw, walls, ni, nj, nk, halfrdx, slab_z(nk));
     BQ_LAUNCH_CHECK("gradient_masked_walls_kernel");
 }
 

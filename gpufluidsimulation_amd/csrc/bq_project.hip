@@ -1039,6 +1039,9 @@ struct SweepMask { const unsigned char *solid = nullptr, *rows = nullptr; float 
 // Closed domain walls (WALLS = true).  solid: the obstacle flags plus BQ_FLAG_WALL in the wall cells; rows:
 // still the summary of the OBSTACLE flags; walls: the closed sides (BQ_WALL_* bits).
 struct SweepMaskWalls : SweepMask { int walls = 0; };
+// ... on a z-slab rank (SLABZ = true).  wzl, wzh: the LOCAL plane with a closed z side below / above it -- global plane 1 /
+// nkg - 2 -- or -8 where that side is open or the plane lies in another rank's array (walls_z_planes: formed on the host)
+struct SweepMaskWallsZ : SweepMaskWalls { int wzl = -8, wzh = -8; };
 template <bool WALLS, typename M> __device__ __forceinline__ int walls_of(const M &m) { if constexpr (WALLS) return m.walls; else return 0; }
 
 // Per cell of a float4 column a code byte: 7 = solid, else s = the number of solid neighbours.  own / lw / rw: the flag words
@@ -1101,12 +1104,15 @@ __device__ __forceinline__ R4 mask_finish(R4 sum, R4 ce, unsigned code, const Sw
 // interior column, row and plane.  Their number is a function of the position alone: such a block reads no flag and scales the
 // unscaled sum by beta_s with s = [x wall] + [y wall] (per row: wave-uniform) + [z wall] (per plane) -- the floats mask_finish
 // gives for the same s.  A dirty block takes the flag words (of solid + walls) as before.
-template <int W, int R, int S, bool MASK = false, bool WALLS = false>
+// SLABZ (with WALLS): the z term by the GLOBAL plane, for z-slab ranks -- an instantiation of its own, so that the kernel of one
+// domain stays the code it was (the same source with the two planes as kernel arguments measured 3 % slower there).
+template <int W, int R, int S, bool MASK = false, bool WALLS = false, bool SLABZ = false>
 __global__ __launch_bounds__((W + 2 * ((S - 1 + R - 1) / R)) * 64) void jacobi_lds_kernel(const float *__restrict__ p, const float *__restrict__ div,
                                                                   float *__restrict__ out, int nx, int ny, int nz,
                                                                   int nby, int nblk, int kchunk, float alpha, float beta, Slab sl, PairRanges rg,
-                                                                  std::conditional_t<WALLS, SweepMaskWalls, SweepMask> mk)
+                                                                  std::conditional_t<SLABZ, SweepMaskWallsZ, std::conditional_t<WALLS, SweepMaskWalls, SweepMask>> mk)
 {
+    static_assert(WALLS || !SLABZ, "the slab form is a state of the walled kernel");
     static_assert((R == 1 || R == 2) && (S == 3 || S == 4), "one or two rows per wave, three or four sweeps per launch");
     static_assert(MASK || !WALLS, "walls are a state of the masked kernel");
     constexpr int H = (S - 1 + R - 1) / R, NW = W + 2 * H, NS = NW * R, P = 4, A = P - 2;   // A: the plane loaded in step q is q + A
@@ -1186,6 +1192,7 @@ __global__ __launch_bounds__((W + 2 * ((S - 1 + R - 1) / R)) * 64) void jacobi_l
         for (int a = 0; a < R; a++) wy[a] = (int)((wl & 4) != 0 && j + a == 1) + (int)((wl & 8) != 0 && j + a == ny - 2);
         wxl = xlo && (wl & 1) != 0; wxh = xhi && (wl & 2) != 0;
         wzl = (wl & 16) != 0 ? 1 : -8; wzh = (wl & 32) != 0 ? nz - 2 : -8;      // the plane with a closed z side below / above it
+        if constexpr (SLABZ) { wzl = mk.wzl; wzh = mk.wzh; }
     }
     auto pw_finish = [&](R4 sum, R4 ce, int a, int pl) -> R4 {
         const int n = wy[a] + (int)(pl == wzl) + (int)(pl == wzh);
@@ -1663,7 +1670,7 @@ static void jacobi_sweep(const plan::JacobiTuning &tun, const float *in, const f
 // nothing launched.  Records the kernel's name for fl_jacobi_kernel_name.  The caller guarantees that both buffers carry the same
 // boundary layer.
 static bool launch_fused(const plan::LaunchPlan &pl, const float *in, const float *div, float *out, int ni, int nj, int nk, float alpha,
-                         float beta, const geom::PlaneRanges &pr, const SweepMaskWalls *mask = nullptr)
+                         float beta, const geom::PlaneRanges &pr, const SweepMaskWallsZ *mask = nullptr)
 {
     using plan::Kernel;
     if (pl.kernel == Kernel::kNone) return false;
@@ -1696,7 +1703,10 @@ static bool launch_fused(const plan::LaunchPlan &pl, const float *in, const floa
         break;
     case Kernel::kLds:
         if (mask && mask->walls) {
-            jacobi_lds_kernel<8, 1, 3, true, true><<<pl.grid, pl.block, 0, st>>>(in, div, out, ni, nj, nk, pl.row_blocks, pl.nblk, pl.kc, alpha, beta, sl, rg, *mask);
+            if (rt().slab_on)
+                jacobi_lds_kernel<8, 1, 3, true, true, true><<<pl.grid, pl.block, 0, st>>>(in, div, out, ni, nj, nk, pl.row_blocks, pl.nblk, pl.kc, alpha, beta, sl, rg, *mask);
+            else
+                jacobi_lds_kernel<8, 1, 3, true, true><<<pl.grid, pl.block, 0, st>>>(in, div, out, ni, nj, nk, pl.row_blocks, pl.nblk, pl.kc, alpha, beta, sl, rg, SweepMaskWalls(*mask));
             name = "jacobi_lds3_walls_kernel"; what = "jacobi_lds_kernel<walls>";
             break;
         }
@@ -1746,16 +1756,39 @@ static bool jacobi_sweep_quad(const plan::JacobiTuning &tun, const float *in, co
                         whole_array(nk));
 }
 
+// The z term of the positional state: a swept plane lies in [1, nk - 1), so a plane of another rank's array (an index <= 0 or
+// >= nk - 1 here) never matches, like -8.  One domain: planes 1 and nk - 2.
+static void walls_z_planes(SweepMaskWallsZ &mk, int nk)
+{
+    const Slab sl = slab_of(nk);
+    mk.wzl = (mk.walls & BQ_WALL_ZLO) ? 1 - sl.koff : -8;
+    mk.wzh = (mk.walls & BQ_WALL_ZHI) ? sl.nkg - 2 - sl.koff : -8;
+}
+
 // Three MASKED sweeps in one launch (bq_obstacle.hip: gpu_jacobi_sweeps_masked; walls != 0: gpu_jacobi_sweeps_masked_walls, solid then
 // being solid + walls); false = not applicable, nothing launched
 bool jacobi_sweep_triple_masked(const plan::JacobiTuning &tun, const float *in, const float *div, float *out, int ni, int nj, int nk, float alpha,
                                 const unsigned char *solid, const unsigned char *rows, const float betas[7], int walls)
 {
-    SweepMaskWalls mk;
+    SweepMaskWallsZ mk;
     mk.solid = solid; mk.rows = rows; mk.walls = walls;
+    walls_z_planes(mk, nk);
     mk.b0 = betas[0]; mk.b1 = betas[1]; mk.b2 = betas[2]; mk.b3 = betas[3]; mk.b4 = betas[4]; mk.b5 = betas[5]; mk.b6 = betas[6];
     return launch_fused(plan::plan_triple_masked(ni, nj, nk, aligned16(in, div, out), tun, rt().num_cus, rt().slab_on, walls != 0), in, div, out, ni, nj, nk,
                         alpha, betas[0], whole_array(nk), &mk);
+}
+// The walled triple on the output planes `pr` (gpu_jacobi_sweep_masked_walls_triple_ranges), z-slab ranks included: the kernel takes
+// its z term from the global plane.  walls != 0.
+bool jacobi_sweep_triple_masked_ranges(const plan::JacobiTuning &tun, const float *in, const float *div, float *out, int ni, int nj, int nk, float alpha,
+                                       const unsigned char *solid, const unsigned char *rows, const float betas[7], int walls,
+                                       const geom::PlaneRanges &pr)
+{
+    SweepMaskWallsZ mk;
+    mk.solid = solid; mk.rows = rows; mk.walls = walls;
+    walls_z_planes(mk, nk);
+    mk.b0 = betas[0]; mk.b1 = betas[1]; mk.b2 = betas[2]; mk.b3 = betas[3]; mk.b4 = betas[4]; mk.b5 = betas[5]; mk.b6 = betas[6];
+    return launch_fused(plan::plan_triple_masked_ranges(ni, nj, nk, aligned16(in, div, out), pr, tun, rt().num_cus), in, div, out, ni, nj, nk,
+                        alpha, betas[0], pr, &mk);
 }
 
 static const int kResidualBlocks = 1024;

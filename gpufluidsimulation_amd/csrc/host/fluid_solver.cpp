@@ -47,6 +47,8 @@
 #pragma weak gpu_jacobi_sweeps_masked_walls
 #pragma weak gpu_gradient_masked_walls
 #pragma weak gpu_pcg_gradient_walls
+#pragma weak gpu_jacobi_sweep_masked_walls_range
+#pragma weak gpu_jacobi_sweep_masked_walls_triple_ranges
 #pragma weak gpu_flow_stats
 #pragma weak gpu_render_density
 #pragma weak gpu_vorticity_confinement
@@ -943,7 +945,8 @@ bool BimocqGPUSolver::wallOperators()
 }
 
 // setWalls (BimocqSolver.cpp:938-948 as an opt-in): the closed sides; 0 releases solidw and the step is exactly the one without
-// this feature.  A refused mask leaves the previous one in place.
+// this feature.  A refused mask leaves the previous one in place.  On a z-slab rank solidw covers the rank's local planes, with
+// the walls where the GLOBAL grid has them (gpu_wall_flags reads the slab context), and `rows` is all zero: no obstacles there.
 bool BimocqGPUSolver::setWalls(int mask)
 {
     if (mask < 0 || mask > 63) {
@@ -958,16 +961,22 @@ bool BimocqGPUSolver::setWalls(int mask)
         dropWalls();
         return true;
     }
-    if (GpuSolver->slab.on) {
-        fl_report_error(FL_ERR_UNSUPPORTED, "setWalls: walls are not supported on z-slab ranks");
-        return false;
-    }
     if (projection_kind == BQ_PROJECTION_MGCG) {
         fl_report_error(FL_ERR_UNSUPPORTED, "setWalls: walls need the Jacobi or the PCG projection (not BQ_PROJECTION_MGCG)");
         return false;
     }
     if (!wallOperators()) {
         fl_report_error(FL_ERR_UNSUPPORTED, "setWalls: the operator library has no wall operators");
+        return false;
+    }
+    // z-slab ranks: a library with the two range operators promises that its wall operators honour the slab context
+    // (include/bimocq_gpu.h); any other would put a wall on every rank's first and last local plane
+    if (GpuSolver->slab.on && !(gpu_jacobi_sweep_masked_walls_range && gpu_jacobi_sweep_masked_walls_triple_ranges)) {
+        fl_report_error(FL_ERR_UNSUPPORTED, "setWalls: the operator library has no wall operators for z-slab ranks");
+        return false;
+    }
+    if (GpuSolver->slab.on && projection_kind != BQ_PROJECTION_JACOBI) {
+        fl_report_error(FL_ERR_UNSUPPORTED, "setWalls: walls on z-slab ranks need the Jacobi projection");
         return false;
     }
     const size_t nrows = (size_t)g.nj * (size_t)g.nk;
@@ -1110,8 +1119,9 @@ bool BimocqGPUSolver::projection(bool with_delta)
                                                mg.levels.data(), (int)mg.levels.size(), mg_iters, (double)halfrdx);
         return false;
     }
-    if (!boundaries.empty() || walls) return projectionObstacles(with_delta);   // (setBoundary / setWalls admit one GPU + Jacobi or PCG only)
-    return slabs ? projectionJacobiSlabs(with_delta) : projectionJacobi(with_delta);
+    if (slabs) return projectionJacobiSlabs(with_delta);                 // (walls included; setBoundary refuses slab ranks)
+    if (!boundaries.empty() || walls) return projectionObstacles(with_delta);
+    return projectionJacobi(with_delta);
 }
 
 bool BimocqGPUSolver::projectionJacobi(bool with_delta)
@@ -1139,17 +1149,29 @@ bool BimocqGPUSolver::projectionJacobi(bool with_delta)
 // one exchange of G ghost planes of p buys G sweeps, because each sweep shrinks the correct ghost depth by one plane (the ghost
 // planes are swept redundantly, which yields the very values the neighbour computes).  What a chunk consists of is stated in
 // slab_jacobi_plan.hpp; this function issues it and keeps the plan's two permissions up to date when the library refuses a launch.
+// WALLS ON: the same loop on the plan's walled mode with the walled launches -- the wall faces first
+// (with_delta: their share of d*Proj), one sweep or three per launch on the same plane ranges, the walled gradient last.  Every
+// wall operator places the walls by the global plane, so the ghost planes are swept to the values their owner computes.
 bool BimocqGPUSolver::projectionJacobiSlabs(bool with_delta)
 {
     gpuMapper &gs = *GpuSolver;
     const float alpha = -1.f, beta = (float)(1.0 / 6.0);
     const int G = gs.slab.G;
+    const bool walled = walls != 0;
+    const unsigned char *sw = walled ? solidw.u8() : nullptr, *rw = walled ? rows.u8() : nullptr;
+    float *du = with_delta ? duProj.get() : nullptr, *dv = with_delta ? dvProj.get() : nullptr, *dw = with_delta ? dwProj.get() : nullptr;
     // The redundant ghost sweeps need div on all G ghost planes.  Rather than refreshing three velocity components to
     // depth G and evaluating div there, div is evaluated where the velocities are valid (the owned planes need one ghost
     // plane of w) and its own ghost planes are fetched: one field instead of three, the same values (a neighbour's
     // owned-plane divergence is the very expression this rank would evaluate).
     gs.require({ &VelocityU, &VelocityV, &VelocityW }, 1);
     div.zero(); p.zero(); p_temp.zero();                                 // GPU_Advection.h:604-606
+    if (walled) {
+        // a pointwise pass on the faces of the window; the w face between the window and a closed z plane just outside it is
+        // the one the pass cannot decide (gpu_wall_faces): w's outermost ghost plane no longer counts
+        gpu_wall_faces(VelocityU, VelocityV, VelocityW, du, dv, dw, sw, g.ni, g.nj, g.nk);
+        gs.produced(VelocityW, std::min(VelocityW.valid, G - 1));
+    }
     gpu_divergence(VelocityU, VelocityV, VelocityW, div, g.ni, g.nj, g.nk, halfrdx);
     gs.produced(div, std::min({ VelocityU.valid, VelocityV.valid, VelocityW.valid - 1 }));
     gs.require({ &div }, G);
@@ -1157,11 +1179,23 @@ bool BimocqGPUSolver::projectionJacobiSlabs(bool with_delta)
     gs.produced(*cur, G);                                                // zeros everywhere
     const int own0 = G, own1 = g.nk - G;                                 // local owned planes [own0, own1)
     // S = 2 or 3 sweeps in one launch on up to two plane ranges; false: the library refuses (nothing was launched)
+    // (the walled family has no pairs, and its plan names none)
     auto fused = [&](int S, DeviceField &in, DeviceField &out, slab::Planes a, slab::Planes b = slab::Planes{0, 0}) {
+        if (walled)
+            return S == 3 && gpu_jacobi_sweep_masked_walls_triple_ranges(in, div, out, sw, rw, walls, g.ni, g.nj, g.nk, a.k0, a.k1, b.k0, b.k1,
+                                                                         alpha, beta) != 0;
         return (S == 3 ? gpu_jacobi_sweep_triple_ranges : gpu_jacobi_sweep_pair_ranges)(in, div, out, g.ni, g.nj, g.nk, a.k0, a.k1, b.k0, b.k1,
                                                                                          alpha, beta) != 0;
     };
-    auto single = [&](DeviceField &in, DeviceField &out, slab::Planes a) { gpu_jacobi_sweep_range(in, div, out, g.ni, g.nj, g.nk, a.k0, a.k1, alpha, beta); };
+    auto single = [&](DeviceField &in, DeviceField &out, slab::Planes a) {
+        if (walled) gpu_jacobi_sweep_masked_walls_range(in, div, out, sw, rw, walls, g.ni, g.nj, g.nk, a.k0, a.k1, alpha, beta);
+        else gpu_jacobi_sweep_range(in, div, out, g.ni, g.nj, g.nk, a.k0, a.k1, alpha, beta);
+    };
+    // `n` sweeps on the whole array, one launch or several as the library sees fit; 1: the newest iterate is in `b`
+    auto sweeps = [&](DeviceField &a, DeviceField &b, int n) {
+        return walled ? gpu_jacobi_sweeps_masked_walls(a, div, b, sw, rw, walls, g.ni, g.nj, g.nk, n, alpha, beta)
+                      : gpu_jacobi_sweeps(a, div, b, g.ni, g.nj, g.nk, n, alpha, beta);
+    };
     // the G ghost planes of `f` start travelling on the halo stream; fl_halo_wait (or the next blocking exchange) joins them
     auto startExchange = [&](DeviceField &f) {
         float *ptr = f.get(); size_t pe = f.plane; int ex = 0;
@@ -1191,13 +1225,15 @@ bool BimocqGPUSolver::projectionJacobiSlabs(bool with_delta)
     plan.G = G; plan.owned = own1 - own0;
     plan.pairs_ok = G >= 2 && own1 - own0 >= 5;                          // until the operator library says it cannot
     plan.triples_ok = true;                                              // likewise
-    plan.overlap_exchanges = gs.overlap_exchanges; plan.ends_first = gs.jacobi_ends_first; plan.triples = gs.jacobi_triples;
+    plan.overlap_exchanges = gs.overlap_exchanges; plan.triples = gs.jacobi_triples;
+    plan.ends_first = walled ? gs.jacobi_ends_first_walled : gs.jacobi_ends_first;
+    plan.walled = walled;
     bool in_flight = false;                                              // the exchange of `cur`'s ghost planes has been started
     while (plan.left > 0) {
         int where, chunk;
         if (!in_flight && cur->valid >= std::min(plan.left, G)) {
             chunk = std::min(plan.left, G);
-            where = gpu_jacobi_sweeps(*cur, div, *oth, g.ni, g.nj, g.nk, chunk, alpha, beta);
+            where = sweeps(*cur, *oth, chunk);
         } else {
             // The ghost planes of `cur` travel on the halo stream while the compute stream sweeps what does not
             // depend on them; the planes next to them follow the exchange.
@@ -1236,7 +1272,7 @@ bool BimocqGPUSolver::projectionJacobiSlabs(bool with_delta)
                 i += passes; d -= passes * c.S;
             }
             const int rest = c.sweeps - (G - d);
-            const int w2 = rest > 0 ? gpu_jacobi_sweeps(*in, div, *out, g.ni, g.nj, g.nk, rest, alpha, beta) : 0;
+            const int w2 = rest > 0 ? sweeps(*in, *out, rest) : 0;
             DeviceField *newest = w2 ? out : in;
             where = newest == cur ? 0 : 1;
             chunk = c.sweeps;
@@ -1251,7 +1287,10 @@ bool BimocqGPUSolver::projectionJacobiSlabs(bool with_delta)
     if (cur != &p) p.swap(p_temp);                                       // the newest iterate becomes `p` (no copy-back)
     gs.require({ &p }, 1);
     const int vu = std::min(VelocityU.valid, p.valid), vv = std::min(VelocityV.valid, p.valid), vw = std::min(VelocityW.valid, p.valid - 1);
-    if (with_delta) {
+    if (walled) {
+        gpu_gradient_masked_walls(VelocityU, VelocityV, VelocityW, p, du, dv, dw, sw, walls, g.ni, g.nj, g.nk, halfrdx);
+        if (with_delta) { gs.produced(duProj, vu); gs.produced(dvProj, vv); gs.produced(dwProj, vw); }
+    } else if (with_delta) {
         gpu_gradient_delta(VelocityU, VelocityV, VelocityW, p, duProj, dvProj, dwProj, g.ni, g.nj, g.nk, halfrdx);
         gs.produced(duProj, vu); gs.produced(dvProj, vv); gs.produced(dwProj, vw);
     } else {

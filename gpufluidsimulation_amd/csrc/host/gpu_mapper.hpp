@@ -258,6 +258,7 @@ public:
     long long global_prev_bytes = 0;        // bytes received by assembleGlobal so far (statistics)
     bool overlap_exchanges = true;          // BQ_OPT_OVERLAP_EXCHANGES
     bool jacobi_ends_first = true;          // BQ_OPT_JACOBI_ENDS_FIRST
+    bool jacobi_ends_first_walled = false;  // ... = 2: the walled chunks too (off by default: measured slower)
     bool jacobi_triples = true;             // BQ_OPT_JACOBI_TRIPLES
     bool concurrent_maps = false;           // BQ_OPT_CONCURRENT_MAPS (measured: no gain, EXPERIMENTS.md section 9)
     bool node_lookups = true;               // BQ_OPT_NODE_LOOKUPS

@@ -7,6 +7,8 @@
 // Where another chunk follows, the last two fused passes may run ENDS FIRST: their planes next to the slab ends, then the
 // exchange for the next chunk starts, then their interiors (BimocqGPUSolver::projectionJacobiSlabs issues the sequence).
 // With d the ghost depth still correct after a pass, every plane range below is [own0 - d, own1 + d), plus G for the ends.
+// WALLED (closed domain walls): the walled kernel family has one sweep or three per launch and no pairs, so
+// a walled chunk is one overlapped single sweep, triples, and a tail of `rest` sweeps through gpu_jacobi_sweeps_masked_walls.
 // Pure integer arithmetic: no HIP, no solver state, no operator calls (tests/test_slab_jacobi_plan_cpu.py checks it exhaustively).
 #pragma once
 #include <algorithm>
@@ -20,6 +22,7 @@ struct ChunkIn {
     bool pairs_ok;          // the grid admits two-sweep launches and none was refused in this projection
     bool triples_ok;        // no three-sweep launch was refused in this projection
     bool overlap_exchanges, ends_first, triples;        // BQ_OPT_OVERLAP_EXCHANGES, BQ_OPT_JACOBI_ENDS_FIRST, BQ_OPT_JACOBI_TRIPLES
+    bool walled = false;    // the walled kernel family: singles and triples only (pairs_ok is not read)
 };
 
 struct Chunk {
@@ -31,8 +34,28 @@ struct Chunk {
     int depth_after(int G, int pass) const { return G - first - (pass + 1) * S; }      // ghost planes still correct after fused pass `pass`
 };
 
+// The walled chunk: 1 + 3 * fused + rest.  Ends first needs two triples that close the chunk (no tail behind them: the planes
+// the neighbours receive must be final), so a full chunk that another one follows anyway gives up its `rest` sweeps -- G = 8 runs
+// 1, 3, 3 and exchanges every 7 sweeps, as the unwalled single-sweep mode does.  The interior between the two ends of the first
+// of the two triples, which leaves 3 + (G - sweeps) ghost planes correct, must keep at least 2 planes.
+inline Chunk plan_chunk_walled(const ChunkIn &in)
+{
+    Chunk c{};
+    c.sweeps = std::min(in.left, in.G);
+    c.first = 1;
+    c.S = 3;
+    const bool triples = in.triples && in.triples_ok;
+    c.fused = triples ? (c.sweeps - 1) / 3 : 0;
+    c.rest = c.sweeps - 1 - 3 * c.fused;
+    c.ends_first = in.overlap_exchanges && in.ends_first && c.fused >= 2 && in.left > in.G &&
+                   in.owned >= 2 * in.G + 2 * (3 + c.rest) + 2;
+    if (c.ends_first) { c.sweeps -= c.rest; c.rest = 0; }
+    return c;
+}
+
 inline Chunk plan_chunk(const ChunkIn &in)
 {
+    if (in.walled) return plan_chunk_walled(in);
     Chunk c{};
     c.sweeps = std::min(in.left, in.G);
     c.first = in.pairs_ok && c.sweeps >= 2 ? 2 : 1;

@@ -131,6 +131,7 @@ void bq_solver_set_option(bq_solver *s, int option, int value)
         s->solver->GpuSolver->overlap_exchanges = value != 0;
     } else if (option == BQ_OPT_JACOBI_ENDS_FIRST) {
         s->solver->GpuSolver->jacobi_ends_first = value != 0;
+        s->solver->GpuSolver->jacobi_ends_first_walled = value == 2;
     } else if (option == BQ_OPT_JACOBI_TRIPLES) {
         s->solver->GpuSolver->jacobi_triples = value != 0;
     } else if (option == BQ_OPT_MGCG_SHARED) {
@@ -172,7 +173,7 @@ int bq_solver_get_option(const bq_solver *s, int option)
     case BQ_OPT_FULL_STATE:          return s->solver->keep_full_state ? 1 : 0;
     case BQ_OPT_FUSED_HOUSEKEEPING:  return s->solver->GpuSolver->fuse_housekeeping ? 1 : 0;
     case BQ_OPT_OVERLAP_EXCHANGES:   return s->solver->GpuSolver->overlap_exchanges ? 1 : 0;
-    case BQ_OPT_JACOBI_ENDS_FIRST:   return s->solver->GpuSolver->jacobi_ends_first ? 1 : 0;
+    case BQ_OPT_JACOBI_ENDS_FIRST:   return s->solver->GpuSolver->jacobi_ends_first_walled ? 2 : s->solver->GpuSolver->jacobi_ends_first ? 1 : 0;
     case BQ_OPT_JACOBI_TRIPLES:      return s->solver->GpuSolver->jacobi_triples ? 1 : 0;
     case BQ_OPT_CONCURRENT_MAPS:     return s->solver->GpuSolver->concurrent_maps ? 1 : 0;
     case BQ_OPT_NODE_LOOKUPS:        return s->solver->GpuSolver->node_lookups ? 1 : 0;

@@ -862,7 +862,8 @@ void gpu_obstacle_faces_pose(float *u, float *v, float *w, float *du, float *dv,
  * projection treats as obstacle cells with velocity 0, :1157-1164, :1184-1256, :1288-1356) -------------------------------
  * `walls`: the closed sides, a sum of BQ_WALL_* bits.  A border cell of a closed side that no obstacle covers is a wall
  * cell: solid, velocity 0.  Open sides keep p = 0 in the border cell.  `solidw`: the obstacle flags plus BQ_FLAG_WALL in
- * the wall cells; `rows` stays the summary of the OBSTACLE flags (all zero without obstacles).  Single GPU. */
+ * the wall cells; `rows` stays the summary of the OBSTACLE flags (all zero without obstacles).  One domain, or z-slab ranks
+ * without obstacles (below). */
 #ifndef BQ_WALLS_DEFINED
 #define BQ_WALLS_DEFINED
 enum { BQ_WALL_XLO = 1, BQ_WALL_XHI = 2, BQ_WALL_YLO = 4, BQ_WALL_YHI = 8, BQ_WALL_ZLO = 16, BQ_WALL_ZHI = 32 };
@@ -894,6 +895,33 @@ void gpu_gradient_masked_walls(float *u, float *v, float *w, const float *p, flo
                                const unsigned char *solidw, int walls, int ni, int nj, int nk, float halfrdx);
 void gpu_pcg_gradient_walls(float *u, float *v, float *w, const double *p, const unsigned char *solidw, int walls,
                             int ni, int nj, int nk, double halfrdx);
+/* Z-SLAB RANKS (fl_set_slab).  A library that exports the two range operators below promises that gpu_wall_flags,
+ * gpu_wall_faces, gpu_jacobi_sweep_masked_walls / gpu_jacobi_sweeps_masked_walls and gpu_gradient_masked_walls honour the
+ * slab context, and the host relies on it (a library without them runs walls on one domain only):
+ *   - every position along z is GLOBAL: local plane k is global plane k + koff of nkg, BQ_WALL_ZLO is global plane 0 and
+ *     BQ_WALL_ZHI global plane nkg - 1, so a rank in the middle has x and y walls only; the wall cells, the wall-neighbour
+ *     count of the sweeps and the gradient's window (cell 1 instead of 2 behind a closed low side) follow from that;
+ *   - planes of the rank's array outside the global grid hold no cell: flag 0, nothing written; the sweeps leave global
+ *     planes 0 and nkg - 1 alone;
+ *   - gpu_wall_faces decides a w face on the first or last plane of the window from the cell inside the window where the
+ *     other one lies outside the window but inside the grid (exact for x and y walls; the face next to a closed z plane
+ *     just outside the window belongs to a ghost plane the caller must count as stale); gpu_gradient_masked_walls leaves w
+ *     on the window's first plane alone where the plane below it is not in the window (dw: 0), as gpu_gradient does.
+ * With the context off every operator computes what it computed before.  gpu_pcg_gradient_walls stays single-domain.
+ *
+ * One walled sweep in -> out on the local planes [k_begin, k_end) (clipped to the interior), and three walled sweeps in one
+ * launch with `out` written on [k0a, k1a) and [k0b, k1b) (either may be empty; the input valid three planes beyond each
+ * range, both buffers with the same boundary layer): the walled counterparts of gpu_jacobi_sweep_range and
+ * gpu_jacobi_sweep_triple_ranges, value for value gpu_jacobi_sweep_masked_walls on the same operands.  Each returns 1 when
+ * it ran and 0 when it refuses, having launched nothing: bad arguments (latched), walls = 0 (latched: the masked family has
+ * no range sweeps), and for the triple the shapes the whole-array walled triple refuses and FL_OPT_JACOBI_FUSE 0 / 4.  Where
+ * `rows` is clean neither loads a flag. */
+int  gpu_jacobi_sweep_masked_walls_range(const float *in, const float *div, float *out, const unsigned char *solidw,
+                                         const unsigned char *rows, int walls, int ni, int nj, int nk, int k_begin, int k_end,
+                                         float alpha, float beta);
+int  gpu_jacobi_sweep_masked_walls_triple_ranges(const float *in, const float *div, float *out, const unsigned char *solidw,
+                                                 const unsigned char *rows, int walls, int ni, int nj, int nk,
+                                                 int k0a, int k1a, int k0b, int k1b, float alpha, float beta);
 
 /* ---- shaped, moving smoke sources (reference: Emitter and BimocqSolver::emitSmoke of the CPU
  * solver, BimocqSolver.h:31-59, BimocqSolver.cpp:696-813) ----------------------------------------------------------------

@@ -96,7 +96,10 @@ enum {
      * another chunk follows run on the planes next to the slab ends first, the exchange for the next chunk starts there,
      * and their interiors (and the next chunk's first interior) run while it travels -- three launches hide the 8-plane
      * exchange instead of one, at two more short launches per chunk (+ 2 % compute on a 512 x 512 x 64 rank).  0: the
-     * exchange starts when the chunk is complete.  Same values either way. */
+     * exchange starts when the chunk is complete.  Same values either way.  2: ... and with closed walls too -- the walled
+     * chunk of a rank with at least 2 G + 8 + 2 ((G - 1) mod 3) + 2 owned planes and G >= 7 gives up the sweeps behind its last
+     * triple (G = 8: 7 sweeps per exchange) and runs its last two triples ends first.  With 1 a walled chunk keeps the
+     * plain order: on a rank whose exchange costs nothing the ends-first order is slower there. */
     BQ_OPT_JACOBI_ENDS_FIRST = 7,
     /* 1: advanceBimocq brackets its phases with events on the compute stream (read with bq_solver_phase_ms): where the
      * step's time goes on this rank, the waits for ghost planes included in the phase that needs them.  Default 0. */
@@ -241,10 +244,13 @@ int   bq_solver_boundary_pose(const bq_solver *s, int i, double out[10]);
 /* Closed domain walls (the reference's container, BimocqSolver.cpp:938-948): `walls` is a sum of
  * BQ_WALL_* bits (include/bimocq_gpu.h), BQ_WALLS_NONE (default: every side open, p = 0 in the border cells) or
  * BQ_WALLS_REFERENCE_BOX (every side closed but +y).  Border cells of a closed side are solid cells with velocity 0 for
- * the projection; no band, no blend, no density clear, and download_solid keeps reporting obstacle cells only.  One GPU,
- * Jacobi projection or BQ_PROJECTION_PCG, every scheme, with or without obstacles, in any call order.  Refused through
- * fl_last_error, the previous setting staying in place: z-slab ranks, BQ_PROJECTION_MGCG (also set_projection(MGCG)
- * while walls are on) and an operator library without the wall operators with FL_ERR_UNSUPPORTED; bits outside 0 .. 63
+ * the projection; no band, no blend, no density clear, and download_solid keeps reporting obstacle cells only.  One GPU
+ * with the Jacobi projection or BQ_PROJECTION_PCG, with or without obstacles, or z-slab ranks with the Jacobi projection
+ * and no obstacles (every rank sets the same mask; BQ_WALL_ZLO / _ZHI are the first / last GLOBAL plane, a rank in the
+ * middle has x and y walls only; every owned plane equals the one-GPU walled run bit for bit); every scheme, in any call
+ * order.  Refused through fl_last_error, the previous setting staying in place: BQ_PROJECTION_MGCG (also
+ * set_projection(MGCG) while walls are on), an operator library without the wall operators, and on a z-slab rank one
+ * without gpu_jacobi_sweep_masked_walls_range / _triple_ranges, with FL_ERR_UNSUPPORTED; bits outside 0 .. 63
  * and all six sides closed (the pressure needs an open side as its reference) with FL_ERR_BAD_ARGUMENT.
  * Returns 0 on success; get_walls returns the setting in force. */
 int   bq_solver_set_walls(bq_solver *s, int walls);

@@ -6,8 +6,12 @@ Jacobi iterations, steps 20-200, library defaults -- the setup of tools/obstacle
      rows summary marked dirty, against gpu_jacobi_sweeps_masked_walls on the same arrays, three alternating runs each
   D  the container + the sphere of section 14 (radius 0.15 L at the centre)
   E  BQ_PROJECTION_PCG in the container: iterations, final max|r| / max|b| and stop reason of every projection
+  S  one GPU playing ONE z-slab rank of 4 (64 owned + 2 x 8 ghost planes) with a transport that moves nothing, as
+     bench.py --emulate-slab does: a middle rank (x and y walls only) and rank 0 (the z-low wall too) in the container with the
+     walled plan's ends-first order on and off, next to the unwalled emulated middle rank; three alternating runs each:
+     projection ms per step and projection us per sweep (the range launches are not inside the sweep loops' event pairs)
 A, B, D: step ms, projection ms, us per sweep launch.  Writes profiles/walls_bench.json and prints the same JSON line.
-Usage: python tools/walls_bench.py [--n 256] [--steps 180] [--warmup 20] [--jacobi-iters 200] [--pcg-steps 20] [--out PATH]"""
+Usage: python tools/walls_bench.py [--n 256] [--steps 180] [--warmup 20] [--jacobi-iters 200] [--pcg-steps 20] [--slab-steps 30] [--out PATH]"""
 import argparse
 import ctypes as C
 import json
@@ -112,6 +116,46 @@ def operator_legs(n, walls, sweeps, runs=3):
             "B_faster_beyond_spread": max(res["B"]) < min(res["C"])}
 
 
+def slab_legs(n, walls, args, runs=3, nranks=4, ghost=8):
+    """the emulated slab ranks, alternating: {name: [projection ms per step, ...]} and the same as us per sweep"""
+    from gpufluidsimulation_amd import transport
+    lib = bq.hip_lib()
+    h = 1.0 / n
+    # BQ_OPT_JACOBI_ENDS_FIRST: 2 = the walled chunks too, 1 (the default) = walled chunks in the plain order
+    cases = (("unwalled middle rank", 0, nranks // 2, 1), ("walled middle rank, ends first", walls, nranks // 2, 2),
+             ("walled middle rank, plain order", walls, nranks // 2, 1), ("walled rank 0, ends first", walls, 0, 2),
+             ("walled rank 0, plain order", walls, 0, 1))
+
+    def run(w, rank, ends_first):
+        keep = transport.NullTransport(lib, rank, nranks)
+        s = BimocqGPUSolver(n, n, n, 1.0, 0.0, 1.0, device=0, rank=rank, nranks=nranks, ghost=ghost)
+        s.setSmoke(0.0, 1.0, rising_smoke(n, h))
+        s.setProjection(args.jacobi_iters, 0.5)
+        s.setWalls(w)
+        s.setOption(7, ends_first)
+        for f in range(5):
+            s.advance(f, 2.0 * h)
+        lib.fl_sync()
+        s.setOption(8, 1)
+        s.phaseMs(reset=True)
+        for f in range(5, 5 + args.slab_steps):
+            s.advance(f, 2.0 * h)
+        lib.fl_sync()
+        phases, psteps = s.phaseMs(reset=True)
+        bq.check()
+        s.close()
+        del keep
+        return phases["projection"] / max(1, psteps)
+    res = {name: [] for name, *_ in cases}
+    for _ in range(runs):
+        for name, w, rank, ef in cases:
+            res[name].append(round(run(w, rank, ef), 3))
+    sweeps = max(1, args.jacobi_iters - 1)
+    return {"leg": "S (emulated slab rank of %d, %d owned + 2 x %d ghost planes)" % (nranks, n // nranks, ghost), "n": n, "walls": walls,
+            "steps": args.slab_steps, "projection_ms": res,
+            "projection_us_per_sweep": {k: [round(v * 1e3 / sweeps, 2) for v in vs] for k, vs in res.items()}}
+
+
 def pcg_leg(n, walls, args):
     h = 1.0 / n
     s = BimocqGPUSolver(n, n, n, 1.0, 0.0, 1.0, device=0)
@@ -140,6 +184,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--jacobi-iters", type=int, default=200)
     ap.add_argument("--pcg-steps", type=int, default=20)
+    ap.add_argument("--slab-steps", type=int, default=30, help="timed steps of each run of the emulated slab ranks (0: none)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "walls_bench.json"))
     args = ap.parse_args()
     box = WALLS_REFERENCE_BOX
@@ -151,6 +196,9 @@ def main():
     print(json.dumps(legs[-1]), file=sys.stderr, flush=True)
     if args.pcg_steps > 0:
         legs.append(pcg_leg(args.n, box, args))
+        print(json.dumps(legs[-1]), file=sys.stderr, flush=True)
+    if args.slab_steps > 0:
+        legs.append(slab_legs(args.n, box, args))
         print(json.dumps(legs[-1]), file=sys.stderr, flush=True)
     a, b = legs[0], legs[1]
     out = {"tool": "walls_bench", "jacobi_iters": args.jacobi_iters, "window": [args.warmup, args.warmup + args.steps], "legs": legs,
