@@ -820,6 +820,18 @@ static bool dims_ok(int ni, int nj, int nk, const char *op)
     return true;
 }
 
+// The same limits for ONE BUFFER of nx x ny x nz floats: the entry points that take a component's own dims (the limiters).
+// Every buffer of a grid within dims_ok is within this -- the w component of the tallest grid, nk + 1 = 65535 planes, included,
+// which dims_ok on buffer dims would turn away as a grid of 65536.
+static bool buffer_dims_ok(int nx, int ny, int nz, const char *op)
+{
+    if (nx < 1 || ny < 1 || nz < 1) { latch(FL_ERR_BAD_ARGUMENT, op, "non-positive buffer dims"); return false; }
+    if (4.0 * (double)nx * (double)ny * (double)nz >= 2147483648.0) { latch(FL_ERR_BAD_ARGUMENT, op, "field larger than 2 GiB"); return false; }
+    if (nz > 65535) { latch(FL_ERR_BAD_ARGUMENT, op, "nk too large for grid.z"); return false; }
+    if ((double)nx * (double)ny >= 8388608.0) { latch(FL_ERR_BAD_ARGUMENT, op, "plane larger than 2^23 elements"); return false; }
+    return true;
+}
+
 #define BQ_DISPATCH1(KERNEL, P2V, GRID, ...)                                                                \
     do {                                                                                                    \
         hipStream_t st_ = rt().compute;                                                                     \
@@ -1244,9 +1256,10 @@ using namespace bq;
     static void name##_impl params
 #endif
 
-#define BQ_ENTER(op, ...)                                                  \
+#define BQ_ENTER(op, ...) BQ_ENTER_IF(dims_ok(ni, nj, nk, op), op, __VA_ARGS__)
+#define BQ_ENTER_IF(dims_fit, op, ...)                                     \
     if (!ensure_ready(op)) return;                                         \
-    if (!dims_ok(ni, nj, nk, op)) return;                                  \
+    if (!(dims_fit)) return;                                               \
     {                                                                      \
         const void *ptrs_[] = { __VA_ARGS__ };                             \
         for (const void *p_ : ptrs_)                                       \
@@ -1616,9 +1629,11 @@ BQ_ENTRY(gpu_clamp_extrema, (float *field, float *fieldTemp, float *u, float *v,
                        int ni, int nj, int nk, int dimx, int dimy, int dimz,
                        float ox, float oy, float oz, float h, float dt), (field, fieldTemp, u, v, w, ni, nj, nk, dimx, dimy, dimz, ox, oy, oz, h, dt))
 {
-    BQ_ENTER("gpu_clamp_extrema", field, fieldTemp, u, v, w)
-    BQ_REQUIRE(field != fieldTemp && ((dimx | dimy | dimz) == 0 || (dimx + dimy + dimz) == 1) &&
-               ni - dimx >= 1 && nj - dimy >= 1 && nk - dimz >= 1, "gpu_clamp_extrema");
+    if (!ensure_ready("gpu_clamp_extrema")) return;
+    BQ_REQUIRE((dimx | dimy | dimz) == 0 || ((dimx | dimy | dimz) == 1 && dimx + dimy + dimz == 1), "gpu_clamp_extrema");
+    // ni, nj, nk are the component's buffer dims: the limits are those of the grid it belongs to
+    BQ_ENTER_IF(dims_ok(ni - dimx, nj - dimy, nk - dimz, "gpu_clamp_extrema"), "gpu_clamp_extrema", field, fieldTemp, u, v, w)
+    BQ_REQUIRE(field != fieldTemp, "gpu_clamp_extrema");
     Spacing sp = make_spacing(h);
     const Grid g = mk_grid(ni - dimx, nj - dimy, nk - dimz);          // the slab context (single GPU: koff 0, nkg = cell planes)
     BQ_DISPATCH1(clamp_extrema_kernel, sp.pow2, grid_for(ni, nj, nk), field, fieldTemp, u, v, w, sp, ni, nj, nk,
@@ -1640,13 +1655,13 @@ BQ_ENTRY(gpu_maccormack, (float *out, const float *f1, const float *f_adv, const
 
 BQ_ENTRY(gpu_clamp_extrema_box, (const float *before, float *after, int ni, int nj, int nk), (before, after, ni, nj, nk))
 {
-    BQ_ENTER("gpu_clamp_extrema_box", before, after)
+    BQ_ENTER_IF(buffer_dims_ok(ni, nj, nk, "gpu_clamp_extrema_box"), "gpu_clamp_extrema_box", before, after)
     clamp_box(before, after, ni, nj, nk, 0);
 }
 
 BQ_ENTRY(gpu_clamp_extrema_box_w, (const float *before, float *after, int ni, int nj, int nk), (before, after, ni, nj, nk))
 {
-    BQ_ENTER("gpu_clamp_extrema_box_w", before, after)
+    BQ_ENTER_IF(buffer_dims_ok(ni, nj, nk, "gpu_clamp_extrema_box_w"), "gpu_clamp_extrema_box_w", before, after)
     clamp_box(before, after, ni, nj, nk, 1);
 }
 

@@ -123,6 +123,25 @@ void profile_end(ProfileSpan &sp, long long launches, long long sweeps);
 // one thread per element: blocks of 64 (x) x 4 (y), planes along grid.z
 static const dim3 kBlock(64, 4, 1);
 inline dim3 grid_for(int nbi, int nbj, int nbk) { return dim3((nbi + 63) / 64, (nbj + 3) / 4, nbk); }
+// grid.z takes at most 65535 planes and the w component has nk + 1.  grid.y has no rule here: the runtime takes more than
+// 65535 blocks on it, so nj is bounded by the plane limit where a launcher has one and not at all where this is its only
+// check (include/bimocq_gpu.h, "Limits").  False: latched under the text every launcher uses for this limit.
+inline bool planes_ok(int nk, const char *op)
+{
+    if (nk + 1 <= 65535) return true;
+    latch(FL_ERR_BAD_ARGUMENT, op, "nk too large for grid.z");
+    return false;
+}
+// the size rules of the obstacle and source operators (size_t indices: 4 GiB, no plane limit), each refusal under its own text
+inline bool obstacle_dims_ok(int ni, int nj, int nk, const char *op)
+{
+    if (ni < 3 || nj < 3 || nk < 3) { latch(FL_ERR_BAD_ARGUMENT, op, "dims below 3"); return false; }
+    if (4.0 * (double)(ni + 1) * (double)(nj + 1) * (double)(nk + 1) >= 4294967296.0) {
+        latch(FL_ERR_BAD_ARGUMENT, op, "field larger than 4 GiB");
+        return false;
+    }
+    return planes_ok(nk, op);
+}
 // true when every pointer is 16-byte aligned (float4 / double2 accesses)
 template <typename... P>
 inline bool aligned16(const P *...p) { return ((... | (uintptr_t)p) & 15u) == 0; }

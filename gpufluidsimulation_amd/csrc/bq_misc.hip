@@ -292,7 +292,8 @@ void gpu_emit_smoke(float *u, float *v, float *w, float *rho, float *T, float h,
                     float centerX, float centerY, float centerZ, float radius, float density, float temperature, float emiter)
 {
     if (!ensure_ready("gpu_emit_smoke")) return;
-    BQ_REQUIRE(u && v && w && rho && T && ni > 0 && nj > 0 && nk > 0 && nk < 65535, "gpu_emit_smoke");
+    BQ_REQUIRE(u && v && w && rho && T && ni > 0 && nj > 0 && nk > 0, "gpu_emit_smoke");
+    if (!planes_ok(nk, "gpu_emit_smoke")) return;
     hipStream_t st = rt().compute;
     int koff, nkg;
     slab_ctx(nk, koff, nkg);
@@ -306,7 +307,8 @@ void gpu_emit_smoke(float *u, float *v, float *w, float *rho, float *T, float h,
 void gpu_add_buoyancy(float *field, float *density, float *temperature, int ni, int nj, int nk, float alpha, float beta, float dt)
 {
     if (!ensure_ready("gpu_add_buoyancy")) return;
-    BQ_REQUIRE(field && density && temperature && ni > 0 && nj > 0 && nk > 0 && nk < 65535, "gpu_add_buoyancy");
+    BQ_REQUIRE(field && density && temperature && ni > 0 && nj > 0 && nk > 0, "gpu_add_buoyancy");
+    if (!planes_ok(nk, "gpu_add_buoyancy")) return;
     int koff, nkg;
     slab_ctx(nk, koff, nkg);
     buoyancy_kernel<<<grid_for(ni, nj, nk), kBlock, 0, rt().compute>>>(field, density, temperature, ni, nj, nk, alpha, beta, dt, koff, nkg);
@@ -343,7 +345,8 @@ void gpu_mad(float *field, float *field1, float *field2, float coeff1, float coe
 void gpu_init_maps(float *x, float *y, float *z, float h, int ni, int nj, int nk)
 {
     if (!ensure_ready("gpu_init_maps")) return;
-    BQ_REQUIRE(x && y && z && ni > 0 && nj > 0 && nk > 0 && nk < 65535, "gpu_init_maps");
+    BQ_REQUIRE(x && y && z && ni > 0 && nj > 0 && nk > 0, "gpu_init_maps");
+    if (!planes_ok(nk, "gpu_init_maps")) return;
     int koff, nkg;
     slab_ctx(nk, koff, nkg);
     init_maps_kernel<<<grid_for(ni, nj, nk), kBlock, 0, rt().compute>>>(x, y, z, h, ni, nj, nk, koff, nkg);
@@ -427,7 +430,8 @@ void gpu_map_travel_z(const float *bz, const float *fz, float h, int ni, int nj,
 {
     if (out) out[0] = out[1] = 0.f;
     if (!ensure_ready("gpu_map_travel_z")) return;
-    if (!bz || !fz || !out || ni < 1 || nj < 1 || nk < 1 || nk >= 65535 || !(h > 0.f)) { latch(FL_ERR_BAD_ARGUMENT, "gpu_map_travel_z", "bad argument"); return; }
+    if (!bz || !fz || !out || ni < 1 || nj < 1 || nk < 1 || !(h > 0.f)) { latch(FL_ERR_BAD_ARGUMENT, "gpu_map_travel_z", "bad argument"); return; }
+    if (!planes_ok(nk, "gpu_map_travel_z")) return;
     const Runtime &r = rt();
     const int p0 = r.slab_on ? r.slab_own0 - r.slab_koff : 0, p1 = r.slab_on ? r.slab_own1 - r.slab_koff : nk;
     int koff, nkg;

@@ -344,10 +344,7 @@ __global__ __launch_bounds__(256) void obstacle_blend_kernel(float *__restrict__
 static bool obs_args_ok(const bq_boundary *b, int n, int ni, int nj, int nk, const char *op, bool slab_ok = false)
 {
     if (!ensure_ready(op)) return false;
-    if (ni < 3 || nj < 3 || nk < 3 || 4.0 * (double)(ni + 1) * (double)(nj + 1) * (double)(nk + 1) >= 4294967296.0 || nk + 1 > 65535) {
-        latch(FL_ERR_BAD_ARGUMENT, op, "grid dims out of range");
-        return false;
-    }
+    if (!obstacle_dims_ok(ni, nj, nk, op)) return false;
     if (n < 0 || n > BQ_MAX_BOUNDARIES || (n > 0 && !b)) { latch(FL_ERR_BAD_ARGUMENT, op, "1 .. 16 obstacles"); return false; }
     if (rt().slab_on && !slab_ok) { latch(FL_ERR_UNSUPPORTED, op, "obstacles on z-slab ranks"); return false; }
     return true;

@@ -1588,6 +1588,16 @@ static bool dims_ok(int ni, int nj, int nk, const char *op)
     return true;
 }
 
+// the same limits for ONE BUFFER of ni x nj x nk floats: the diffusion sweeps run on a component's own dims, and the w component
+// of the tallest grid has nk + 1 = 65535 planes, which dims_ok on buffer dims would turn away as a grid of 65536
+static bool buffer_dims_ok(int ni, int nj, int nk, const char *op)
+{
+    if (ni < 1 || nj < 1 || nk < 1) { latch(FL_ERR_BAD_ARGUMENT, op, "non-positive buffer dims"); return false; }
+    if (4.0 * (double)ni * (double)nj * (double)nk >= 4294967296.0) { latch(FL_ERR_BAD_ARGUMENT, op, "field larger than 4 GiB"); return false; }
+    if (nk > 65535) { latch(FL_ERR_BAD_ARGUMENT, op, "nk too large for grid.z"); return false; }
+    return true;
+}
+
 // per-context state of this file (bq_host.h: Runtime::project_state), behind the names it always had
 struct SweepSpan { hipEvent_t a, b; long long launches, sweeps; };
 struct ProjectState {
@@ -1837,9 +1847,10 @@ void profile_end(ProfileSpan &sp, long long launches, long long sweeps)
 
 using namespace bq;
 
-#define BQ_ENTER(op, ...)                                                  \
+#define BQ_ENTER(op, ...) BQ_ENTER_IF(dims_ok(ni, nj, nk, op), op, __VA_ARGS__)
+#define BQ_ENTER_IF(dims_fit, op, ...)                                     \
     if (!ensure_ready(op)) return;                                         \
-    if (!dims_ok(ni, nj, nk, op)) return;                                  \
+    if (!(dims_fit)) return;                                               \
     {                                                                      \
         const void *ptrs_[] = { __VA_ARGS__ };                             \
         for (const void *p_ : ptrs_)                                       \
@@ -2080,7 +2091,7 @@ const char *fl_jacobi_kernel_name(void) { return ps().last_pair_kernel; }
 // GPU_kernel.cu:855-876
 void gpu_diffuse_field(float *field, float *fieldTemp0, float *filedTemp1, int ni, int nj, int nk, int iter, float coef)
 {
-    BQ_ENTER("gpu_diffuse_field", field, fieldTemp0, filedTemp1)
+    BQ_ENTER_IF(buffer_dims_ok(ni, nj, nk, "gpu_diffuse_field"), "gpu_diffuse_field", field, fieldTemp0, filedTemp1)
     BQ_REQUIRE(field != fieldTemp0 && field != filedTemp1 && fieldTemp0 != filedTemp1 && iter >= 0, "gpu_diffuse_field");
     const size_t bytes = (size_t)ni * nj * nk * sizeof(float);
     float *in = fieldTemp0, *out = filedTemp1;
@@ -2101,7 +2112,7 @@ void gpu_diffuse_field(float *field, float *fieldTemp0, float *filedTemp1, int n
 // of gpu_diffuse_field a z-slab host needs to refresh ghost planes between chunks of sweeps.
 int gpu_diffuse_sweeps(const float *field, float *in, float *out, int ni, int nj, int nk, int sweeps, float coef)
 {
-    if (!ensure_ready("gpu_diffuse_sweeps") || !dims_ok(ni, nj, nk, "gpu_diffuse_sweeps")) return 0;
+    if (!ensure_ready("gpu_diffuse_sweeps") || !buffer_dims_ok(ni, nj, nk, "gpu_diffuse_sweeps")) return 0;
     if (!field || !in || !out || in == out || field == in || field == out || sweeps < 0) {
         latch(FL_ERR_BAD_ARGUMENT, "gpu_diffuse_sweeps", "null or aliased buffers"); return 0;
     }

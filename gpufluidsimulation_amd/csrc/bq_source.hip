@@ -109,10 +109,7 @@ extern "C" void gpu_emit_sources(float *u, float *v, float *w, float *rho, float
 {
     const char *op = "gpu_emit_sources";
     if (!ensure_ready(op)) return;
-    if (ni < 3 || nj < 3 || nk < 3 || 4.0 * (double)(ni + 1) * (double)(nj + 1) * (double)(nk + 1) >= 4294967296.0 || nk + 1 > 65535) {
-        latch(FL_ERR_BAD_ARGUMENT, op, "grid dims out of range");
-        return;
-    }
+    if (!obstacle_dims_ok(ni, nj, nk, op)) return;
     if (n < 0 || n > BQ_MAX_SOURCES || (n > 0 && !src)) { latch(FL_ERR_BAD_ARGUMENT, op, "0 .. 16 sources"); return; }
     if (!u || !v || !w || !rho || !T || !(h > 0.f)) { latch(FL_ERR_BAD_ARGUMENT, op, "null device pointer or spacing"); return; }
     bq_boundary shapes[BQ_MAX_SOURCES];

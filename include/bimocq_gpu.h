@@ -217,17 +217,53 @@ void gpu_multi_grid_conjugate_gradient(float *u, float *v, float *w, double *div
                                        double *tempResult, struct SCoarseLevelInfo *levels,
                                        int levelNum, int iter, double halfrdx);
 
-/* ---- Limits of the operators above (part of the ABI contract; each violation latches an error, nothing is launched) ----
- *   * ONE field must stay below 2 GiB: 4 (ni+1)(nj+1)(nk+1) < 2^31 bytes.  The gather kernels (gpu_solve_*, gpu_advect_*,
- *     gpu_compensate_*, gpu_accumulate_*, gpu_semilag, gpu_clamp_extrema, gpu_maccormack, gpu_estimate_distortion) address a field through
- *     a buffer resource descriptor with 32-bit byte offsets, and the offset 2 GiB is where a cell whose base index is
- *     negative is parked so that the descriptor's range check zeroes its corners (FL_ERR_BAD_ARGUMENT "field larger than
- *     2 GiB").  512^3 is 0.5 GiB; BASELINE config 5 (1024 x 1024 x 512 = 2.0 GiB per field) needs >= 2 z-slab ranks --
+/* ---- Limits of the operators (part of the ABI contract; each violation latches FL_ERR_BAD_ARGUMENT under the text in quotes,
+ * nothing is launched, no buffer is touched).  What the launchers enforce, family by family -- F = 4 (ni+1)(nj+1)(nk+1) bytes,
+ * the bound of every buffer of the grid; P = (ni+1)(nj+1) elements, the bound of every plane:
+ *
+ *   family (where the check is)                                     field            plane        planes
+ *   ------------------------------------------------------------------------------------------------------------------
+ *   descriptor-addressed gathers (bq_advect.hip: dims_ok):          F < 2 GiB        P < 2^23     nk + 1 <= 65535
+ *     gpu_solve_*, gpu_advect_*, gpu_compensate_*, gpu_accumulate_*, gpu_estimate_distortion, gpu_semilag*, gpu_maccormack,
+ *     gpu_clamp_extrema (from the component's dims back to its grid's), gpu_brick_flags, gpu_maps_quarter_safe;
+ *     gpu_clamp_extrema_box / _box_w (buffer_dims_ok: the same three for the ONE buffer nx x ny x nz they are given:
+ *     4 nx ny nz < 2 GiB, nx ny < 2^23, nz <= 65535)
+ *   gpu_flow_stats, gpu_vorticity_confinement, gpu_obstacle_loads,  F < 2 GiB        P < 2^23     nk + 1 <= 65535
+ *     gpu_render_density (each its own check; dims >= 3, render: 1..65534); the tracer entry points (bq_tracers.hip)
+ *   projection (bq_project.hip: dims_ok): gpu_divergence,           F < 4 GiB        --           nk + 1 <= 65535
+ *     gpu_jacobi_sweep*, gpu_gradient*, gpu_residual_norms, gpu_projection_jacobi; gpu_diffuse_field / gpu_diffuse_sweeps
+ *     (buffer_dims_ok: 4 ni nj nk < 4 GiB and nk <= 65535 of the one buffer they are given)
+ *   obstacles and walls (bq_obstacle.hip: obs_args_ok),             F < 4 GiB        --           nk + 1 <= 65535
+ *     gpu_emit_sources (bq_source.hip); dims >= 3
+ *   streaming: gpu_emit_smoke, gpu_add_buoyancy, gpu_init_maps,     --               --           nk + 1 <= 65535
+ *     gpu_map_travel_z (bq_host.h: planes_ok; 64-bit indices); the fp64 projection entry points (nk < 65535 per level)
+ *
+ *   "field larger than 2 GiB": the gather kernels address a field through a buffer resource descriptor with 32-bit byte offsets,
+ *     and the offset 2 GiB is where a cell whose base index is negative is parked so that the descriptor's range check zeroes its
+ *     corners.  512^3 is 0.5 GiB; BASELINE config 5 (1024 x 1024 x 512 = 2.0 GiB per field) needs >= 2 z-slab ranks --
  *     bq_solver_create / gpuMapper refuse it on one rank with FL_ERR_UNSUPPORTED and name the rank count.
- *   * one plane must stay below 2^23 elements: (ni+1)(nj+1) < 8 388 608 (flat indices are formed with 24-bit multiplies).
- *   * nk + 1 <= 65 535: planes are launched along grid.z ("nk too large for grid.z").
- *   * the fused Jacobi kernels take rows of 32..1024 floats with ni % 4 == 0 and 16-byte aligned pointers; any other row
- *     runs the one-sweep kernels (same values).
+ *   "plane larger than 2^23 elements" ("plane of 2^23 elements or more"): flat indices are formed with 24-bit multiplies.
+ *   "nk too large for grid.z": planes are launched along grid.z, and the w component has nk + 1 of them.  An entry point that
+ *     takes a component's own dims accepts that buffer: 65535 planes of w on a grid of nk = 65534.
+ *   nj has no limit of its own: where a family has the plane limit, that bounds it; in the rows marked "--" under "plane"
+ *     only the field size does (projection, obstacles, sources), and in the streaming row nothing does.  Rows go along grid.y
+ *     four to a block, so a grid of few columns puts more than 65535 blocks there; the HIP runtime on gfx950 takes such a launch,
+ *     and at grid.y = 65540 and 65541 (nj = 262160, the v component) the gather, projection, streaming, obstacle, wall and fp64
+ *     operators, gpu_flow_stats and gpu_emit_sources (a source box along the whole grid) equal their references bit for bit
+ *     (tests/test_gpu_needle_grids.py).  Two operators keep a rule of their own, "nj too large for grid.y" when
+ *     (nj + 4) / 4 > 65535: gpu_vorticity_confinement and gpu_obstacle_loads, whose marching kernels tile nj + 1 rows and have
+ *     not been run beyond it.  gpu_render_density takes no dimension above 65534 ("dims outside 1..65534"): a ray's optical
+ *     depth, at most 32 * 2^32 per cell, must stay an integer below 2^53.
+ *   The entry points that take ONE buffer's dims (buffer_dims_ok, both files) bound that buffer, not the grid around it: the
+ *     u, v and w buffers of a grid are each smaller than F, so a buffer passes whenever its grid would, and a buffer just below
+ *     2 (4) GiB also passes whose grid, one node larger per axis, would not.  That is deliberate: these kernels index the one
+ *     buffer they are given (with 64-bit indices), and the w buffer of the tallest grid, 65535 planes, must pass.
+ *   "dims below 3": the obstacle, wall and source operators (bq_host.h: obstacle_dims_ok), gpu_flow_stats,
+ *     gpu_vorticity_confinement and gpu_obstacle_loads need three cells per axis.
+ *   A field between 2 and 4 GiB is accepted by the projection, obstacle and source families and covered by no test: the
+ *     oracle needs minutes for one.  Everything a test covers lies below 2 GiB.
+ *   The fused Jacobi kernels take rows of 32..1024 floats with ni % 4 == 0 and 16-byte aligned pointers; any other row runs
+ *     the one-sweep kernels (same values).
  */
 
 /* ------------------------------------------------------------------------------------------
