@@ -78,6 +78,7 @@ HIP_SIGS = {
     "fl_jacobi_kernel_name": (C.c_char_p, []),
     "fl_mg_smooth_kernel_name": (C.c_char_p, []),
     "fl_mg_fused_launches": (C.c_longlong, []),
+    "fl_mg_residual_launches": (C.c_longlong, []),
     "fl_sparse_stats": (None, [C.POINTER(C.c_longlong), c_i]),
     "fl_sparse_stats_kind": (None, [c_i, C.POINTER(C.c_longlong), c_i]),
     "gpu_brick_flags": (c_i, [VP, VP, c_i, c_i, c_i, VP, C.POINTER(c_i)]),

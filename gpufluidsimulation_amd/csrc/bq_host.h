@@ -83,6 +83,7 @@ struct Runtime {
     const char *map_kernel_name[2] = { "", "" };    // the DMC / forward instance launched last (fl_map_kernel_name)
     int    map_kernels_seen = 0;        // instances launched since the last reset, as bits (fl_map_kernels_seen)
     long long   mg_fused_launches = 0;  // fl_mg_fused_launches
+    long long   mg_residual_launches = 0;   // fl_mg_residual_launches
     const char *mg_smooth_kernel = ""; // the fused kernel the last fp64 smoothing call launched first (fl_mg_smooth_kernel_name)
 };
 

@@ -1419,9 +1419,12 @@ static void mg_smooth(double *x, const double *b, double *temp, double alpha, do
                     for (int t = 0; t < triples + pairs; t++) {
                         const bool three = t < triples;
                         // the last launch, when it is a pair and the caller wants the residual next: two sweeps + the residual
-                        if (!three && t == triples + pairs - 1 && resid && resid_done && LW == 8 && !zin && out == x) {
+                        // (stored as double2 columns like x: a residual array off a 16-byte boundary gets the plain pair, and the
+                        // caller's mg_residual)
+                        if (!three && t == triples + pairs - 1 && resid && resid_done && LW == 8 && !zin && out == x && aligned16(resid)) {
                             mg_lds3_kernel<8, 3, false, true><<<gridl, 12 * 64, 0, rt().compute>>>(in, b, out, ni, nj, nk, nbyl, nblk, kcl, alpha, beta, resid);
                             *resid_done = true;
+                            rt().mg_residual_launches++;
                             double *t2 = in; in = out; out = t2;
                             s += 2; launches++;
                             continue;
@@ -1804,6 +1807,7 @@ extern "C" {
 
 const char *fl_mg_smooth_kernel_name(void) { return rt().mg_smooth_kernel; }
 long long fl_mg_fused_launches(void) { const long long n = rt().mg_fused_launches; rt().mg_fused_launches = 0; return n; }
+long long fl_mg_residual_launches(void) { const long long n = rt().mg_residual_launches; rt().mg_residual_launches = 0; return n; }
 
 void gpu_smoothing_jacobi(double *x, double *b, double *temp, double alpha, double beta,
                           int ni, int nj, int nk, int iter)

@@ -1775,6 +1775,13 @@ static void walls_z_planes(SweepMaskWallsZ &mk, int nk)
     mk.wzh = (mk.walls & BQ_WALL_ZHI) ? sl.nkg - 2 - sl.koff : -8;
 }
 
+// What the masked LDS kernel asks of its arrays: float4 columns of in, div and out, and the four flag bytes of a column as one
+// word (fword) -- a flag array off a 4-byte boundary takes the one-sweep masked kernels, which read bytes.  `rows` is read bytewise.
+static inline bool masked_vectors_ok(const float *in, const float *div, const float *out, const unsigned char *solid)
+{
+    return aligned16(in, div, out) && ((uintptr_t)solid & 3u) == 0;
+}
+
 // Three MASKED sweeps in one launch (bq_obstacle.hip: gpu_jacobi_sweeps_masked; walls != 0: gpu_jacobi_sweeps_masked_walls, solid then
 // being solid + walls); false = not applicable, nothing launched
 bool jacobi_sweep_triple_masked(const plan::JacobiTuning &tun, const float *in, const float *div, float *out, int ni, int nj, int nk, float alpha,
@@ -1784,7 +1791,7 @@ bool jacobi_sweep_triple_masked(const plan::JacobiTuning &tun, const float *in, 
     mk.solid = solid; mk.rows = rows; mk.walls = walls;
     walls_z_planes(mk, nk);
     mk.b0 = betas[0]; mk.b1 = betas[1]; mk.b2 = betas[2]; mk.b3 = betas[3]; mk.b4 = betas[4]; mk.b5 = betas[5]; mk.b6 = betas[6];
-    return launch_fused(plan::plan_triple_masked(ni, nj, nk, aligned16(in, div, out), tun, rt().num_cus, rt().slab_on, walls != 0), in, div, out, ni, nj, nk,
+    return launch_fused(plan::plan_triple_masked(ni, nj, nk, masked_vectors_ok(in, div, out, solid), tun, rt().num_cus, rt().slab_on, walls != 0), in, div, out, ni, nj, nk,
                         alpha, betas[0], whole_array(nk), &mk);
 }
 // The walled triple on the output planes `pr` (gpu_jacobi_sweep_masked_walls_triple_ranges), z-slab ranks included: the kernel takes
@@ -1797,7 +1804,7 @@ bool jacobi_sweep_triple_masked_ranges(const plan::JacobiTuning &tun, const floa
     mk.solid = solid; mk.rows = rows; mk.walls = walls;
     walls_z_planes(mk, nk);
     mk.b0 = betas[0]; mk.b1 = betas[1]; mk.b2 = betas[2]; mk.b3 = betas[3]; mk.b4 = betas[4]; mk.b5 = betas[5]; mk.b6 = betas[6];
-    return launch_fused(plan::plan_triple_masked_ranges(ni, nj, nk, aligned16(in, div, out), pr, tun, rt().num_cus), in, div, out, ni, nj, nk,
+    return launch_fused(plan::plan_triple_masked_ranges(ni, nj, nk, masked_vectors_ok(in, div, out, solid), pr, tun, rt().num_cus), in, div, out, ni, nj, nk,
                         alpha, betas[0], pr, &mk);
 }
 

@@ -264,6 +264,31 @@ void gpu_multi_grid_conjugate_gradient(float *u, float *v, float *w, double *div
  *     oracle needs minutes for one.  Everything a test covers lies below 2 GiB.
  *   The fused Jacobi kernels take rows of 32..1024 floats with ni % 4 == 0 and 16-byte aligned pointers; any other row runs
  *     the one-sweep kernels (same values).
+ *
+ * ---- Alignment (part of the ABI contract; the table per family is in DESIGN.md section 2).  The caller owns every buffer and
+ * may carve u, v, w, p, ... out of one pool: ELEMENT-SIZE ALIGNMENT IS ENOUGH FOR EVERY ARRAY -- 4 bytes for float (and the
+ * tracers' unsigned ids), 8 for double, 1 for the flag arrays solid / solidw / rows.  The values are those on 16-byte aligned
+ * arrays, nothing outside an array is written, and no entry point refuses an array for its alignment.  Alignment only selects
+ * the kernel form, per call, from that call's pointers:
+ *   fp32 Jacobi sweeps (gpu_jacobi_sweeps, _sweep_range, _pair_ranges, _triple_ranges, gpu_projection_jacobi): the float4 and
+ *     fused kernels need ni % 4 == 0, ni >= 32 and in, div, out all on 16-byte boundaries; otherwise one generic sweep per
+ *     launch, and the range entry points return 0 ("does not apply") with nothing written.
+ *   masked and walled sweeps (gpu_jacobi_sweeps_masked[_walls], _walls_triple_ranges): the fused kernel reads the four flag
+ *     bytes of a float4 column as one word, so it needs solid / solidw on a 4-byte boundary as well; otherwise one masked
+ *     sweep per launch (byte reads).  rows is read bytewise everywhere.  gpu_obstacle_loads has a word and a byte form likewise.
+ *   gpu_clamp_extrema_box[_w] and the limiter inside gpu_maccormack / gpu_clamp_extrema: the float4 kernel on rows of 4 m floats
+ *     needs both arrays on 16-byte boundaries; otherwise the scalar kernel.
+ *   fp64 (gpu_smoothing_jacobi, gpu_multi_grid_conjugate_gradient): the double2 kernels need even ni and x, temp, b on 16-byte
+ *     boundaries (the launch that also stores a level's residual: that array too), the fused level-0 passes (FL_OPT_MGCG_FUSE)
+ *     every array; otherwise one cell per lane and the single passes.
+ *   gpu_max_field*, gpu_max_abs3: a scalar head up to the first 16-byte boundary, float4 bulk, scalar tail.
+ *   everything else (gathers, map updates, streaming operators, flags, faces, diagnostics, render, sources, tracers, box
+ *     copies, the PCG operators: gpu_pcg_solve's work array holds 2-byte codes and then doubles at a multiple of 256 bytes) has one
+ *     form, made of accesses no wider than it may assume.
+ *   Three kernels issue accesses wider than their alignment BY DESIGN, because their row length makes it unavoidable, and rely on
+ *     gfx950 serving global and buffer accesses at dword alignment: the float4 limiter on rows of 4 m + 1 floats, the double2
+ *     smoother and stencil on rows of an odd number of doubles, and the two-dword corner loads of the gathers.
+ * tests/test_gpu_alignment.py holds every family to this on arrays 1, 2 and 3 elements off a 16-byte boundary between guard bytes.
  */
 
 /* ------------------------------------------------------------------------------------------
@@ -485,6 +510,9 @@ const char *fl_jacobi_kernel_name(void);
 const char *fl_mg_smooth_kernel_name(void);
 /* launches of the fused level-0 kernels (FL_OPT_MGCG_FUSE) since the previous call (resets the count; for reports and tests) */
 long long fl_mg_fused_launches(void);
+/* smoothing launches that also stored the level's residual r = b - A x (mg_lds3_kernel's pair form: rows of 130 .. 256 doubles,
+ * x, temp, b AND r on 16-byte boundaries) since the previous call (resets the count; for reports and tests) */
+long long fl_mg_residual_launches(void);
 /* FL_OPT_SKIP_EMPTY_BRICKS = 2 or 4: out[0] = blocks tested against the brick flags, out[1] = blocks skipped, since the last reset
  * (blocking; reset != 0 clears the counters) */
 void fl_sparse_stats(long long out[2], int reset);
