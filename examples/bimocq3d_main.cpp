@@ -8,12 +8,13 @@
 // rings blown along x by the reference's emitter velocity formula (main.cpp:52-73, emiter = +1 for both: the rear
 // ring catches up and threads the front one -- leapfrogging), no buoyancy, density dumped every frame.
 //
-//   make example && build/bimocq3d [N=128] [frames=20] [outdir=out] [scheme=0|2|3] [projection=0|1] [async=1] [scene=0|1] [walls=0] [diag_every=0] [preview_every=0] [tracers_per_cell=0] [paddle_spin=0] [confinement=0] [loads_every=0]
+//   make example && build/bimocq3d [N=128] [frames=20] [outdir=out] [scheme=0|2|3] [projection=0|1] [async=1] [scene=0|1] [walls=0] [diag_every=0] [preview_every=0] [tracers_per_cell=0] [paddle_spin=0] [confinement=0] [loads_every=0] [preview_solids=0]
 // diag_every = N > 0: the flow diagnostics of every N-th frame (bq_solver_diagnostics' row: kinetic energy, enstrophy, ...) are
 // sampled on the device while the run goes on, printed one line per sampled frame at the end, and the vorticity magnitude of
 // those frames is dumped next to the density (vorticity_render_%04u.bqd)
 // preview_every = N > 0: a shadowed preview of the density of every N-th frame, drawn on the device (view along +z, lit from
-// above), is written next to the density dumps (preview_%04u.pgm)
+// above), is written next to the density dumps (preview_%04u.pgm); preview_solids = 1 draws the solid obstacles into it
+// (opaque, flat-shaded, shadow-casting: with paddle_spin the paddle shows)
 // tracers_per_cell = N > 0: N jittered passive tracers in every cell of each emitter's bounding box, moved with every step on the
 // device and dumped with every frame (tracers_%04u.bqp: positions and the density sampled at them)
 // paddle_spin = S != 0: a box paddle of half extents (0.3 L, 2 h, 0.15 L) at the centre of the domain (scenes.paddle of the Python
@@ -49,8 +50,9 @@ int main(int argc, char **argv)
     const float paddle_spin = argc > 12 ? (float)std::atof(argv[12]) : 0.f; // angular velocity of the paddle about z (0: no paddle)
     const float confinement = argc > 13 ? (float)std::atof(argv[13]) : 0.f; // vorticity confinement coefficient (0: none)
     const int loads_every = argc > 14 ? std::atoi(argv[14]) : 0;     // pressure loads on the obstacles every N-th frame (0: none)
+    const bool preview_solids = argc > 15 ? std::atoi(argv[15]) != 0 : false; // draw the obstacles into the previews
     if (n < 8 || total_frame < 1 || loads_every < 0 || !(confinement >= 0.f) || !std::isfinite(confinement) || diag_every < 0 || preview_every < 0 || tracers_per_cell < 0 || !std::isfinite(paddle_spin) || (scene == 1 && n % 2) || (scheme != 0 && scheme != 2 && scheme != 3)) {
-        std::fprintf(stderr, "usage: %s [N>=8] [frames] [outdir] [scheme: 0 BiMocq, 2 MacCormack, 3 reflection] [projection] [async] [scene] [walls] [diag_every] [preview_every] [tracers_per_cell] [paddle_spin] [confinement] [loads_every]\n", argv[0]); return 2;
+        std::fprintf(stderr, "usage: %s [N>=8] [frames] [outdir] [scheme: 0 BiMocq, 2 MacCormack, 3 reflection] [projection] [async] [scene] [walls] [diag_every] [preview_every] [tracers_per_cell] [paddle_spin] [confinement] [loads_every] [preview_solids]\n", argv[0]); return 2;
     }
 
     const int ni = n, nj = n, nk = scene == 1 ? n / 2 : n;
@@ -133,7 +135,9 @@ int main(int argc, char **argv)
         if (diag_every > 0 && (i + 1) % diag_every == 0)
             std::printf("[ Vorticity voxel: %ld ]\n", mysolver.outputVorticity((unsigned)i, filepath, 0.1f));
         if (preview_every > 0 && (i + 1) % preview_every == 0)         // eye looking along +z, light falling along -y
-            std::printf("[ Preview bytes: %ld ]\n", mysolver.outputPreview((unsigned)i, filepath, /*view +z*/4, /*light -y*/3, 12.f, 1.f, 0.1f, 0.f));
+            std::printf("[ Preview bytes: %ld ]\n", preview_solids
+                ? mysolver.outputPreviewSolids((unsigned)i, filepath, /*view +z*/4, /*light -y*/3, 12.f, 1.f, 0.1f, 0.6f, 0.15f, 0.f)
+                : mysolver.outputPreview((unsigned)i, filepath, /*view +z*/4, /*light -y*/3, 12.f, 1.f, 0.1f, 0.f));
         if (loads_every > 0 && !mysolver.boundaries.empty() && (i + 1) % loads_every == 0) {
             double row[BQ_OLOAD_ROW];
             if (mysolver.obstacleLoads(row) == 1)

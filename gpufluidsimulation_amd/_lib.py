@@ -186,6 +186,9 @@ HIP_SIGS = {
     # shadowed density preview: rho, shadow (may be NULL without a light), h, dims, view, light, a HOST
     # pointer to three floats (sigma, albedo, ambient), d_image in DEVICE memory
     "gpu_render_density": (c_i, [VP, VP] + _G + [c_i, c_i, VP, VP]),
+    # the same with solid obstacles drawn: rho, solid, rows (may be NULL), shadow, h, dims, view, light,
+    # HOST pointers to (sigma, albedo, ambient) and to the solids' (albedo, ambient), d_image in DEVICE memory (3 W H doubles)
+    "gpu_render_density_solids": (c_i, [VP, VP, VP, VP] + _G + [c_i, c_i, VP, VP, VP]),
     # passive tracer particles: positions are three device arrays of n floats
     "gpu_trace_particles": (c_i, [VP] * 6 + [C.c_long] + _G + [c_f, c_f]),
     "gpu_sample_particles": (c_i, [VP, c_i, c_i, c_i, c_f, c_f, c_f, c_f, VP, VP, VP, VP, C.c_long]),

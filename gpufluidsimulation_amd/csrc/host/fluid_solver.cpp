@@ -51,6 +51,7 @@
 #pragma weak gpu_jacobi_sweep_masked_walls_triple_ranges
 #pragma weak gpu_flow_stats
 #pragma weak gpu_render_density
+#pragma weak gpu_render_density_solids
 #pragma weak gpu_vorticity_confinement
 #pragma weak gpu_obstacle_loads
 
@@ -1889,6 +1890,71 @@ long BimocqGPUSolver::render(int view, int light, float sigma, float albedo, flo
         if (transmittance) transmittance[a] = render_attenuation(host_image[(size_t)count + a]);
     }
     return count;
+}
+
+bool BimocqGPUSolver::renderSolidsOperator() { return gpu_render_density_solids != nullptr; }
+
+// render() with the solid obstacles drawn: gpu_render_density_solids on the obstacle flags.  Without
+// obstacles (an empty list, z-slab ranks) it is render() and hit = 0.
+long BimocqGPUSolver::renderSolids(int view, int light, float sigma, float albedo, float ambient, float solid_albedo, float solid_ambient,
+                                   float *radiance, float *transmittance, unsigned char *hit, long capacity)
+{
+    int w = 0, h = 0;
+    if (!renderSize(view, w, h)) return -1;
+    const long count = (long)w * h;
+    if (!radiance && !transmittance && !hit) return count;
+    const long n = std::min(count, std::max(capacity, 0L));
+    if (boundaries.empty() || GpuSolver->slab.on) {
+        if (!(solid_albedo >= 0.0f) || std::isinf(solid_albedo) || !(solid_ambient >= 0.0f) || std::isinf(solid_ambient) ||
+            solid_albedo + solid_ambient > 4.0f) {
+            fl_report_error(FL_ERR_BAD_ARGUMENT, "render: the solids' albedo and ambient must be finite, >= 0 and sum to at most 4");
+            return -1;
+        }
+        // what the operator would refuse, also when only `hit` is asked for and nothing is drawn
+        if (light < -1 || light > 5 || !(sigma >= 0.0f) || std::isinf(sigma) || !(albedo >= 0.0f) || std::isinf(albedo) ||
+            !(ambient >= 0.0f) || std::isinf(ambient) || albedo + ambient > 4.0f) {
+            fl_report_error(FL_ERR_BAD_ARGUMENT, "render: light is -1..5; sigma, albedo and ambient are finite, >= 0, albedo + ambient <= 4");
+            return -1;
+        }
+        if ((radiance || transmittance) && render(view, light, sigma, albedo, ambient, radiance, transmittance, capacity) < 0) return -1;
+        if (hit) std::fill(hit, hit + n, (unsigned char)0);
+        return count;
+    }
+    if (!renderSolidsOperator()) {
+        fl_report_error(FL_ERR_UNSUPPORTED, "render: the operator library has no gpu_render_density_solids");
+        return -1;
+    }
+    const size_t bytes = 3 * (size_t)count * sizeof(double);
+    if (render_image_solids.bytes() != bytes && !render_image_solids.alloc(bytes)) return -1;
+    if (light >= 0 && Shadow.count() != g.n() && !GpuSolver->allocField(Shadow, FIELD_S)) return -1;
+    GpuSolver->require({ &Density }, 0);
+    const fl_render_params prm = { sigma, albedo, ambient };
+    const fl_render_solid_params sprm = { solid_albedo, solid_ambient };
+    if (gpu_render_density_solids(Density, solid.u8(), rows.u8(), light >= 0 ? Shadow.get() : nullptr, CellSize, g.ni, g.nj, g.nk, view,
+                                  light, &prm, &sprm, render_image_solids.f64()) != FL_OK) return -1;
+    host_image.resize(3 * (size_t)count);
+    fl_memcpy_d2h(host_image.data(), render_image_solids.f64(), bytes);     // blocking, after the queued work
+    if (fl_last_error() != FL_OK) return -1;
+    for (long a = 0; a < n; a++) {
+        const double tag = host_image[2 * (size_t)count + a];
+        if (radiance) radiance[a] = (float)(host_image[a] * (1.0 / 4294967296.0));
+        if (transmittance) transmittance[a] = tag != 0.0 ? 0.0f : render_attenuation(host_image[(size_t)count + a]);
+        if (hit) hit[a] = (unsigned char)tag;
+    }
+    return count;
+}
+
+long BimocqGPUSolver::outputPreviewSolids(unsigned frame, const std::string &filepath, int view, int light, float sigma, float albedo,
+                                          float ambient, float solid_albedo, float solid_ambient, float background)
+{
+    int w = 0, h = 0;
+    if (!renderSize(view, w, h)) return -1;
+    host_radiance.resize((size_t)w * h);
+    host_transmittance.resize((size_t)w * h);
+    if (renderSolids(view, light, sigma, albedo, ambient, solid_albedo, solid_ambient, host_radiance.data(), host_transmittance.data(),
+                     nullptr, (long)w * h) < 0) return -1;
+    if (GpuSolver->slab.on && GpuSolver->slab.rank != 0) return 0;
+    return write_preview_pgm(frame + 1, filepath, host_radiance.data(), host_transmittance.data(), w, h, background);
 }
 
 long BimocqGPUSolver::outputPreview(unsigned frame, const std::string &filepath, int view, int light, float sigma, float albedo,

@@ -261,6 +261,15 @@ public:
     long render(int view, int light, float sigma, float albedo, float ambient, float *radiance, float *transmittance, long capacity);
     long outputPreview(unsigned frame, const std::string &filepath, int view, int light, float sigma, float albedo, float ambient,
                        float background);
+    // the same with the solid obstacles drawn: gpu_render_density_solids on `solid` and `rows`; hit:
+    // the tag o + 1 of the first obstacle cell of the pixel's ray, 0: none (its transmittance is then 0).  Without obstacles
+    // (an empty list, z-slab ranks) it is render() and hit = 0.  The three-plane image is allocated on the first such call.
+    static bool renderSolidsOperator();             // the operator library has gpu_render_density_solids
+    long renderSolids(int view, int light, float sigma, float albedo, float ambient, float solid_albedo, float solid_ambient,
+                      float *radiance, float *transmittance, unsigned char *hit, long capacity);
+    long outputPreviewSolids(unsigned frame, const std::string &filepath, int view, int light, float sigma, float albedo, float ambient,
+                             float solid_albedo, float solid_ambient, float background);
+    DeviceBytes render_image_solids;                // 3 W H doubles: Cfix, Afix, Hfix
     DeviceField Shadow;                             // s per cell, scratch of render()
     DeviceBytes render_image;                       // 2 W H doubles: Cfix, Afix
     std::vector<double> host_image;

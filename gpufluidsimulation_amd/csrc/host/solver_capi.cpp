@@ -476,6 +476,23 @@ long bq_solver_output_preview(bq_solver *s, unsigned frame, const char *path, in
     return s->solver->outputPreview(frame, std::string(path), view, light, sigma, albedo, ambient, background);
 }
 
+long bq_solver_render_solids(bq_solver *s, int view, int light, float sigma, float albedo, float ambient, float solid_albedo,
+                             float solid_ambient, float *radiance, float *transmittance, unsigned char *hit, long capacity)
+{
+    BQ_ENTER(s);
+    return s ? s->solver->renderSolids(view, light, sigma, albedo, ambient, solid_albedo, solid_ambient, radiance, transmittance, hit,
+                                       capacity) : -1;
+}
+
+long bq_solver_output_preview_solids(bq_solver *s, unsigned frame, const char *path, int view, int light, float sigma, float albedo,
+                                     float ambient, float solid_albedo, float solid_ambient, float background)
+{
+    BQ_ENTER(s);
+    if (!s || !path) return -1;
+    return s->solver->outputPreviewSolids(frame, std::string(path), view, light, sigma, albedo, ambient, solid_albedo, solid_ambient,
+                                          background);
+}
+
 int bq_solver_set_tracers(bq_solver *s, const float *xyz, long n)
 {
     BQ_ENTER(s);

@@ -266,6 +266,8 @@ HOST_SIGS = {
     "bq_solver_render": (C.c_long, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_long]),
     "bq_solver_output_preview": (C.c_long, [C.c_void_p, C.c_uint, C.c_char_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
                                             C.c_float]),
+    "bq_solver_render_solids": (C.c_long, [C.c_void_p, C.c_int, C.c_int] + [C.c_float] * 5 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long]),
+    "bq_solver_output_preview_solids": (C.c_long, [C.c_void_p, C.c_uint, C.c_char_p, C.c_int, C.c_int] + [C.c_float] * 6),
     "bq_solver_set_tracers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long]),
     "bq_solver_seed_tracers": (C.c_long, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_uint]),
     "bq_solver_tracer_count": (C.c_long, [C.c_void_p]),
@@ -295,6 +297,8 @@ DIAG_NAMES = ("kinetic", "enstrophy", "div_l2", "div_max", "rho_sum", "centroid_
 DIAG_COUNT = len(DIAG_NAMES)
 # direction codes of render() / outputPreview(): the direction a ray travels (None or "none" as a light: no shadowing)
 DIRECTIONS = {"+x": 0, "-x": 1, "+y": 2, "-y": 3, "+z": 4, "-z": 5}
+# render(solids=True) / outputPreview(solids=True): the solids' (albedo, ambient)
+SOLID_SHADING = (0.6, 0.15)
 PCG_STOP = {0: "converged", 1: "iteration limit", 2: "breakdown"}
 PHASES = ("maps", "advect_compensate", "forces", "projection", "accumulate_reinit")
 
@@ -630,14 +634,38 @@ class BimocqGPUSolver:
             raise _lib.BimocqError(f"bq_solver_render_size failed ({rc})")
         return w.value, h.value
 
-    def render(self, view="+z", light="-y", sigma=8.0, albedo=1.0, ambient=0.1):
+    @staticmethod
+    def _solids(solids):
+        """the solids' (albedo, ambient) of render() / outputPreview(): True is SOLID_SHADING"""
+        if solids is True:
+            return SOLID_SHADING
+        try:
+            albedo, ambient = solids
+            return float(albedo), float(ambient)
+        except (TypeError, ValueError):
+            raise ValueError(f"solids {solids!r}: None, False, True or an (albedo, ambient) pair") from None
+
+    def render(self, view="+z", light="-y", sigma=8.0, albedo=1.0, ambient=0.1, solids=None):
         """a shadowed emission-absorption preview of the current density, drawn on the device: the
         orthographic view along `view`, self-shadowed by one directional light travelling along `light` ("+x" ... "-z", or
         None for no shadowing); sigma is the extinction per unit density and length.  Returns (radiance, transmittance) as
         float32 arrays of shape (H, W): view +-z gives (ny, nx), +-y (nz, nx), +-x (nz, ny), row index = the higher axis.
-        Blocking; on z-slab ranks collective, every rank gets the whole image."""
+        Blocking; on z-slab ranks collective, every rank gets the whole image.
+        solids (None or False: off): True or an (albedo, ambient) pair (True: (0.6, 0.15)) also draws the solid obstacles as
+        opaque, flat-shaded bodies that cast full shadows, and returns (radiance, transmittance, hit): hit is a uint8 (H, W)
+        array with the tag o + 1 of the obstacle a pixel's ray meets first, 0 where it meets none; a hit pixel's
+        transmittance is 0.  Domain walls are not drawn."""
         w, h = self.renderSize(view)
         rad, tr = np.empty(w * h, dtype=np.float32), np.empty(w * h, dtype=np.float32)
+        if solids is not None and solids is not False:
+            sa, sb = self._solids(solids)
+            hit = np.empty(w * h, dtype=np.uint8)
+            n = self.lib.bq_solver_render_solids(self.s, self._direction(view), self._direction(light, True), sigma, albedo, ambient,
+                                                 sa, sb, rad.ctypes.data, tr.ctypes.data, hit.ctypes.data, w * h)
+            self._check()
+            if n != w * h:
+                raise _lib.BimocqError("bq_solver_render_solids failed")
+            return rad.reshape(h, w), tr.reshape(h, w), hit.reshape(h, w)
         n = self.lib.bq_solver_render(self.s, self._direction(view), self._direction(light, True), sigma, albedo, ambient,
                                       rad.ctypes.data, tr.ctypes.data, w * h)
         self._check()
@@ -645,9 +673,17 @@ class BimocqGPUSolver:
             raise _lib.BimocqError("bq_solver_render failed")
         return rad.reshape(h, w), tr.reshape(h, w)
 
-    def outputPreview(self, frame, path, view="+z", light="-y", sigma=8.0, albedo=1.0, ambient=0.1, background=0.0):
+    def outputPreview(self, frame, path, view="+z", light="-y", sigma=8.0, albedo=1.0, ambient=0.1, background=0.0, solids=None):
         """writes the preview as <path>/preview_%04u.pgm for frame + 1 (binary 8-bit P5, +y or +z up; on z-slab ranks rank 0
-        writes); returns the bytes written"""
+        writes); returns the bytes written.  solids: as for render() -- the obstacles are drawn too"""
+        if solids is not None and solids is not False:
+            sa, sb = self._solids(solids)
+            n = self.lib.bq_solver_output_preview_solids(self.s, frame, path.encode(), self._direction(view),
+                                                         self._direction(light, True), sigma, albedo, ambient, sa, sb, background)
+            self._check()
+            if n < 0:
+                raise _lib.BimocqError("bq_solver_output_preview_solids failed")
+            return n
         n = self.lib.bq_solver_output_preview(self.s, frame, path.encode(), self._direction(view), self._direction(light, True),
                                               sigma, albedo, ambient, background)
         self._check()

@@ -1182,6 +1182,39 @@ int gpu_obstacle_loads(const float *p, const double *p64, const unsigned char *s
 typedef struct { float sigma, albedo, ambient; } fl_render_params;
 int gpu_render_density(const float *rho, float *shadow, float h, int ni, int nj, int nk, int view, int light,
                        const fl_render_params *p, double *d_image);
+/* gpu_render_density_solids: the same image with the solid obstacles drawn as opaque, flat-shaded,
+ * shadow-casting bodies.  Everything above holds -- one IEEE operation per line, no contraction, every sum an integer below
+ * 2^53 --, and in addition:
+ *   solid cells   a cell is solid iff (solid[cell] & 0x7f) != 0: the low bits are the tag o + 1 that gpu_obstacle_flags* wrote.
+ *                 Bit 0x80 (BQ_FLAG_WALL of solidw) is ignored: solidw may be passed, domain walls stay undrawn.
+ *   density       a solid cell's density is ignored: its D is 0 whatever rho holds, NaN and huge values included.
+ *   blocking      along a ray c0, c1, ... in travel order B(c_m) = 1 iff some c_n, n < m, is solid (the exclusive "blocked"
+ *                 prefix); A is the exclusive prefix of D as before;  att'(A, B) = B ? 0.0f : att(A).
+ *   s    = att'(A_light, B_light), written to `shadow` for every cell, solid cells included (light = -1: s = 1.0f): the first
+ *          solid cell along a light ray is lit, everything behind it is in full shadow.
+ *   Tv   = att'(A_view, B_view)
+ *   fluid cell    today's term with that Tv.
+ *   solid cell    qs   = sp->albedo * s + sp->ambient        (two float operations)
+ *                 term = trunc((double)Tv * (double)qs * 2^32)
+ *                 so only the first solid cell of a view ray can contribute.  Shading is flat, there is no normal term: a
+ *                 sphere shows a lit half and an ambient half through s alone.
+ * d_image (DEVICE, 3 W H doubles): plane 0 Cfix = sum of term, plane 1 Afix = sum of D over the whole ray (solids add 0),
+ * plane 2 Hfix = the tag of the first solid cell on the view ray, 0 when there is none.  A caller derives radiance =
+ * Cfix * 2^-32 and transmittance = Hfix ? 0 : att(Afix).  With all flags zero planes 0 and 1 and the shadow field are the bits
+ * of gpu_render_density and plane 2 is zero.
+ * Limits: sp->albedo and sp->ambient finite and >= 0, sp->albedo + sp->ambient <= 4: a solid term is <= 2^34 and every sum
+ * stays below 2^53.
+ * rows: the obstacles' rows summary (nj * nk bytes, above) or NULL; a row whose byte is 0 holds no solid cell.  The result is
+ * the same bits with it or with NULL.  The kernels along x skip the flag loads of a row whose byte is 0 (measured: DESIGN.md
+ * section 27); the marches along y and z read the flags of every cell.
+ * FL_OPT_RENDER_KCHUNK applies unchanged.  Asynchronous on the compute stream.  FL_ERR_BAD_ARGUMENT, nothing launched: everything
+ * gpu_render_density refuses (d_image counted as 3 W H doubles), a NULL solid or sp, sp values outside the limits, solid or
+ * rows overlapping shadow or d_image.  FL_ERR_UNSUPPORTED, nothing launched: a z-slab context (fl_set_slab) -- obstacles do
+ * not exist there.  Returns FL_OK or the error it latched. */
+typedef struct { float albedo, ambient; } fl_render_solid_params;
+int gpu_render_density_solids(const float *rho, const unsigned char *solid, const unsigned char *rows, float *shadow, float h,
+                              int ni, int nj, int nk, int view, int light, const fl_render_params *p,
+                              const fl_render_solid_params *sp, double *d_image);
 
 /* ---- passive tracer particles ---------------------------------------------------------------------
  * Particles are three device arrays of n floats each (px, py, pz): world positions, cell centre i at i h like everything

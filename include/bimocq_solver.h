@@ -349,6 +349,19 @@ long  bq_solver_render(bq_solver *s, int view, int light, float sigma, float alb
  * first, so +y or +z points up.  On z-slab ranks only rank 0 writes (the others return 0).  Returns the bytes written or -1. */
 long  bq_solver_output_preview(bq_solver *s, unsigned frame, const char *path, int view, int light, float sigma, float albedo,
                                float ambient, float background);
+/* The preview with the solid obstacles drawn (the contract of gpu_render_density_solids): opaque bodies
+ * with flat shading solid_albedo * s + solid_ambient that cast full shadows; solid_albedo, solid_ambient finite, >= 0, sum <= 4.
+ * hit receives per pixel the tag o + 1 of the first obstacle cell on the view ray (o: index in the boundary list), 0 where
+ * there is none; a hit pixel's transmittance is 0, so the background does not shine through a body.  Returns W * H and copies
+ * min(W * H, capacity) pixels into each non-NULL array; all three NULL: only the count; -1 on error.  With an empty boundary
+ * list and on z-slab ranks (no obstacles there) this is bq_solver_render and hit = 0.  The three-plane image buffer is
+ * allocated on the first call that draws obstacles.  FL_ERR_UNSUPPORTED with obstacles on an operator library without
+ * gpu_render_density_solids.  Domain walls are not drawn. */
+long  bq_solver_render_solids(bq_solver *s, int view, int light, float sigma, float albedo, float ambient, float solid_albedo,
+                              float solid_ambient, float *radiance, float *transmittance, unsigned char *hit, long capacity);
+/* bq_solver_output_preview with that image: the same file, the same pixel formula */
+long  bq_solver_output_preview_solids(bq_solver *s, unsigned frame, const char *path, int view, int light, float sigma, float albedo,
+                                      float ambient, float solid_albedo, float solid_ambient, float background);
 /* Passive tracer particles (the operators' contracts are in include/bimocq_gpu.h).  The solver owns
  * the positions on the device.  In every scheme, while the count is non-zero, advance() moves each tracer over the whole dt
  * through the velocity the step STARTS with, in sub-steps of that step's getCFL() value, clamped to [h, (n - 1) h]: the
