@@ -4,6 +4,8 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <functional>
+#include <initializer_list>
 #include "../../include/bimocq_gpu.h"
 
 namespace bq {
@@ -120,6 +122,12 @@ plan::JacobiTuning jacobi_tuning();
 struct ProfileSpan { hipEvent_t a = nullptr, b = nullptr; };
 bool profile_begin(ProfileSpan &sp);
 void profile_end(ProfileSpan &sp, long long launches, long long sweeps);
+// bq_project.hip: the loop of the gpu_jacobi_sweeps* entry points -- `sweeps` sweeps ping-ponging from p to p_temp.  Each stage in turn
+// launches its `sweeps` per launch in -> out while that many are left and it returns true (false: not applicable, nothing launched);
+// `single` takes the rest one by one (false: a failed launch check ends the loop).  Returns 0: the newest iterate is in p, 1: in p_temp.
+using SweepLaunch = std::function<bool(const float *in, float *out)>;
+struct SweepStage { int sweeps; bool on; SweepLaunch launch; };
+int run_sweeps(float *p, float *p_temp, int sweeps, std::initializer_list<SweepStage> stages, const SweepLaunch &single);
 
 // one thread per element: blocks of 64 (x) x 4 (y), planes along grid.z
 static const dim3 kBlock(64, 4, 1);

@@ -398,12 +398,8 @@ bool jacobi_sweep_triple_masked_ranges(const plan::JacobiTuning &tun, const floa
                                        const unsigned char *solid, const unsigned char *rows, const float betas[7], int walls,
                                        const geom::PlaneRanges &pr);                                                          // bq_project.hip
 
-// the z-slab context of the wall operators: the global plane of local plane 0 and the global plane count
-static inline SlabZ slab_z(int nk)
-{
-    const Runtime &r = rt();
-    return r.slab_on ? SlabZ{r.slab_koff, r.slab_nkg} : SlabZ{0, nk};
-}
+// the z-slab context of the wall operators (slab_ctx): the global plane of local plane 0 and the global plane count
+static inline SlabZ slab_z(int nk) { SlabZ z; slab_ctx(nk, z.koff, z.nkg); return z; }
 
 } // namespace bq
 
@@ -416,14 +412,28 @@ void gpu_obstacle_flags(unsigned char *solid, unsigned char *rows, const bq_boun
     obstacle_flags(solid, rows, b, n, nullptr, nullptr, h, ni, nj, nk, "gpu_obstacle_flags");
 }
 
+// the velocities of a list, by entry, as the faces kernels take them
+static ObsVel make_obs_vel(const bq_boundary *b, int n)
+{
+    ObsVel ov{};
+    for (int o = 0; o < n; o++) { ov.vx[o] = b[o].vx; ov.vy[o] = b[o].vy; ov.vz[o] = b[o].vz; }
+    return ov;
+}
+
+// the pointers of a faces pass: three components, the flags, and all three deltas or none
+static bool faces_ptrs_ok(const float *u, const float *v, const float *w, const float *du, const float *dv, const float *dw,
+                          const unsigned char *solid, const char *op)
+{
+    if (u && v && w && solid && (!du) == (!dv) && (!du) == (!dw)) return true;
+    latch(FL_ERR_BAD_ARGUMENT, op, "null device pointer");
+    return false;
+}
+
 void gpu_obstacle_faces(float *u, float *v, float *w, float *du, float *dv, float *dw, const unsigned char *solid,
                         const bq_boundary *b, int n, int ni, int nj, int nk)
 {
-    if (!obs_args_ok(b, n, ni, nj, nk, "gpu_obstacle_faces")) return;
-    if (!u || !v || !w || !solid || (!du) != (!dv) || (!du) != (!dw)) { latch(FL_ERR_BAD_ARGUMENT, "gpu_obstacle_faces", "null device pointer"); return; }
-    ObsVel ov{};
-    for (int o = 0; o < n; o++) { ov.vx[o] = b[o].vx; ov.vy[o] = b[o].vy; ov.vz[o] = b[o].vz; }
-    obstacle_faces_kernel<<<grid_for(ni + 1, nj + 1, nk + 1), kBlock, 0, rt().compute>>>(u, v, w, du, dv, dw, solid, ov, ni, nj, nk);
+    if (!obs_args_ok(b, n, ni, nj, nk, "gpu_obstacle_faces") || !faces_ptrs_ok(u, v, w, du, dv, dw, solid, "gpu_obstacle_faces")) return;
+    obstacle_faces_kernel<<<grid_for(ni + 1, nj + 1, nk + 1), kBlock, 0, rt().compute>>>(u, v, w, du, dv, dw, solid, make_obs_vel(b, n), ni, nj, nk);
     BQ_LAUNCH_CHECK("obstacle_faces_kernel");
 }
 
@@ -436,49 +446,66 @@ static BetaTab beta_table(float beta)
     return t;
 }
 
-void gpu_jacobi_sweep_masked(const float *in, const float *div, float *out, const unsigned char *solid,
-                             const unsigned char *rows, int ni, int nj, int nk, float alpha, float beta)
-{
-    if (!obs_args_ok(nullptr, 0, ni, nj, nk, "gpu_jacobi_sweep_masked")) return;
-    if (!in || !div || !out || !solid || !rows || in == out) { latch(FL_ERR_BAD_ARGUMENT, "gpu_jacobi_sweep_masked", "null or aliased buffers"); return; }
-    jacobi_masked_kernel<<<grid_for(ni, nj, nk), kBlock, 0, rt().compute>>>(in, div, out, solid, rows, ni, nj, nk, alpha, beta_table(beta));
-    BQ_LAUNCH_CHECK("jacobi_masked_kernel");
-}
-
-// FL_OPT_JACOBI_FUSE >= 2 (the caller vouches that p and p_temp carry the same boundary layer and the same values in solid
-// cells): three sweeps per launch through the masked LDS kernel where it applies; the rest one per launch
-int gpu_jacobi_sweeps_masked(float *p, const float *div, float *p_temp, const unsigned char *solid,
-                             const unsigned char *rows, int ni, int nj, int nk, int sweeps, float alpha, float beta)
-{
-    if (!obs_args_ok(nullptr, 0, ni, nj, nk, "gpu_jacobi_sweeps_masked")) return 0;
-    if (!p || !div || !p_temp || !solid || !rows || p == p_temp) { latch(FL_ERR_BAD_ARGUMENT, "gpu_jacobi_sweeps_masked", "null or aliased buffers"); return 0; }
-    const BetaTab bt = beta_table(beta);
-    float *in = p, *out = p_temp;
-    ProfileSpan span;
-    const bool prof = sweeps > 0 && profile_begin(span);      // FL_OPT_PROFILE_JACOBI, like gpu_jacobi_sweeps
-    int s = 0;
-    long long launches = 0;
-    const plan::JacobiTuning tun = jacobi_tuning();
-    while (tun.sweeps_fuse == plan::SweepsFuse::kAll && s + 3 <= sweeps &&
-           jacobi_sweep_triple_masked(tun, in, div, out, ni, nj, nk, alpha, solid, rows, bt.b)) {
-        float *t = in; in = out; out = t;
-        s += 3; launches++;
-    }
-    for (; s < sweeps; s++) {
-        jacobi_masked_kernel<<<grid_for(ni, nj, nk), kBlock, 0, rt().compute>>>(in, div, out, solid, rows, ni, nj, nk, alpha, bt);
-        if (!BQ_LAUNCH_CHECK("jacobi_masked_kernel")) break;
-        float *t = in; in = out; out = t;
-        launches++;
-    }
-    if (prof) profile_end(span, launches, sweeps);
-    return in == p ? 0 : 1;
-}
-
 static bool walls_ok(int walls, const char *op)
 {
     if (walls >= 0 && walls < 63) return true;
     latch(FL_ERR_BAD_ARGUMENT, op, "walls: BQ_WALL_* bits, at least one side open");
     return false;
+}
+
+// The argument check of the masked sweep entry points.  kNone: the family without walls, which refuses a slab rank; kAny: a walled entry
+// point (walls = 0 is forwarded to the family without walls before it gets here); kClosed: the walled sweeps on plane ranges of a z-slab
+// rank's schedule, which refuse walls = 0 -- the masked family without walls has no sweep on plane ranges.
+enum class Walls { kNone, kAny, kClosed };
+static bool masked_sweep_args(const float *in, const float *div, const float *out, const unsigned char *solid, const unsigned char *rows,
+                              int ni, int nj, int nk, const char *op, Walls kind = Walls::kNone, int walls = 0)
+{
+    if (!obs_args_ok(nullptr, 0, ni, nj, nk, op, kind != Walls::kNone)) return false;
+    if (kind == Walls::kAny && !walls_ok(walls, op)) return false;
+    if (kind == Walls::kClosed && (walls <= 0 || walls >= 63)) { latch(FL_ERR_BAD_ARGUMENT, op, "walls: BQ_WALL_* bits, at least one side closed and one open"); return false; }
+    if (!in || !div || !out || !solid || !rows || in == out) { latch(FL_ERR_BAD_ARGUMENT, op, "null or aliased buffers"); return false; }
+    return true;
+}
+
+// One masked sweep in -> out: jacobi_masked_kernel, or with walls (solid then being solid + walls) jacobi_masked_walls_kernel on
+// the local planes [klo, khi).  false: the launch check failed (latched).
+static bool masked_sweep(const float *in, const float *div, float *out, const unsigned char *solid, const unsigned char *rows, int walls,
+                         int ni, int nj, int nk, float alpha, const BetaTab &bt, int klo, int khi)
+{
+    if (walls == 0) {
+        jacobi_masked_kernel<<<grid_for(ni, nj, nk), kBlock, 0, rt().compute>>>(in, div, out, solid, rows, ni, nj, nk, alpha, bt);
+        return BQ_LAUNCH_CHECK("jacobi_masked_kernel");
+    }
+    jacobi_masked_walls_kernel<<<grid_for(ni, nj, khi - klo), kBlock, 0, rt().compute>>>(in, div, out, solid, rows, walls, ni, nj, nk, alpha, bt,
+                                                                                        slab_z(nk), klo, khi);
+    return BQ_LAUNCH_CHECK("jacobi_masked_walls_kernel");
+}
+
+// `sweeps` checked masked sweeps.  FL_OPT_JACOBI_FUSE >= 2 (the caller vouches that p and p_temp carry the same boundary layer and the same
+// values in solid cells): three sweeps per launch through the masked LDS kernel where plan_triple_masked admits the shape
+static int masked_sweeps(float *p, const float *div, float *p_temp, const unsigned char *solid, const unsigned char *rows, int walls,
+                         int ni, int nj, int nk, int sweeps, float alpha, float beta)
+{
+    const BetaTab bt = beta_table(beta);
+    const plan::JacobiTuning tun = jacobi_tuning();
+    return run_sweeps(p, p_temp, sweeps,
+                      {{3, tun.sweeps_fuse == plan::SweepsFuse::kAll, [&](const float *in, float *out) {
+                            return jacobi_sweep_triple_masked(tun, in, div, out, ni, nj, nk, alpha, solid, rows, bt.b, walls); }}},
+                      [&](const float *in, float *out) { return masked_sweep(in, div, out, solid, rows, walls, ni, nj, nk, alpha, bt, 0, nk); });
+}
+
+void gpu_jacobi_sweep_masked(const float *in, const float *div, float *out, const unsigned char *solid,
+                             const unsigned char *rows, int ni, int nj, int nk, float alpha, float beta)
+{
+    if (!masked_sweep_args(in, div, out, solid, rows, ni, nj, nk, "gpu_jacobi_sweep_masked")) return;
+    masked_sweep(in, div, out, solid, rows, 0, ni, nj, nk, alpha, beta_table(beta), 0, nk);
+}
+
+int gpu_jacobi_sweeps_masked(float *p, const float *div, float *p_temp, const unsigned char *solid,
+                             const unsigned char *rows, int ni, int nj, int nk, int sweeps, float alpha, float beta)
+{
+    if (!masked_sweep_args(p, div, p_temp, solid, rows, ni, nj, nk, "gpu_jacobi_sweeps_masked")) return 0;
+    return masked_sweeps(p, div, p_temp, solid, rows, 0, ni, nj, nk, sweeps, alpha, beta);
 }
 
 void gpu_wall_flags(unsigned char *solidw, const unsigned char *solid, int walls, int ni, int nj, int nk)
@@ -491,8 +518,7 @@ void gpu_wall_flags(unsigned char *solidw, const unsigned char *solid, int walls
 
 void gpu_wall_faces(float *u, float *v, float *w, float *du, float *dv, float *dw, const unsigned char *solidw, int ni, int nj, int nk)
 {
-    if (!obs_args_ok(nullptr, 0, ni, nj, nk, "gpu_wall_faces", true)) return;
-    if (!u || !v || !w || !solidw || (!du) != (!dv) || (!du) != (!dw)) { latch(FL_ERR_BAD_ARGUMENT, "gpu_wall_faces", "null device pointer"); return; }
+    if (!obs_args_ok(nullptr, 0, ni, nj, nk, "gpu_wall_faces", true) || !faces_ptrs_ok(u, v, w, du, dv, dw, solidw, "gpu_wall_faces")) return;
     wall_faces_kernel<<<grid_for(ni + 1, nj + 1, nk + 1), kBlock, 0, rt().compute>>>(u, v, w, du, dv, dw, solidw, ni, nj, nk, slab_z(nk));
     BQ_LAUNCH_CHECK("wall_faces_kernel");
 }
@@ -501,22 +527,8 @@ void gpu_jacobi_sweep_masked_walls(const float *in, const float *div, float *out
                                    const unsigned char *rows, int walls, int ni, int nj, int nk, float alpha, float beta)
 {
     if (walls == 0) { gpu_jacobi_sweep_masked(in, div, out, solidw, rows, ni, nj, nk, alpha, beta); return; }
-    if (!obs_args_ok(nullptr, 0, ni, nj, nk, "gpu_jacobi_sweep_masked_walls", true) || !walls_ok(walls, "gpu_jacobi_sweep_masked_walls")) return;
-    if (!in || !div || !out || !solidw || !rows || in == out) { latch(FL_ERR_BAD_ARGUMENT, "gpu_jacobi_sweep_masked_walls", "null or aliased buffers"); return; }
-    jacobi_masked_walls_kernel<<<grid_for(ni, nj, nk), kBlock, 0, rt().compute>>>(in, div, out, solidw, rows, walls, ni, nj, nk, alpha, beta_table(beta),
-                                                                                 slab_z(nk), 0, nk);
-    BQ_LAUNCH_CHECK("jacobi_masked_walls_kernel");
-}
-
-// The walled sweeps of a z-slab rank's schedule (one domain: of any caller that wants part of the planes).  walls = 0 is refused:
-// the masked family without walls has no sweep on plane ranges.
-static bool walls_range_args(const float *in, const float *div, float *out, const unsigned char *solidw, const unsigned char *rows,
-                             int walls, int ni, int nj, int nk, const char *op)
-{
-    if (!obs_args_ok(nullptr, 0, ni, nj, nk, op, true)) return false;
-    if (walls <= 0 || walls >= 63) { latch(FL_ERR_BAD_ARGUMENT, op, "walls: BQ_WALL_* bits, at least one side closed and one open"); return false; }
-    if (!in || !div || !out || !solidw || !rows || in == out) { latch(FL_ERR_BAD_ARGUMENT, op, "null or aliased buffers"); return false; }
-    return true;
+    if (!masked_sweep_args(in, div, out, solidw, rows, ni, nj, nk, "gpu_jacobi_sweep_masked_walls", Walls::kAny, walls)) return;
+    masked_sweep(in, div, out, solidw, rows, walls, ni, nj, nk, alpha, beta_table(beta), 0, nk);
 }
 
 // one walled sweep in -> out on the local planes [k_begin, k_end), clipped to the interior: returns 1 (0: refused arguments)
@@ -524,12 +536,9 @@ int gpu_jacobi_sweep_masked_walls_range(const float *in, const float *div, float
                                         const unsigned char *rows, int walls, int ni, int nj, int nk, int k_begin, int k_end,
                                         float alpha, float beta)
 {
-    if (!walls_range_args(in, div, out, solidw, rows, walls, ni, nj, nk, "gpu_jacobi_sweep_masked_walls_range")) return 0;
+    if (!masked_sweep_args(in, div, out, solidw, rows, ni, nj, nk, "gpu_jacobi_sweep_masked_walls_range", Walls::kClosed, walls)) return 0;
     const int k0 = std::max(k_begin, 1), k1 = std::min(k_end, nk - 1);
-    if (k0 >= k1) return 1;
-    jacobi_masked_walls_kernel<<<grid_for(ni, nj, k1 - k0), kBlock, 0, rt().compute>>>(in, div, out, solidw, rows, walls, ni, nj, nk, alpha,
-                                                                                      beta_table(beta), slab_z(nk), k0, k1);
-    BQ_LAUNCH_CHECK("jacobi_masked_walls_kernel");
+    if (k0 < k1) masked_sweep(in, div, out, solidw, rows, walls, ni, nj, nk, alpha, beta_table(beta), k0, k1);
     return 1;
 }
 
@@ -540,40 +549,18 @@ int gpu_jacobi_sweep_masked_walls_triple_ranges(const float *in, const float *di
                                                 const unsigned char *rows, int walls, int ni, int nj, int nk,
                                                 int k0a, int k1a, int k0b, int k1b, float alpha, float beta)
 {
-    if (!walls_range_args(in, div, out, solidw, rows, walls, ni, nj, nk, "gpu_jacobi_sweep_masked_walls_triple_ranges")) return 0;
+    if (!masked_sweep_args(in, div, out, solidw, rows, ni, nj, nk, "gpu_jacobi_sweep_masked_walls_triple_ranges", Walls::kClosed, walls)) return 0;
     const BetaTab bt = beta_table(beta);
     return jacobi_sweep_triple_masked_ranges(jacobi_tuning(), in, div, out, ni, nj, nk, alpha, solidw, rows, bt.b, walls,
                                              geom::PlaneRanges(k0a, k1a, k0b, k1b, nk)) ? 1 : 0;
 }
 
-// gpu_jacobi_sweeps_masked's loop with the walled kernels (FL_OPT_JACOBI_FUSE >= 2: three sweeps per launch where
-// plan_triple_masked admits the shape)
 int gpu_jacobi_sweeps_masked_walls(float *p, const float *div, float *p_temp, const unsigned char *solidw, const unsigned char *rows,
                                    int walls, int ni, int nj, int nk, int sweeps, float alpha, float beta)
 {
     if (walls == 0) return gpu_jacobi_sweeps_masked(p, div, p_temp, solidw, rows, ni, nj, nk, sweeps, alpha, beta);
-    if (!obs_args_ok(nullptr, 0, ni, nj, nk, "gpu_jacobi_sweeps_masked_walls", true) || !walls_ok(walls, "gpu_jacobi_sweeps_masked_walls")) return 0;
-    if (!p || !div || !p_temp || !solidw || !rows || p == p_temp) { latch(FL_ERR_BAD_ARGUMENT, "gpu_jacobi_sweeps_masked_walls", "null or aliased buffers"); return 0; }
-    const BetaTab bt = beta_table(beta);
-    float *in = p, *out = p_temp;
-    ProfileSpan span;
-    const bool prof = sweeps > 0 && profile_begin(span);
-    int s = 0;
-    long long launches = 0;
-    const plan::JacobiTuning tun = jacobi_tuning();
-    while (tun.sweeps_fuse == plan::SweepsFuse::kAll && s + 3 <= sweeps &&
-           jacobi_sweep_triple_masked(tun, in, div, out, ni, nj, nk, alpha, solidw, rows, bt.b, walls)) {
-        float *t = in; in = out; out = t;
-        s += 3; launches++;
-    }
-    for (; s < sweeps; s++) {
-        jacobi_masked_walls_kernel<<<grid_for(ni, nj, nk), kBlock, 0, rt().compute>>>(in, div, out, solidw, rows, walls, ni, nj, nk, alpha, bt, slab_z(nk), 0, nk);
-        if (!BQ_LAUNCH_CHECK("jacobi_masked_walls_kernel")) break;
-        float *t = in; in = out; out = t;
-        launches++;
-    }
-    if (prof) profile_end(span, launches, sweeps);
-    return in == p ? 0 : 1;
+    if (!masked_sweep_args(p, div, p_temp, solidw, rows, ni, nj, nk, "gpu_jacobi_sweeps_masked_walls", Walls::kAny, walls)) return 0;
+    return masked_sweeps(p, div, p_temp, solidw, rows, walls, ni, nj, nk, sweeps, alpha, beta);
 }
 
 void gpu_gradient_masked(float *u, float *v, float *w, const float *p, float *du, float *dv, float *dw,
@@ -643,10 +630,8 @@ void gpu_obstacle_faces_pose(float *u, float *v, float *w, float *du, float *dv,
         os.ox[o] = pose[o].ox; os.oy[o] = pose[o].oy; os.oz[o] = pose[o].oz;
     }
     if (!os.spin) { gpu_obstacle_faces(u, v, w, du, dv, dw, solid, b, n, ni, nj, nk); return; }
-    if (!u || !v || !w || !solid || (!du) != (!dv) || (!du) != (!dw)) { latch(FL_ERR_BAD_ARGUMENT, op, "null device pointer"); return; }
-    ObsVel ov{};
-    for (int o = 0; o < n; o++) { ov.vx[o] = b[o].vx; ov.vy[o] = b[o].vy; ov.vz[o] = b[o].vz; }
-    obstacle_faces_pose_kernel<<<grid_for(ni + 1, nj + 1, nk + 1), kBlock, 0, rt().compute>>>(u, v, w, du, dv, dw, solid, ov, os, h, ni, nj, nk);
+    if (!faces_ptrs_ok(u, v, w, du, dv, dw, solid, op)) return;
+    obstacle_faces_pose_kernel<<<grid_for(ni + 1, nj + 1, nk + 1), kBlock, 0, rt().compute>>>(u, v, w, du, dv, dw, solid, make_obs_vel(b, n), os, h, ni, nj, nk);
     BQ_LAUNCH_CHECK("obstacle_faces_pose_kernel");
 }
 

@@ -1766,13 +1766,17 @@ static bool jacobi_sweep_quad(const plan::JacobiTuning &tun, const float *in, co
                         whole_array(nk));
 }
 
-// The z term of the positional state: a swept plane lies in [1, nk - 1), so a plane of another rank's array (an index <= 0 or
-// >= nk - 1 here) never matches, like -8.  One domain: planes 1 and nk - 2.
-static void walls_z_planes(SweepMaskWallsZ &mk, int nk)
+// The mask argument of the masked LDS kernel.  The z term of the positional state: a swept plane lies in [1, nk - 1), so a plane
+// of another rank's array (an index <= 0 or >= nk - 1 here) never matches, like -8.  One domain: planes 1 and nk - 2.
+static SweepMaskWallsZ make_sweep_mask(const unsigned char *solid, const unsigned char *rows, const float betas[7], int walls, int nk)
 {
     const Slab sl = slab_of(nk);
-    mk.wzl = (mk.walls & BQ_WALL_ZLO) ? 1 - sl.koff : -8;
-    mk.wzh = (mk.walls & BQ_WALL_ZHI) ? sl.nkg - 2 - sl.koff : -8;
+    SweepMaskWallsZ mk;
+    mk.solid = solid; mk.rows = rows; mk.walls = walls;
+    mk.wzl = (walls & BQ_WALL_ZLO) ? 1 - sl.koff : -8;
+    mk.wzh = (walls & BQ_WALL_ZHI) ? sl.nkg - 2 - sl.koff : -8;
+    mk.b0 = betas[0]; mk.b1 = betas[1]; mk.b2 = betas[2]; mk.b3 = betas[3]; mk.b4 = betas[4]; mk.b5 = betas[5]; mk.b6 = betas[6];
+    return mk;
 }
 
 // What the masked LDS kernel asks of its arrays: float4 columns of in, div and out, and the four flag bytes of a column as one
@@ -1787,10 +1791,7 @@ static inline bool masked_vectors_ok(const float *in, const float *div, const fl
 bool jacobi_sweep_triple_masked(const plan::JacobiTuning &tun, const float *in, const float *div, float *out, int ni, int nj, int nk, float alpha,
                                 const unsigned char *solid, const unsigned char *rows, const float betas[7], int walls)
 {
-    SweepMaskWallsZ mk;
-    mk.solid = solid; mk.rows = rows; mk.walls = walls;
-    walls_z_planes(mk, nk);
-    mk.b0 = betas[0]; mk.b1 = betas[1]; mk.b2 = betas[2]; mk.b3 = betas[3]; mk.b4 = betas[4]; mk.b5 = betas[5]; mk.b6 = betas[6];
+    const SweepMaskWallsZ mk = make_sweep_mask(solid, rows, betas, walls, nk);
     return launch_fused(plan::plan_triple_masked(ni, nj, nk, masked_vectors_ok(in, div, out, solid), tun, rt().num_cus, rt().slab_on, walls != 0), in, div, out, ni, nj, nk,
                         alpha, betas[0], whole_array(nk), &mk);
 }
@@ -1800,10 +1801,7 @@ bool jacobi_sweep_triple_masked_ranges(const plan::JacobiTuning &tun, const floa
                                        const unsigned char *solid, const unsigned char *rows, const float betas[7], int walls,
                                        const geom::PlaneRanges &pr)
 {
-    SweepMaskWallsZ mk;
-    mk.solid = solid; mk.rows = rows; mk.walls = walls;
-    walls_z_planes(mk, nk);
-    mk.b0 = betas[0]; mk.b1 = betas[1]; mk.b2 = betas[2]; mk.b3 = betas[3]; mk.b4 = betas[4]; mk.b5 = betas[5]; mk.b6 = betas[6];
+    const SweepMaskWallsZ mk = make_sweep_mask(solid, rows, betas, walls, nk);
     return launch_fused(plan::plan_triple_masked_ranges(ni, nj, nk, masked_vectors_ok(in, div, out, solid), pr, tun, rt().num_cus), in, div, out, ni, nj, nk,
                         alpha, betas[0], pr, &mk);
 }
@@ -1850,6 +1848,35 @@ void profile_end(ProfileSpan &sp, long long launches, long long sweeps)
     ps().spans.push_back(SweepSpan{sp.a, sp.b, launches, sweeps});
 }
 
+// bq_host.h.  Owns the profile span, the swaps, the launch count and fl_jacobi_kernel_name: the fused kernel this call launched most
+// often (more sweeps per launch first on a tie).  launch_fused records every launch's name, so with one stage (the masked and walled
+// loops) that is the name the stage recorded last, which those loops have always reported; with no fused launch the name stays.
+int run_sweeps(float *p, float *p_temp, int sweeps, std::initializer_list<SweepStage> stages, const SweepLaunch &single)
+{
+    float *in = p, *out = p_temp;
+    int s = 0;
+    long long launches = 0;
+    ProfileSpan span;
+    const bool prof = sweeps > 0 && profile_begin(span);      // FL_OPT_PROFILE_JACOBI (the z-slab projection runs through here)
+    const char *most_name = nullptr;
+    long long most = 0;
+    for (const SweepStage &stage : stages) {
+        long long n_here = 0;
+        while (stage.on && s + stage.sweeps <= sweeps && stage.launch(in, out)) {
+            std::swap(in, out);                        // the newest iterate sits in the former `out`
+            s += stage.sweeps; launches++;
+            if (++n_here > most) { most = n_here; most_name = ps().last_pair_kernel; }
+        }
+    }
+    if (most_name) ps().last_pair_kernel = most_name;
+    for (; s < sweeps && single(in, out); s++) {
+        std::swap(in, out);
+        launches++;
+    }
+    if (prof) profile_end(span, launches, sweeps);
+    return in == p ? 0 : 1;
+}
+
 } // namespace bq
 
 using namespace bq;
@@ -1879,36 +1906,16 @@ int gpu_jacobi_sweeps(float *p, const float *div, float *p_temp, int ni, int nj,
     if (!dims_ok(ni, nj, nk, "gpu_jacobi_sweeps")) return 0;
     if (!p || !div || !p_temp || p == p_temp) { latch(FL_ERR_BAD_ARGUMENT, "gpu_jacobi_sweeps", "null or aliased buffers"); return 0; }
     const plan::JacobiTuning tun = jacobi_tuning();
-    float *in = p, *out = p_temp;
-    int s = 0;
-    long long launches = 0;
-    ProfileSpan span;
-    const bool prof = sweeps > 0 && profile_begin(span);      // FL_OPT_PROFILE_JACOBI (the z-slab projection runs through here)
     // FL_OPT_JACOBI_FUSE >= 2: the caller vouches that p and p_temp carry the same boundary layer, so sweeps may share a launch:
     // four where plan_quad admits them, then three, then two (FL_OPT_JACOBI_FUSE = 4: two only), the rest one by one
-    using Launcher = bool (*)(const plan::JacobiTuning &, const float *, const float *, float *, int, int, int, float, float);
     const bool all = tun.sweeps_fuse == plan::SweepsFuse::kAll;
-    const struct { int sweeps; bool on; Launcher launch; } stages[] = {
-        {4, all, jacobi_sweep_quad}, {3, all, jacobi_sweep_triple}, {2, tun.sweeps_fuse != plan::SweepsFuse::kNone, jacobi_sweep_pair}};
-    // fl_jacobi_kernel_name: the fused kernel this call launched most often (more sweeps per launch first on a tie)
-    const char *most_name = nullptr;
-    long long most = 0;
-    for (const auto &stage : stages) {
-        long long n_here = 0;
-        while (stage.on && s + stage.sweeps <= sweeps && stage.launch(tun, in, div, out, ni, nj, nk, alpha, beta)) {
-            float *t = in; in = out; out = t;          // the newest iterate sits in the former `out`
-            s += stage.sweeps; launches++;
-            if (++n_here > most) { most = n_here; most_name = ps().last_pair_kernel; }
-        }
-    }
-    if (most_name) ps().last_pair_kernel = most_name;
-    for (; s < sweeps; s++) {
-        jacobi_sweep(tun, in, div, out, ni, nj, nk, alpha, beta);
-        float *t = in; in = out; out = t;
-        launches++;
-    }
-    if (prof) profile_end(span, launches, sweeps);
-    return in == p ? 0 : 1;
+    const auto fused = [&](auto launcher) {
+        return [&, launcher](const float *in, float *out) { return launcher(tun, in, div, out, ni, nj, nk, alpha, beta); };
+    };
+    return run_sweeps(p, p_temp, sweeps,
+                      {{4, all, fused(jacobi_sweep_quad)}, {3, all, fused(jacobi_sweep_triple)},
+                       {2, tun.sweeps_fuse != plan::SweepsFuse::kNone, fused(jacobi_sweep_pair)}},
+                      [&](const float *in, float *out) { jacobi_sweep(tun, in, div, out, ni, nj, nk, alpha, beta); return true; });
 }
 
 // one sweep in -> out restricted to the local planes [k_begin, k_end) (clipped to the interior)
@@ -2036,9 +2043,8 @@ void gpu_projection_jacobi(float *u, float *v, float *w, float *div, float *p, f
     const int stride = rt().opt_residual_stride;
     const bool dbg = debugParam != nullptr && stride > 0;
     float *in = p, *out = p_temp;
-    const bool prof = rt().opt_profile_jacobi && !dbg && iter > 1;
-    SweepSpan span{nullptr, nullptr, 0, (long long)(iter - 1)};
-    if (prof && BQ_HIP(hipEventCreate(&span.a)) && BQ_HIP(hipEventCreate(&span.b))) BQ_HIP(hipEventRecord(span.a, st));
+    ProfileSpan span;
+    const bool prof = !dbg && iter > 1 && profile_begin(span);
     long long launches = 0;
     const plan::JacobiTuning tun = jacobi_tuning();
     const bool may_fuse = iter > 2 && (tun.trust == plan::Trust::kVouched ||
@@ -2066,8 +2072,7 @@ void gpu_projection_jacobi(float *u, float *v, float *w, float *div, float *p, f
         launches++;
         float *t = in; in = out; out = t;
     }
-    span.launches = launches;
-    if (prof && span.a && span.b) { BQ_HIP(hipEventRecord(span.b, st)); ps().spans.push_back(span); }
+    if (prof) profile_end(span, launches, iter - 1);
     if (dbg && iter > 0 && (iter - 1) % stride == 0 && iter - 1 < 2000)
         residual_norms_async(div, in, ni, nj, nk, nullptr, nullptr, debugParam + iter - 1, debugParam + 2000 + iter - 1);
     if (in != p) fl_memcpy_d2d(p, in, (size_t)ni * nj * nk * sizeof(float));

@@ -101,12 +101,69 @@ static void obstacle_blend(float *u, float *v, float *w, float *rho, float *T, c
     else    gpu_obstacle_blend(u, v, w, rho, T, us, vs, ws, rhos, Ts, solid, b, n, h, ni, nj, nk);
 }
 
-static void obstacle_faces(float *u, float *v, float *w, float *du, float *dv, float *dw, const unsigned char *solid,
-                           const bq_boundary *b, const bq_pose *pose, int n, float h, int ni, int nj, int nk)
-{
-    if (pose) gpu_obstacle_faces_pose(u, v, w, du, dv, dw, solid, b, pose, n, h, ni, nj, nk);
-    else      gpu_obstacle_faces(u, v, w, du, dv, dw, solid, b, n, ni, nj, nk);
-}
+// The operators of one projection, chosen once from the obstacle list and the walls: plain (neither), masked (obstacles), walled
+// (closed sides, with or without obstacles).  Every choice between the three families is made in here; a _walls entry point is
+// reached only with walls != 0, so an operator library without them is never called through a null reference.  Plane ranges
+// exist for the plain and the walled family (the z-slab projection; setBoundary refuses slab ranks).
+struct ProjectionOps {
+    static constexpr float alpha = -1.f, beta = (float)(1.0 / 6.0);
+    enum Kind { kPlain, kMasked, kWalled };
+    BimocqGPUSolver &s;
+    const Kind kind;
+    float *const u, *const v, *const w, *const div;
+    const int ni, nj, nk, walls;
+    const unsigned char *const flags, *const rows;      // the flags the projection reads (walls on: solid + walls), the rows summary
+
+    explicit ProjectionOps(BimocqGPUSolver &s_)
+        : s(s_), kind(s.walls ? kWalled : s.boundaries.empty() ? kPlain : kMasked), u(s.VelocityU), v(s.VelocityV), w(s.VelocityW),
+          div(s.div), ni(s.g.ni), nj(s.g.nj), nk(s.g.nk), walls(s.walls), flags(s.projectionFlags()), rows(s.rows.u8()) {}
+
+    // solid faces take the obstacle velocity, wall faces 0 (du: their share of d*Proj); disjoint faces, so the order is free
+    void faces(float *du, float *dv, float *dw) const
+    {
+        const int n = (int)s.boundaries.size();
+        if (n && s.poseList()) gpu_obstacle_faces_pose(u, v, w, du, dv, dw, s.solid.u8(), s.boundaries.data(), s.poseList(), n, s.CellSize, ni, nj, nk);
+        else if (n) gpu_obstacle_faces(u, v, w, du, dv, dw, s.solid.u8(), s.boundaries.data(), n, ni, nj, nk);
+        if (kind == kWalled) gpu_wall_faces(u, v, w, du, dv, dw, flags, ni, nj, nk);
+    }
+    // `count` sweeps on the whole array, one launch or several as the library sees fit; 1: the newest iterate is in `b`
+    int sweeps(float *a, float *b, int count) const
+    {
+        if (kind == kWalled) return gpu_jacobi_sweeps_masked_walls(a, div, b, flags, rows, walls, ni, nj, nk, count, alpha, beta);
+        if (kind == kMasked) return gpu_jacobi_sweeps_masked(a, div, b, flags, rows, ni, nj, nk, count, alpha, beta);
+        return gpu_jacobi_sweeps(a, div, b, ni, nj, nk, count, alpha, beta);
+    }
+    // one sweep on the planes `a`
+    void single(const float *in, float *out, slab::Planes a) const
+    {
+        if (kind == kWalled) gpu_jacobi_sweep_masked_walls_range(in, div, out, flags, rows, walls, ni, nj, nk, a.k0, a.k1, alpha, beta);
+        else if (kind == kPlain) gpu_jacobi_sweep_range(in, div, out, ni, nj, nk, a.k0, a.k1, alpha, beta);
+        else fl_report_error(FL_ERR_UNSUPPORTED, "projection: the masked sweeps have no plane ranges");
+    }
+    // S = 2 or 3 sweeps in one launch on up to two plane ranges; false: the library refuses (nothing was launched).  The walled
+    // family has no pairs, and its plan names none.
+    bool fused(int S, const float *in, float *out, slab::Planes a, slab::Planes b = slab::Planes{0, 0}) const
+    {
+        if (kind != kPlain)
+            return kind == kWalled && S == 3 && gpu_jacobi_sweep_masked_walls_triple_ranges(in, div, out, flags, rows, walls, ni, nj, nk, a.k0, a.k1,
+                                                                                            b.k0, b.k1, alpha, beta) != 0;
+        return (S == 3 ? gpu_jacobi_sweep_triple_ranges : gpu_jacobi_sweep_pair_ranges)(in, div, out, ni, nj, nk, a.k0, a.k1, b.k0, b.k1,
+                                                                                         alpha, beta) != 0;
+    }
+    // p's gradient off the faces between fluid cells (du: the change handed out, all three or none); p64: the PCG projection's
+    void gradient(const float *p, float *du, float *dv, float *dw) const
+    {
+        if (kind == kWalled) gpu_gradient_masked_walls(u, v, w, p, du, dv, dw, flags, walls, ni, nj, nk, s.halfrdx);
+        else if (kind == kMasked) gpu_gradient_masked(u, v, w, p, du, dv, dw, flags, ni, nj, nk, s.halfrdx);
+        else if (du) gpu_gradient_delta(u, v, w, p, du, dv, dw, ni, nj, nk, s.halfrdx);
+        else gpu_gradient(u, v, w, p, ni, nj, nk, s.halfrdx);
+    }
+    void gradient(const double *p64) const
+    {
+        if (kind == kWalled) gpu_pcg_gradient_walls(u, v, w, p64, flags, walls, ni, nj, nk, (double)s.halfrdx);
+        else gpu_pcg_gradient(u, v, w, p64, flags, ni, nj, nk, (double)s.halfrdx);
+    }
+};
 
 // Every level-set grid of a list (entry o is one when is_ls[o]; ls[o].phi a HOST array) copied into ONE device allocation,
 // `descs` receiving one descriptor per entry whose phi points into it.  `who` prefixes the refusal (more than `cap` bytes
@@ -1052,31 +1109,6 @@ void BimocqGPUSolver::blendBoundary(bool band)
                        solid.u8(), b, n, levelsetList(), poseList(), CellSize, g.ni, g.nj, g.nk);
 }
 
-// the Jacobi projection with obstacles (:1120-1413): solid faces take the obstacle velocity (with_delta: its share of
-// d*Proj), divergence as always, iter-1 masked sweeps, gradient on the faces between fluid cells only
-bool BimocqGPUSolver::projectionObstacles(bool with_delta)
-{
-    const float alpha = -1.f, beta = (float)(1.0 / 6.0);
-    float *du = with_delta ? duProj.get() : nullptr, *dv = with_delta ? dvProj.get() : nullptr, *dw = with_delta ? dwProj.get() : nullptr;
-    div.zero(); p.zero(); p_temp.zero();
-    if (!boundaries.empty())
-        obstacle_faces(VelocityU, VelocityV, VelocityW, du, dv, dw, solid.u8(), boundaries.data(), poseList(), (int)boundaries.size(),
-                       CellSize, g.ni, g.nj, g.nk);
-    if (walls) gpu_wall_faces(VelocityU, VelocityV, VelocityW, du, dv, dw, solidw.u8(), g.ni, g.nj, g.nk);   // (disjoint faces: the order is free)
-    gpu_divergence(VelocityU, VelocityV, VelocityW, div, g.ni, g.nj, g.nk, halfrdx);
-    int where = 0;
-    if (jacobi_iters > 1) {
-        JacobiFuseVouched same_shell;       // p and p_temp carry the same (zero) boundary layer and +0 in every solid cell: three masked sweeps per launch
-        where = walls ? gpu_jacobi_sweeps_masked_walls(p, div, p_temp, solidw.u8(), rows.u8(), walls, g.ni, g.nj, g.nk, jacobi_iters - 1, alpha, beta)
-                      : gpu_jacobi_sweeps_masked(p, div, p_temp, solid.u8(), rows.u8(), g.ni, g.nj, g.nk, jacobi_iters - 1, alpha, beta);
-    }
-    if (where) p.swap(p_temp);
-    if (walls) gpu_gradient_masked_walls(VelocityU, VelocityV, VelocityW, p, du, dv, dw, solidw.u8(), walls, g.ni, g.nj, g.nk, halfrdx);
-    else       gpu_gradient_masked(VelocityU, VelocityV, VelocityW, p, du, dv, dw, solid.u8(), g.ni, g.nj, g.nk, halfrdx);
-    if (load_open && !boundaries.empty()) sampleLoads(p, nullptr);
-    return with_delta;
-}
-
 bool BimocqGPUSolver::pcgOperators() { return gpu_divergence_double && gpu_pcg_solve && gpu_pcg_gradient; }
 
 // BQ_PROJECTION_PCG: solid faces (obstacles only), fp64 divergence, the solve to pcg_tol, the masked
@@ -1084,22 +1116,17 @@ bool BimocqGPUSolver::pcgOperators() { return gpu_divergence_double && gpu_pcg_s
 bool BimocqGPUSolver::projectionPcg()
 {
     if (!allocMgcg()) return false;
-    const bool obst = !boundaries.empty();
-    const unsigned char *sol = projectionFlags();       // (walls on: solid + walls)
-    if (obst)
-        obstacle_faces(VelocityU, VelocityV, VelocityW, nullptr, nullptr, nullptr, solid.u8(), boundaries.data(), poseList(),
-                       (int)boundaries.size(), CellSize, g.ni, g.nj, g.nk);
-    if (walls) gpu_wall_faces(VelocityU, VelocityV, VelocityW, nullptr, nullptr, nullptr, solidw.u8(), g.ni, g.nj, g.nk);
+    const ProjectionOps ops(*this);
+    ops.faces(nullptr, nullptr, nullptr);
     gpu_divergence_double(VelocityU, VelocityV, VelocityW, mg.div.f64(), g.ni, g.nj, g.nk, (double)halfrdx);
     SCoarseLevelInfo &L0 = mg.levels[0];
-    gpu_pcg_solve(mg.div.f64(), mg.p.f64(), sol, mg.residual.f64(), mg.dir.f64(), mg.temp0.f64(), mg.temp1.f64(), L0.b, L0.r,
+    gpu_pcg_solve(mg.div.f64(), mg.p.f64(), ops.flags, mg.residual.f64(), mg.dir.f64(), mg.temp0.f64(), mg.temp1.f64(), L0.b, L0.r,
                   mg.levels.data(), (int)mg.levels.size(), pcg_iters, pcg_tol, pcg_stats);
     if (fl_last_error() != FL_OK) return false;
     pcg_projections++;
     if (pcg_stats[3] != BQ_PCG_CONVERGED) pcg_unconverged++;
-    if (walls) gpu_pcg_gradient_walls(VelocityU, VelocityV, VelocityW, mg.p.f64(), sol, walls, g.ni, g.nj, g.nk, (double)halfrdx);
-    else       gpu_pcg_gradient(VelocityU, VelocityV, VelocityW, mg.p.f64(), sol, g.ni, g.nj, g.nk, (double)halfrdx);
-    if (load_open && obst) sampleLoads(nullptr, mg.p.f64());
+    ops.gradient(mg.p.f64());
+    if (load_open && !boundaries.empty()) sampleLoads(nullptr, mg.p.f64());
     return false;
 }
 
@@ -1121,29 +1148,32 @@ bool BimocqGPUSolver::projection(bool with_delta)
         return false;
     }
     if (slabs) return projectionJacobiSlabs(with_delta);                 // (walls included; setBoundary refuses slab ranks)
-    if (!boundaries.empty() || walls) return projectionObstacles(with_delta);
     return projectionJacobi(with_delta);
 }
 
+// One GPU, every family (:1120-1413 with obstacles): gpu_projection_jacobi (GPU_kernel.cu:1839-1895) in its pieces -- solid faces
+// (with_delta: their share of d*Proj), divergence, iter-1 sweeps, the newest iterate made `p` by a buffer swap instead
+// of the copy-back, gradient on the faces between fluid cells with the change handed out
 bool BimocqGPUSolver::projectionJacobi(bool with_delta)
 {
-    const float alpha = -1.f, beta = (float)(1.0 / 6.0);
-    if (!with_delta) {
-        GpuSolver->projectionJacobi(VelocityU, VelocityV, VelocityW, div, p, p_temp, debugParam, jacobi_iters, halfrdx, alpha, beta);
+    const ProjectionOps ops(*this);
+    if (ops.kind == ProjectionOps::kPlain && !with_delta) {              // the reference's own entry point
+        GpuSolver->projectionJacobi(VelocityU, VelocityV, VelocityW, div, p, p_temp, debugParam, jacobi_iters, halfrdx, ops.alpha, ops.beta);
         return false;
     }
-    // gpu_projection_jacobi (GPU_kernel.cu:1839-1895) in its pieces: divergence, iter-1 sweeps, the
-    // newest iterate made `p` by a buffer swap instead of the copy-back, gradient with the change handed out
+    float *du = with_delta ? duProj.get() : nullptr, *dv = with_delta ? dvProj.get() : nullptr, *dw = with_delta ? dwProj.get() : nullptr;
     div.zero(); p.zero(); p_temp.zero();                                 // GPU_Advection.h:604-606
+    ops.faces(du, dv, dw);
     gpu_divergence(VelocityU, VelocityV, VelocityW, div, g.ni, g.nj, g.nk, halfrdx);
     int where = 0;
     if (jacobi_iters > 1) {
-        JacobiFuseVouched same_shell;                                    // p and p_temp carry the same (zero) boundary layer
-        where = gpu_jacobi_sweeps(p, div, p_temp, g.ni, g.nj, g.nk, jacobi_iters - 1, alpha, beta);
+        JacobiFuseVouched same_shell;       // p and p_temp carry the same (zero) boundary layer and +0 in every solid cell: sweeps may share a launch
+        where = ops.sweeps(p, p_temp, jacobi_iters - 1);
     }
     if (where) p.swap(p_temp);
-    gpu_gradient_delta(VelocityU, VelocityV, VelocityW, p, duProj, dvProj, dwProj, g.ni, g.nj, g.nk, halfrdx);
-    return true;
+    ops.gradient(p, du, dv, dw);
+    if (load_open && !boundaries.empty()) sampleLoads(p, nullptr);
+    return with_delta;
 }
 
 // z-slab form of gpu_projection_jacobi (GPU_kernel.cu:1839-1895): same three kernels, with the sweeps issued in chunks of G:
@@ -1156,10 +1186,9 @@ bool BimocqGPUSolver::projectionJacobi(bool with_delta)
 bool BimocqGPUSolver::projectionJacobiSlabs(bool with_delta)
 {
     gpuMapper &gs = *GpuSolver;
-    const float alpha = -1.f, beta = (float)(1.0 / 6.0);
     const int G = gs.slab.G;
-    const bool walled = walls != 0;
-    const unsigned char *sw = walled ? solidw.u8() : nullptr, *rw = walled ? rows.u8() : nullptr;
+    const ProjectionOps ops(*this);
+    const bool walled = ops.kind == ProjectionOps::kWalled;              // (for the schedule and the ghost-plane bookkeeping only)
     float *du = with_delta ? duProj.get() : nullptr, *dv = with_delta ? dvProj.get() : nullptr, *dw = with_delta ? dwProj.get() : nullptr;
     // The redundant ghost sweeps need div on all G ghost planes.  Rather than refreshing three velocity components to
     // depth G and evaluating div there, div is evaluated where the velocities are valid (the owned planes need one ghost
@@ -1167,36 +1196,16 @@ bool BimocqGPUSolver::projectionJacobiSlabs(bool with_delta)
     // owned-plane divergence is the very expression this rank would evaluate).
     gs.require({ &VelocityU, &VelocityV, &VelocityW }, 1);
     div.zero(); p.zero(); p_temp.zero();                                 // GPU_Advection.h:604-606
-    if (walled) {
-        // a pointwise pass on the faces of the window; the w face between the window and a closed z plane just outside it is
-        // the one the pass cannot decide (gpu_wall_faces): w's outermost ghost plane no longer counts
-        gpu_wall_faces(VelocityU, VelocityV, VelocityW, du, dv, dw, sw, g.ni, g.nj, g.nk);
-        gs.produced(VelocityW, std::min(VelocityW.valid, G - 1));
-    }
+    // a pointwise pass on the faces of the window; the w face between the window and a closed z plane just outside it is the one
+    // the wall pass cannot decide (gpu_wall_faces): w's outermost ghost plane no longer counts
+    ops.faces(du, dv, dw);
+    if (walled) gs.produced(VelocityW, std::min(VelocityW.valid, G - 1));
     gpu_divergence(VelocityU, VelocityV, VelocityW, div, g.ni, g.nj, g.nk, halfrdx);
     gs.produced(div, std::min({ VelocityU.valid, VelocityV.valid, VelocityW.valid - 1 }));
     gs.require({ &div }, G);
     DeviceField *cur = &p, *oth = &p_temp;
     gs.produced(*cur, G);                                                // zeros everywhere
     const int own0 = G, own1 = g.nk - G;                                 // local owned planes [own0, own1)
-    // S = 2 or 3 sweeps in one launch on up to two plane ranges; false: the library refuses (nothing was launched)
-    // (the walled family has no pairs, and its plan names none)
-    auto fused = [&](int S, DeviceField &in, DeviceField &out, slab::Planes a, slab::Planes b = slab::Planes{0, 0}) {
-        if (walled)
-            return S == 3 && gpu_jacobi_sweep_masked_walls_triple_ranges(in, div, out, sw, rw, walls, g.ni, g.nj, g.nk, a.k0, a.k1, b.k0, b.k1,
-                                                                         alpha, beta) != 0;
-        return (S == 3 ? gpu_jacobi_sweep_triple_ranges : gpu_jacobi_sweep_pair_ranges)(in, div, out, g.ni, g.nj, g.nk, a.k0, a.k1, b.k0, b.k1,
-                                                                                         alpha, beta) != 0;
-    };
-    auto single = [&](DeviceField &in, DeviceField &out, slab::Planes a) {
-        if (walled) gpu_jacobi_sweep_masked_walls_range(in, div, out, sw, rw, walls, g.ni, g.nj, g.nk, a.k0, a.k1, alpha, beta);
-        else gpu_jacobi_sweep_range(in, div, out, g.ni, g.nj, g.nk, a.k0, a.k1, alpha, beta);
-    };
-    // `n` sweeps on the whole array, one launch or several as the library sees fit; 1: the newest iterate is in `b`
-    auto sweeps = [&](DeviceField &a, DeviceField &b, int n) {
-        return walled ? gpu_jacobi_sweeps_masked_walls(a, div, b, sw, rw, walls, g.ni, g.nj, g.nk, n, alpha, beta)
-                      : gpu_jacobi_sweeps(a, div, b, g.ni, g.nj, g.nk, n, alpha, beta);
-    };
     // the G ghost planes of `f` start travelling on the halo stream; fl_halo_wait (or the next blocking exchange) joins them
     auto startExchange = [&](DeviceField &f) {
         float *ptr = f.get(); size_t pe = f.plane; int ex = 0;
@@ -1212,11 +1221,11 @@ bool BimocqGPUSolver::projectionJacobiSlabs(bool with_delta)
     // first; a later refusal would leave `in` half-updated, so it is an error, not a fall-back.
     auto endsFirst = [&](int S, DeviceField &in, DeviceField &out, int d) {
         const slab::Ends ea = slab::ends(own0, own1, G, d), eb = slab::ends(own0, own1, G, d - S);
-        if (!fused(S, in, out, ea.a, ea.b)) return false;
-        bool later = fused(S, out, in, eb.a, eb.b);
+        if (!ops.fused(S, in, out, ea.a, ea.b)) return false;
+        bool later = ops.fused(S, out, in, eb.a, eb.b);
         startExchange(in);
-        later &= fused(S, in, out, slab::interior(own0, own1, G, d));
-        later &= fused(S, out, in, slab::interior(own0, own1, G, d - S));
+        later &= ops.fused(S, in, out, slab::interior(own0, own1, G, d));
+        later &= ops.fused(S, out, in, slab::interior(own0, own1, G, d - S));
         if (!later) fl_report_error(FL_ERR_UNSUPPORTED, "projection on slabs: a follow-up launch of an ends-first group was refused after the first one ran");
         return true;
     };
@@ -1234,23 +1243,23 @@ bool BimocqGPUSolver::projectionJacobiSlabs(bool with_delta)
         int where, chunk;
         if (!in_flight && cur->valid >= std::min(plan.left, G)) {
             chunk = std::min(plan.left, G);
-            where = sweeps(*cur, *oth, chunk);
+            where = ops.sweeps(*cur, *oth, chunk);
         } else {
             // The ghost planes of `cur` travel on the halo stream while the compute stream sweeps what does not
             // depend on them; the planes next to them follow the exchange.
             if (!in_flight) startExchange(*cur);
             in_flight = false;
             slab::Chunk c = slab::plan_chunk(plan);
-            if (c.first == 2 && !fused(2, *cur, *oth, slab::first_interior(own0, own1, 2))) {
+            if (c.first == 2 && !ops.fused(2, *cur, *oth, slab::first_interior(own0, own1, 2))) {
                 plan.pairs_ok = false;                                   // the fused kernel does not apply to this grid
                 c = slab::plan_chunk(plan);
             }
             const slab::Ends fe = slab::first_ends(own0, own1, g.nk, c.first);
-            if (c.first == 1) single(*cur, *oth, slab::first_interior(own0, own1, 1));
+            if (c.first == 1) ops.single(*cur, *oth, slab::first_interior(own0, own1, 1));
             fl_halo_wait();
             gs.produced(*cur, G);
-            if (c.first == 2) fused(2, *cur, *oth, fe.a, fe.b);          // (one launch for both ends)
-            else { single(*cur, *oth, fe.a); single(*cur, *oth, fe.b); }
+            if (c.first == 2) ops.fused(2, *cur, *oth, fe.a, fe.b);          // (one launch for both ends)
+            else { ops.single(*cur, *oth, fe.a); ops.single(*cur, *oth, fe.b); }
             // The remaining sweeps of the chunk start from `oth`.  Nothing reads the planes beyond the depth that stays correct:
             // every fused pass is restricted to the planes that will still be correct after it (G = 8 in pairs: 264, 260, 256 of
             // 272 planes).
@@ -1258,7 +1267,7 @@ bool BimocqGPUSolver::projectionJacobiSlabs(bool with_delta)
             int d = G - c.first;                                         // correct ghost planes of `in`
             for (int i = 0; i < c.fused;) {
                 const bool group = c.ends_first && i == c.fused - 2;     // this pass and the next, ends first
-                const bool ran = group ? endsFirst(c.S, *in, *out, d - c.S) : fused(c.S, *in, *out, slab::whole(own0, own1, d - c.S));
+                const bool ran = group ? endsFirst(c.S, *in, *out, d - c.S) : ops.fused(c.S, *in, *out, slab::whole(own0, own1, d - c.S));
                 if (!ran && c.S == 3 && i == 0) {                        // the kernels do not apply to this grid: pairs from now on
                     plan.triples_ok = false;
                     c = slab::plan_chunk(plan);
@@ -1273,7 +1282,7 @@ bool BimocqGPUSolver::projectionJacobiSlabs(bool with_delta)
                 i += passes; d -= passes * c.S;
             }
             const int rest = c.sweeps - (G - d);
-            const int w2 = rest > 0 ? sweeps(*in, *out, rest) : 0;
+            const int w2 = rest > 0 ? ops.sweeps(*in, *out, rest) : 0;
             DeviceField *newest = w2 ? out : in;
             where = newest == cur ? 0 : 1;
             chunk = c.sweeps;
@@ -1288,15 +1297,8 @@ bool BimocqGPUSolver::projectionJacobiSlabs(bool with_delta)
     if (cur != &p) p.swap(p_temp);                                       // the newest iterate becomes `p` (no copy-back)
     gs.require({ &p }, 1);
     const int vu = std::min(VelocityU.valid, p.valid), vv = std::min(VelocityV.valid, p.valid), vw = std::min(VelocityW.valid, p.valid - 1);
-    if (walled) {
-        gpu_gradient_masked_walls(VelocityU, VelocityV, VelocityW, p, du, dv, dw, sw, walls, g.ni, g.nj, g.nk, halfrdx);
-        if (with_delta) { gs.produced(duProj, vu); gs.produced(dvProj, vv); gs.produced(dwProj, vw); }
-    } else if (with_delta) {
-        gpu_gradient_delta(VelocityU, VelocityV, VelocityW, p, duProj, dvProj, dwProj, g.ni, g.nj, g.nk, halfrdx);
-        gs.produced(duProj, vu); gs.produced(dvProj, vv); gs.produced(dwProj, vw);
-    } else {
-        gpu_gradient(VelocityU, VelocityV, VelocityW, p, g.ni, g.nj, g.nk, halfrdx);
-    }
+    ops.gradient(p, du, dv, dw);
+    if (with_delta) { gs.produced(duProj, vu); gs.produced(dvProj, vv); gs.produced(dwProj, vw); }
     gs.produced(VelocityU, vu);
     gs.produced(VelocityV, vv);
     gs.produced(VelocityW, vw);

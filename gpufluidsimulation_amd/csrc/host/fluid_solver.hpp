@@ -68,7 +68,7 @@ public:
     void diffuseFieldSlab(DeviceField &field, DeviceField &t0, DeviceField &t1, int bi, int bj, int bk, int iter, float nu, float dt);
     void diffuseVelocity(float dt);
     bool projection(bool with_delta = false);
-    bool projectionJacobi(bool with_delta);         // one GPU
+    bool projectionJacobi(bool with_delta);         // one GPU: plain, with obstacles, with walls
     bool projectionJacobiSlabs(bool with_delta);    // z-slab ranks: chunks of G sweeps per exchange (slab_jacobi_plan.hpp)
     void velocityReinitialize();
     void scalarReinitialize();
@@ -178,7 +178,6 @@ public:
     const bq_pose *poseList() const { return posed_list ? poses.data() : nullptr; }
     void dropBoundaries();
     bool buildFlags(const std::vector<bq_boundary> &list, const bq_levelset *ls, const bq_pose *pose);
-    bool projectionObstacles(bool with_delta);
     // Closed domain walls (the reference's container, BimocqSolver.cpp:938-948): `walls` the closed sides
     // (BQ_WALL_* bits), `solidw` = solid + BQ_FLAG_WALL in the wall cells, allocated only while walls are on and rebuilt when the
     // walls or the obstacle flags change.  solid and rows stay the obstacles' own (rows: all zero while the list is empty).

@@ -6,7 +6,8 @@
 
 Every function of namespace bq in the first file is matched to the function of the second file with the same base name and
 the same leading boolean template arguments (a kernel that gained trailing template parameters, as the render kernels did with
-SOLID, matches its instantiation whose added booleans are all 0); comments, directives and the numbering of branch labels are
+SOLID, matches its instantiation whose added booleans are all 0; where that rule finds several, the one with the same mangled
+name); comments, directives and the numbering of branch labels are
 dropped, everything else -- opcodes, registers, operands, order -- is compared.  Prints one line per kernel, IDENTICAL or
 DIFFERENT (--show N: the first N lines of a unified diff), and exits 1 when any kernel differs or has no counterpart.
 DESIGN.md section 27 uses it to show that the eight kernels of gpu_render_density are the code they were."""
@@ -57,6 +58,8 @@ def main():
     for name, code in old.items():
         base, bools = key(name)
         match = [n for n in new if key(n)[0] == base and key(n)[1][:len(bools)] == bools and all(b == "0" for b in key(n)[1][len(bools):])]
+        if len(match) != 1 and name in new:     # instantiations that differ in other than boolean arguments: by the whole mangled name
+            match, base = [name], name
         if len(match) != 1:
             print(f"{base}{list(bools)}: {len(match)} counterparts")
             bad += 1

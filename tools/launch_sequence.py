@@ -10,7 +10,13 @@ value back, so the sequence does not depend on the data) and writes what every c
 reports to --log.  `reduce` turns the kernel trace into the ordered list of launches -- kernel name with its template
 arguments, grid size, workgroup size -- written as a table of the distinct launches and the sequence of their numbers.
 Two builds agree when both files are equal line for line.  --extended adds the shape and the option combinations of EXTENDED below
-to the table (the lists without it are those of profiles/launch_geom_launches_*.txt, with it of profiles/jacobi_plan_launches_*.txt).
+to the table (the lists without it are those of profiles/launch_geom_launches_*.txt, with it of profiles/jacobi_plan_launches_*.txt,
+both from before the walled sweeps joined the table; with them: profiles/jacobi_family_launches_*.txt).
+
+    rocprofv3 --kernel-trace --output-format csv -d <dir> -- python tools/launch_sequence.py step --scene box --scheme reflection
+
+`step` runs three steps of the rising-smoke scene at 64^3 with 20 Jacobi iterations through the host solver -- scene plain, sphere (one
+sphere obstacle) or box (the closed container), scheme bimocq or reflection -- for the same comparison at the level of a solver step.
 """
 import argparse
 import csv
@@ -24,6 +30,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FP32_SHAPES = [(256, 256, 256), (128, 128, 128), (64, 256, 192), (320, 64, 48), (512, 512, 64)]
 FP64_SHAPES = FP32_SHAPES + [(127, 127, 127)]
 VARIANT, KCHUNK, ROWS, FUSE, KCHUNK2, RESERVE_CUS, MGCG_FUSE = 3, 5, 6, 8, 9, 16, 20
+BOX = 1 | 2 | 4 | 16 | 32           # BQ_WALL_*: the reference's container, open at +y
 # (option, value) pairs on top of FL_OPT_JACOBI_FUSE = 2
 FP32_SETTINGS = ([[(ROWS, r)] for r in range(1, 8)] + [[(VARIANT, v)] for v in (1, 2)] +
                  [[(KCHUNK, k)] for k in (1, 2, 18, 19, 24, 25, 26)] + [[(KCHUNK2, 8)], [(RESERVE_CUS, 8)]])
@@ -135,10 +142,33 @@ def run(log_path, extended=False):
         options([(KCHUNK, 0)])
         lib.gpu_jacobi_sweep_masked(p, d, t, solid, rows, ni, nj, nk, a, b6)
         note(f"{tag} gpu_jacobi_sweep_masked")
+
+        # the walled sweeps on the same zero flags, every side closed but +y: the whole array, plane ranges, the fused triple on ranges
+        def walled(label):
+            lib.gpu_jacobi_sweep_masked_walls(p, d, t, solid, rows, BOX, ni, nj, nk, a, b6)
+            note(f"{tag} {label} gpu_jacobi_sweep_masked_walls")
+            for k0, k1 in ((5, nk - 5), (0, 7), (nk - 9, nk), (-3, nk + 3), (4, 4)):
+                note(f"{tag} {label} gpu_jacobi_sweep_masked_walls_range {k0} {k1}",
+                     lib.gpu_jacobi_sweep_masked_walls_range(p, d, t, solid, rows, BOX, ni, nj, nk, k0, k1, a, b6))
+            for r in ((8, nk - 8, 0, 0), (0, 8, nk - 8, nk), (0, nk, 0, 0), (3, 11, nk - 20, nk - 2), (4, 4, 0, 0)):
+                note(f"{tag} {label} walls_triple_ranges {r}",
+                     lib.gpu_jacobi_sweep_masked_walls_triple_ranges(p, d, t, solid, rows, BOX, ni, nj, nk, *r, a, b6))
+
+        for f in (1, 2):
+            options([(FUSE, f)])
+            note(f"{tag} fuse={f} gpu_jacobi_sweeps_masked_walls 11", lib.gpu_jacobi_sweeps_masked_walls(p, d, t, solid, rows, BOX, ni, nj, nk, 11, a, b6))
+            walled(f"fuse={f}")
+        for k in (19, 24):
+            options([(KCHUNK, k)])
+            note(f"{tag} kchunk={k} gpu_jacobi_sweeps_masked_walls 9", lib.gpu_jacobi_sweeps_masked_walls(p, d, t, solid, rows, BOX, ni, nj, nk, 9, a, b6))
+        options([(KCHUNK, 0)])
+        note(f"{tag} walls=0 gpu_jacobi_sweeps_masked_walls 9", lib.gpu_jacobi_sweeps_masked_walls(p, d, t, solid, rows, 0, ni, nj, nk, 9, a, b6))
         # a z-slab rank: the same buffers as planes [16, 16 + nk) of nk + 32
         lib.fl_set_slab(16, nk + 32, 24, 8 + nk, nk)
         sweeps("slab")
         ranges("slab")
+        note(f"{tag} slab gpu_jacobi_sweeps_masked_walls 11", lib.gpu_jacobi_sweeps_masked_walls(p, d, t, solid, rows, BOX, ni, nj, nk, 11, a, b6))
+        walled("slab")
         lib.fl_set_slab(0, 0, 0, 0, 0)
         options([(FUSE, 1)])
         # the other launchers that share the block shape and the lane rule
@@ -188,6 +218,26 @@ def run(log_path, extended=False):
     print("done", file=log, flush=True)
 
 
+def step(scene, scheme):
+    sys.path.insert(0, ROOT)
+    import gpufluidsimulation_amd as bq
+    from gpufluidsimulation_amd.scenes import rising_smoke
+    from gpufluidsimulation_amd.solver import SCHEME_BIMOCQ, SCHEME_MAC_REFLECTION, BimocqGPUSolver
+    n = 64
+    s = BimocqGPUSolver(n, n, n, 1.0, 0.0, 1.0, device=0, scheme=SCHEME_MAC_REFLECTION if scheme == "reflection" else SCHEME_BIMOCQ)
+    s.setSmoke(0.0, 1.0, rising_smoke(n, 1.0 / n))
+    s.setProjection(20, 0.5)
+    if scene == "sphere":
+        s.setBoundary([(0, 0.5, 0.5, 0.5, 0.15, 0.0, 0.0, 0.0, 0.0, 0.0)])
+    if scene == "box":
+        s.setWalls(BOX)
+    for f in range(3):
+        s.advance(f, 2.0 / n)
+    bq.hip_lib().fl_sync()
+    bq.check()
+    s.close()
+
+
 def strip_parameters(name):
     """the demangled kernel name without its parameter list (template arguments stay)"""
     if not name.endswith(")"):
@@ -225,12 +275,16 @@ def reduce(trace_dir):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=["run", "reduce"])
+    ap.add_argument("mode", choices=["run", "step", "reduce"])
     ap.add_argument("trace_dir", nargs="?")
     ap.add_argument("--log", default="")
     ap.add_argument("--extended", action="store_true")
+    ap.add_argument("--scene", choices=["plain", "sphere", "box"], default="plain")
+    ap.add_argument("--scheme", choices=["bimocq", "reflection"], default="bimocq")
     args = ap.parse_args()
     if args.mode == "run":
         run(args.log, args.extended)
+    elif args.mode == "step":
+        step(args.scene, args.scheme)
     else:
         reduce(args.trace_dir)
