@@ -81,6 +81,7 @@ HIP_SIGS = {
     "fl_mg_residual_launches": (C.c_longlong, []),
     "fl_sparse_stats": (None, [C.POINTER(C.c_longlong), c_i]),
     "fl_sparse_stats_kind": (None, [c_i, C.POINTER(C.c_longlong), c_i]),
+    "fl_sparse_wave_stats": (None, [C.POINTER(C.c_longlong), c_i]),
     "gpu_brick_flags": (c_i, [VP, VP, c_i, c_i, c_i, VP, C.POINTER(c_i)]),
     # 3. additive
     "gpu_init_maps": (None, [VP, VP, VP] + _G),
@@ -214,6 +215,7 @@ FL_OPT_SKIP_EMPTY_BRICKS = 21
 FL_OPT_DIAG_KCHUNK = 22
 FL_OPT_RENDER_KCHUNK = 23
 FL_OPT_CONFINE_KCHUNK = 24
+FL_OPT_SKIP_EMPTY_TAPS = 25
 # rows of gpu_flow_stats' d_out (BQ_STAT_*)
 STAT_NAMES = ("e2", "m2", "d2", "div_max", "rho", "rho_i", "rho_j", "rho_k", "T", "vort_max")
 STAT_COUNT = len(STAT_NAMES)

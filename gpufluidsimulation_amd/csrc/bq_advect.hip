@@ -190,19 +190,41 @@ __device__ __forceinline__ void mapped9(const Map3 &m, const Spacing &sp, const 
 // with the tap's cell and weights located once for all fields (they share dims and origin).
 // Positions are inside the grid and origins are <= 0, so pos - org >= 0 (locate's NONNEG form).
 // GE1: every position is >= h on every axis, hence q >= 1 and the lerps may take their one-fma form (lerp_w<true>).
-template <bool P2, bool PT, int NF, bool GE1>
+// STASHED (with stash: LDS, this thread's word of 3 * STASHED rows of 256): the last STASHED positions wait in LDS until their
+// taps come up.  For a caller that enters with all nine positions in registers -- the wave test of cumulate_kernel, whose
+// branch keeps the scheduler from computing the late positions late -- where two taps in flight on top of them would spill
+// to scratch.  The compiler barriers keep the values from being forwarded in registers and the reads from being hoisted.
+template <bool P2, bool PT, int NF, bool GE1, int STASHED = 0>
 __device__ __forceinline__ void blend9_gather_w(const Field (&src)[NF], const Spacing &sp, f3 org, const f3 (&mp)[9],
-                                                const float (&w)[NF], float (&sum)[NF], float (&value)[NF])
+                                                const float (&w)[NF], float (&sum)[NF], float (&value)[NF], float *stash = nullptr)
 {
+    static_assert(STASHED == 0 || !PT, "point mode has one position");
+    auto pos = [&](int ii) -> f3 {
+        if constexpr (STASHED > 0) {
+            if (ii >= 9 - STASHED) {
+                if (ii == 9 - STASHED) asm volatile("" ::: "memory");
+                const int t = 3 * (ii - (9 - STASHED));
+                return mk3(stash[256 * t], stash[256 * (t + 1)], stash[256 * (t + 2)]);
+            }
+        }
+        return mp[ii];
+    };
+    if constexpr (STASHED > 0) {
+#pragma unroll
+        for (int t = 0; t < STASHED; t++) {
+            stash[256 * (3 * t)] = mp[9 - STASHED + t].x; stash[256 * (3 * t + 1)] = mp[9 - STASHED + t].y; stash[256 * (3 * t + 2)] = mp[9 - STASHED + t].z;
+        }
+        asm volatile("" ::: "memory");
+    }
     if (!PT) {
 #pragma unroll
         for (int ii = 0; ii < 8; ii++) {
-            const Cell c = locate<P2, true>(src[0], sp, org, mp[ii]);
+            const Cell c = locate<P2, true>(src[0], sp, org, pos(ii));
 #pragma unroll
             for (int f = 0; f < NF; f++) sum[f] += w[f] * gather<GE1>(src[f], c);
         }
     }
-    const Cell c = locate<P2, true>(src[0], sp, org, mp[8]);
+    const Cell c = locate<P2, true>(src[0], sp, org, pos(8));
 #pragma unroll
     for (int f = 0; f < NF; f++) {
         value[f] = gather<GE1>(src[f], c);
@@ -368,6 +390,11 @@ __global__ __launch_bounds__(256) void unit_blend_kernel(float *field, Grid g, i
 
 // ---- A6/A8: cumulate_kernel (GPU_kernel.cu:376-436): dst += blend9(coeff*src(map(x))) ------
 // ID: the map is the identity map of gpu_init_maps (mx/my/mz are not read).
+// SPARSE: 1 and 2 as in advect_kernel; 3 = FL_OPT_SKIP_EMPTY_TAPS, the launch that tests its own taps wave by wave
+// (bq_sparse.hip.h: wave_taps_may_read) -- a wave whose taps all land in cells with a clear flag runs the stores of SPARSE == 1,
+// every other wave the same gather in another schedule (positions parked in LDS for one field, field by field for two: the
+// branch keeps all nine positions in registers, and the plain schedule on top of them spills).  Where the flag pass found no
+// empty brick the launch returns at once and a SPARSE == 2 launch with an empty list, i.e. the plain kernel, follows.
 template <bool P2, bool PT, int SD, int NF, bool ID, bool Q4 = false, int SPARSE = 0>
 __global__ __launch_bounds__(256, NF == 1 ? 7 : 6) void cumulate_kernel(CumulateArgs<NF> a,
                                                        const float *mx, const float *my, const float *mz,
@@ -380,6 +407,9 @@ __global__ __launch_bounds__(256, NF == 1 ? 7 : 6) void cumulate_kernel(Cumulate
     int bX = blockIdx.x, bY = blockIdx.y, bZ = blockIdx.z;
     if constexpr (SPARSE == 1) { if (*sps.word != sps.epoch) return; }
     if constexpr (SPARSE == 2) { if (!listed_block(sps, bX, bY, bZ)) return; }
+    // SPARSE == 3 (FL_OPT_SKIP_EMPTY_TAPS): the flag pass found no empty brick -> nothing to do here, the launch that follows
+    // (SPARSE == 2 with an empty list) is then the plain one
+    if constexpr (SPARSE == 3) { if (*sps.word != sps.epoch) return; }
     BQ_IJK_WINDOW_AT(bX, bY, bZ, m + dx, nbi - m - 1, m + dy, nbj - m - 1, m + dz, g.nkg + dz - m - 1)
     if (block_out) return;
     const float h = sp.h;
@@ -454,6 +484,26 @@ __global__ __launch_bounds__(256, NF == 1 ? 7 : 6) void cumulate_kernel(Cumulate
     const bool ge1 = NF == 1 && wave_all_ge<PT>(mp, h);   // (two fields: both code paths together need too many registers)
 #pragma unroll
     for (int a9 = 0; a9 < 9; a9++) mp[a9] = clamp3_ordered(mp[a9], lo, hi);
+    if constexpr (SPARSE == 3) {
+        static_assert(P2, "the wave test locates its cells by the power-of-two form of locate()");
+        // the cells of the nine taps as locate() finds them below, one cell flag each.  No lane votes "may read": every
+        // corner word of every tap of this wave is 0x00000000 in every field, none has to be loaded
+        const bool skip = !wave_taps_may_read(sps, sp, mp);
+        count_wave(sps, skip);
+        if (skip) {
+            // the stores of the SPARSE == 1 branch above: the full path's statements with +0.0f for every gather result
+#pragma unroll
+            for (int f = 0; f < NF; f++) {
+                const float w = Op::weight(PT, a.coeff[f]);
+                float sum = 0.f;
+#pragma unroll
+                for (int ii = 0; ii < (PT ? 1 : 8); ii++) sum += w * 0.f;
+                // (dst[0] == dst[1]: the load follows the first field's store in program order, as in the full path)
+                a.dst[f][id] += Op::result(sum, 0.f, a.coeff[f], 0.f);
+            }
+            return;
+        }
+    }
     Field src[NF];
     float sum[NF], value[NF], w[NF];
 #pragma unroll
@@ -462,8 +512,33 @@ __global__ __launch_bounds__(256, NF == 1 ? 7 : 6) void cumulate_kernel(Cumulate
         sum[f] = 0.f;
         w[f] = Op::weight(PT, a.coeff[f]);
     }
+    if constexpr (SPARSE == 3 && NF == 1) {
+        // (the last positions wait in LDS: 6 KiB on top of the tile, which still lets 7 blocks share a CU's 160 KiB)
+        constexpr int stashed = 2;
+        __shared__ float late[3 * stashed * 256];
+        float *mine = late + threadIdx.x + 64 * threadIdx.y;
+        if (ge1) blend9_gather_w<P2, PT, NF, true, stashed>(src, sp, n.org, mp, w, sum, value, mine);
+        else     blend9_gather_w<P2, PT, NF, false, stashed>(src, sp, n.org, mp, w, sum, value, mine);
+    } else if constexpr (SPARSE == 3) {
+        // Two fields: one after the other.  With all nine positions in registers two taps of both fields in flight (32
+        // registers of corners) would spill; a field at a time needs half of that.  The second pass locates its cells again
+        // (about a hundred instructions: 5 % of the kernel) from positions the compiler cannot tell are the same -- sharing the
+        // nine cells between the passes would keep 36 registers alive instead of 27.  A field's taps are summed in the same order.
+#pragma unroll
+        for (int f = 0; f < NF; f++) {
+#pragma unroll
+            for (int a9 = 0; a9 < 9; a9++) asm volatile("" : "+v"(mp[a9].x), "+v"(mp[a9].y), "+v"(mp[a9].z));
+            const f3 (&p)[9] = mp;
+            const Field s1[1] = { src[f] };
+            const float w1[1] = { w[f] };
+            float sum1[1] = { 0.f }, value1[1];
+            blend9_gather_w<P2, PT, 1, false>(s1, sp, n.org, p, w1, sum1, value1);
+            sum[f] = sum1[0]; value[f] = value1[0];
+        }
+    } else {
     if (NF == 1 && ge1) blend9_gather_w<P2, PT, NF, true>(src, sp, n.org, mp, w, sum, value);
     else                blend9_gather_w<P2, PT, NF, false>(src, sp, n.org, mp, w, sum, value);
+    }
 #pragma unroll
     for (int f = 0; f < NF; f++) {
         a.dst[f][id] += Op::result(sum[f], value[f], a.coeff[f], 0.f);     // dst[0] == dst[1] is allowed: applied in order
@@ -987,6 +1062,12 @@ static bool march_launch(const GatherArgs<NF> &a, const float *mx, const float *
 // without the skip (option off, or the launch is not one the skip is built for -- the caller passes `eligible`).
 // The flag array and the header (pass word, counters) are per-context scratch that grows on demand, like map_tab_dev.
 // kind: whose counters the launch feeds (0 advection, 1 error stage, 2 accumulation).
+constexpr size_t kSparseHdrBytes = 128;         // pass word, the block counters (bytes 8..55), the wave counters (bytes 64..79)
+static inline size_t sparse_cells_at(size_t nflags, size_t nblocks)
+{
+    const size_t list_at = (nflags + 255) & ~(size_t)255;
+    return (list_at + 4 * (nblocks + 1) + 255) & ~(size_t)255;
+}
 template <int NF>
 static Sparse brick_flags(bool eligible, int kind, const float *const (&src)[NF], int nbi, int nbj, int nbk, size_t nblocks, bool force = false)
 {
@@ -998,11 +1079,13 @@ static Sparse brick_flags(bool eligible, int kind, const float *const (&src)[NF]
     if (nby > 65535 || nbz > 65535) return none;
     // the flags, then (4-byte aligned) the block list of the classifying launch: a count and one entry per block of its grid
     const size_t nflags = (size_t)nbx * nby * nbz, list_at = (nflags + 255) & ~(size_t)255;
-    const size_t need = list_at + 4 * (nblocks + 1);
+    // ... then the cell flags of FL_OPT_SKIP_EMPTY_TAPS (cell_flags below)
+    const CellDims cd = cell_dims(nbi, nbj, nbk);
+    const size_t need = sparse_cells_at(nflags, nblocks) + (size_t)cd.ncx * cd.ncy * cd.ncz;
     if (nblocks >= 0x7fffffffu) return none;
     if (!r.sparse_hdr) {
-        if (!BQ_HIP(hipMalloc((void **)&r.sparse_hdr, 64))) { r.sparse_hdr = nullptr; return none; }
-        if (!BQ_HIP(hipMemsetAsync(r.sparse_hdr, 0, 64, r.compute))) return none;
+        if (!BQ_HIP(hipMalloc((void **)&r.sparse_hdr, kSparseHdrBytes))) { r.sparse_hdr = nullptr; return none; }
+        if (!BQ_HIP(hipMemsetAsync(r.sparse_hdr, 0, kSparseHdrBytes, r.compute))) return none;
         r.sparse_epoch = 0;
     }
     if (need > r.sparse_cap) {
@@ -1022,6 +1105,23 @@ static Sparse brick_flags(bool eligible, int kind, const float *const (&src)[NF]
     if (!BQ_LAUNCH_CHECK("brick_flags_kernel")) return none;
     unsigned long long *stats = (r.opt_skip_empty_bricks == 2 || r.opt_skip_empty_bricks == 4) ? reinterpret_cast<unsigned long long *>(r.sparse_hdr + 2) + 2 * kind : nullptr;
     return Sparse{ r.sparse_flags, r.sparse_hdr, stats, list, epoch, nbx, nby };
+}
+// FL_OPT_SKIP_EMPTY_TAPS: the cell-flag pass behind the flag pass `s` (bq_sparse.hip.h: cell_flags_kernel), on the same stream.
+// Returns the Sparse of the wave-test launch -- the CELL flags and their dims, the wave counters where FL_OPT_SKIP_EMPTY_BRICKS
+// counts, no list -- or one without flags when the launch failed.
+static Sparse cell_flags(const Sparse &s, int nbi, int nbj, int nbk, size_t nblocks)
+{
+    Runtime &r = rt();
+    const Sparse none{ nullptr, nullptr, nullptr, nullptr, 0, 0, 0 };
+    const int nbz = (nbk + kBrick - 1) >> kBrickShift;
+    const CellDims cd = cell_dims(nbi, nbj, nbk);
+    const size_t ncells = (size_t)cd.ncx * cd.ncy * cd.ncz;
+    if (ncells >= 0x7fffffffu) return none;
+    unsigned char *cells = r.sparse_flags + sparse_cells_at((size_t)s.nbx * s.nby * nbz, nblocks);
+    cell_flags_kernel<<<dim3((unsigned)((ncells + 3) / 4)), kBlock, 0, r.compute>>>(s.flags, cells, nbi, nbj, nbk);
+    if (!BQ_LAUNCH_CHECK("cell_flags_kernel")) return none;
+    unsigned long long *stats = (r.opt_skip_empty_bricks == 2 || r.opt_skip_empty_bricks == 4) ? reinterpret_cast<unsigned long long *>(r.sparse_hdr + 16) : nullptr;
+    return Sparse{ cells, s.word, stats, nullptr, s.epoch, cd.ncx, cd.ncy };
 }
 // the launches the skip is built for: unstaggered, one GPU, the whole array, the staged one-plane kernels
 static inline bool sparse_eligible(const Grid &g, int planes, int dx, int dy, int dz, bool staged)
@@ -1067,9 +1167,17 @@ static void gather_launch(const GatherArgs<NF> &a, const float *mx, const float 
     // The accumulate takes part at option values 3 / 4 only: it usually samples through a BACKWARD map, whose zeroed border
     //  its window reaches; at 256^3 half of its blocks then cannot be skipped and the two launches cost more
     // than the one (EXPERIMENTS section 14), so the default leaves this operator alone.
+    // At values 1 / 2 it takes the wave-test form instead (FL_OPT_SKIP_EMPTY_TAPS, power-of-two spacing): flag pass, cell-flag
+    // pass, and the kernel tests the taps it has computed wave by wave -- a border lane's nine taps land at nine definite
+    // points, which no longer spoil the block.
     const bool staged = !pt && rt().opt_structured_maps && (tabled || (sp.pow2 && !identity));
-    const Sparse sps = brick_flags<NF>((KIND != kOpCumulate || rt().opt_skip_empty_bricks >= 3) && sparse_eligible(g, planes, dx, dy, dz, staged),
-                                       Op::counter_slot, a.src, g.ni, g.nj, g.nk, (size_t)grid.x * grid.y * grid.z);
+    const bool eligible = sparse_eligible(g, planes, dx, dy, dz, staged);
+    const int skip_opt = rt().opt_skip_empty_bricks;
+    const bool wave = KIND == kOpCumulate && sp.pow2 && rt().opt_skip_empty_taps && (skip_opt == 1 || skip_opt == 2) && eligible;
+    const size_t nblocks = (size_t)grid.x * grid.y * grid.z;
+    Sparse sps = brick_flags<NF>((KIND != kOpCumulate || skip_opt >= 3 || wave) && eligible, Op::counter_slot, a.src, g.ni, g.nj, g.nk, nblocks);
+    const Sparse bricks = sps;          // (the flag pass's own view: brick flags, the block list)
+    if (wave && sps.flags) sps = cell_flags(sps, g.ni, g.nj, g.nk, nblocks);
     const auto ka = plane_args<KIND>(a);
     dispatch_sd(sp.pow2, pt, sda, [&](auto P2, auto PT, auto SD) {
         constexpr bool p2 = decltype(P2)::value, ptc = decltype(PT)::value;
@@ -1083,6 +1191,20 @@ static void gather_launch(const GatherArgs<NF> &a, const float *mx, const float 
         };
         using T = std::true_type; using F = std::false_type;
         using Plain = std::integral_constant<int, 0>; using Classify = std::integral_constant<int, 1>; using Listed = std::integral_constant<int, 2>;
+        if constexpr (KIND == kOpCumulate && p2 && sd == 0 && kStaged<p2, ptc, sd>) {
+            if (wave && sps.flags) {
+                // the launch with the wave test, then the unchanged kernel on an EMPTY block list (nothing classifies, the
+                // flag pass left the count at 0): with an empty brick somewhere the second launch returns at once, without
+                // one the first does and the second is the plain launch -- a dense pair pays nothing inside the operator
+                using WaveTest = std::integral_constant<int, 3>;
+                if (q4) launch(F{}, T{}, WaveTest{});
+                else launch(F{}, F{}, WaveTest{});
+                sps = bricks;
+                if (q4) launch(F{}, T{}, Listed{});
+                else launch(F{}, F{}, Listed{});
+                return;
+            }
+        }
         if constexpr (sd == 0 && kStaged<p2, ptc, sd>) {
             if (sps.flags) {            // classify (and finish the blocks that can be skipped), then the listed blocks
                 launch(F{}, F{}, Classify{});
@@ -1778,6 +1900,23 @@ void fl_sparse_stats_kind(int kind, long long out[2], int reset)
 {
     if (kind < 0 || kind > 2) { latch(FL_ERR_BAD_ARGUMENT, "fl_sparse_stats_kind", "kind must be 0, 1 or 2"); return; }
     sparse_stats(kind, kind + 1, out, reset);
+}
+// FL_OPT_SKIP_EMPTY_TAPS with FL_OPT_SKIP_EMPTY_BRICKS = 2: out[0] = waves of the accumulation that tested their taps against the
+// cell flags, out[1] = how many of them were skipped, since the last reset (blocking; reset != 0 clears)
+void fl_sparse_wave_stats(long long out[2], int reset)
+{
+    if (!out) return;
+    out[0] = out[1] = 0;
+    Runtime &r = rt();
+    if (!r.ready || !r.sparse_hdr) return;
+    unsigned long long *host = (unsigned long long *)pinned(64);
+    if (!host) return;
+    hipStream_t st = r.compute;
+    unsigned long long *dev = reinterpret_cast<unsigned long long *>(r.sparse_hdr + 16);
+    if (!BQ_HIP(hipMemcpyAsync(host, dev, 16, hipMemcpyDeviceToHost, st))) return;
+    if (reset && !BQ_HIP(hipMemsetAsync(dev, 0, 16, st))) return;
+    if (!BQ_HIP(hipStreamSynchronize(st))) return;
+    out[0] = (long long)(host[0] + host[1]); out[1] = (long long)host[1];
 }
 
 // The flag pass on its own (for tests and tools/brick_occupancy.py): flags of the 8 x 8 x 8 bricks of one field, or of two

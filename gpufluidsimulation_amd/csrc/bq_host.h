@@ -75,12 +75,22 @@ struct Runtime {
     float  map_tab_h = 0.f;
     int    map_tab_dims[3] = {0, 0, 0}, map_tab_stride = 0, map_tab_ok = 0;
     // FL_OPT_SKIP_EMPTY_BRICKS (bq_advect.hip: brick_flags): one flag per 8^3 brick of the arrays the last flag pass read, and a
-    // header -- word 0: number of the last pass that found an empty brick; bytes 8..55: three pairs of 64-bit block counters (option value 2)
+    // header -- word 0: number of the last pass that found an empty brick; bytes 8..55: three pairs of 64-bit block counters (option value 2);
+    // bytes 64..79: the pair of wave counters of FL_OPT_SKIP_EMPTY_TAPS.  Behind the brick flags and the block list, sparse_flags
+    // holds that option's CELL flags: one byte per brick of base nodes, (n >> 3) + 1 bricks per axis, 0 only if every word a
+    // cell based there can deliver to corners() is zero (bq_sparse.hip.h: cell_flags_kernel).
     unsigned char *sparse_flags = nullptr;
     size_t sparse_cap = 0;
     int   *sparse_hdr = nullptr;
     int    sparse_epoch = 0;            // passes issued so far
     int    opt_skip_empty_bricks = 1;   // 0 off, 1 on (advection, error stage), 2 = 1 and counting, 3 = 1 plus the accumulation, 4 = 3 and counting
+    // FL_OPT_SKIP_EMPTY_TAPS: with opt_skip_empty_bricks 1 or 2 the unstaggered accumulation runs as a launch that tests the
+    // taps it has computed against the cell flags, wave by wave, followed by the unchanged kernel on an empty block list, which
+    // does the work where the flag pass found no empty brick (no classifying launch: the backward map's zeroed border makes the
+    // tile range of half the blocks useless, while the nine taps of a border lane land at nine definite, usually empty points).
+    // A skipped wave may read no corner word of any tap -- the flags vouch that all of them are 0x00000000 -- and its stores are
+    // the full path's statements with +0.0f for every gather result.
+    int    opt_skip_empty_taps = 1;
     int    nonfinite_seen = 0;          // sticky: a gpu_max_abs3 met a NaN or an Inf (fl_nonfinite_seen)
     const char *map_kernel_name[2] = { "", "" };    // the DMC / forward instance launched last (fl_map_kernel_name)
     int    map_kernels_seen = 0;        // instances launched since the last reset, as bits (fl_map_kernels_seen)

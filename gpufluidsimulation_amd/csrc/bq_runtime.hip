@@ -474,6 +474,7 @@ void fl_set_option(int option, int value)
     case FL_OPT_FIELD_WINDOW:    g_rt.opt_field_window = value < 0 ? -1 : value; break;
     case FL_OPT_COMM_CHECK:      g_rt.opt_comm_check = value != 0; break;
     case FL_OPT_SKIP_EMPTY_BRICKS: g_rt.opt_skip_empty_bricks = (value >= 1 && value <= 4) ? value : 0; break;
+    case FL_OPT_SKIP_EMPTY_TAPS: g_rt.opt_skip_empty_taps = value != 0; break;
     case FL_OPT_DIAG_KCHUNK:     g_rt.opt_diag_kchunk = value < 0 ? -1 : value; break;
     case FL_OPT_RENDER_KCHUNK:   g_rt.opt_render_kchunk = value < 0 ? -1 : value; break;
     case FL_OPT_CONFINE_KCHUNK:  g_rt.opt_confine_kchunk = value < 0 ? -1 : value; break;
@@ -518,6 +519,7 @@ int fl_get_option(int option)
     case FL_OPT_FIELD_WINDOW:    return g_rt.opt_field_window;
     case FL_OPT_COMM_CHECK:      return g_rt.opt_comm_check;
     case FL_OPT_SKIP_EMPTY_BRICKS: return g_rt.opt_skip_empty_bricks;
+    case FL_OPT_SKIP_EMPTY_TAPS: return g_rt.opt_skip_empty_taps;
     case FL_OPT_DIAG_KCHUNK:     return g_rt.opt_diag_kchunk;
     case FL_OPT_RENDER_KCHUNK:   return g_rt.opt_render_kchunk;
     case FL_OPT_CONFINE_KCHUNK:  return g_rt.opt_confine_kchunk;

@@ -9,6 +9,10 @@
 // it reads the map tile for its range only, runs the stores of the blocks it can skip and appends every other block to a
 // list; 2 is the plain kernel on the listed blocks.  Keeping the two apart keeps the heavy path at the registers and the
 // occupancy it has without the skip, and lets the light one run at full occupancy (it is bound by the latency of its loads).
+//
+// The accumulation takes another form (FL_OPT_SKIP_EMPTY_TAPS, at the end of this file): a launch that tests the taps it
+// has computed against cell flags, wave by wave (and the SPARSE == 2 launch on an empty list behind it, for the dense case).
+// Its map is a backward map whose zeroed border defeats the tile range.
 #pragma once
 #include "bq_device.hip.h"
 
@@ -232,6 +236,87 @@ __device__ __forceinline__ bool listed_block(const Sparse &s, int &bX, int &bY, 
 __device__ __forceinline__ void count_block(const Sparse &s, bool skipped)
 {
     if (s.stats && threadIdx.x == 0 && threadIdx.y == 0) atomicAdd(s.stats + (skipped ? 1 : 0), 1ull);
+}
+
+// ---- FL_OPT_SKIP_EMPTY_TAPS: the test inside the operator's own launch, wave by wave (SPARSE == 3) ----
+//
+// A block's tile range bounds where its taps COULD land; the kernel computes where they DO land, and that costs it only the
+// map look-up.  So there is no classifying launch: after map9_lds and the clamp every lane finds the cell of each of its nine
+// taps -- by locate()'s own expressions, so it is the cell corners() will read -- and looks up one byte per tap, the CELL flag
+// of the 8 x 8 x 8 brick that holds the cell's base node.  If no lane of the wave finds a set flag, every word the wave's
+// gathers could load is 0x00000000 and the wave runs the operator's stores with every gather result taken as +0.0f.
+//
+// The cell flag of brick C is 0 only if every word corners() can deliver for a cell whose base node lies in C is 0x00000000.
+// A cell with base (i, j, k) reads the flat indices base + {0, 1} + nx {0, 1} + nx ny {0, 1}: the nodes of C and of its +1
+// neighbours on each axis, and at the array's upper ends what the flat index wraps into (the rule stated at
+// taps_in_empty_bricks: x past nx - 1 is the start of the next row, y past ny - 1 the start of the next plane, z past nz - 1 lies
+// outside the allocation and reads 0).  Base indices run to n INCLUSIVE on every axis -- the accumulate clamps to [0, h n] --
+// so the array has (n >> 3) + 1 bricks per axis, which covers base index n where n is a multiple of 8.
+//
+// A Sparse for this form carries the CELL flags in `flags`, their dims in nbx / nby, the wave counters in `stats`, no list.
+struct CellDims { int ncx, ncy, ncz; };
+__host__ __device__ inline CellDims cell_dims(int nx, int ny, int nz)
+{
+    return CellDims{ (nx >> kBrickShift) + 1, (ny >> kBrickShift) + 1, (nz >> kBrickShift) + 1 };
+}
+
+// One wave per cell brick (four to a block): the node range its cells' corners cover, by the rule above, then an OR over the
+// brick flags of that range, the lanes taking one brick each.  Every brick index lies inside the flag array: the ranges are
+// cut to [0, n - 1] before they are used.
+__global__ __launch_bounds__(256) void cell_flags_kernel(const unsigned char *flags, unsigned char *cells, int nx, int ny, int nz)
+{
+    const CellDims d = cell_dims(nx, ny, nz);
+    const int c = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + threadIdx.y));
+    if (c >= d.ncx * d.ncy * d.ncz) return;
+    const int cx = c % d.ncx, t = c / d.ncx, cy = t % d.ncy, cz = t / d.ncy;
+    // base nodes [8 c, min(8 c + 7, n)], their corners one further
+    int x0 = cx << kBrickShift, x1 = min(x0 + kBrick - 1, nx) + 1;
+    int y0 = cy << kBrickShift, y1 = min(y0 + kBrick - 1, ny) + 1;
+    int z0 = cz << kBrickShift, z1 = min(z0 + kBrick - 1, nz) + 1;
+    if (x1 > nx - 1) { x0 = 0; x1 = nx - 1; y1 += 1; }
+    if (y1 > ny - 1) { y0 = 0; y1 = ny - 1; z1 += 1; }
+    z1 = min(z1, nz - 1);
+    bool occupied = false;
+    if (z0 <= z1) {                                         // (else: every corner lies past the last plane and reads 0)
+        const int nbx = (nx + kBrick - 1) >> kBrickShift, nby = (ny + kBrick - 1) >> kBrickShift;
+        const int bx0 = x0 >> kBrickShift, by0 = y0 >> kBrickShift, bz0 = z0 >> kBrickShift;
+        const int wx = (x1 >> kBrickShift) - bx0 + 1, wy = (y1 >> kBrickShift) - by0 + 1, wz = (z1 >> kBrickShift) - bz0 + 1;
+        for (int e = (int)threadIdx.x; e < wx * wy * wz; e += 64) {
+            const int ex = e % wx, r = e / wx, ey = r % wy, ez = r / wy;
+            occupied |= flags[(size_t)(bx0 + ex) + (size_t)nbx * ((by0 + ey) + (size_t)nby * (bz0 + ez))] != 0;
+        }
+    }
+    const bool any = __any(occupied);
+    if (threadIdx.x == 0) cells[c] = any ? 1 : 0;
+}
+
+// true when some tap of some lane of this wave may read a word that is not 0x00000000.  mp: the clamped positions; the sampled
+// fields are unstaggered, origin 0 on every axis.  The cell is locate<true, true>'s: there q = fma(pos, 1 / h, +0), here
+// q = pos * (1 / h) -- both round the same exact product once and can differ in the sign of a zero only, which floor does not
+// see.  (Written as a product on purpose: stated as locate's fma the compiler shares the nine cells with the gathers further
+// down and keeps 27 more registers alive across the test, which spills.)  The clamp to [0, h n] with h a power of two bounds
+// every index by [0, n]: each byte read lies inside the cell-flag array.  The nine loads go out together: one wait.
+__device__ __forceinline__ bool wave_taps_may_read(const Sparse &s, const Spacing &sp, const f3 (&mp)[9])
+{
+    unsigned char fl[9];
+#pragma unroll
+    for (int a9 = 0; a9 < 9; a9++) {
+        const int i = floor_to_int(mp[a9].x * sp.inv_h), j = floor_to_int(mp[a9].y * sp.inv_h), k = floor_to_int(mp[a9].z * sp.inv_h);
+        fl[a9] = s.flags[(unsigned)((i >> kBrickShift) + __mul24(s.nbx, (j >> kBrickShift) + __mul24(s.nby, k >> kBrickShift)))];
+    }
+    unsigned acc = 0u;
+#pragma unroll
+    for (int a9 = 0; a9 < 9; a9++) acc |= fl[a9];
+    return __any(acc != 0u);
+}
+
+// the counters of fl_sparse_wave_stats: [0] waves tested and kept, [1] waves tested and skipped -- one atomic per wave, by its
+// first active lane
+__device__ __forceinline__ void count_wave(const Sparse &s, bool skipped)
+{
+    if (!s.stats) return;
+    const unsigned long long live = __ballot(1);
+    if (__lane_id() == (unsigned)(__ffsll((long long)live) - 1)) atomicAdd(s.stats + (skipped ? 1 : 0), 1ull);
 }
 
 } // inline namespace BQ_VARIANT

@@ -490,6 +490,23 @@ enum {
                                  * count that costs the fewest rounds of blocks, about 32 planes per block, bq_launch_geom.h);
                                  * k > 0 = chunks of k planes (tests and tuning); negative = the one-thread-per-output-node
                                  * kernel (the A/B partner).  Same bits in every output whatever the value.           */
+    FL_OPT_SKIP_EMPTY_TAPS = 25,/* the unstaggered accumulation (gpu_accumulate_field/_field2, the second stage of
+                                 * gpu_compensate_field) on power-of-two spacing while FL_OPT_SKIP_EMPTY_BRICKS is 1 or 2: 1 (default)
+                                 * runs it behind the flag pass and a small cell-flag pass (one byte per brick of base nodes: 0
+                                 * only if every word a cell based there can hand to the gather is 0x00000000, the +1 neighbours
+                                 * and the flat-index wrap at the upper ends included) as a launch that tests its own taps: after
+                                 * the map look-up and the clamp every lane looks up the flag of the cell of each of its nine
+                                 * taps; a wave in which no lane finds a set flag loads no corner at all and runs the operator's
+                                 * stores with every gather result taken as +0.0f -- the statements of the full path, so dst +=
+                                 * ..., the products with the coefficient and the dst[0] == dst[1] order stay.  Every other wave
+                                 * runs the same gather in another schedule (about a fifth more instructions for two fields).
+                                 * Same bits in every output.  A flag pass that finds no empty brick makes that launch return at
+                                 * once; the unchanged kernel, launched behind it on an empty block list, then does the work (and
+                                 * returns at once otherwise): a dense pair pays the two passes and one empty launch.  The block
+                                 * classification of option 21 is not used here: the map is a backward map, whose zeroed border
+                                 * widens the tile range of half the blocks to the whole grid, while the taps of a border node
+                                 * land at nine definite points.  0: the accumulation as option 21 alone runs it.  With option
+                                 * 21 = 2 the waves are counted (fl_sparse_wave_stats).                                */
     FL_OPT_MAP_QUARTER_FP32 = 13 /* 0 (default): every lerp of the structured map look-up follows the double-rounding
                                  * contract.  1: the caller vouches that every value of the map arrays it passes to the
                                  * 9-point operators is 0 or lies in [h/256, 1024 h] (gpu_maps_quarter_safe checks a map
@@ -518,6 +535,9 @@ long long fl_mg_residual_launches(void);
 void fl_sparse_stats(long long out[2], int reset);
 /* the same for one operator: kind 0 = the advection, 1 = the error stage, 2 = the accumulation */
 void fl_sparse_stats_kind(int kind, long long out[2], int reset);
+/* FL_OPT_SKIP_EMPTY_TAPS with FL_OPT_SKIP_EMPTY_BRICKS = 2: out[0] = waves that tested their taps against the cell flags, out[1] =
+ * waves skipped, since the last reset (blocking; reset != 0 clears the counters) */
+void fl_sparse_wave_stats(long long out[2], int reset);
 /* the flag pass of FL_OPT_SKIP_EMPTY_BRICKS on its own (for tests and tools): one byte per 8 x 8 x 8 brick of f1 -- of f1 and
  * f2 taken together when f2 is not NULL -- into flags_host (HOST memory, ceil(ni/8) ceil(nj/8) ceil(nk/8) bytes, x fastest):
  * 1 = some word of the brick is not 0x00000000.  *any_empty (may be NULL): 1 when a brick is empty.  Blocking.  Returns the

@@ -7,8 +7,10 @@ and 199, one JSON line with
     nonzero_nodes      share of the nodes of rho whose word is not 0x00000000 (T: the same test)
     occupied_bricks    share of the 8 x 8 x 8 bricks the flag pass marks for the pair (gpu_brick_flags)
     skipped / tested   blocks of that step's advection, error-stage and accumulation launch
+With --waves the option value is 2: the accumulation runs in its wave-test form (FL_OPT_SKIP_EMPTY_TAPS) and its row holds the
+WAVES tested and skipped (fl_sparse_wave_stats) instead of blocks.
 
-    python tools/brick_occupancy.py [--n 256] [--jacobi-iters 200]
+    python tools/brick_occupancy.py [--n 256] [--jacobi-iters 200] [--waves]
 """
 import argparse
 import ctypes as C
@@ -24,6 +26,7 @@ def main():
     ap.add_argument("--n", type=int, default=256)
     ap.add_argument("--jacobi-iters", type=int, default=200)
     ap.add_argument("--report", type=int, nargs="*", default=[0, 20, 100, 199])
+    ap.add_argument("--waves", action="store_true")
     a = ap.parse_args()
     import numpy as np
     import gpufluidsimulation_amd as bq
@@ -31,7 +34,7 @@ def main():
     from gpufluidsimulation_amd.scenes import rising_smoke
     from gpufluidsimulation_amd.solver import BimocqGPUSolver
     lib, n = bq.hip_lib(), a.n
-    lib.fl_set_option(bq._lib.FL_OPT_SKIP_EMPTY_BRICKS, 4)
+    lib.fl_set_option(bq._lib.FL_OPT_SKIP_EMPTY_BRICKS, 2 if a.waves else 4)
     s = BimocqGPUSolver(n, n, n, 1.0, 0.0, 1.0)
     s.setSmoke(0.0, 1.0, rising_smoke(n, 1.0 / n))
     s.setProjection(a.jacobi_iters, 0.5)
@@ -41,6 +44,7 @@ def main():
     for f in range(max(a.report) + 1):
         for kind in range(3):
             lib.fl_sparse_stats_kind(kind, out, 1)
+        lib.fl_sparse_wave_stats(out, 1)
         s.advance(f, 2.0 / n)
         if f not in a.report:
             continue
@@ -48,6 +52,9 @@ def main():
         for kind, name in enumerate(("advect", "error", "accumulate")):
             lib.fl_sparse_stats_kind(kind, out, 1)
             row[name] = {"tested": int(out[0]), "skipped": int(out[1]), "ratio": round(out[1] / out[0], 4) if out[0] else None}
+        if a.waves:
+            lib.fl_sparse_wave_stats(out, 1)
+            row["accumulate_waves"] = {"tested": int(out[0]), "skipped": int(out[1]), "ratio": round(out[1] / out[0], 4) if out[0] else None}
         rho, T = s.field("rho"), s.field("T")
         row["nonzero_nodes"] = {"rho": float((np.ascontiguousarray(rho).view(np.uint32) != 0).mean()),
                                 "T": float((np.ascontiguousarray(T).view(np.uint32) != 0).mean())}
