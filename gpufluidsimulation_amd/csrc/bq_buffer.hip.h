@@ -1,5 +1,5 @@
 // bq_buffer.hip.h -- 16-byte buffer loads / stores through resource descriptors, for the marching kernels
-// (bq_project.hip: jacobi_lean*_kernel, bq_mgcg.hip: mg_lean2r_kernel).
+// (bq_sweep_pack.hip.h: sweep_lean2r_kernel and the packs' loads / stores; bq_project.hip: jacobi_lean3r_kernel, the LDS kernels).
 // Resource descriptor in SGPRs, a 32-bit byte offset per thread (VGPR), a wave-uniform byte offset (SGPR): no 64-bit
 // address arithmetic per load, and the range check of the descriptor answers 0 for offsets beyond the array.
 // hipcc 7.2's __builtin_amdgcn_raw_buffer_load_b128 lowers to a ONE-dword load, so the LLVM intrinsics are declared

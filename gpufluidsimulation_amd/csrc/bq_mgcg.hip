@@ -21,8 +21,7 @@
 //   fallbacks      mg_smooth_kernel / mg_smooth2_kernel / mg_residual_kernel / mg_poisson_kernel / mg_prolong_kernel
 //                  (one thread per cell; FL_OPT_MGCG_TILE = 0, FL_OPT_JACOBI_FUSE = 0, FL_OPT_JACOBI_ROWS = 3 select them).
 #include "bq_device.hip.h"
-#include "bq_buffer.hip.h"
-#include <type_traits>
+#include "bq_sweep_pack.hip.h"
 #include "bq_host.h"
 #include "bq_jacobi_plan.h"
 #include "bq_mgcg_slab_plan.h"
@@ -402,225 +401,11 @@ __global__ __launch_bounds__(THREADS) void mg_smooth2_kernel(const double *__res
     }
 }
 
-// ---- two sweeps per launch, lean form (the fp64 twin of jacobi_lean2r_kernel, bq_project.hip) ----------------------
-// mg_smooth2_kernel rotates its plane registers by moves, computes 64-bit addresses per load and owns one row per
-// thread: 130 us per launch at 256^3 = 402 MB of compulsory traffic at 3.1 TB/s.  This is the two-row kernel of the
-// fp32 projection on double2 columns: loads and stores through buffer descriptors (row offset in a VGPR, plane offset
-// in an SGPR), plane rings with compile-time indices (loop unrolled 3 + PF times, nothing is moved), a thread owns the
-// double2 columns of rows j, j+1 and keeps L0 on rows j-1 .. j+2 (+ j-2, j+3 of the centre plane); rows of 2-4 waves
-// (nx = 256 doubles is two waves) let the first / last lane of a wave keep the column just outside the wave in a ring
-// of its own.  Every value is mg_smooth_kernel's expression on the same operands.  Preconditions as for
-// mg_smooth2_kernel, plus: x-boundary columns are stored with their L0 value (what `out` already holds there).
-struct D2 { double a, b; };                                 // two consecutive cells of a row
-__device__ __forceinline__ D2 ld_d2(v4i rs, unsigned voff, unsigned soff)
-{
-    const v2d v = __builtin_bit_cast(v2d, bq_buffer_load_x4(rs, (int)voff, (int)soff, 0));
-    return D2{v.x, v.y};
-}
-__device__ __forceinline__ double ld_d(v4i rs, unsigned voff, unsigned soff)
-{
-    return __builtin_bit_cast(double, bq_buffer_load_x2(rs, (int)voff, (int)soff, 0));
-}
-template <int AUX = 0>
-__device__ __forceinline__ void st_d2(D2 v, v4i rs, unsigned voff, unsigned soff)
-{
-    bq_buffer_store_x4(__builtin_bit_cast(v4f, v2d{v.a, v.b}), rs, (int)voff, (int)soff, AUX);
-}
-// smoothing_jacobi_kernel's expression (:1443-1461) on a double2 column; WIDE: `outside` replaces the neighbour lane's
-// value at a wave's first / last lane
-template <bool WIDE>
-__device__ __forceinline__ D2 jac_d2(D2 ce, D2 fr, D2 bk, D2 dn, D2 up, D2 dv, double alpha, double beta, bool xlo, bool xhi,
-                                     double outside, bool edgeL, bool edgeR)
-{
-    double left = lane_up(ce.b), right = lane_down(ce.a);
-    if (WIDE) {
-        if (edgeL) left = outside;
-        if (edgeR) right = outside;
-    }
-    D2 o;
-    o.a = ((left + ce.b + fr.a + bk.a + dn.a + up.a) + alpha * dv.a) * beta;
-    o.b = ((ce.a + right + fr.b + bk.b + dn.b + up.b) + alpha * dv.b) * beta;
-    if (xlo) o.a = ce.a;
-    if (xhi) o.b = ce.b;
-    return o;
-}
-
-// ZIN: the input field is all zeros and is not read (V_Cycle's first sweep of a level starts from a cleared x)
-template <bool WIDE, int PF, bool ZIN = false>
-__global__ __launch_bounds__(256) void mg_lean2r_kernel(const double *__restrict__ p, const double *__restrict__ div,
-                                                        double *__restrict__ out, int nx, int ny, int nz,
-                                                        int cw, int nby, int kchunk, double alpha, double beta)
-{
-    constexpr int P = 3 + PF;                                       // ring period
-    // PF = 2: loads two planes ahead and streaming stores, the form for arrays that come from HBM
-    constexpr bool HBM = PF >= 2;
-    constexpr int ST = HBM ? 2 : 0;
-    const int nblk = gridDim.x;
-    int b = blockIdx.x;
-    if ((nblk & 7) == 0) b = (b & 7) * (nblk >> 3) + (b >> 3);      // XCD-contiguous block order
-    const int by = b % nby, bz = b / nby;
-    const int rows = 256 / cw;
-    // a wave holds one row pair when rows are at least one wave long: the row index is then wave-uniform
-    const int c = threadIdx.x % cw;
-    const int r = cw >= 64 ? __builtin_amdgcn_readfirstlane((int)threadIdx.x / cw) : (int)threadIdx.x / cw;
-    const int xraw = 2 * c, j = 2 * (by * rows + r);
-    const int kA = 1, kB = nz - 1;
-    const int kbeg = max(kA, bz * kchunk), kend = min(kB, bz * kchunk + kchunk);
-    if (kbeg >= kend) return;
-    const bool xok = xraw < nx;
-    // odd rows: the last lane of a row holds the single boundary column nx-1 in .a (its .b is the next row's first cell:
-    // loaded, never used, never stored -- the lane stores nothing, `out` already holds the boundary column)
-    const bool xlast = xok && xraw == nx - 1;
-    const bool active0 = xok && !xlast && j >= 1 && j <= ny - 2, active1 = xok && !xlast && j + 1 >= 1 && j + 1 <= ny - 2;
-    const int x = xok ? xraw : 0;                                   // out-of-range lanes, rows, planes: clamped into the array
-    const bool xlo = x == 0 || xlast, xhi = x + 1 == nx - 1;
-    const unsigned bytes = (unsigned)nx * (unsigned)ny * (unsigned)nz * 8u;
-    const v4i rp = make_rsrc4(p, bytes), rd = make_rsrc4(div, bytes), ro = make_rsrc4(out, bytes);
-    unsigned vo[6];                                                 // byte offsets of this thread's column in rows j-2 .. j+3
-    bool rowb[4];                                                   // rows j-1 .. j+2 are boundary rows (keep L0)
-#pragma unroll
-    for (int a = 0; a < 6; a++) vo[a] = ((unsigned)x + (unsigned)nx * (unsigned)min(max(j - 2 + a, 0), ny - 1)) * 8u;
-#pragma unroll
-    for (int a = 0; a < 4; a++) rowb[a] = j - 1 + a <= 0 || j - 1 + a >= ny - 1;
-    // only the first and the last row block can hold a boundary row: everybody else runs the loop without the selects
-    const bool edge_block = 2 * by * rows - 1 <= 0 || 2 * (by * rows + rows - 1) + 2 >= ny - 1;
-    const unsigned pstride = (unsigned)nx * (unsigned)ny * 8u;
-    auto po = [&](int pl) -> unsigned { return pstride * (unsigned)min(max(pl, 0), nz - 1); };
-    // WIDE: the first / last lane of a wave looks after the column just outside its wave (xe) -- it needs that column's
-    // L0 on rows j-1 .. j+2 (x-neighbour of our own first sweep) and its L1 on rows j, j+1 (x-neighbour of our second
-    // sweep), which it evaluates itself from that column's own neighbours (outer x-neighbour xo, rows, planes, div).
-    // The other 62 lanes run the same eight scalar loads per plane with an offset beyond the descriptor's range: the range
-    // check answers 0 and nothing goes to the caches.
-    const int lane = threadIdx.x & 63;
-    const bool edgeL = WIDE && lane == 0 && xok && xraw > 0, edgeR = WIDE && lane == 63 && xraw + 2 < nx;
-    const bool edge = edgeL || edgeR;
-    const int xe = edgeL ? xraw - 1 : (edgeR ? xraw + 2 : x), xo = edgeL ? xe - 1 : (edgeR ? xe + 1 : x);
-    const bool xe_boundary = xe <= 0 || xe >= nx - 1;
-    unsigned ve[4], vx[2];
-#pragma unroll
-    for (int a = 0; a < 4; a++) ve[a] = ((unsigned)min(max(xe, 0), nx - 1) + (unsigned)nx * (unsigned)min(max(j - 1 + a, 0), ny - 1)) * 8u;
-#pragma unroll
-    for (int a = 0; a < 2; a++) vx[a] = ((unsigned)min(max(xo, 0), nx - 1) + (unsigned)nx * (unsigned)min(max(j + a, 0), ny - 1)) * 8u;
-    if (WIDE && !edge) {
-        // an offset beyond the descriptor's range: the load returns 0 without touching the caches (2 GiB + any plane
-        // offset of an array below 2 GiB neither wraps nor lands inside it)
-#pragma unroll
-        for (int a = 0; a < 4; a++) ve[a] = 0x80000000u;
-        vx[0] = vx[1] = 0x80000000u;
-    }
-
-    // Rings indexed by the plane's slot (t + d) mod P, t = q - (kbeg - 1) the iteration number, d the plane's distance
-    // from q -- all compile-time inside the unrolled loop, so no value is ever moved to rotate planes:
-    //   L0[.][0..3]  p on rows j-1 .. j+2            (live: planes q-1 .. q+PF; q+1+PF arriving)
-    //   H[.][0..1]   p on rows j-2, j+3              (live: plane q .. q+PF-1; q+PF arriving)
-    //   L1[.][0..3]  first sweep on rows j-1 .. j+2  (q being made; q-1; q-2 (rows j, j+1))
-    //   D[.][0..3]   div on rows j-1 .. j+2          (q-1 (rows j, j+1) .. q+PF-1; q+PF arriving)
-    //   WIDE: E[.][0..3] p(xe) on rows j-1 .. j+2 like L0; Eo / Eb p(xo) / div(xe) on rows j, j+1 like H; X the outside
-    //   column's L1 on rows j, j+1 (q being made, q-1 live)
-    auto run = [&](auto EDGE_T) {
-    constexpr bool EDGE = decltype(EDGE_T)::value;
-    D2 L0[P][4], H[P][2], L1[P][4], D[P][4];
-    double E[P][4], Eo[P][2], Eb[P][2], X[P][2];
-    const D2 zero = D2{0.0, 0.0};
-#pragma unroll
-    for (int a = 0; a < P; a++) {
-#pragma unroll
-        for (int bb = 0; bb < 4; bb++) L1[a][bb] = zero;
-        X[a][0] = 0.0; X[a][1] = 0.0;
-    }
-    int q = kbeg - 1;
-#pragma unroll
-    for (int d = -1; d <= PF; d++) {                                // prologue: planes q-1 .. q+PF
-        constexpr int dummy = 0; (void)dummy;
-        const int sl_ = (d + P) % P;
-        const unsigned pp = po(q + d);
-#pragma unroll
-        for (int a = 0; a < 4; a++) L0[sl_][a] = ZIN ? zero : ld_d2(rp, vo[a + 1], pp);
-        if (WIDE) {
-#pragma unroll
-            for (int a = 0; a < 4; a++) E[sl_][a] = ZIN ? 0.0 : ld_d(rp, ve[a], pp);
-        }
-        if (d >= 0 && d < PF) {
-#pragma unroll
-            for (int a = 0; a < 4; a++) D[sl_][a] = ld_d2(rd, vo[a + 1], pp);
-            H[sl_][0] = ZIN ? zero : ld_d2(rp, vo[0], pp); H[sl_][1] = ZIN ? zero : ld_d2(rp, vo[5], pp);
-            if (WIDE) {
-#pragma unroll
-                for (int a = 0; a < 2; a++) { Eo[sl_][a] = ZIN ? 0.0 : ld_d(rp, vx[a], pp); Eb[sl_][a] = ld_d(rd, ve[a + 1], pp); }
-            }
-        }
-    }
-#define MG_SL(T, d) (((T) + (d) + P) % P)
-#define MG_LEAN_PHASE(T)                                                                                            \
-    {                                                                                                               \
-        constexpr int im = MG_SL(T, -1), ic = MG_SL(T, 0), in_ = MG_SL(T, 1), ia = MG_SL(T, 1 + PF), ha = MG_SL(T, PF); \
-        constexpr int mp = MG_SL(T, -1), mpp = MG_SL(T, -2);                                                        \
-        const unsigned pa = po(q + 1 + PF), pb = po(q + PF);                                                        \
-        _Pragma("unroll") for (int a = 0; a < 4; a++) { L0[ia][a] = ZIN ? zero : ld_d2(rp, vo[a + 1], pa); D[ha][a] = ld_d2(rd, vo[a + 1], pb); } \
-        H[ha][0] = ZIN ? zero : ld_d2(rp, vo[0], pb); H[ha][1] = ZIN ? zero : ld_d2(rp, vo[5], pb);                 \
-        if (WIDE) {                                                                                                 \
-            _Pragma("unroll") for (int a = 0; a < 4; a++) E[ia][a] = ZIN ? 0.0 : ld_d(rp, ve[a], pa);                  \
-            _Pragma("unroll") for (int a = 0; a < 2; a++) { Eo[ha][a] = ZIN ? 0.0 : ld_d(rp, vx[a], pb); Eb[ha][a] = ld_d(rd, ve[a + 1], pb); } \
-        }                                                                                                           \
-        const bool qb = q < kA || q >= kB;                                                                          \
-        if (qb) {                                               /* a boundary plane keeps L0 */                      \
-            _Pragma("unroll") for (int a = 0; a < 4; a++) L1[ic][a] = L0[ic][a];                                      \
-        } else {                                                                                                    \
-            L1[ic][0] = jac_d2<WIDE>(L0[ic][0], H[ic][0], L0[ic][1], L0[im][0], L0[in_][0], D[ic][0], alpha, beta, xlo, xhi, E[ic][0], edgeL, edgeR);   \
-            L1[ic][1] = jac_d2<WIDE>(L0[ic][1], L0[ic][0], L0[ic][2], L0[im][1], L0[in_][1], D[ic][1], alpha, beta, xlo, xhi, E[ic][1], edgeL, edgeR);  \
-            L1[ic][2] = jac_d2<WIDE>(L0[ic][2], L0[ic][1], L0[ic][3], L0[im][2], L0[in_][2], D[ic][2], alpha, beta, xlo, xhi, E[ic][2], edgeL, edgeR);  \
-            L1[ic][3] = jac_d2<WIDE>(L0[ic][3], L0[ic][2], H[ic][1], L0[im][3], L0[in_][3], D[ic][3], alpha, beta, xlo, xhi, E[ic][3], edgeL, edgeR);   \
-            if (EDGE) {                                                                                             \
-                _Pragma("unroll") for (int a = 0; a < 4; a++)                                                        \
-                    if (rowb[a]) L1[ic][a] = L0[ic][a];                                                             \
-            }                                                                                                       \
-        }                                                                                                           \
-        if (WIDE) {                                             /* the outside column's own first sweep, rows j, j+1 */ \
-            _Pragma("unroll") for (int rr = 0; rr < 2; rr++) {                                                       \
-                const double own = edgeL ? L0[ic][rr + 1].a : L0[ic][rr + 1].b;                                       \
-                const double l = edgeL ? Eo[ic][rr] : own, rg2 = edgeL ? own : Eo[ic][rr];                           \
-                const double v = (l + rg2 + E[ic][rr] + E[ic][rr + 2] + E[im][rr + 1] + E[in_][rr + 1] + alpha * Eb[ic][rr]) * beta; \
-                const bool keep = qb || xe_boundary || (j + rr <= 0 || j + rr >= ny - 1);                           \
-                X[ic][rr] = keep ? E[ic][rr + 1] : v;                                                               \
-            }                                                                                                       \
-        }                                                                                                           \
-        const int k = q - 1;                                                                                        \
-        if (k >= kbeg && k < kend) {                                                                                \
-            const D2 o0 = jac_d2<WIDE>(L1[mp][1], L1[mp][0], L1[mp][2], L1[mpp][1], L1[ic][1], D[mp][1], alpha, beta, xlo, xhi, X[mp][0], edgeL, edgeR); \
-            const D2 o1 = jac_d2<WIDE>(L1[mp][2], L1[mp][1], L1[mp][3], L1[mpp][2], L1[ic][2], D[mp][2], alpha, beta, xlo, xhi, X[mp][1], edgeL, edgeR); \
-            const unsigned pk = pstride * (unsigned)k;                                                              \
-            if (active0) st_d2<ST>(o0, ro, vo[2], pk);                                                              \
-            if (active1) st_d2<ST>(o1, ro, vo[3], pk);                                                              \
-        }                                                                                                           \
-        q++;                                                                                                        \
-    }
-    while (true) {
-        MG_LEAN_PHASE(0)
-        if (q > kend) break;
-        MG_LEAN_PHASE(1)
-        if (q > kend) break;
-        MG_LEAN_PHASE(2)
-        if (q > kend) break;
-        MG_LEAN_PHASE(3)
-        if (q > kend) break;
-        if constexpr (P > 4) {
-            MG_LEAN_PHASE(4)
-            if (q > kend) break;
-        }
-        if constexpr (P > 5) {
-            MG_LEAN_PHASE(5)
-            if (q > kend) break;
-        }
-        if constexpr (P > 6) {
-            MG_LEAN_PHASE(6)
-            if (q > kend) break;
-        }
-    }
-    };
-    if (edge_block) run(std::true_type{}); else run(std::false_type{});
-#undef MG_LEAN_PHASE
-}
-
+// ---- two sweeps per launch, lean form -------------------------------------------------------------------------------
+// mg_lean2r_kernel is sweep_lean2r_kernel<PackD2, WIDE, PF, ZIN> (bq_sweep_pack.hip.h, shared with the fp32 projection) on
+// the whole array: double2 columns, rows of one wave or (WIDE, nx = 256 doubles is two waves) of 2-4 waves, odd rows.
+// Preconditions as for mg_smooth2_kernel, plus: x-boundary columns are stored with their L0 value (what `out` already
+// holds there).
 
 // ---- THREE sweeps per launch, the intermediate levels' neighbour rows exchanged through LDS ------------------------------
 // The fp64 twin of jacobi_lds_kernel<W, 1, 3> (bq_project.hip): a block is W output waves + two halo waves at either end, a
@@ -761,19 +546,18 @@ __global__ __launch_bounds__((W + 2 * (S - 1)) * 64) void mg_lds3_kernel(const d
 #pragma unroll
     for (int a = 0; a < P; a++) { D[a] = zero; L1[a] = zero; L2[a] = zero; Lx[a] = zero; }
     int q = kbeg - (S - 1);
-#define MG_SL4(T, d) ((((T) + (d)) % P + P) % P)
 #pragma unroll
     for (int d = -1; d <= 1; d++) {                                 // prologue: planes q-1, q, q+1 of x; b of plane q
-        const int sl_ = MG_SL4(0, d);
+        const int sl_ = ring_slot(0, d, P);
         const unsigned pp = po(q + d);
         L0[sl_] = ZIN ? zero : ld_own(rp, pp);
         if (OUTER && d >= 0) Lx[sl_] = ZIN ? zero : ld_far(pp);
         if (d == 0) D[sl_] = ld_own(rd, pp);
     }
-    if (!ZIN) { put(lds[0][q & 1], L0[MG_SL4(0, 0)]); __syncthreads(); }    // the first step's centre plane for the neighbours
+    if (!ZIN) { put(lds[0][q & 1], L0[ring_slot(0, 0, P)]); __syncthreads(); }    // the first step's centre plane for the neighbours
 #define MG_LDS_PHASE(T)                                                                                             \
     {                                                                                                               \
-        constexpr int im = MG_SL4(T, -1), ic = MG_SL4(T, 0), in_ = MG_SL4(T, 1), ia = MG_SL4(T, 2);                   \
+        constexpr int im = ring_slot(T, -1, P), ic = ring_slot(T, 0, P), in_ = ring_slot(T, 1, P), ia = ring_slot(T, 2, P);                   \
         const unsigned pa = po(q + 2), pb = po(q + 1);                                                              \
         L0[ia] = ZIN ? zero : ld_own(rp, pa);                                                                       \
         if (OUTER) Lx[ia] = ZIN ? zero : ld_far(pa);                                                                \
@@ -800,7 +584,7 @@ __global__ __launch_bounds__((W + 2 * (S - 1)) * 64) void mg_lds3_kernel(const d
         if (SM >= 2) { nlo2 = get(lds[1][(q - 1) & 1], rlo); nhi2 = get(lds[1][(q - 1) & 1], rhi); }                \
         put(lds[1][q & 1], L1[ic]);                                                                                 \
         if (SM >= 2) {      /* second sweep on plane q - 1 */                                                       \
-            constexpr int cs = MG_SL4(T, -1), us = MG_SL4(T, 0), ds = MG_SL4(T, -2);                                 \
+            constexpr int cs = ring_slot(T, -1, P), us = ring_slot(T, 0, P), ds = ring_slot(T, -2, P);                                 \
             const int ps = q - 1;                                                                                   \
             D4 v = jac_d4(L1[cs], nlo2, nhi2, L1[ds], L1[us], adv(D[cs]), beta, xlo, xhi, first, last);             \
             if (ps < kA || ps >= kB || (EDGE && rowb)) v = L1[cs];                                                  \
@@ -818,7 +602,7 @@ __global__ __launch_bounds__((W + 2 * (S - 1)) * 64) void mg_lds3_kernel(const d
             }                                                                                                       \
         }                                                                                                           \
         if (S >= 3 && SM >= 3) {      /* third sweep on plane q - 2 */                                                        \
-            constexpr int cs = MG_SL4(T, -2), us = MG_SL4(T, -1), ds = MG_SL4(T, -3);                                \
+            constexpr int cs = ring_slot(T, -2, P), us = ring_slot(T, -1, P), ds = ring_slot(T, -3, P);                                \
             const int ps = q - 2;                                                                                   \
             if (ps >= kbeg && ps < kend) {                                                                          \
                 if constexpr (!RES) {                                                                               \
@@ -862,7 +646,6 @@ __global__ __launch_bounds__((W + 2 * (S - 1)) * 64) void mg_lds3_kernel(const d
     };
     if (edge_block) go(std::true_type{}); else go(std::false_type{});
 #undef MG_LDS_PHASE
-#undef MG_SL4
 }
 
 // ---- residual / A x in the marching form ------------------------------------------------------------------------------
@@ -1451,7 +1234,7 @@ static void mg_smooth(double *x, const double *b, double *temp, double alpha, do
             for (; s + 2 * pair_group <= iter; s += 2 * pair_group)
                 for (int h = 0; h < pair_group; h++) {
                     launches++;
-#define MG_L2(W, F, Z) mg_lean2r_kernel<W, F, Z><<<nby2 * nbz, 256, 0, rt().compute>>>(in, b, out, ni, nj, nk, cw, nby2, kc, alpha, beta)
+#define MG_L2(W, F, Z) sweep_lean2r_kernel<PackD2, W, F, Z><<<nby2 * nbz, 256, 0, rt().compute>>>(in, b, out, ni, nj, nk, cw, nby2, kc, alpha, beta, WholeArray{})
                     if (zin) {
                         if (wide) { if (pf == 1) MG_L2(true, 1, true); else MG_L2(true, 2, true); }
                         else      { if (pf == 1) MG_L2(false, 1, true); else MG_L2(false, 2, true); }

@@ -7,8 +7,7 @@
 // registers, and moves everything as 16-byte vectors; see DESIGN.md "Jacobi kernel".
 // Summation order is the reference's (GPU_kernel.cu:1834), so results are bit-identical.
 #include "bq_device.hip.h"
-#include "bq_buffer.hip.h"
-#include <type_traits>
+#include "bq_sweep_pack.hip.h"
 #include "bq_host.h"
 #include "bq_jacobi_plan.h"
 #include <algorithm>
@@ -630,279 +629,16 @@ __global__ __launch_bounds__(WAVES * 64) void jacobi_march2r_kernel(const float 
 }
 
 // ---- the two-row fused kernel again, written for the instruction count --------------------------------------------
-// jacobi_march2r_kernel is bound by instruction ISSUE, not by memory: one wave per SIMD issues one VALU instruction
-// per ~4 cycles, and the compiler's rendering of that kernel spends ~680 instructions per plane (64-bit address
-// arithmetic for every load, ~120 register moves to rotate planes and to pair operands, selects for boundaries that a
-// wave almost never has).  Same algorithm, same expression per value, different plumbing:
-//   * loads and stores through buffer descriptors: per-thread row offsets computed once (VGPR), the plane offset in an
-//     SGPR -- no address arithmetic in the loop;
-//   * every plane set lives in a ring of four buffers indexed by (plane mod 4); the loop is unrolled four times so that
-//     all ring indices are compile-time: nothing is ever moved to rotate planes;
-//   * float4 columns as two float2 halves (clang ext vectors -> v_pk_add_f32 / v_pk_mul_f32);
-//   * boundary rows are a property of the BLOCK (template flag EDGE: only the first and last row blocks pay the
-//     selects), boundary planes one wave-uniform branch;
-//   * x-boundary columns are stored too: they hold L0's value (a sweep never changes them), which is what `out`
-//     already holds there (the fused kernels' precondition: both buffers carry the same boundary layer).
-// Rows of one wave (nx <= 256); wider rows keep jacobi_march2r_kernel<.., true>.
-struct R4 { v2f a, b; };                                    // (x, y), (z, w) of one float4 column
-
-__device__ __forceinline__ R4 ld_r4(v4i rs, unsigned voff, unsigned soff)
-{
-    const v4f v = bq_buffer_load_x4(rs, (int)voff, (int)soff, 0);
-    return R4{v2f{v.x, v.y}, v2f{v.z, v.w}};
-}
-__device__ __forceinline__ float ld_f(v4i rs, unsigned voff, unsigned soff) { return bq_buffer_load_x1(rs, (int)voff, (int)soff, 0); }
-// AUX: cache policy bits of the store (2 = nt: a streaming store, for arrays that will not be read again from the caches)
-template <int AUX = 0>
-__device__ __forceinline__ void st_r4(R4 v, v4i rs, unsigned voff, unsigned soff)
-{
-    bq_buffer_store_x4(v4f{v.a.x, v.a.y, v.b.x, v.b.y}, rs, (int)voff, (int)soff, AUX);
-}
-
-// jacobi_kernel's expression (GPU_kernel.cu:1833) on a float4 column: ((((((l + r) + f) + b) + d) + u) + alpha div) beta
-// WIDE (rows of several waves): the x-neighbour of a wave's first / last lane lives in another wave; `outside` is its
-// value, supplied by that lane itself (edgeL / edgeR mark the two lanes)
-// PRE: dv already holds alpha * div (the product is formed once per loaded div value and reused by every level that needs
-// it -- the same float either way)
-// own + (value of `from` in lane - 1) / (lane + 1), the neighbour taken through the add's own DPP operand: one instruction
-// where a DPP move, a move to pair the operands and a packed add stood.  A lane without a source lane (0 / 63) reads 0
-// (bound_ctrl): those are x-boundary or out-of-range columns, whose result is replaced or never stored.  The s_nop covers the
-// two wait states a DPP read needs after a VALU write of its source, which the compiler cannot see inside the asm.
-// `volatile` (round 4, ADVICE): the result depends on EXEC and on the neighbouring lanes, which the compiler cannot see either --
-// a pure two-operand asm could be sunk into a divergent region or merged across EXEC changes; volatile statements stay where
-// the source puts them (every use is in wave-uniform code of the plane loop).  Same ISA at today's -O3, same timings.
-__device__ __forceinline__ float add_from_left_lane(float from, float own)
-{
-    float r;
-    asm volatile("s_nop 1\n\tv_add_f32_dpp %0, %1, %2 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0" : "=v"(r) : "v"(from), "v"(own));
-    return r;
-}
-__device__ __forceinline__ float add_from_right_lane(float from, float own)
-{
-    float r;
-    asm volatile("s_nop 1\n\tv_add_f32_dpp %0, %1, %2 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:0" : "=v"(r) : "v"(from), "v"(own));
-    return r;
-}
-
-// DPPADD (rows of one wave only): the l + r stage as four scalar adds, the two outer ones with a DPP operand
-template <bool WIDE = false, bool PRE = false, bool DPPADD = false>
-__device__ __forceinline__ R4 jac_r4(R4 ce, R4 fr, R4 bk, R4 dn, R4 up, R4 dv, float alpha, float beta, bool xlo, bool xhi,
-                                     float outside = 0.f, bool edgeL = false, bool edgeR = false)
-{
-    if (DPPADD && !WIDE) {
-        // (l + r) per cell: cell 0 = left + x1, 1 = x0 + x2, 2 = x1 + x3, 3 = x2 + right -- the same sums as below
-        v2f s0 = v2f{add_from_left_lane(ce.b.y, ce.a.y), ce.a.x + ce.b.x};
-        v2f s1 = v2f{ce.a.y + ce.b.y, add_from_right_lane(ce.a.x, ce.b.x)};
-        s0 = s0 + fr.a; s1 = s1 + fr.b;
-        s0 = s0 + bk.a; s1 = s1 + bk.b;
-        s0 = s0 + dn.a; s1 = s1 + dn.b;
-        s0 = s0 + up.a; s1 = s1 + up.b;
-        if (PRE) { s0 = s0 + dv.a; s1 = s1 + dv.b; }
-        else     { s0 = s0 + alpha * dv.a; s1 = s1 + alpha * dv.b; }
-        s0 = s0 * beta; s1 = s1 * beta;
-        if (xlo) s0.x = ce.a.x;
-        if (xhi) s1.y = ce.b.y;
-        return R4{s0, s1};
-    }
-    float left = lane_up(ce.b.y), right = lane_down(ce.a.x);
-    if (WIDE) {
-        if (edgeL) left = outside;
-        if (edgeR) right = outside;
-    }
-    // (the compiler forms two v_pk_add_f32 here and assembles their operand pairs {left, x0}, {x1, x2}, {x3, right} with
-    // six moves; four scalar adds with the neighbour lanes taken through the adds' own DPP operand (inline asm) are 4
-    // instructions instead of 10, but measured no faster: 13.25 vs 13.23 us per sweep in the three-sweep kernel)
-    v2f s0 = v2f{left + ce.a.y, ce.a.x + ce.b.x};
-    v2f s1 = v2f{ce.a.y + ce.b.y, ce.b.x + right};
-    s0 = s0 + fr.a; s1 = s1 + fr.b;
-    s0 = s0 + bk.a; s1 = s1 + bk.b;
-    s0 = s0 + dn.a; s1 = s1 + dn.b;
-    s0 = s0 + up.a; s1 = s1 + up.b;
-    if (PRE) { s0 = s0 + dv.a; s1 = s1 + dv.b; }
-    else     { s0 = s0 + alpha * dv.a; s1 = s1 + alpha * dv.b; }
-    s0 = s0 * beta; s1 = s1 * beta;
-    if (xlo) s0.x = ce.a.x;
-    if (xhi) s1.y = ce.b.y;
-    return R4{s0, s1};
-}
-
-// PF: how many planes ahead the loads run (1 or 2; 3 and 4 measured no better anywhere, tools/batches/r02_m.sh).  The rings hold 3 + PF planes and the loop is unrolled 3 + PF times.
-template <bool WIDE, int PF>
-__global__ __launch_bounds__(256) void jacobi_lean2r_kernel(const float *__restrict__ p, const float *__restrict__ div,
-                                                            float *__restrict__ out, int nx, int ny, int nz,
-                                                            int cw, int nby, int kchunk, float alpha, float beta, Slab sl, PairRanges rg)
-{
-    constexpr int P = 3 + PF;                                       // ring period
-    // PF = 2 is the form for arrays that come from HBM (larger than the Infinity Cache): loads two planes ahead and
-    // streaming stores (512^3: 174.6 -> 162.8 us per sweep; in-cache sizes lose with them: 256^3 15.9 -> 20.3).
-    constexpr bool HBM = PF >= 2;
-    constexpr int ST = HBM ? 2 : 0;
-    const int nblk = gridDim.x;
-    int b = blockIdx.x;
-    if ((nblk & 7) == 0) b = (b & 7) * (nblk >> 3) + (b >> 3);      // XCD-contiguous block order
-    const int by = b % nby, bz = b / nby;
-    const int rows = 256 / cw;
-    // a wave holds one row pair when rows are at least one wave long: the row index is then wave-uniform
-    const int c = threadIdx.x % cw;
-    const int r = cw >= 64 ? __builtin_amdgcn_readfirstlane((int)threadIdx.x / cw) : (int)threadIdx.x / cw;
-    const int xraw = 4 * c, j = 2 * (by * rows + r);
-    const int kA = max(1, 1 - sl.koff), kB = min(nz - 1, sl.nkg - 1 - sl.koff);
-    const int r0 = bz < rg.nchA ? rg.k0a + bz * kchunk : rg.k0b + (bz - rg.nchA) * kchunk, r1 = bz < rg.nchA ? rg.k1a : rg.k1b;
-    const int kbeg = max(kA, r0), kend = min(min(kB, r1), r0 + kchunk);
-    if (kbeg >= kend) return;
-    const bool xok = xraw < nx;
-    const bool active0 = xok && j >= 1 && j <= ny - 2, active1 = xok && j + 1 >= 1 && j + 1 <= ny - 2;
-    const int x = xok ? xraw : nx - 4;                              // out-of-range lanes, rows, planes: clamped into the array
-    const bool xlo = x == 0, xhi = x + 3 == nx - 1;
-    const unsigned bytes = (unsigned)nx * (unsigned)ny * (unsigned)nz * 4u;
-    const v4i rp = make_rsrc4(p, bytes), rd = make_rsrc4(div, bytes), ro = make_rsrc4(out, bytes);
-    unsigned vo[6];                                                 // byte offsets of this thread's column in rows j-2 .. j+3
-    bool rowb[4];                                                   // rows j-1 .. j+2 are boundary rows (keep L0)
-#pragma unroll
-    for (int a = 0; a < 6; a++) vo[a] = ((unsigned)x + (unsigned)nx * (unsigned)min(max(j - 2 + a, 0), ny - 1)) * 4u;
-#pragma unroll
-    for (int a = 0; a < 4; a++) rowb[a] = j - 1 + a <= 0 || j - 1 + a >= ny - 1;
-    // only the first and the last row block can hold a boundary row: everybody else runs the loop without the selects
-    const bool edge_block = 2 * by * rows - 1 <= 0 || 2 * (by * rows + rows - 1) + 2 >= ny - 1;
-    const unsigned pstride = (unsigned)nx * (unsigned)ny * 4u;
-    auto po = [&](int pl) -> unsigned { return pstride * (unsigned)min(max(pl, 0), nz - 1); };
-    // WIDE: the first / last lane of a wave looks after the column just outside its wave (xe) -- it needs that column's
-    // L0 on rows j-1 .. j+2 (x-neighbour of our own first sweep) and its L1 on rows j, j+1 (x-neighbour of our second
-    // sweep), which it evaluates itself from that column's own neighbours (outer x-neighbour xo, rows, planes, div).
-    // The other 62 lanes run the same eight scalar loads per plane, but with an offset beyond the descriptor's range: the
-    // range check answers 0 and nothing goes to the caches (512^3: 200 -> 175 us per sweep against loading their own
-    // column; an exec-masked branch around the loads does the same at 512^3 but costs 7 % in-cache).
-    const int lane = threadIdx.x & 63;
-    const bool edgeL = WIDE && lane == 0 && xok && xraw > 0, edgeR = WIDE && lane == 63 && xraw + 4 < nx;
-    const bool edge = edgeL || edgeR;
-    const int xe = edgeL ? xraw - 1 : (edgeR ? xraw + 4 : x), xo = edgeL ? xe - 1 : (edgeR ? xe + 1 : x);
-    const bool xe_boundary = xe <= 0 || xe >= nx - 1;
-    unsigned ve[4], vx[2];
-#pragma unroll
-    for (int a = 0; a < 4; a++) ve[a] = ((unsigned)min(max(xe, 0), nx - 1) + (unsigned)nx * (unsigned)min(max(j - 1 + a, 0), ny - 1)) * 4u;
-#pragma unroll
-    for (int a = 0; a < 2; a++) vx[a] = ((unsigned)min(max(xo, 0), nx - 1) + (unsigned)nx * (unsigned)min(max(j + a, 0), ny - 1)) * 4u;
-    if (WIDE && !edge) {
-        // an offset beyond the descriptor's range: the load returns 0 without touching the caches (2 GiB + any plane
-        // offset of an array below 2 GiB neither wraps nor lands inside it)
-#pragma unroll
-        for (int a = 0; a < 4; a++) ve[a] = 0x80000000u;
-        vx[0] = vx[1] = 0x80000000u;
-    }
-
-    // Rings indexed by the plane's slot (t + d) mod P, t = q - (kbeg - 1) the iteration number, d the plane's distance
-    // from q -- all compile-time inside the unrolled loop, so no value is ever moved to rotate planes:
-    //   L0[.][0..3]  p on rows j-1 .. j+2            (live: planes q-1 .. q+PF; q+1+PF arriving)
-    //   H[.][0..1]   p on rows j-2, j+3              (live: plane q .. q+PF-1; q+PF arriving)
-    //   L1[.][0..3]  first sweep on rows j-1 .. j+2  (q being made; q-1; q-2 (rows j, j+1))
-    //   D[.][0..3]   div on rows j-1 .. j+2          (q-1 (rows j, j+1) .. q+PF-1; q+PF arriving)
-    //   WIDE: E[.][0..3] p(xe) on rows j-1 .. j+2 like L0; Eo / Eb p(xo) / div(xe) on rows j, j+1 like H; X the outside
-    //   column's L1 on rows j, j+1 (q being made, q-1 live)
-    auto run = [&](auto EDGE_T) {
-    constexpr bool EDGE = decltype(EDGE_T)::value;
-    R4 L0[P][4], H[P][2], L1[P][4], D[P][4];
-    float E[P][4], Eo[P][2], Eb[P][2], X[P][2];
-    const R4 zero = R4{v2f{0.f, 0.f}, v2f{0.f, 0.f}};
-#pragma unroll
-    for (int a = 0; a < P; a++) {
-#pragma unroll
-        for (int bb = 0; bb < 4; bb++) L1[a][bb] = zero;
-        X[a][0] = 0.f; X[a][1] = 0.f;
-    }
-    int q = kbeg - 1;
-#pragma unroll
-    for (int d = -1; d <= PF; d++) {                                // prologue: planes q-1 .. q+PF
-        constexpr int dummy = 0; (void)dummy;
-        const int sl_ = (d + P) % P;
-        const unsigned pp = po(q + d);
-#pragma unroll
-        for (int a = 0; a < 4; a++) L0[sl_][a] = ld_r4(rp, vo[a + 1], pp);
-        if (WIDE) {
-#pragma unroll
-            for (int a = 0; a < 4; a++) E[sl_][a] = ld_f(rp, ve[a], pp);
-        }
-        if (d >= 0 && d < PF) {
-#pragma unroll
-            for (int a = 0; a < 4; a++) D[sl_][a] = ld_r4(rd, vo[a + 1], pp);
-            H[sl_][0] = ld_r4(rp, vo[0], pp); H[sl_][1] = ld_r4(rp, vo[5], pp);
-            if (WIDE) {
-#pragma unroll
-                for (int a = 0; a < 2; a++) { Eo[sl_][a] = ld_f(rp, vx[a], pp); Eb[sl_][a] = ld_f(rd, ve[a + 1], pp); }
-            }
-        }
-    }
-#define BQ_SL(T, d) (((T) + (d) + P) % P)
-#define BQ_LEAN_PHASE(T)                                                                                            \
-    {                                                                                                               \
-        constexpr int im = BQ_SL(T, -1), ic = BQ_SL(T, 0), in_ = BQ_SL(T, 1), ia = BQ_SL(T, 1 + PF), ha = BQ_SL(T, PF); \
-        constexpr int mp = BQ_SL(T, -1), mpp = BQ_SL(T, -2);                                                        \
-        const unsigned pa = po(q + 1 + PF), pb = po(q + PF);                                                        \
-        _Pragma("unroll") for (int a = 0; a < 4; a++) { L0[ia][a] = ld_r4(rp, vo[a + 1], pa); D[ha][a] = ld_r4(rd, vo[a + 1], pb); } \
-        H[ha][0] = ld_r4(rp, vo[0], pb); H[ha][1] = ld_r4(rp, vo[5], pb);                                           \
-        if (WIDE) {                                                                                                 \
-            _Pragma("unroll") for (int a = 0; a < 4; a++) E[ia][a] = ld_f(rp, ve[a], pa);                              \
-            _Pragma("unroll") for (int a = 0; a < 2; a++) { Eo[ha][a] = ld_f(rp, vx[a], pb); Eb[ha][a] = ld_f(rd, ve[a + 1], pb); } \
-        }                                                                                                           \
-        const bool qb = q < kA || q >= kB;                                                                          \
-        if (qb) {                                               /* a boundary plane keeps L0 */                      \
-            _Pragma("unroll") for (int a = 0; a < 4; a++) L1[ic][a] = L0[ic][a];                                      \
-        } else {                                                                                                    \
-            /* alpha * div once per value: rows j, j+1 reuse the product in the second sweep */                      \
-            _Pragma("unroll") for (int a = 0; a < 4; a++) { D[ic][a].a = alpha * D[ic][a].a; D[ic][a].b = alpha * D[ic][a].b; } \
-            L1[ic][0] = jac_r4<WIDE, true>(L0[ic][0], H[ic][0], L0[ic][1], L0[im][0], L0[in_][0], D[ic][0], alpha, beta, xlo, xhi, E[ic][0], edgeL, edgeR);   \
-            L1[ic][1] = jac_r4<WIDE, true>(L0[ic][1], L0[ic][0], L0[ic][2], L0[im][1], L0[in_][1], D[ic][1], alpha, beta, xlo, xhi, E[ic][1], edgeL, edgeR);  \
-            L1[ic][2] = jac_r4<WIDE, true>(L0[ic][2], L0[ic][1], L0[ic][3], L0[im][2], L0[in_][2], D[ic][2], alpha, beta, xlo, xhi, E[ic][2], edgeL, edgeR);  \
-            L1[ic][3] = jac_r4<WIDE, true>(L0[ic][3], L0[ic][2], H[ic][1], L0[im][3], L0[in_][3], D[ic][3], alpha, beta, xlo, xhi, E[ic][3], edgeL, edgeR);   \
-            if (EDGE) {                                                                                             \
-                _Pragma("unroll") for (int a = 0; a < 4; a++)                                                        \
-                    if (rowb[a]) L1[ic][a] = L0[ic][a];                                                             \
-            }                                                                                                       \
-        }                                                                                                           \
-        if (WIDE) {                                             /* the outside column's own first sweep, rows j, j+1 */ \
-            _Pragma("unroll") for (int rr = 0; rr < 2; rr++) {                                                       \
-                const float own = edgeL ? L0[ic][rr + 1].a.x : L0[ic][rr + 1].b.y;                                   \
-                const float l = edgeL ? Eo[ic][rr] : own, rg2 = edgeL ? own : Eo[ic][rr];                           \
-                const float v = (l + rg2 + E[ic][rr] + E[ic][rr + 2] + E[im][rr + 1] + E[in_][rr + 1] + alpha * Eb[ic][rr]) * beta; \
-                const bool keep = qb || xe_boundary || (j + rr <= 0 || j + rr >= ny - 1);                           \
-                X[ic][rr] = keep ? E[ic][rr + 1] : v;                                                               \
-            }                                                                                                       \
-        }                                                                                                           \
-        const int k = q - 1;                                                                                        \
-        if (k >= kbeg && k < kend) {                                                                                \
-            const R4 o0 = jac_r4<WIDE, true>(L1[mp][1], L1[mp][0], L1[mp][2], L1[mpp][1], L1[ic][1], D[mp][1], alpha, beta, xlo, xhi, X[mp][0], edgeL, edgeR); \
-            const R4 o1 = jac_r4<WIDE, true>(L1[mp][2], L1[mp][1], L1[mp][3], L1[mpp][2], L1[ic][2], D[mp][2], alpha, beta, xlo, xhi, X[mp][1], edgeL, edgeR); \
-            const unsigned pk = pstride * (unsigned)k;                                                              \
-            if (active0) st_r4<ST>(o0, ro, vo[2], pk);                                                              \
-            if (active1) st_r4<ST>(o1, ro, vo[3], pk);                                                              \
-        }                                                                                                           \
-        q++;                                                                                                        \
-    }
-    while (true) {
-        BQ_LEAN_PHASE(0)
-        if (q > kend) break;
-        BQ_LEAN_PHASE(1)
-        if (q > kend) break;
-        BQ_LEAN_PHASE(2)
-        if (q > kend) break;
-        BQ_LEAN_PHASE(3)
-        if (q > kend) break;
-        if constexpr (P > 4) {
-            BQ_LEAN_PHASE(4)
-            if (q > kend) break;
-        }
-        if constexpr (P > 5) {
-            BQ_LEAN_PHASE(5)
-            if (q > kend) break;
-        }
-        if constexpr (P > 6) {
-            BQ_LEAN_PHASE(6)
-            if (q > kend) break;
-        }
-    }
-    };
-    if (edge_block) run(std::true_type{}); else run(std::false_type{});
-#undef BQ_LEAN_PHASE
-}
+// jacobi_lean2r_kernel is sweep_lean2r_kernel<PackF4, WIDE, PF> (bq_sweep_pack.hip.h, shared with the fp64 smoother) on the
+// plane ranges of a z-slab launch.  Rows of one wave (nx <= 256) or, WIDE, of 2-4 waves.
+struct SlabPairs {
+    Slab sl;
+    PairRanges rg;
+    __device__ __forceinline__ int kA() const { return max(1, 1 - sl.koff); }
+    __device__ __forceinline__ int kB(int nz) const { return min(nz - 1, sl.nkg - 1 - sl.koff); }
+    __device__ __forceinline__ int r0(int bz, int kchunk) const { return bz < rg.nchA ? rg.k0a + bz * kchunk : rg.k0b + (bz - rg.nchA) * kchunk; }
+    __device__ __forceinline__ int r1(int bz) const { return bz < rg.nchA ? rg.k1a : rg.k1b; }
+};
 
 // ---- THREE sweeps per launch (rows of one wave, whole array) ---------------------------------------------------------
 // With the lean plumbing the two-sweep kernel is bound by the fabric again (6.9 TB/s of real traffic at 256^3); what is
@@ -961,10 +697,9 @@ __global__ __launch_bounds__(256) void jacobi_lean3r_kernel(const float *__restr
         for (int bb = 0; bb < 4; bb++) L2[a][bb] = zero;
     }
     int q = kbeg - 2;
-#define BQ_SL3(T, d) ((((T) + (d)) % P + P) % P)
 #pragma unroll
     for (int d = -1; d <= PF; d++) {                                // prologue: planes q-1 .. q+PF
-        const int sl_ = BQ_SL3(0, d);
+        const int sl_ = ring_slot(0, d, P);
         const unsigned pp = po(q + d);
 #pragma unroll
         for (int a = 0; a < 6; a++) L0[sl_][a] = ld_r4(rp, vo[a + 1], pp);
@@ -976,11 +711,11 @@ __global__ __launch_bounds__(256) void jacobi_lean3r_kernel(const float *__restr
     }
 #define BQ_LEAN3_PHASE(T)                                                                                           \
     {                                                                                                               \
-        constexpr int im = BQ_SL3(T, -1), ic = BQ_SL3(T, 0), in_ = BQ_SL3(T, 1), ia = BQ_SL3(T, 1 + PF);  /* L0 */    \
-        constexpr int hc = BQ_SL3(T, 0), ha = BQ_SL3(T, PF);                                                        \
-        constexpr int a0 = BQ_SL3(T, 0), a1 = BQ_SL3(T, -1), a2 = BQ_SL3(T, -2);             /* L1: q, q-1, q-2 */    \
-        constexpr int b1 = BQ_SL3(T, -1), b2 = BQ_SL3(T, -2), b3 = BQ_SL3(T, -3);            /* L2: q-1, q-2, q-3 */  \
-        constexpr int d0 = BQ_SL3(T, 0), d1 = BQ_SL3(T, -1), d2 = BQ_SL3(T, -2);                                    \
+        constexpr int im = ring_slot(T, -1, P), ic = ring_slot(T, 0, P), in_ = ring_slot(T, 1, P), ia = ring_slot(T, 1 + PF, P);  /* L0 */    \
+        constexpr int hc = ring_slot(T, 0, P), ha = ring_slot(T, PF, P);                                                        \
+        constexpr int a0 = ring_slot(T, 0, P), a1 = ring_slot(T, -1, P), a2 = ring_slot(T, -2, P);             /* L1: q, q-1, q-2 */    \
+        constexpr int b1 = ring_slot(T, -1, P), b2 = ring_slot(T, -2, P), b3 = ring_slot(T, -3, P);            /* L2: q-1, q-2, q-3 */  \
+        constexpr int d0 = ring_slot(T, 0, P), d1 = ring_slot(T, -1, P), d2 = ring_slot(T, -2, P);                                    \
         const unsigned pa = po(q + 1 + PF), pb = po(q + PF);                                                        \
         _Pragma("unroll") for (int a = 0; a < 6; a++) { L0[ia][a] = ld_r4(rp, vo[a + 1], pa); D[ha][a] = ld_r4(rd, vo[a + 1], pb); } \
         H[ha][0] = ld_r4(rp, vo[0], pb); H[ha][1] = ld_r4(rp, vo[7], pb);                                           \
@@ -1030,7 +765,6 @@ __global__ __launch_bounds__(256) void jacobi_lean3r_kernel(const float *__restr
     };
     if (edge_block) run(std::true_type{}); else run(std::false_type{});
 #undef BQ_LEAN3_PHASE
-#undef BQ_SL3
 }
 
 // Obstacles (MASK = true; bq_obstacle.hip).  solid: one byte per cell, 0 = fluid; rows: one byte per
@@ -1219,10 +953,9 @@ __global__ __launch_bounds__((W + 2 * ((S - 1 + R - 1) / R)) * 64) void jacobi_l
             for (int l = 0; l < S; l++) Lv[l][a][c] = zero;
         }
     int q = kbeg - (S - 1);
-#define BQ_SL4(T, d) ((((T) + (d)) % P + P) % P)
 #pragma unroll
     for (int d = -1; d <= A - 1; d++) {                             // prologue: planes q-1 .. q+A-1 of p; div of planes q .. q+A-2
-        const int sl_ = BQ_SL4(0, d);
+        const int sl_ = ring_slot(0, d, P);
         const unsigned pp = po(q + d);
 #pragma unroll
         for (int a = 0; a < R + 2; a++) L0[sl_][a] = ld_r4(rp, vo[a], pp);
@@ -1237,7 +970,7 @@ __global__ __launch_bounds__((W + 2 * ((S - 1 + R - 1) / R)) * 64) void jacobi_l
     }
 #define BQ_LDS_PHASE(T)                                                                                             \
     {                                                                                                               \
-        constexpr int im = BQ_SL4(T, -1), ic = BQ_SL4(T, 0), in_ = BQ_SL4(T, 1), ia = BQ_SL4(T, A), id_ = BQ_SL4(T, A - 1); \
+        constexpr int im = ring_slot(T, -1, P), ic = ring_slot(T, 0, P), in_ = ring_slot(T, 1, P), ia = ring_slot(T, A, P), id_ = ring_slot(T, A - 1, P); \
         const unsigned pa = po(q + A), pb = po(q + A - 1);                                                          \
         _Pragma("unroll") for (int a = 0; a < R + 2; a++) L0[ia][a] = ld_r4(rp, vo[a], pa);                           \
         if (MK) { _Pragma("unroll") for (int a = 0; a < R + 2; a++) Fw[ia][a] = fword(j - 1 + a, q + A); }               \
@@ -1265,7 +998,7 @@ __global__ __launch_bounds__((W + 2 * ((S - 1 + R - 1) / R)) * 64) void jacobi_l
         /* sweep s on plane q - (s - 1): rows j-1, j+R of level s-1 on that plane were put into LDS before the last barrier */ \
         _Pragma("unroll") for (int s = 2; s <= S; s++) {                                                             \
             const int ps = q - (s - 1);                                                                             \
-            const int cs = BQ_SL4(T, -(s - 1)), us = BQ_SL4(T, -(s - 2)), ds = BQ_SL4(T, -s);                       \
+            const int cs = ring_slot(T, -(s - 1), P), us = ring_slot(T, -(s - 2), P), ds = ring_slot(T, -s, P);                       \
             if (s <= SM && (s < S || (ps >= kbeg && ps < kend))) {   /* (a step without the two wave-uniform plane tests measured slower) */ \
                 const bool keep = ps < kA || ps >= kB;                                                              \
                 _Pragma("unroll") for (int a = 0; a < R; a++) {                                                      \
@@ -1321,7 +1054,6 @@ __global__ __launch_bounds__((W + 2 * ((S - 1 + R - 1) / R)) * 64) void jacobi_l
     }
     if (edge_block) go(std::true_type{}, std::integral_constant<int, 0>{}); else go(std::false_type{}, std::integral_constant<int, 0>{});
 #undef BQ_LDS_PHASE
-#undef BQ_SL4
 }
 
 // ---- THREE sweeps per launch for rows of 260 .. 512 floats: two float4 segments per lane -----------------------------------
@@ -1425,20 +1157,19 @@ __global__ __launch_bounds__((W + 4) * 64) void jacobi_lds2seg_kernel(const floa
 #pragma unroll
     for (int a = 0; a < P; a++) { D[a] = zero; L1[a] = zero; L2[a] = zero; Lx[a] = zero; }
     int q = kbeg - (S - 1);
-#define BQ_SL4(T, d) ((((T) + (d)) % P + P) % P)
 #pragma unroll
     for (int d = -1; d <= 1; d++) {                                 // prologue: planes q-1, q, q+1 of p; div of plane q
-        const int sl_ = BQ_SL4(0, d);
+        const int sl_ = ring_slot(0, d, P);
         const unsigned pp = po(q + d);
         L0[sl_] = ld_own(rp, pp);
         if (OUTER && d >= 0) Lx[sl_] = ld_far(pp);
         if (d == 0) D[sl_] = ld_own(rd, pp);
     }
-    put(lds[0][q & 1], L0[BQ_SL4(0, 0)]);                           // the first step's centre plane for the neighbours
+    put(lds[0][q & 1], L0[ring_slot(0, 0, P)]);                           // the first step's centre plane for the neighbours
     __syncthreads();
 #define BQ_L2S_PHASE(T)                                                                                             \
     {                                                                                                               \
-        constexpr int im = BQ_SL4(T, -1), ic = BQ_SL4(T, 0), in_ = BQ_SL4(T, 1), ia = BQ_SL4(T, 2);                   \
+        constexpr int im = ring_slot(T, -1, P), ic = ring_slot(T, 0, P), in_ = ring_slot(T, 1, P), ia = ring_slot(T, 2, P);                   \
         const unsigned pa = po(q + 2), pb = po(q + 1);                                                              \
         L0[ia] = ld_own(rp, pa);                                                                                    \
         if (OUTER) Lx[ia] = ld_far(pa);                                                                             \
@@ -1461,7 +1192,7 @@ __global__ __launch_bounds__((W + 4) * 64) void jacobi_lds2seg_kernel(const floa
         if (SM >= 2) { nlo2 = get(lds[1][(q - 1) & 1], rlo); nhi2 = get(lds[1][(q - 1) & 1], rhi); }                \
         put(lds[1][q & 1], L1[ic]);                                                                                 \
         if (SM >= 2) {      /* second sweep on plane q - 1 */                                                       \
-            constexpr int cs = BQ_SL4(T, -1), us = BQ_SL4(T, 0), ds = BQ_SL4(T, -2);                                 \
+            constexpr int cs = ring_slot(T, -1, P), us = ring_slot(T, 0, P), ds = ring_slot(T, -2, P);                                 \
             const int ps = q - 1;                                                                                   \
             R8 v = jac_r8(L1[cs], nlo2, nhi2, L1[ds], L1[us], D[cs], beta, xlo, xhi, first, last);                  \
             if (ps < kA || ps >= kB || (EDGE && rowb)) v = L1[cs];                                                  \
@@ -1470,7 +1201,7 @@ __global__ __launch_bounds__((W + 4) * 64) void jacobi_lds2seg_kernel(const floa
             put(lds[2][ps & 1], v);                                                                                 \
         }                                                                                                           \
         if (SM >= 3) {      /* third sweep on plane q - 2 */                                                        \
-            constexpr int cs = BQ_SL4(T, -2), us = BQ_SL4(T, -1), ds = BQ_SL4(T, -3);                                \
+            constexpr int cs = ring_slot(T, -2, P), us = ring_slot(T, -1, P), ds = ring_slot(T, -3, P);                                \
             const int ps = q - 2;                                                                                   \
             if (ps >= kbeg && ps < kend) {                                                                          \
                 R8 v = jac_r8(L2[cs], nlo3, nhi3, L2[ds], L2[us], D[cs], beta, xlo, xhi, first, last);              \
@@ -1503,7 +1234,6 @@ __global__ __launch_bounds__((W + 4) * 64) void jacobi_lds2seg_kernel(const floa
     };
     if (edge_block) go(std::true_type{}); else go(std::false_type{});
 #undef BQ_L2S_PHASE
-#undef BQ_SL4
 }
 
 // ---- residual norms (A15 re-specified): r = div - (sum6 p - 6p), sum r^2 and max|r| --------
@@ -1691,7 +1421,7 @@ static bool launch_fused(const plan::LaunchPlan &pl, const float *in, const floa
     const char *name = "", *what = nullptr;             // the name reported, and the one an error message carries where it differs
     switch (pl.kernel) {
     case Kernel::kLean2r:
-#define BQ_LEAN2R(W, F) jacobi_lean2r_kernel<W, F><<<pl.grid, 256, 0, st>>>(in, div, out, ni, nj, nk, pl.cw, pl.row_blocks, pl.kc, alpha, beta, sl, rg)
+#define BQ_LEAN2R(W, F) sweep_lean2r_kernel<PackF4, W, F, false><<<pl.grid, 256, 0, st>>>(in, div, out, ni, nj, nk, pl.cw, pl.row_blocks, pl.kc, alpha, beta, SlabPairs{sl, rg})
         if (pl.wide) { if (pl.pf == 1) BQ_LEAN2R(true, 1); else BQ_LEAN2R(true, 2); }
         else         { if (pl.pf == 1) BQ_LEAN2R(false, 1); else BQ_LEAN2R(false, 2); }
 #undef BQ_LEAN2R

@@ -103,7 +103,24 @@ def test_mgcg_with_fused_smoothing_on_every_level(hip):
     try:
         test_mgcg_matches_oracle(hip, 64, 64, 64, 4, 2, 0.5)
         test_mgcg_matches_oracle(hip, 40, 36, 32, 3, 2, 1.0)
+        # below 2^19 cells the tile smoother takes the V-cycle's smoothing: with it (and the LDS triples) off, one-level
+        # V-cycles run their 32 sweeps from a cleared x through mg_lean2r_kernel -- the first launch in its ZIN form -- with
+        # the loads one and two planes ahead
+        hip.fl_set_option(bq._lib.FL_OPT_MGCG_TILE, 0)
+        hip.fl_set_option(bq._lib.FL_OPT_JACOBI_ROWS, 5)
+        for pf in (1, 2):
+            hip.fl_set_option(bq._lib.FL_OPT_JACOBI_KCHUNK, pf)
+            for ni, nj, nk in ((64, 12, 9),       # even rows, one wave per row
+                               (65, 8, 7),        # an odd row: the lane that holds the last column alone
+                               (300, 6, 9),       # rows of four waves: the edge lanes
+                               (257, 5, 7)):      # a wide odd row
+                test_mgcg_matches_oracle(hip, ni, nj, nk, 1, 1, 0.5)
+                name = hip.fl_mg_smooth_kernel_name().decode()     # (one level: the last smoothing call is level 0's)
+                assert name == "mg_lean2r_kernel", (pf, ni, nj, nk, name)
     finally:
+        hip.fl_set_option(bq._lib.FL_OPT_JACOBI_KCHUNK, 0)
+        hip.fl_set_option(bq._lib.FL_OPT_JACOBI_ROWS, 0)
+        hip.fl_set_option(bq._lib.FL_OPT_MGCG_TILE, 1)
         hip.fl_set_option(bq._lib.FL_OPT_JACOBI_FUSE, 1)
 
 
@@ -204,13 +221,15 @@ def test_smoothing_lds_triples_on_random_shapes(hip):
 
 
 @pytest.mark.parametrize("ni,nj,nk,levels", [(136, 24, 24, 2), (256, 16, 20, 2), (200, 12, 32, 3)])
-def test_mgcg_with_three_sweep_lds_smoother(hip, ni, nj, nk, levels):
+def test_mgcg_with_three_sweep_lds_smoother(hip, ni, nj, nk, levels, rows=8):
     """the whole operator with level 0 smoothed by mg_lds3_kernel (forced on small grids through the chunk-length option):
     V_Cycle's 32 sweeps from a cleared x run as 10 triples + 1 pair -- an ODD number of launches, the first of which does not
-    read its input and writes straight into x -- its 4 sweeps on the way up as two pairs; bit-identical to the oracle, twice"""
+    read its input and writes straight into x -- its 4 sweeps on the way up as two pairs; bit-identical to the oracle, twice.
+    rows 4: blocks of four output rows (mg_lds3_kernel<4, ..>, FL_OPT_JACOBI_KCHUNK = 14), its ZIN forms included"""
     import gpufluidsimulation_amd as bq
     hip.fl_set_option(bq._lib.FL_OPT_JACOBI_FUSE, 2)
     hip.fl_set_option(bq._lib.FL_OPT_JACOBI_KCHUNK2, 12)
+    hip.fl_set_option(bq._lib.FL_OPT_JACOBI_KCHUNK, 14 if rows == 4 else 0)
     try:
         # (default: that last pair launch also writes the residual the restriction reads -- mg_lds3_kernel<8, 3, false, true>)
         test_mgcg_matches_oracle(hip, ni, nj, nk, levels, 2, 0.5)
@@ -220,6 +239,7 @@ def test_mgcg_with_three_sweep_lds_smoother(hip, ni, nj, nk, levels):
         hip.fl_set_option(bq._lib.FL_OPT_MGCG_BOTTOM, 1)
         hip.fl_set_option(bq._lib.FL_OPT_JACOBI_FUSE, 1)
         hip.fl_set_option(bq._lib.FL_OPT_JACOBI_KCHUNK2, 0)
+        hip.fl_set_option(bq._lib.FL_OPT_JACOBI_KCHUNK, 0)
 
 
 @pytest.mark.parametrize("ni,nj,nk,levels,iters", [(64, 64, 64, 4, 2), (72, 40, 24, 3, 2), (129, 33, 17, 3, 1), (40, 36, 32, 3, 2),
@@ -260,13 +280,19 @@ def test_mgcg_rejects_bad_arguments(hip):
         bq.check()
 
 
-@pytest.mark.parametrize("ni,nj,nk", [(256, 12, 9), (128, 20, 40), (130, 9, 7), (127, 16, 11), (63, 63, 63), (31, 9, 70),
-                                      (64, 5, 5), (65, 4, 3), (9, 8, 7), (300, 6, 5), (514, 5, 4)])
+FUSED_PAIR_SHAPES = [(256, 12, 9), (128, 20, 40), (130, 9, 7), (127, 16, 11), (63, 63, 63), (31, 9, 70),
+                     (64, 5, 5), (65, 4, 3), (9, 8, 7), (300, 6, 5), (514, 5, 4)]
+
+
+@pytest.mark.parametrize("ni,nj,nk", FUSED_PAIR_SHAPES)
 @pytest.mark.parametrize("iters", [4, 8, 3, 2])
-def test_smoothing_fused_pairs(hip, ni, nj, nk, iters):
+def test_smoothing_fused_pairs(hip, ni, nj, nk, iters, pf=1):
     """gpu_smoothing_jacobi (two sweeps per launch where it applies: double2 lanes for even rows, one cell
     per lane for odd rows, rows spanning 1-4 waves with the edge-lane path, too-wide rows and odd leftovers
-    on the single-sweep kernel) == the oracle's sweep-by-sweep smoothing, bit for bit, boundary untouched"""
+    on the single-sweep kernel) == the oracle's sweep-by-sweep smoothing, bit for bit, boundary untouched;
+    with the loads one and two planes ahead (pf: mg_lean2r_kernel<WIDE, PF>, by default chosen by the array's size).
+    pf 1 is what these small arrays get by default; test_smoothing_fused_pairs_two_planes_ahead runs pf 2.
+    An odd sweep count is rounded up and pairs come in twos, so the two-sweep kernel runs from three sweeps on."""
     import gpufluidsimulation_amd as bq
     rng = np.random.default_rng(ni * 7 + nj)
     n = ni * nj * nk
@@ -277,17 +303,24 @@ def test_smoothing_fused_pairs(hip, ni, nj, nk, iters):
     for arr in (t0,):
         arr[0], arr[-1], arr[:, 0], arr[:, -1], arr[:, :, 0], arr[:, :, -1] = x0[0], x0[-1], x0[:, 0], x0[:, -1], x0[:, :, 0], x0[:, :, -1]
     x0, t0 = x0.ravel().copy(), t0.ravel().copy()
-    for fuse in (2, 0):                                  # 2: fused wherever it applies, whatever the size
-        hip.fl_set_option(bq._lib.FL_OPT_JACOBI_FUSE, fuse)
-        xr, tr = x0.copy(), t0.copy()
-        oracle().orc_mg_smooth(dp(xr), dp(b), dp(tr), -8.0, 1.0 / 6.0, ni, nj, nk, iters)
-        dx, db, dt = Dev(hip, x0), Dev(hip, b), Dev(hip, t0)
-        hip.gpu_smoothing_jacobi(dx.ptr, db.ptr, dt.ptr, -8.0, 1.0 / 6.0, ni, nj, nk, iters)
-        bq.check()
-        assert F.same(xr, dx.numpy()), fuse
-        if not fuse:
-            assert F.same(tr, dt.numpy())           # sweep by sweep the older iterate matches too
-    hip.fl_set_option(bq._lib.FL_OPT_JACOBI_FUSE, 1)
+    hip.fl_set_option(bq._lib.FL_OPT_JACOBI_KCHUNK, pf)
+    try:
+        for fuse in (2, 0):                              # 2: fused wherever it applies, whatever the size
+            hip.fl_set_option(bq._lib.FL_OPT_JACOBI_FUSE, fuse)
+            xr, tr = x0.copy(), t0.copy()
+            oracle().orc_mg_smooth(dp(xr), dp(b), dp(tr), -8.0, 1.0 / 6.0, ni, nj, nk, iters)
+            dx, db, dt = Dev(hip, x0), Dev(hip, b), Dev(hip, t0)
+            hip.gpu_smoothing_jacobi(dx.ptr, db.ptr, dt.ptr, -8.0, 1.0 / 6.0, ni, nj, nk, iters)
+            name = hip.fl_mg_smooth_kernel_name().decode()
+            bq.check()
+            assert F.same(xr, dx.numpy()), fuse
+            if fuse and 8 <= ni <= 512 and nj >= 4 and (iters + 1) // 2 * 2 >= 4:
+                assert name == "mg_lean2r_kernel", name
+            if not fuse:
+                assert F.same(tr, dt.numpy())       # sweep by sweep the older iterate matches too
+    finally:
+        hip.fl_set_option(bq._lib.FL_OPT_JACOBI_KCHUNK, 0)
+        hip.fl_set_option(bq._lib.FL_OPT_JACOBI_FUSE, 1)
 
 
 @pytest.mark.parametrize("ni,nj,nk,kc", [(256, 12, 30, 10), (130, 9, 24, 8), (200, 21, 40, 13), (254, 8, 16, 16), (256, 64, 48, 24),
@@ -327,3 +360,30 @@ def test_smoothing_lds_triples(hip, ni, nj, nk, kc, iters):
     assert name2 == "mg_lean2r_kernel", name2
     assert F.same(xr, dx.numpy())
     assert F.same(xr, dx2.numpy())
+
+
+@pytest.mark.parametrize("ni,nj,nk,kc", [(132, 4, 12, 12), (256, 7, 13, 8)])
+@pytest.mark.parametrize("iters", [6, 10])
+def test_smoothing_lds_triples_in_blocks_of_four_rows(hip, ni, nj, nk, kc, iters):
+    """mg_lds3_kernel<4, ..> (FL_OPT_JACOBI_KCHUNK = 14: four output rows and eight waves per block) on the two smallest
+    shapes of test_smoothing_lds_triples: one block that covers the four rows exactly, two blocks of which the second is
+    partly outside the grid"""
+    import gpufluidsimulation_amd as bq
+    hip.fl_set_option(bq._lib.FL_OPT_JACOBI_KCHUNK, 14)
+    try:
+        test_smoothing_lds_triples(hip, ni, nj, nk, kc, iters)
+    finally:
+        hip.fl_set_option(bq._lib.FL_OPT_JACOBI_KCHUNK, 0)
+
+
+def test_mgcg_with_three_sweep_lds_smoother_in_blocks_of_four_rows(hip):
+    """the whole operator through mg_lds3_kernel<4, ..>, the forms that start from a cleared x included"""
+    test_mgcg_with_three_sweep_lds_smoother(hip, 136, 24, 24, 2, rows=4)
+
+
+@pytest.mark.parametrize("ni,nj,nk", FUSED_PAIR_SHAPES)
+@pytest.mark.parametrize("iters", [4, 8, 3, 2])
+def test_smoothing_fused_pairs_two_planes_ahead(hip, ni, nj, nk, iters):
+    """test_smoothing_fused_pairs with the loads two planes ahead and streaming stores (mg_lean2r_kernel<WIDE, 2>, by default
+    the form of arrays beyond the Infinity Cache)"""
+    test_smoothing_fused_pairs(hip, ni, nj, nk, iters, pf=2)

@@ -12,7 +12,8 @@ import argparse, csv, re
 FAMILIES = [
     (r"jacobi_lds_kernel<\d+, \d+, 3>|jacobi_lds2seg_kernel", 12, "fabric / HBM; compulsory bytes of a 3-sweep launch"),
     (r"jacobi_lds_kernel<\d+, \d+, 4>", 12, "fabric; compulsory bytes of a 4-sweep launch"),
-    (r"jacobi_lean3r_kernel|jacobi_lean2r_kernel|jacobi_march2", 12, "fabric / HBM; compulsory bytes of a fused launch"),
+    # (jacobi_lean2r_kernel became sweep_lean2r_kernel<bq::PackF4, ..>; CSVs from before carry the old name)
+    (r"jacobi_lean3r_kernel|jacobi_lean2r_kernel|sweep_lean2r_kernel<(bq::)?PackF4|jacobi_march2", 12, "fabric / HBM; compulsory bytes of a fused launch"),
     (r"jacobi_march_kernel|jacobi_generic|jacobi_tile", 12, "fabric / HBM"),
     (r"advect_kernel<.*, 2, true>", 40, "VALU issue + texture addresser (two fields)"),
     (r"advect_kernel", 20, "VALU issue + texture addresser"),
